@@ -2,7 +2,12 @@
 """Headline benchmark of the hot path (BASELINE.json): fwd + loss + bwd Mpixels/s at
 1920x1080 on 1 M synthetic Gaussians, SH degree 3 (config 3), one view per GPU.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline alone: set-up, the W warm-up steps (and the untimed settle / survey steps below), the K
+timed steps, the outputs of the last timed step when --dump-outputs DIR is given (DIR/<name>.npy: image, loss, gradients) and
+the JSON line.  Everything else the line can carry — cpu_baseline, other_tile_lists, extra_configs, steady_state, the measured
+triad of the roofline and, for N > 1, the other exchange forms and the `exchange` timing pass — runs with --full only.
 
 Launch contract.  One process per GPU.  Two equivalent ways to get them:
   * `python bench.py --gpus N` with NO `RANK` in the environment: this process starts N rank processes itself
@@ -13,7 +18,7 @@ Either way a rank refuses to run (exit 2) when the world size that came up diffe
 JSON line carries `ranks_seen` = `dist.get_world_size()` next to `n_gpus`.
 Every rank process is a GPU-free SUPERVISOR (`supervise`): it never imports torch; it runs the line's SECTIONS one after the
 other in fresh child processes, each with a wall-clock limit (`--section-timeout`), and rank 0 merges their records into the
-ONE line.  N = 1: `headline` (the contract's measurement), `cpu_baseline`, `extras` (other tile-list mode + `extra_configs`).
+ONE line.  With --full, N = 1: `headline` (the contract's measurement), `cpu_baseline`, `extras` (other tile-list mode + `extra_configs`).
 N > 1: one fresh rank group per exchange form — the plain all-reduce FIRST, then `factored`, `factored+overlap` — with
 collective timeouts set; the headline is the library-default form if its group completed, else the best completed form,
 `exchange.forms[form]` holds every group's numbers or its {"error" | "timeout"}; exit 0 whenever the first section completed.
@@ -39,16 +44,16 @@ Prints ONE JSON line (rank 0) with the contract fields plus
                  W warm-up steps and 15 more untimed "settle" steps (`untimed_steps`): the first ~18 steps after the
                  device has been idle are up to 5 % slower (tools/step_times.py), and the timed region should see the
                  steady state of a training loop;
-  cpu_baseline — the oracle (C restatement of the reference algorithm, OpenMP) timed on
+  cpu_baseline — (--full) the oracle (C restatement of the reference algorithm, OpenMP) timed on
                  this host's cores on the same workload (rank 0, N = 1 only);
-  extra_configs — (N = 1, headline configuration only) the same measurement for BASELINE.json's other single-GPU
+  extra_configs — (--full; N = 1, headline configuration only) the same measurement for BASELINE.json's other single-GPU
                  configs and the §8f rows: config2 (100 k, fwd+bwd), config5 (5 M @ 4K, fwd+bwd), rgbd (the
                  reference's default training mode, config-3 size), trainer_step (prologue + Adam: `tail_step` =
                  gsr_trainer_tail_step after the backward, `tail_in_backward` = gsr_backward_trainer_tail);
-  exchange     — (N > 1) the gradient exchange: form that the headline ran, HIP-event time around the collectives,
+  exchange     — (--full; N > 1) the gradient exchange: form that the headline ran, HIP-event time around the collectives,
                  bytes each GPU sends over xGMI, the resulting GB/s against 7 x 153 GB/s, and `forms`: every form
                  (plain all-reduce / factored / factored+overlap), each from its own fresh rank group of the same run;
-  steady_state — wall-clock mean of `--steady-steps` (2000) further steps after the timed region: a 3 s corroboration of
+  steady_state — (--full) wall-clock mean of `--steady-steps` (2000) further steps after the timed region: a 3 s corroboration of
                  the K-step number that does not depend on HIP events;
   untimed_steps_total — W + 15 settle + 5 survey + 5 re-settle steps run before the timed region (`warmup` is the CLI's W).
 `value` / `ms_per_step` follow the driver contract (K steps between two barriers+synchronize, total / K);
@@ -209,8 +214,15 @@ def parse_args(argv=None):
                     help="run every section in THIS process instead of fresh children of the GPU-free supervisor (implied under "
                          "rocprofv3: a profiled process must not spawn); for --gpus > 1 the process must already be a rank")
     ap.add_argument("--steady-steps", type=int, default=2000,
-                    help="further untimed-by-events steps after the K-step timed region whose wall-clock mean is reported as "
-                         "`steady_state` (0 disables; a quarter of it for N > 1)")
+                    help="with --full: further untimed-by-events steps after the K-step timed region whose wall-clock mean is "
+                         "reported as `steady_state` (0 disables; a quarter of it for N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: cpu_baseline, the other tile-list mode, extra_configs (scenes, "
+                         "training protocol), steady_state, the measured triad of the roofline, and for N > 1 every exchange form "
+                         "in its own rank group plus the `exchange` timing pass.  Without it a run measures the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32; per-Gaussian arrays and large images as a fixed seeded sample; at most 64 MB in all)")
     return ap.parse_args(argv)
 
 
@@ -256,10 +268,15 @@ def plan_sections(args, world):
     """The child processes a supervisor runs, in order.  N > 1: one per exchange form (a fresh rank group each, the plain
     all-reduce first).  N = 1: the headline measurement, then the CPU baseline, then the extras (other tile-list mode,
     BASELINE.json's other single-GPU configs, the forward-only path, the trainer step) — each in its own process, so that
-    an oracle build hiccup or an out-of-memory 5 M scene cannot suppress the headline."""
+    an oracle build hiccup or an out-of-memory 5 M scene cannot suppress the headline.  All of that needs --full: a plain
+    run has one section, the headline's (N > 1: the rank group of the form the headline asks for)."""
     if world > 1 or dist_forced():
+        if not args.full:  # the form the line's headline asks for, alone
+            return ["plain" if args.headline_form == "plain" else default_exchange_form()]
         return list(DIST_SECTIONS)
     secs = ["headline"]
+    if not args.full:
+        return secs
     if not args.no_cpu_baseline:
         secs.append("cpu_baseline")
     single = not args.with_optimizer
@@ -431,7 +448,7 @@ def supervise(args, argv):
         sync.done(i, deadline + 15.0)
         if i == 0 and world == 1 and not dist_forced() and ("error" in rec or "timeout" in rec):
             break  # no headline: nothing to attach the other sections to
-        if rank == 0:
+        if rank == 0 and len(sections) > 1:
             write_partial(args, sections, results, t_all)
     sync.cleanup()
     first = results[sections[0]]
@@ -684,6 +701,7 @@ class Workload:
         self.set_exchange_form(exchange_form)
         self.with_optimizer, self.unfused_tail, self.tail_in_backward = with_optimizer, unfused_tail, tail_in_backward
         self.tail = None
+        self.last = None  # (image, loss | None, gradients | None) of the latest step
         if with_optimizer:
             # raw parameters the trainer optimises (training.jl:234-239): points, f_dc, f_rest, opacity logits,
             # log-scales, rotations; one NU.Adam each
@@ -773,13 +791,14 @@ class Workload:
             params[0], params[4] = raw[0], raw[5]
             tail["n_steps"] += 1
         if self.forward_only:
-            rast.forward_raw(*params, self.cam, self.deg, self.bg, forward_only=True)
+            self.last = (rast.forward_raw(*params, self.cam, self.deg, self.bg, forward_only=True), None, None)
             return
         img = rast.forward_raw(*params, self.cam, self.deg, self.bg)
+        loss = None
         if self.no_loss:
             vp = self.vpix_fixed
         else:
-            _, vp = pkg.fused_ssim.l1_ssim_loss(rast, img, self.target)
+            loss, vp = pkg.fused_ssim.l1_ssim_loss(rast, img, self.target)
         # the loss head's cotangent has zeros in its depth / alpha / normal channels (the loss only sees features[1:3],
         # training.jl:656,684-685): said to the backward (GSR_GRADS_COLOR_COTANGENT; nothing to say in :rgb mode)
         color = not self.no_loss
@@ -789,9 +808,11 @@ class Workload:
                                                self.deg, self.bg, color_cotangent=color)
             e4 = torch.cuda.Event(enable_timing=True); e4.record()
             tail["_last"] = (ev[0], ev[1], ev[2], ev[3], e4)
+            self.last = (img, loss, None)
             return
-        rast.backward_raw(vp, *params, self.cam, self.deg, self.bg, arena=self.arena, factored_sh=self.factored,
-                          color_cotangent=color)
+        grads = rast.backward_raw(vp, *params, self.cam, self.deg, self.bg, arena=self.arena, factored_sh=self.factored,
+                                  color_cotangent=color)
+        self.last = (img, loss, grads)
         exchanged = None
         if self.dist_on:
             if self.exchange_events is not None:
@@ -852,6 +873,22 @@ class Workload:
 
     def close(self):
         self.rast.close()
+
+    def outputs(self):
+        """What a caller of the step received from the latest one, by name (--dump-outputs): the image, the loss, the five
+        gradients (after the exchange when N > 1) and, with the optimizer, the parameters it left."""
+        img, loss, grads = self.last
+        out = {"image": img}
+        if loss is not None:
+            out["loss"] = loss
+        if grads is not None:
+            names = ("grad_means", "grad_colors" if self.factored else "grad_shs", "grad_opacities", "grad_scales", "grad_rotations")
+            out.update(zip(names, grads[:5]))
+            if self.factored and self.tail is None:
+                out["grad_shs"] = self.vshs_sum  # rebuilt from every view's colour cotangent
+        if self.tail is not None:
+            out.update(("param_" + g, t) for g, t in self.raw_map.items())
+        return out
 
     # -- measurement --------------------------------------------------------------------------------------------
     def time_plain(self, steps, warmup):
@@ -1031,6 +1068,39 @@ def measure_triad(pkg, dev):
         pkg._lib.check(lib.gsr_stream_triad(ta.data_ptr(), tb.data_ptr(), tc.data_ptr(), n_tri, 0.5, cs))
     e1.record(); e1.synchronize()
     return 5 * 12.0 * n_tri / (e0.elapsed_time(e1) * 1e-3) / 1e9
+
+
+DUMP_MAX_BYTES = 64_000_000
+DUMP_IMAGE_BYTES = 25_000_000  # an image up to this size (1920 x 1080 :rgb) is written whole, a larger one as a sample of its pixels
+DUMP_ROWS = 65536              # rows of each per-Gaussian output
+DUMP_SEED = 7
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: every tensor of `outputs` (Workload.outputs) as out_dir/<name>.npy in float32.  `loss` is written whole,
+    the image as (pixels, channels), every other array (per Gaussian) as DUMP_ROWS of its rows; a larger image or a larger
+    model is cut to a fixed, seeded, sorted choice of pixels / rows, the same from run to run."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        if name == "image":
+            t = t.reshape(-1, t.shape[-1])
+            k = DUMP_IMAGE_BYTES // (4 * t.shape[1])
+        else:
+            k = DUMP_ROWS
+        if name != "loss" and t.shape[0] > k:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(t.shape[0], size=k, replace=False))
+            t = t[torch.as_tensor(rows, device=t.device)]
+        arrays[name] = t.to(torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def exchange_timing(wl, steps, warmup):
@@ -1284,6 +1354,8 @@ def run_section(args, section):
         time.sleep(1e6)
 
     m = wl.measure(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.outputs())
     dt, per_step = m["dt"], m["per_step"]
     ms_median = (None if not per_step else per_step[len(per_step) // 2] if len(per_step) % 2 else
                  0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2]))
@@ -1291,7 +1363,7 @@ def run_section(args, section):
     Dn, V = int(wl.rast.stats.n_rendered), int(wl.rast.stats.n_visible)
     ms_step = 1e3 * dt / args.steps
     value = world * P / (dt / args.steps) / 1e6
-    roofline = wl.roofline(m, triad_gbs=measure_triad(pkg, dev))
+    roofline = wl.roofline(m, triad_gbs=measure_triad(pkg, dev) if args.full else None)
     rast, tail = wl.rast, wl.tail
     is_headline = is_headline_config(args)
 
@@ -1348,7 +1420,7 @@ def run_section(args, section):
                                        "inside the backward (gsr_backward_trainer_tail: 'adam' = composite_bwd + per-Gaussian backward + tail)"
                                        if args.tail_in_backward else "fused (gsr_trainer_tail_step: 'adam' is the whole tail)")
         out["config"]["workload"] += " + prologue + Adam (trainer tail, not the headline metric)"
-    if args.steady_steps > 0 and tail is None:
+    if args.full and args.steady_steps > 0 and tail is None:
         # a long steady-state mean next to the K-step contract number: K = 20 steps are 30 ms inside a run of many seconds,
         # and nothing but our own HIP events corroborated them (round-3 verdict, weak #11); plain wall clock, no events
         ss = max(1, args.steady_steps if not wl.dist_on else args.steady_steps // 4)
@@ -1356,9 +1428,9 @@ def run_section(args, section):
         out["steady_state"] = ({"steps": ss, "ms_per_step": round(1e3 * dts, 4), "value": round(world * P / dts / 1e6, 3),
                                 "timing": "host wall clock around `steps` further steps between two synchronisations, no events"}
                                if isinstance(dts, float) else dts)
-    if wl.dist_on and tail is None:
+    if args.full and wl.dist_on and tail is None:
         out["exchange"] = guarded(exchange_timing, wl, max(5, args.steps // 2), 2)
-    if section == "all":  # --in-process: the other sections here too, each guarded
+    if section == "all" and args.full:  # --in-process: the other sections here too, each guarded
         wl.close()
         del wl
         torch.cuda.empty_cache()

@@ -74,7 +74,7 @@ def test_bench_gpus_2_self_launches_two_ranks(launch_ranks):
     HIP): two ranks share the one GPU of the box, gloo carries the collectives.  The JSON line must say n_gpus = 2 =
     ranks_seen and carry the exchange report with every form timed."""
     rc, out = launch_ranks([sys.executable, BENCH, "--gpus", "2", "--gaussians", "20000", "--width", "640", "--height", "480",
-                            "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--steady-steps", "20"], 1,
+                            "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--steady-steps", "20", "--full"], 1,
                            env={"GSR_DIST_BACKEND": "gloo"}, timeout=900, raw=True)
     assert rc == [0], out[0]
     line = [ln for ln in out[0].splitlines() if ln.startswith("{")][-1]
@@ -102,25 +102,25 @@ def _fake(argv, timeout=300, **env):
 
 
 def test_supervisor_n1_merges_sections_into_one_line():
-    p, rep, lines = _fake(["--steps", "3", "--warmup", "1"])
+    p, rep, lines = _fake(["--steps", "3", "--warmup", "1", "--full"])
     assert p.returncode == 0 and len(lines) == 1, p.stderr
     assert rep["ms_per_step"] == 1.5 and rep["cpu_baseline"]["kind"] == "port" and "config2" in rep["extra_configs"]
 
 
 def test_a_failing_or_hanging_extra_section_never_costs_the_headline():
-    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--section-timeout", "3"], GSR_BENCH_FAIL_FORM="extras")
+    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--section-timeout", "3", "--full"], GSR_BENCH_FAIL_FORM="extras")
     assert p.returncode == 0 and rep["ms_per_step"] == 1.5 and "error" in rep["extras_error"]
     assert rep["cpu_baseline"]["kind"] == "port"
-    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--section-timeout", "2"], GSR_BENCH_HANG_FORM="cpu_baseline")
+    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--section-timeout", "2", "--full"], GSR_BENCH_HANG_FORM="cpu_baseline")
     assert p.returncode == 0 and rep["cpu_baseline"] == {"timeout": 2.0, "wall_s": rep["cpu_baseline"]["wall_s"]}
     assert "extra_configs" in rep
-    p, rep, _ = _fake(["--steps", "3", "--warmup", "1"], GSR_BENCH_FAIL_FORM="headline")
+    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--full"], GSR_BENCH_FAIL_FORM="headline")
     assert p.returncode != 0 and rep is None
 
 
 @pytest.mark.parametrize("hang", ["factored", "factored+overlap"])
 def test_a_hanging_exchange_form_is_recorded_and_the_line_survives(hang):
-    p, rep, lines = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1", "--section-timeout", "3"], GSR_BENCH_HANG_FORM=hang)
+    p, rep, lines = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1", "--section-timeout", "3", "--full"], GSR_BENCH_HANG_FORM=hang)
     assert p.returncode == 0 and len(lines) == 1, p.stderr
     forms = rep["exchange"]["forms"]
     assert forms[hang] == {"timeout": 3.0, "wall_s": forms[hang]["wall_s"]}
@@ -131,9 +131,9 @@ def test_a_hanging_exchange_form_is_recorded_and_the_line_survives(hang):
 
 
 def test_a_failing_plain_form_is_recorded_and_all_forms_failing_fails():
-    p, rep, _ = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1"], GSR_BENCH_FAIL_FORM="plain")
+    p, rep, _ = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], GSR_BENCH_FAIL_FORM="plain")
     assert p.returncode == 0 and "error" in rep["exchange"]["forms"]["plain"] and rep["exchange"]["headline_form"] == "factored+overlap"
-    p, rep, _ = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1", "--section-timeout", "2"],
+    p, rep, _ = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1", "--section-timeout", "2", "--full"],
                       GSR_BENCH_FAKE="hang-all")
     assert p.returncode != 0 and rep is None and "rank(s) failed" in p.stderr
 
@@ -150,7 +150,7 @@ def test_supervisors_under_torchrun_rendezvous_each_form_on_a_fresh_port():
     store and its TORCHELASTIC_* variables must not leak into the children)."""
     from bench import _free_port
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                        "127.0.0.1", "--master-port", str(_free_port()), BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1"],
+                        "127.0.0.1", "--master-port", str(_free_port()), BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        env=_env(GSR_BENCH_FAKE="dist"), capture_output=True, text=True, timeout=600)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stderr[-3000:]
@@ -183,7 +183,7 @@ def test_bench_one_rank_rccl_runs_every_form_in_its_own_process(launch_ranks):
     path of every exchange form (communicator creation with a timeout, the two extra communicators of the overlapped form, async
     work handles, stream joins) through the supervisor on a one-GPU box: three sections, three fresh processes, one line."""
     rc, out = launch_ranks([sys.executable, BENCH, "--gpus", "1", "--gaussians", "20000", "--width", "640", "--height", "480",
-                            "--steps", "4", "--warmup", "1", "--steady-steps", "20"], 1,
+                            "--steps", "4", "--warmup", "1", "--steady-steps", "20", "--full"], 1,
                            env={"GSR_DIST_FORCE": "1"}, timeout=900, raw=True)
     assert rc == [0], out[0]
     rep = json.loads([ln for ln in out[0].splitlines() if ln.startswith("{")][-1])
@@ -199,20 +199,20 @@ def test_headline_form_flag_and_the_form_named_in_the_line():
     """--headline-form plain makes the line's top-level numbers the ONE all-reduce north_star names (default: the library
     default form); either way config.parallelism / config.exchange_form say which form `value` is, every form is reported with
     its expected_ms (bytes / 7 x 153 GB/s), and a failed plain group falls back to the best completed form — and says so."""
-    p, rep, lines = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1"])
+    p, rep, lines = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"])
     assert p.returncode == 0 and len(lines) == 1, p.stderr
     ex = rep["exchange"]
     assert ex["headline_form"] == "factored+overlap" and ex["headline_form_requested"] == "default"
     assert rep["config"]["exchange_form"] == "factored+overlap" and "factored+overlap" in rep["config"]["parallelism"]
     assert rep["ms_per_step"] == 1.8 and all(f["expected_ms"] == 0.1 for f in ex["forms"].values())
-    p, rep, lines = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1", "--headline-form", "plain"])
+    p, rep, lines = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1", "--headline-form", "plain", "--full"])
     assert p.returncode == 0 and len(lines) == 1, p.stderr
     ex = rep["exchange"]
     assert ex["headline_form"] == "plain" and ex["headline_form_requested"] == "plain" and ex["library_default_form"] == "factored+overlap"
     assert rep["ms_per_step"] == 3.0 and rep["config"]["exchange_form"] == "plain"
     assert rep["config"]["parallelism"].startswith("[exchange form of this line: plain]")
     assert ex["forms"]["factored+overlap"]["ms_per_step"] == 1.8  # the others are still there
-    p, rep, _ = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1", "--headline-form", "plain"], GSR_BENCH_FAIL_FORM="plain")
+    p, rep, _ = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1", "--headline-form", "plain", "--full"], GSR_BENCH_FAIL_FORM="plain")
     assert p.returncode == 0 and rep["exchange"]["headline_form"] == "factored+overlap" and rep["config"]["exchange_form"] == "factored+overlap"
 
 
@@ -260,11 +260,11 @@ def test_scenes_section_is_merged_and_priced():
     """extra_configs.scenes comes from its own child process; annotate_predictions prices every record against the headline's
     stage times (and never costs the line)."""
     import bench
-    p, rep, lines = _fake(["--steps", "3", "--warmup", "1"])
+    p, rep, lines = _fake(["--steps", "3", "--warmup", "1", "--full"])
     assert p.returncode == 0 and rep["extra_configs"]["scenes"]["hot_tile_32k"]["ms_per_step"] == 2.0
-    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--section-timeout", "3"], GSR_BENCH_HANG_FORM="scenes")
+    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--section-timeout", "3", "--full"], GSR_BENCH_HANG_FORM="scenes")
     assert p.returncode == 0 and "timeout" in rep["extra_configs"]["scenes"] and "config2" in rep["extra_configs"]
-    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--no-scenes"])
+    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--no-scenes", "--full"])
     assert p.returncode == 0 and "scenes" not in rep["extra_configs"]
     head = {"preprocess": 0.126, "tile_scan": 0.013, "sort_composite_fwd": 0.355, "loss_fwd": 0.067, "loss_bwd": 0.051,
             "composite_bwd": 0.656, "pergauss_bwd": 0.142}
@@ -304,7 +304,7 @@ def test_total_budget_bounds_the_run_and_skipped_sections_are_recorded():
     wall is below the budget by construction, and the merged-so-far line is written out after every section."""
     import bench
     # worst case by construction: every section hangs until its limit -> the sum of the limits handed out stays below the budget
-    args = bench.parse_args([])
+    args = bench.parse_args(["--full"])
     assert args.total_budget == 900.0 and args.total_budget < 1800.0
     secs = bench.plan_sections(args, 1)
     assert secs == ["headline", "cpu_baseline", "extras", "scenes", "train_protocol"]
@@ -319,7 +319,7 @@ def test_total_budget_bounds_the_run_and_skipped_sections_are_recorded():
     # five fake sections of ~7.5 s each under a 62 s budget (30 s of it the reserve): the first ones run, the rest is skipped — and
     # says so
     t0 = time.time()
-    p, rep, lines = _fake(["--steps", "3", "--warmup", "1", "--total-budget", "62"], GSR_BENCH_FAKE_SLEEP="7", timeout=200)
+    p, rep, lines = _fake(["--steps", "3", "--warmup", "1", "--total-budget", "62", "--full"], GSR_BENCH_FAKE_SLEEP="7", timeout=200)
     wall = time.time() - t0
     assert p.returncode == 0 and len(lines) == 1, p.stderr
     assert rep["ms_per_step"] == 1.5 and rep["cpu_baseline"]["kind"] == "port"
@@ -337,10 +337,85 @@ def test_total_budget_bounds_the_run_and_skipped_sections_are_recorded():
     first = json.loads(partial[0].split(": ", 1)[1])
     assert first["ms_per_step"] == 1.5 and first["partial"]["sections_done"] == ["headline"] and "cpu_baseline" not in first
     # a hanging LATE section costs its own limit, never the line; and everything that fits is there
-    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--section-timeout", "3"], GSR_BENCH_HANG_FORM="train_protocol")
+    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--section-timeout", "3", "--full"], GSR_BENCH_HANG_FORM="train_protocol")
     assert p.returncode == 0 and "timeout" in rep["extra_configs"]["train_protocol"] and "hot_tile_32k" in rep["extra_configs"]["scenes"]
-    p, rep, _ = _fake(["--steps", "3", "--warmup", "1"])
+    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--full"])
     assert rep["extra_configs"]["train_protocol"]["ms_per_step"]["mean"] == 1.2
     assert rep["extra_configs"]["scenes"]["trained_by_protocol"]["ms_per_step"] == 1.9   # (c): the trained scene joins the scenes
-    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--no-train-protocol"])
+    p, rep, _ = _fake(["--steps", "3", "--warmup", "1", "--no-train-protocol", "--full"])
     assert "train_protocol" not in rep["extra_configs"] and "trained_by_protocol" not in rep["extra_configs"]["scenes"]
+
+
+# ---- a plain run measures the headline alone (everything else: --full); --dump-outputs ------------------------------------
+def test_a_plain_run_measures_the_headline_alone():
+    """Without --full the supervisor runs one section — N = 1: the headline; N > 1: the rank group of the form the headline asks
+    for — and nothing else: no CPU baseline, no extras, no other exchange form, no partial line."""
+    import bench
+    assert bench.plan_sections(bench.parse_args([]), 1) == ["headline"]
+    assert bench.plan_sections(bench.parse_args(["--gpus", "2"]), 2) == ["factored+overlap"]
+    assert bench.plan_sections(bench.parse_args(["--gpus", "2", "--headline-form", "plain"]), 2) == ["plain"]
+    p, rep, lines = _fake(["--steps", "3", "--warmup", "1"])
+    assert p.returncode == 0 and len(lines) == 1, p.stderr
+    assert rep["ms_per_step"] == 1.5 and rep["steps"] == 3 and list(rep["bench_budget"]["sections"]) == ["headline"]
+    assert not {"cpu_baseline", "other_tile_lists", "extra_configs", "extras_error"} & set(rep)
+    assert "partial line" not in p.stderr
+    p, rep, lines = _fake(["--gpus", "2", "--steps", "3", "--warmup", "1"])
+    assert p.returncode == 0 and len(lines) == 1, p.stderr
+    assert list(rep["exchange"]["forms"]) == ["factored+overlap"] and rep["ms_per_step"] == 1.8
+
+
+def test_dump_outputs_writes_float32_and_the_same_sample_every_time(tmp_path):
+    """dump_outputs: float32 .npy per output; the loss and an image up to 1920 x 1080 x 3 whole; a larger image and every
+    per-Gaussian array beyond DUMP_ROWS rows as a fixed, sorted choice of pixels / rows — the same rows for every array and
+    every run — and never more than 64 MB."""
+    import numpy as np
+    import torch
+
+    import bench
+    n = 100_000
+    g = torch.Generator().manual_seed(0)
+    idx = torch.arange(n, dtype=torch.float32)
+    outs = {"image": torch.arange(1080 * 1920, dtype=torch.float32).repeat_interleave(5).view(1080, 1920, 5),
+            "loss": torch.tensor(0.25, dtype=torch.float64),
+            "grad_means": torch.stack([idx, -idx, idx], 1), "grad_shs": idx.view(n, 1, 1).expand(n, 16, 3).contiguous(),
+            "grad_opacities": torch.randn(n, 1, generator=g)}
+    total = bench.dump_outputs(str(tmp_path / "a"), outs)
+    assert total <= bench.DUMP_MAX_BYTES
+    bench.dump_outputs(str(tmp_path / "b"), outs)
+    got = {}
+    for name in outs:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+        got[name] = a
+    assert got["loss"] == np.float32(0.25)
+    pix = got["image"][:, 0]
+    assert got["image"].shape == (bench.DUMP_IMAGE_BYTES // 20, 5) and np.all(np.diff(pix) > 0)
+    assert np.array_equal(got["image"], np.repeat(pix[:, None], 5, 1))
+    rows = got["grad_means"][:, 0]
+    assert rows.shape == (bench.DUMP_ROWS,) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["grad_shs"], np.broadcast_to(rows[:, None, None], (bench.DUMP_ROWS, 16, 3)))
+    assert np.array_equal(got["grad_opacities"], outs["grad_opacities"].numpy()[rows.astype(np.int64)])
+    # 1920 x 1080 :rgb is written whole, and so is a model of at most DUMP_ROWS Gaussians
+    small = {"image": torch.rand(1080, 1920, 3, generator=g), "grad_means": torch.rand(bench.DUMP_ROWS, 3, generator=g)}
+    bench.dump_outputs(str(tmp_path / "c"), small)
+    assert np.array_equal(np.load(tmp_path / "c" / "image.npy"), small["image"].view(-1, 3).numpy())
+    assert np.array_equal(np.load(tmp_path / "c" / "grad_means.npy"), small["grad_means"].numpy())
+
+
+@pytest.mark.gpu
+def test_a_plain_run_dumps_the_last_timed_step(launch_ranks, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the headline alone, K timed steps, and the
+    image / loss / five gradients of the last timed step as float32 .npy files."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    rc, o = launch_ranks([sys.executable, BENCH, "--gpus", "1", "--gaussians", "20000", "--width", "640", "--height", "480",
+                          "--steps", "4", "--warmup", "1", "--dump-outputs", str(out)], 1, timeout=600, raw=True)
+    assert rc == [0], o[0]
+    rep = json.loads([ln for ln in o[0].splitlines() if ln.startswith("{")][-1])
+    assert rep["steps"] == 4 and rep["ms_per_step"] > 0 and rep["value"] > 0 and rep["dtype"] == "f32"
+    assert not {"cpu_baseline", "other_tile_lists", "extra_configs", "steady_state"} & set(rep)
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(got) == {"image", "loss", "grad_means", "grad_shs", "grad_opacities", "grad_scales", "grad_rotations"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got["image"].shape == (640 * 480, 3) and got["grad_shs"].shape == (20000, 16, 3) and float(got["loss"]) > 0
+    assert np.abs(got["grad_means"]).sum() > 0
