@@ -185,7 +185,9 @@ EXPORTS = ["gsr_create", "gsr_destroy", "gsr_release_scene_buffers", "gsr_memory
            "gsr_mask_findall_scratch_bytes", "gsr_mask_findall", "gsr_gather_rows", "gsr_sh_grad_from_views", "gsr_sh_grad_from_views_tail", "gsr_trainer_tail_step",
            "gsr_backward_trainer_tail",
            "gsr_densify_grad_mean", "gsr_densify_mask", "gsr_compose_rows", "gsr_split_transform", "gsr_reset_opacity", "gsr_morton_codes",
-           "gsr_ply_pack_rows", "gsr_ply_unpack_rows", "gsr_count_nonfinite"] + POLICY_EXPORTS
+           "gsr_ply_pack_rows", "gsr_ply_unpack_rows", "gsr_count_nonfinite",
+           "gsr_bilateral_scratch_bytes", "gsr_bilateral_tv_scratch_bytes", "gsr_bilateral_slice_forward",
+           "gsr_bilateral_slice_backward", "gsr_bilateral_tv", "gsr_bilateral_adam_tail"] + POLICY_EXPORTS
 
 _lib = None
 
@@ -262,6 +264,16 @@ def load():
     lib.gsr_trainer_tail_step.argtypes = [i32, i32, i32, C.POINTER(TailGrads), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                           C.POINTER(f32), C.POINTER(C.c_uint32), f32, f32, f32, vp, vp, vp, vp]
     lib.gsr_backward_trainer_tail.argtypes = [vp, C.POINTER(Inputs), C.POINTER(CameraS), vp, C.POINTER(TailState), vp]
+    sz = C.c_size_t
+    lib.gsr_bilateral_scratch_bytes.argtypes = [i32] * 5
+    lib.gsr_bilateral_scratch_bytes.restype = sz
+    lib.gsr_bilateral_tv_scratch_bytes.argtypes = [i32]
+    lib.gsr_bilateral_tv_scratch_bytes.restype = sz
+    lib.gsr_bilateral_slice_forward.argtypes = [i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]
+    lib.gsr_bilateral_slice_backward.argtypes = [i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+    lib.gsr_bilateral_tv.argtypes = [i32, i32, i32, i32, vp, f32, vp, vp, vp, sz, vp]
+    lib.gsr_bilateral_adam_tail.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, i32, f32, f32, C.c_uint32, f32, f32, f32,
+                                            vp, vp, sz, vp]
     lib.gsr_stream_triad.argtypes = [vp, vp, vp, C.c_size_t, f32, vp]
     lib.gsr_ssim_precision.argtypes = [i32]
     lib.gsr_preprocess_form.argtypes = [i32]

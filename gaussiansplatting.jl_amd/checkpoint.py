@@ -144,7 +144,7 @@ def read_adam(opt, ckpt: Checkpoint, prefix: str, numel=None) -> None:
 
 
 def save_state(filename: str, gaussians, optimizers: Dict[str, object], step: int, strategy=None,
-               extra_meta: Optional[Dict[str, str]] = None) -> None:
+               extra_meta: Optional[Dict[str, str]] = None, bilateral_grid=None) -> None:
     """The Gaussian + optimizer part of `save_state` (training.jl:418-445).  `strategy` (a densification.DefaultStrategy):
     its split-noise position is added as two metadata scalars (`strategy.split_seed_base`, `strategy.split_rounds`) —
     keys the reference's reader never asks for, so the file stays a valid reference checkpoint; the reference itself draws
@@ -166,14 +166,21 @@ def save_state(filename: str, gaussians, optimizers: Dict[str, object], step: in
         for k in STRATEGY_STATS:
             if getattr(strategy, k, None) is not None:
                 tensors[f"strategy.{k}"] = _host(getattr(strategy, k))
+    if bilateral_grid is not None:
+        # training.jl:429-433: the grids with their Julia shape (gx, gy, gz, 12, n) and their NU.Adam
+        grids = _host(bilateral_grid.grids)
+        tensors["bilateral.grids"] = grids
+        write_adam(tensors, meta, "bilateral.opt", bilateral_grid.optimizer, shape=grids.shape)
     for k, v in (extra_meta or {}).items():
         meta[str(k)] = str(v)
     save_checkpoint(filename, tensors, meta)
 
 
-def load_state(filename: str, optimizers: Dict[str, object], strategy=None):
+def load_state(filename: str, optimizers: Dict[str, object], strategy=None, bilateral_grid=None):
     """Counterpart (training.jl:447-470): returns (GaussianModel, step); optimizers are filled in place, and so is
-    `strategy`'s split-noise position when the file carries one."""
+    `strategy`'s split-noise position when the file carries one.  `bilateral_grid` (a bilateral_grid.BilateralGrid): its
+    grids and optimizer are restored in place when the file has them (training.jl:452-459, `haskey` semantics: a file
+    without them leaves the grids as they are)."""
     ckpt = load_checkpoint(filename)
     g = read_gaussians(ckpt, "gaussians")
     for name in OPTIMIZER_NAMES:
@@ -189,4 +196,13 @@ def load_state(filename: str, optimizers: Dict[str, object], strategy=None):
                 raise ValueError(f"strategy.{k}: {host.size} entries for {n} Gaussians")
             cur = getattr(strategy, k)
             setattr(strategy, k, torch.from_numpy(np.ascontiguousarray(host)).to(cur.device if cur is not None else "cpu"))
+    if bilateral_grid is not None and "bilateral.grids" in ckpt:
+        import torch
+        host = ckpt.tensor("bilateral.grids")
+        cur = bilateral_grid.grids
+        if tuple(host.shape) != tuple(cur.shape):
+            raise ValueError(f"bilateral.grids: file shape {ckpt.raw_tensor('bilateral.grids').shape} does not match the "
+                             f"trainer's grids (Julia shape {tuple(reversed(tuple(cur.shape)))})")
+        cur.copy_(torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32)))
+        read_adam(bilateral_grid.optimizer, ckpt, "bilateral.opt", numel=int(host.size))
     return g, ckpt.read_scalar("step")

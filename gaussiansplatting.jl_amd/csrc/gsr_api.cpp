@@ -1340,6 +1340,105 @@ int gsr_gather_rows(const gsr_gather_group* groups, int32_t n_groups, const uint
     return GSR_OK;
 }
 
+// ---- bilateral grid (bilateral.hip; src/bilateral_grid.jl) ----
+namespace {
+constexpr int kBilateralMaxGz = 64;         // LDS of the pullback: gz x 4 waves x 48 floats
+constexpr int kBilateralMaxSlab = 16384;    // floats of one (image, coefficient) slab staged in LDS by the TV passes
+
+int check_bilateral_grid(int32_t gx, int32_t gy, int32_t gz) {
+    if (gx < 1 || gy < 1 || gz < 1) return fail(GSR_E_INVALID_ARG, "grid size (%d, %d, %d): every side must be >= 1", gx, gy, gz);
+    if (gz > kBilateralMaxGz) return fail(GSR_E_INVALID_ARG, "grid size (%d, %d, %d): gz must be <= %d", gx, gy, gz, kBilateralMaxGz);
+    if ((int64_t)gx * gy * gz > kBilateralMaxSlab)
+        return fail(GSR_E_INVALID_ARG, "grid size (%d, %d, %d): gx*gy*gz must be <= %d", gx, gy, gz, kBilateralMaxSlab);
+    return GSR_OK;
+}
+int check_bilateral_image(int32_t W, int32_t H, int32_t C) {
+    if (W < 1 || H < 1 || (int64_t)W * H > 0x7FFFFFFF) return fail(GSR_E_INVALID_ARG, "image size %d x %d", W, H);
+    if (C != 3 && C != 5 && C != 8) return fail(GSR_E_INVALID_ARG, "C = %d: the image has 3, 5 or 8 channels", C);
+    return GSR_OK;
+}
+// the constants of the TV prior, once, on the host: the standalone TV and the fused tail read the same floats
+gsr::BilateralTv bilateral_tv_consts(int32_t n, int32_t gx, int32_t gy, int32_t gz, float weight) {
+    gsr::BilateralTv tv;
+    tv.weight = weight;
+    tv.nx = (float)std::max<int64_t>(1, (int64_t)(gx - 1) * gy * gz);   // bilateral_grid.jl:115-117
+    tv.ny = (float)std::max<int64_t>(1, (int64_t)gx * (gy - 1) * gz);
+    tv.nz = (float)std::max<int64_t>(1, (int64_t)gx * gy * (gz - 1));
+    tv.n12 = 12.0f * (float)n;
+    tv.rx = 2.0f / (tv.nx * tv.n12);
+    tv.ry = 2.0f / (tv.ny * tv.n12);
+    tv.rz = 2.0f / (tv.nz * tv.n12);
+    return tv;
+}
+}  // namespace
+
+size_t gsr_bilateral_scratch_bytes(int32_t W, int32_t H, int32_t gx, int32_t gy, int32_t gz) {
+    if (W < 1 || H < 1 || gx < 1 || gy < 1 || gz < 1) return 0;
+    return gsr_bilateral_partial_bytes(W, H, gx, gy, gz);
+}
+
+size_t gsr_bilateral_tv_scratch_bytes(int32_t n_images) {
+    return n_images < 1 ? 0 : (size_t)n_images * 12 * 3 * sizeof(float);
+}
+
+int gsr_bilateral_slice_forward(int32_t W, int32_t H, int32_t C, const float* image, const float* grid, int32_t gx,
+                                int32_t gy, int32_t gz, float* out, void* stream) {
+    int rc;
+    if ((rc = check_bilateral_image(W, H, C)) || (rc = check_bilateral_grid(gx, gy, gz))) return rc;
+    if (!image || !grid || !out) return fail(GSR_E_INVALID_ARG, "null array");
+    gsr_launch_bilateral_fwd((hipStream_t)stream, W, H, C, image, grid, gx, gy, gz, out);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_bilateral_slice_backward(int32_t W, int32_t H, int32_t C, const float* image, const float* grid, int32_t gx,
+                                 int32_t gy, int32_t gz, const float* vout, float* vimage, float* vgrid, void* scratch,
+                                 size_t scratch_bytes, void* stream) {
+    int rc;
+    if ((rc = check_bilateral_image(W, H, C)) || (rc = check_bilateral_grid(gx, gy, gz))) return rc;
+    if (!image || !grid || !vout || !vimage || !vgrid || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
+    const size_t need = gsr_bilateral_scratch_bytes(W, H, gx, gy, gz);
+    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the pullback needs %zu", scratch_bytes, need);
+    gsr_launch_bilateral_bwd((hipStream_t)stream, W, H, C, image, grid, gx, gy, gz, vout, vimage, vgrid, (float*)scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_bilateral_tv(int32_t n_images, int32_t gx, int32_t gy, int32_t gz, const float* grids, float weight,
+                     float* loss_out, float* grad_out, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc;
+    if (n_images < 1) return fail(GSR_E_INVALID_ARG, "n_images = %d", n_images);
+    if ((rc = check_bilateral_grid(gx, gy, gz))) return rc;
+    if (!grids || !loss_out || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
+    const size_t need = gsr_bilateral_tv_scratch_bytes(n_images);
+    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the TV needs %zu", scratch_bytes, need);
+    gsr_launch_bilateral_tv((hipStream_t)stream, n_images, gx, gy, gz, grids, bilateral_tv_consts(n_images, gx, gy, gz, weight),
+                            loss_out, grad_out, (float*)scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_bilateral_adam_tail(int32_t n_images, int32_t gx, int32_t gy, int32_t gz, float* grids, float* mu, float* nu,
+                            const float* vgrid_view, int32_t view, float tv_weight, float lr, uint32_t current_step,
+                            float beta1, float beta2, float eps, float* tv_loss_out, void* scratch, size_t scratch_bytes,
+                            void* stream) {
+    int rc;
+    if (n_images < 1) return fail(GSR_E_INVALID_ARG, "n_images = %d", n_images);
+    if ((rc = check_bilateral_grid(gx, gy, gz))) return rc;
+    if (view < 0 || view >= n_images) return fail(GSR_E_INVALID_ARG, "view %d of %d images", view, n_images);
+    if (!grids || !mu || !nu || !vgrid_view || !tv_loss_out || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
+    if (current_step == 0) return fail(GSR_E_INVALID_ARG, "current_step counts from 1");
+    const size_t need = gsr_bilateral_tv_scratch_bytes(n_images);
+    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the tail needs %zu", scratch_bytes, need);
+    const float t = (float)current_step;
+    const float lr_t = lr * sqrtf(1.0f - powf(beta2, t)) / (1.0f - powf(beta1, t));  // as gsr_adam_step
+    const gsr::AdamHyper h{lr_t, beta1, beta2, 1.0f - beta1, 1.0f - beta2, eps};
+    gsr_launch_bilateral_adam_tail((hipStream_t)stream, n_images, gx, gy, gz, grids, mu, nu, vgrid_view, view,
+                                   bilateral_tv_consts(n_images, gx, gy, gz, tv_weight), h, tv_loss_out, (float*)scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
 int gsr_densify_grad_mean(int64_t n, const float* accum, const float* denom, float* grad_out, void* stream) {
     if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
     if (n == 0) return GSR_OK;

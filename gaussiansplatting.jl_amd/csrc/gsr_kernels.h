@@ -230,3 +230,22 @@ void gsr_launch_ply_rows(hipStream_t s, bool pack, long long n, int kr, float* p
 GSR_SSIM_DECL(exact)
 GSR_SSIM_DECL(fast)
 #undef GSR_SSIM_DECL
+
+// ---- bilateral.hip (compiled with -ffp-contract=off) ----
+namespace gsr {
+struct AdamHyper;
+// constants of the TV prior (bilateral_grid.jl:106-119), evaluated once on the host for every kernel that uses them:
+// term = weight · ((Sx/nx + Sy/ny) + Sz/nz) / n12, ∂term/∂θ = weight · ((tx·rx + ty·ry) + tz·rz)
+struct BilateralTv { float weight, nx, ny, nz, n12, rx, ry, rz; };
+}
+int gsr_bilateral_chunks(int W, int H, int gx, int gy);
+size_t gsr_bilateral_partial_bytes(int W, int H, int gx, int gy, int gz);
+void gsr_launch_bilateral_fwd(hipStream_t s, int W, int H, int C, const float* image, const float* grid, int gx, int gy,
+                              int gz, float* out);
+void gsr_launch_bilateral_bwd(hipStream_t s, int W, int H, int C, const float* image, const float* grid, int gx, int gy,
+                              int gz, const float* vout, float* vimage, float* vgrid, float* partial);
+void gsr_launch_bilateral_tv(hipStream_t s, int n, int gx, int gy, int gz, const float* grids, const gsr::BilateralTv& tv,
+                             float* loss_out, float* grad_out, float* partial);
+void gsr_launch_bilateral_adam_tail(hipStream_t s, int n, int gx, int gy, int gz, float* grids, float* mu, float* nu,
+                                    const float* vgrid, int view, const gsr::BilateralTv& tv, const gsr::AdamHyper& h,
+                                    float* tv_loss_out, float* partial);

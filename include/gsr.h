@@ -585,6 +585,46 @@ GSR_API int gsr_ply_pack_rows(int64_t n, int32_t k_rest, const float* points, co
 GSR_API int gsr_ply_unpack_rows(int64_t n, int32_t k_rest, const float* rows, float* points, float* features_dc,
                                 float* features_rest, float* opacities, float* scales, float* rotations, void* stream);
 
+/* Bilateral grid appearance correction (src/bilateral_grid.jl; switched on by `use_bilateral_grid`, src/utils.jl:56-63;
+ * used by `step!`, training.jl:676-681,703-706,784-790).  Each training image owns a (gx,gy,gz,12) grid of 3x4 affine
+ * colour transforms, coefficient (d-1)*4 + c mapping input channel c (r, g, b, 1) to output channel d; all grids of a
+ * trainer are one (gx,gy,gz,12,n) array.  Images are (C,W,H), C = 3, 5 or 8 (the rasterizer's modes).  All pointers
+ * device, all sizes >= 1.  Every entry point refuses gz > 64 (the pullback's LDS) and gx*gy*gz > 16384 (the TV and
+ * the Adam tail stage one grid slab in 64 KiB of LDS; one limit for all four, so any grid they accept works with all
+ * of them).  Every result is run-to-run bit-identical: no float atomics anywhere.
+ *
+ * gsr_bilateral_slice_forward  : `bilateral_slice(image, grid)` (bilateral_grid.jl:75-85,152-175): channels 0-2 of
+ *                                `out` get the corrected rgb, channels >= 3 are copied, so `out` can go to
+ *                                gsr_loss_l1_ssim in place of the render.
+ * gsr_bilateral_slice_backward : its pullback (bilateral_grid.jl:87-100,177-242).  vout: the cotangent of `out`;
+ *                                vimage (may be vout: in place) gets ∇image, channels >= 3 the cotangent unchanged — the
+ *                                loss head's buffer stays valid for GSR_GRADS_COLOR_COTANGENT; vgrid (gx,gy,gz,12) gets
+ *                                the FULL ∇grid of the view (overwritten).  scratch: gsr_bilateral_scratch_bytes(W, H,
+ *                                gx, gy, gz) bytes.
+ * gsr_bilateral_tv             : weight · tv_loss(grids) (bilateral_grid.jl:102-119) into *loss_out (device) and,
+ *                                unless grad_out is NULL, weight · ∇tv_loss into grad_out (gx,gy,gz,12,n).  scratch:
+ *                                gsr_bilateral_tv_scratch_bytes(n_images) bytes.
+ * gsr_bilateral_adam_tail      : `NU.step!(bgrid.optimizer, bgrid.grids, ∇grids)` (training.jl:784-790) where ∇grids =
+ *                                tv_weight · ∇tv_loss(grids) + the slice gradient `vgrid_view` of view `view` (0-based),
+ *                                in one pass over all grids; *tv_loss_out (device) = tv_weight · tv_loss of the grids
+ *                                BEFORE the update (the TV term of the step's loss, training.jl:703-706).  θ, μ, ν
+ *                                bit-identical to gsr_bilateral_tv (gradient) + adding vgrid_view to view `view` +
+ *                                gsr_adam_step.  current_step counts from 1 (after the increment).  scratch:
+ *                                gsr_bilateral_tv_scratch_bytes(n_images) bytes. */
+GSR_API size_t gsr_bilateral_scratch_bytes(int32_t W, int32_t H, int32_t gx, int32_t gy, int32_t gz);
+GSR_API size_t gsr_bilateral_tv_scratch_bytes(int32_t n_images);
+GSR_API int gsr_bilateral_slice_forward(int32_t W, int32_t H, int32_t C, const float* image, const float* grid, int32_t gx,
+                                        int32_t gy, int32_t gz, float* out, void* stream);
+GSR_API int gsr_bilateral_slice_backward(int32_t W, int32_t H, int32_t C, const float* image, const float* grid, int32_t gx,
+                                         int32_t gy, int32_t gz, const float* vout, float* vimage, float* vgrid,
+                                         void* scratch, size_t scratch_bytes, void* stream);
+GSR_API int gsr_bilateral_tv(int32_t n_images, int32_t gx, int32_t gy, int32_t gz, const float* grids, float weight,
+                             float* loss_out, float* grad_out, void* scratch, size_t scratch_bytes, void* stream);
+GSR_API int gsr_bilateral_adam_tail(int32_t n_images, int32_t gx, int32_t gy, int32_t gz, float* grids, float* mu, float* nu,
+                                    const float* vgrid_view, int32_t view, float tv_weight, float lr, uint32_t current_step,
+                                    float beta1, float beta2, float eps, float* tv_loss_out, void* scratch,
+                                    size_t scratch_bytes, void* stream);
+
 /* New: the SH-coefficient gradient of a batch of views from the factored
  * per-view colour cotangents written by gsr_backward (gsr_grads.vcolors):
  *   vshs[:, k, i] = Σ_v basis_k(normalize(means[:, i] - camera_centers[:, v])) * vcolors_all[:, i, v]

@@ -371,4 +371,56 @@ function backward_trainer_tail!(rast::GaussianRasterizer, vpixels, θ::NTuple{6}
     foreach(o -> o.current_step += 0x1, opts)
 end
 
+# ---- bilateral grid (src/bilateral_grid.jl) ----
+
+# bilateral_slice(image, grid) (bilateral_grid.jl:75-85) on gsr_bilateral_slice_forward: a method for device arrays, so
+# `step!` (training.jl:679-681) reaches it unchanged.  Channels >= 3 of a (C,W,H) image are copied.
+function GaussianSplatting.bilateral_slice(image::ROCArray{Float32, 3}, grid::ROCArray{Float32, 4})
+    out = similar(image)
+    check(ccall((:gsr_bilateral_slice_forward, LIB), Cint,
+        (Int32, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Int32, Ptr{Float32}, Ptr{Cvoid}),
+        size(image, 2), size(image, 3), size(image, 1), dptr(image), dptr(grid), size(grid, 1), size(grid, 2), size(grid, 3),
+        dptr(out), hipstream()))
+    return out
+end
+
+# its rrule (bilateral_grid.jl:87-100) on gsr_bilateral_slice_backward: no float atomics, run-to-run bit-identical ∇grid
+function ChainRulesCore.rrule(::typeof(GaussianSplatting.bilateral_slice), image::ROCArray{Float32, 3},
+        grid::ROCArray{Float32, 4})
+    out = GaussianSplatting.bilateral_slice(image, grid)
+    function _bilateral_slice_pullback(Δ)
+        vout = ROCArray{Float32}(unthunk(Δ))
+        ∇image = similar(image); ∇grid = similar(grid)
+        w, h, gx, gy, gz = size(image, 2), size(image, 3), size(grid, 1), size(grid, 2), size(grid, 3)
+        nb = ccall((:gsr_bilateral_scratch_bytes, LIB), Csize_t, (Int32, Int32, Int32, Int32, Int32), w, h, gx, gy, gz)
+        scratch = AMDGPU.zeros(UInt8, max(Int(nb), 1))
+        check(ccall((:gsr_bilateral_slice_backward, LIB), Cint,
+            (Int32, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32},
+             Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+            w, h, size(image, 1), dptr(image), dptr(grid), gx, gy, gz, dptr(vout), dptr(∇image), dptr(∇grid),
+            Ptr{Cvoid}(UInt(pointer(scratch))), Csize_t(length(scratch)), hipstream()))
+        return NoTangent(), ∇image, ∇grid
+    end
+    return out, _bilateral_slice_pullback
+end
+
+# Optional (callers opt in): `NU.step!(bgrid.optimizer, bgrid.grids, ∇grids)` (training.jl:784-790) with ∇grids =
+# tv_weight·∇tv_loss + the view's slice gradient `∇grid_view`, in one pass (gsr_bilateral_adam_tail); returns the device
+# scalar tv_weight·tv_loss of the grids before the update (the `tv_term` of training.jl:704-705).  `view` is 1-based.
+function bilateral_adam_tail!(bgrid, ∇grid_view, view::Integer; tv_weight::Float32 = 10f0, β1=0.9f0, β2=0.999f0, ϵ=1f-15)
+    grids, opt = bgrid.grids, bgrid.optimizer
+    gx, gy, gz, _, n = size(grids)
+    tv = AMDGPU.zeros(Float32, 1)
+    nb = ccall((:gsr_bilateral_tv_scratch_bytes, LIB), Csize_t, (Int32,), n)
+    scratch = AMDGPU.zeros(UInt8, max(Int(nb), 1))
+    check(ccall((:gsr_bilateral_adam_tail, LIB), Cint,
+        (Int32, Int32, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int32, Cfloat, Cfloat, UInt32,
+         Cfloat, Cfloat, Cfloat, Ptr{Float32}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        n, gx, gy, gz, dptr(grids), dptr(opt.μ[1]), dptr(opt.ν[1]), dptr(∇grid_view), view - 1, tv_weight, Float32(opt.lr),
+        UInt32(opt.current_step + 0x1), β1, β2, ϵ, dptr(tv), Ptr{Cvoid}(UInt(pointer(scratch))), Csize_t(length(scratch)),
+        hipstream()))
+    opt.current_step += 0x1
+    return tv
+end
+
 end # module
