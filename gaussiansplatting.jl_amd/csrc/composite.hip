@@ -327,13 +327,6 @@ template <int C> struct AccRow { static constexpr int N = C == 3 ? 9 : (C == 5 ?
 #ifndef GSR_BWD_MINWAVES
 #define GSR_BWD_MINWAVES 1
 #endif
-#ifndef GSR_BWD_BATCH
-#define GSR_BWD_BATCH 64
-#endif
-#ifndef GSR_BWD_PPL
-#define GSR_BWD_PPL 4
-#endif
-constexpr int BWD_BATCH = GSR_BWD_BATCH;  // splats staged per round (LDS: one accumulator slab per wave)
 
 // ACC — the backward's per-pixel arithmetic in its ACCURATE form (round 6; gsr_config.grad_precision = GSR_GRAD_ACCURATE /
 // GSR_GRAD_FP32_REFERENCE): libm-accurate expf instead of v_exp_f32 on the rounded product sigma x log2(e), IEEE division
@@ -348,15 +341,42 @@ constexpr int BWD_BATCH = GSR_BWD_BATCH;  // splats staged per round (LDS: one a
 template <bool ACC> __device__ __forceinline__ float bwd_exp_neg(float sigma) { return ACC ? expf(-sigma) : __expf(-sigma); }
 template <bool ACC> __device__ __forceinline__ float bwd_rcp(float x) { return ACC ? __fdiv_rn(1.0f, x) : __builtin_amdgcn_rcpf(x); }
 
-// PPL = pixels per lane.  PPL == 1: 4 waves per tile, a wave owns a 16x4 strip.  PPL == 2:
-// 2 waves per tile, a wave owns 16x8 pixels and lane l the pixels (x, y) and (x, y+4).
-// PPL == 4 (default): ONE wave64 per tile, lane l owns (x, y), (x, y+4), (x, y+8), (x, y+12).
-// The LDS reads, the cross-lane reduction and the row store — ~60 % of the instructions of a
-// visited (strip, splat) pair — are paid once for 2x / 4x the pixels (measured at config 3:
-// 1.115 / 0.975 / 0.917 ms for PPL = 1 / 2 / 4).
-// LISTED: the tiles of one tier list of the scan (lists longer than GSR_BWD_SPLIT_LEN) — launched with PPL = 1, four
-// waves per tile on a second stream next to the main PPL = 4 launch, which leaves those tiles out: one wave walking a
-// list of 30 k instances is milliseconds long (real captures have such tiles; config 3 has none).
+// Both backward kernels — composite_bwd_kernel (a whole tile list) and composite_bwd_long_kernel (one segment of a long
+// list) — walk with ONE wave64 for all 256 pixels of a tile: lane l owns (x, y), (x, y+4), (x, y+8), (x, y+12).  The LDS
+// reads, the cross-lane reduction and the row store — ~60 % of the instructions of a visited (pixels, splat) pair — are
+// then paid once for four pixels (measured at config 3: 1.115 / 0.975 / 0.917 ms for one / two / four pixels per lane).
+
+// One 64-byte (:rgb 48-byte) gradient row per instance from its reduced sums r, plain stores, written for EVERY emitted
+// instance exactly once per backward (zeros when no pixel touched it), so the row buffer needs no memset; the per-Gaussian
+// kernel sums a Gaussian's rows in a fixed order — no fp32 atomics (35 M per view before), bit-reproducible gradients.
+// a, b: planes 0 and 1 of the instance's stream entry; slot: its Gaussian-major row slot (uint bits).
+template <int C, int VC>
+__device__ __forceinline__ void bwd_store_row(float4* rows, const float4 a, const float4 b, float slot,
+                                              const float (&r)[AccRow<VC>::N]) {
+    constexpr int NA = AccRow<VC>::N;
+    const float mo = -b.y, mh = -0.5f * b.y;  // vσ = -o·G·vα (render.jl:260)
+    float4* row = rows + (size_t)GSR_ROW_F4(C) * __float_as_uint(slot);
+    row[0] = make_float4(r[0], r[1], r[2], r[3]);
+    row[1] = make_float4(mh * r[4], mh * r[5], mh * r[6], VC > 3 ? r[9 < NA ? 9 : 0] : 0.0f);
+    // conic a = 2·ha, c = 2·hc (the stream carries the halves)
+    row[2] = make_float4(mo * (2.0f * a.z * r[7] + a.w * r[8]), mo * (a.w * r[7] + 2.0f * b.x * r[8]),
+                         VC > 5 ? r[10 < NA ? 10 : 0] : 0.0f, VC > 5 ? r[11 < NA ? 11 : 0] : 0.0f);
+    if (C > 5) row[3] = make_float4(VC > 5 ? r[12 < NA ? 12 : 0] : 0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// Instances behind every pixel's last contributor are never staged: their rows are zero.  The wave's lanes take list
+// positions p, p + 64, ... up to end.
+template <int C>
+__device__ __forceinline__ void bwd_zero_rows(float4* rows, const GsrStream stream, uint32_t p, uint32_t end) {
+    for (; p < end; p += 64) {
+        float4* row = rows + (size_t)GSR_ROW_F4(C) * __float_as_uint(stream.s2[p].y);
+        const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        row[0] = z; row[1] = z; row[2] = z;
+        if (C > 5) row[3] = z;
+    }
+}
+
+// The backward of a tile whose list is at most tiers.split_len long (the longer ones are composite_bwd_long_kernel's).
 // BG0: the background is exactly (0, 0, 0) — the reference's default (rasterizer.jl:209) and what a trainer without a sky
 // colour passes: the term -T_final/(1-α)·(bg·v) (render.jl:259) vanishes identically, and with it the per-pixel bgT state and
 // one FMA per active visit.  WHO LAUNCHES WHAT (gsr_launch_composite_bwd, below; measured in
@@ -367,13 +387,13 @@ template <bool ACC> __device__ __forceinline__ float bwd_rcp(float x) { return A
 //                    visit less, 0.720 -> 0.713 ms — launched whenever the background is zero (with the coordinates rebuilt it
 //                    reaches 80 VGPRs = six waves and is 6 % SLOWER: 0.724 -> 0.770 ms);
 //   C == 3 (:rgb)  : NEVER the BG0 kernel (74 -> 70 VGPRs = seven waves: 0.659 -> 0.676 ms; round 3's forced-occupancy probes:
-//                    789 / 735 / 677 / 695 us at 4 / 5 / 6 / 7 waves) — <3, PPL, false, true> is not instantiated.
+//                    789 / 735 / 677 / 695 us at 4 / 5 / 6 / 7 waves) — <3, true> is not instantiated.
 // VC: channels of the pixel cotangent that can be non-zero.  VC == 3 < C (the cotangent comes from the photometric loss head, which
 // only sees features[1:3] — training.jl:656,684-685: depth / alpha / normal channels of vpixels are exact zeros and their feature
 // gradients too): the pixels' cotangent state, the colour·v dot product and the reduction are the :rgb kernel's; the stream, the
 // blend thresholds and the row layout stay the mode's.
-template <int C, int PPL, bool LISTED, bool BG0, int VC = C, bool ACC = false>
-__global__ __launch_bounds__(256 / PPL, GSR_BWD_MINWAVES) void composite_bwd_kernel(int W, int H, int grid_x,
+template <int C, bool BG0, int VC = C, bool ACC = false>
+__global__ __launch_bounds__(64, GSR_BWD_MINWAVES) void composite_bwd_kernel(int W, int H, int grid_x,
                                                                 const uint32_t* __restrict__ tile_start,
                                                                 const uint32_t* __restrict__ tile_order,
                                                                 GsrStream stream, Bg bg,
@@ -383,10 +403,10 @@ __global__ __launch_bounds__(256 / PPL, GSR_BWD_MINWAVES) void composite_bwd_ker
                                                                 GsrTierLists tiers) {
     static_assert(VC == C || VC == 3, "all channels, or colour only");
     constexpr int NA = AccRow<VC>::N, ST = AccRow<VC>::STRIDE;
-    constexpr int BB = BWD_BATCH, NT = 256 / PPL, NW = NT / 64, ROWS = 4 * PPL;
-    // the long tiles are the critical path of the step and share their SIMDs with the main launch's waves: issue priority
-    if (LISTED) __builtin_amdgcn_s_setprio(3);
-    static_assert(BB <= NT && BB % 64 == 0, "one staging thread per splat");
+    // one wave64 per tile, four pixels per lane, 64 splats staged per batch.  (The wave index, the per-wave slab and mask
+    // and the batch loop over 64-entry ballots stay written out for a general NW: folding NW = 1 into them changes the
+    // register allocation of every instantiation, one to two VGPRs, and :rgb's would cross from six to seven waves.)
+    constexpr int PPL = 4, BB = 64, NT = 64, NW = NT / 64, ROWS = 4 * PPL;
     __shared__ float4 l0[BB], l1[BB], l2[BB];
     __shared__ float4 l3[C > 3 ? BB : 1];
     // One accumulator slab per wave: a wave stores its reduced partials with plain ds_write
@@ -400,34 +420,21 @@ __global__ __launch_bounds__(256 / PPL, GSR_BWD_MINWAVES) void composite_bwd_ker
     const gsr::LaneBits lane_bits(lane);
     const int red_slot = gsr::wave_reduce_index<NA>(lane);  // which partial this lane ends up holding
     const bool red_writer = gsr::wave_reduce_writer(lane);
-#ifdef GSR_BWD_MFMA
-    const gsr::RowColConstsM rowcol(lane);
-#else
     const gsr::RowColConsts rowcol(lane);
-#endif
     const gsr::RowColConstsD rowcol_d(lane);
-    // main launch: 1-D grid in launch order, longest lists first; LISTED: the scan's three tier lists back to back,
-    // longest tier first
-    int tile;
-    if (LISTED) {
-        uint32_t b = blockIdx.x;
-        const uint32_t* list = tiers.lists;                                              // lists > 8192
-        if (b >= tiers.n_big) { b -= tiers.n_big; list = tiers.lists + tiers.n_tiles;    // (4096, 8192]
-            if (b >= tiers.n_mid8) { b -= tiers.n_mid8; list = tiers.lists + 2 * (size_t)tiers.n_tiles; } }  // (1024, 4096]
-        tile = (int)list[b];
-    } else tile = (int)tile_order[blockIdx.x];
+    const int tile = (int)tile_order[blockIdx.x];  // 1-D grid in launch order, longest lists first
     const int tile_x = tile % grid_x, tile_y = tile / grid_x;
     const int px = tile_x * GSR_TILE + (lane & 15);
     const int py0 = tile_y * GSR_TILE + ROWS * wave + (lane >> 4);
     const float fx = (float)px;
     const uint32_t start = tile_start[tile], end = tile_start[tile + 1];
     if (end == start) return;
-    if (!LISTED && end - start > tiers.split_len) return;  // the four-wave launch over the tier lists owns this tile
+    if (end - start > tiers.split_len) return;  // composite_bwd_long_kernel owns this tile
 
-    // per-pixel state (PPL pixels per lane: rows py0 and py0 + 4)
+    // per-pixel state (rows py0, py0 + 4, py0 + 8, py0 + 12)
     // (:rgbdn: the rows' y coordinates are rebuilt from the first one — fy0 + 4q, exact in fp32, so dy and sigma keep their
     //  bits — instead of living in PPL registers: one more add per visited group, three registers less)
-    constexpr bool FY_REBUILD = C > 5 && PPL > 1;
+    constexpr bool FY_REBUILD = C > 5;
     float fy[FY_REBUILD ? 1 : PPL], T[PPL], A[PPL], bgT[BG0 ? 1 : PPL], vp[PPL][VC];
     int last_contributor[PPL];
     int wave_last = 0;  // deepest list position any pixel of this wave blended
@@ -513,17 +520,13 @@ __global__ __launch_bounds__(256 / PPL, GSR_BWD_MINWAVES) void composite_bwd_ker
 #pragma unroll
             for (int c = 0; c < VC; c++) col[c] = 0.0f;
             unsigned long long any_active = 0ull;
-#ifndef GSR_BWD_NO_ROW_SKIP
             const uint32_t rowbits = __builtin_amdgcn_readfirstlane(__float_as_uint(c2.w)) >> (ROWS * wave);
-#endif
 #pragma unroll
             for (int q = 0; q < PPL; q++) {
-#ifndef GSR_BWD_NO_ROW_SKIP
                 // pixel rows 4q..4q+3 of this wave: untouched by the splat's footprint -> wave-uniform skip
                 // (readfirstlane of the already-uniform bits: tells the compiler that this branch, and everything that
                 // merges behind it — the ballot accumulator —, is scalar; without it the test and `any_active` were VALU)
-                if (PPL > 1 && __builtin_amdgcn_readfirstlane((int)((rowbits >> (4 * q)) & 0xFu)) == 0) continue;
-#endif
+                if (__builtin_amdgcn_readfirstlane((int)((rowbits >> (4 * q)) & 0xFu)) == 0) continue;
                 const float fyq = FY_REBUILD ? fy[0] + (float)(4 * q) : fy[FY_REBUILD ? 0 : q];
                 const float dy = a.y - fyq, dy2 = __fmul_rn(dy, dy);
                 const float sigma = sigma_of(sx, b.x, dy, dy2);
@@ -567,11 +570,7 @@ __global__ __launch_bounds__(256 / PPL, GSR_BWD_MINWAVES) void composite_bwd_ker
             if (VC == 3) {
                 // :rgb — reduce {P, U1, U2, rgb} over the 4 lanes of each pixel column first, apply the
                 // column's dx weights, then finish over the 16 columns (wave_reduce.h: 5 swaps, not 8)
-#ifdef GSR_BWD_MFMA
-                const float total = gsr::wave_reduce_rowcol_rgb_mfma(P, U1, U2, col[0], col[1], col[2], dx, lane_bits, rowcol);
-#else
                 const float total = gsr::wave_reduce_rowcol_rgb(P, U1, U2, col[0], col[1], col[2], dx, lane_bits, rowcol);
-#endif
                 if (rowcol.slot >= 0) my_row[rowcol.slot] = total;
             } else if (C == 5) {
                 // :rgbd (the reference's default training mode): the same row-then-column scheme with the depth sum
@@ -594,8 +593,8 @@ __global__ __launch_bounds__(256 / PPL, GSR_BWD_MINWAVES) void composite_bwd_ker
                 if (VC > 5) { part[10] = col[VC > 5 ? 5 : 0]; part[11] = col[VC > 5 ? 6 : 0]; part[12] = col[VC > 5 ? 7 : 0]; }
                 // transposed wave64 reduction: ~3·NA/2 + 6 VALU ops, then ONE ds_write for all NA sums
                 const float total = gsr::wave_reduce_transposed<NA>(part, lane_bits);
-                // (storing the sums straight into the global row when NW == 1 measured 3 % slower than
-                // the LDS slab + coalesced 64-byte row stores below)
+                // (storing the sums straight into the global row measured 3 % slower than the LDS slab + the
+                // coalesced row stores of the flush)
                 if (red_writer) my_row[red_slot] = total;
             }
           }
@@ -609,40 +608,17 @@ __global__ __launch_bounds__(256 / PPL, GSR_BWD_MINWAVES) void composite_bwd_ker
             float r[NA];
 #pragma unroll
             for (int k = 0; k < NA; k++) r[k] = 0.0f;
-            bool any = false;
 #pragma unroll
             for (int w = 0; w < NW; w++) {
                 if ((lmask[w][tid >> 6] >> (tid & 63)) & 1ull) {
-                    any = true;
 #pragma unroll
                     for (int k = 0; k < NA; k++) r[k] += lacc[w][tid * ST + k];
                 }
             }
-            (void)any;
-            {
-                // one 64-byte gradient row per instance, plain stores, written for EVERY emitted
-                // instance exactly once per backward (zeros when no pixel touched it), so the row
-                // buffer needs no memset; the per-Gaussian kernel sums a Gaussian's rows in a fixed
-                // order — no fp32 atomics (35 M per view before), bit-reproducible gradients
-                const float4 a = l0[tid], b = l1[tid];
-                const float mo = -b.y, mh = -0.5f * b.y;  // vσ = -o·G·vα (render.jl:260)
-                float4* row = inst.rows + (size_t)GSR_ROW_F4(C) * __float_as_uint(l2[tid].w);  // Gaussian-major slot
-                row[0] = make_float4(r[0], r[1], r[2], r[3]);
-                row[1] = make_float4(mh * r[4], mh * r[5], mh * r[6], VC > 3 ? r[9 < NA ? 9 : 0] : 0.0f);
-                // conic a = 2·ha, c = 2·hc (the stream carries the halves)
-                row[2] = make_float4(mo * (2.0f * a.z * r[7] + a.w * r[8]), mo * (a.w * r[7] + 2.0f * b.x * r[8]),
-                                     VC > 5 ? r[10 < NA ? 10 : 0] : 0.0f, VC > 5 ? r[11 < NA ? 11 : 0] : 0.0f);
-                if (C > 5) row[3] = make_float4(VC > 5 ? r[12 < NA ? 12 : 0] : 0.0f, 0.0f, 0.0f, 0.0f);
-            }
+            bwd_store_row<C, VC>(inst.rows, l0[tid], l1[tid], l2[tid].w, r);
         }
     }
-    // instances behind every pixel's last contributor were never staged: their rows are zero
-    for (uint32_t p = start + (uint32_t)tile_last + tid; p < end; p += NT) {
-        float4* row = inst.rows + (size_t)GSR_ROW_F4(C) * __float_as_uint(stream.s2[p].y);
-        const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        row[0] = z; row[1] = z; row[2] = z;
-        if (C > 5) row[3] = z;
-    }
+    bwd_zero_rows<C>(inst.rows, stream, start + (uint32_t)tile_last + tid, end);
 }
 
 // ---------------------------------------------------------------------------------
@@ -650,7 +626,7 @@ __global__ __launch_bounds__(256 / PPL, GSR_BWD_MINWAVES) void composite_bwd_ker
 // ---------------------------------------------------------------------------------
 // A list of tens of thousands of instances is serial for whoever walks it: the hot-tile scene's critical path was ONE wave of
 // a neighbour of the hot tile visiting 15 000 entries that touch its 16x4 strip (profiles/r05/experiments/long_tiles.txt) —
-// more waves per tile by PIXELS (the PPL = 1 kernel above, four strips) do not help where one strip takes all the visits, and
+// more waves per tile by PIXELS (round 2's four 16x4 strips per tile) do not help where one strip takes all the visits, and
 // more waves in ONE workgroup stop at the four SIMDs of its CU (eight segment waves in one workgroup: 1.77 -> 1.24 ms only).
 // Here a tile's list is cut into up to LONG_SEGS SEGMENTS, each walked by its own single-wave workgroup anywhere on the chip:
 // a wave owns a contiguous run of list positions and ALL 256 pixels (four per lane, the main kernel's layout: row-then-column
@@ -731,15 +707,7 @@ __global__ __launch_bounds__(64) void composite_bwd_long_kernel(int W, int H, in
     const int seg = (((tile_last + LONG_SEGS - 1) / LONG_SEGS) + 63) & ~63;
     const int hi = tile_last - g * seg, lo = max(0, hi - seg);
     float2* const st_tile = state + (size_t)listed * LONG_SEGS * 256;
-    if (PASS == 2 && g == 0) {
-        // instances behind every pixel's last contributor are never staged: their rows are zero (once per tile)
-        for (uint32_t p = start + (uint32_t)tile_last + lane; p < end; p += 64) {
-            float4* row = inst.rows + (size_t)GSR_ROW_F4(C) * __float_as_uint(stream.s2[p].y);
-            const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            row[0] = z; row[1] = z; row[2] = z;
-            if (C > 5) row[3] = z;
-        }
-    }
+    if (PASS == 2 && g == 0) bwd_zero_rows<C>(inst.rows, stream, start + (uint32_t)tile_last + lane, end);  // once per tile
     if (hi <= 0) {  // an empty segment (a list shorter than LONG_SEGS batches): the identity
         if (PASS == 1) {
 #pragma unroll
@@ -819,7 +787,7 @@ __global__ __launch_bounds__(64) void composite_bwd_long_kernel(int W, int H, in
             A[q] = mc.x * A[q] + mc.y;
         }
     }
-    // ---- the gradient walk of the segment (the main kernel's body: one wave = the whole tile) ----
+    // ---- the gradient walk of the segment (the main kernel's arithmetic, ACC = false: one wave = the whole tile) ----
     for (int top = hi; top > lo; top -= 64) {
         const int cnt = min(64, top - lo);
         unsigned long long wl = stage(top, cnt);
@@ -904,14 +872,7 @@ __global__ __launch_bounds__(64) void composite_bwd_long_kernel(int W, int H, in
             const bool hit = (touched >> lane) & 1ull;
 #pragma unroll
             for (int k = 0; k < NA; k++) r[k] = hit ? my[lane * ST + k] : 0.0f;
-            const float4 a = l0[lane], b = l1[lane];
-            const float mo = -b.y, mh = -0.5f * b.y;
-            float4* row = inst.rows + (size_t)GSR_ROW_F4(C) * __float_as_uint(l2[lane].w);
-            row[0] = make_float4(r[0], r[1], r[2], r[3]);
-            row[1] = make_float4(mh * r[4], mh * r[5], mh * r[6], C > 3 ? r[9 < NA ? 9 : 0] : 0.0f);
-            row[2] = make_float4(mo * (2.0f * a.z * r[7] + a.w * r[8]), mo * (a.w * r[7] + 2.0f * b.x * r[8]),
-                                 C > 5 ? r[10 < NA ? 10 : 0] : 0.0f, C > 5 ? r[11 < NA ? 11 : 0] : 0.0f);
-            if (C > 5) row[3] = make_float4(r[12 < NA ? 12 : 0], 0.0f, 0.0f, 0.0f);
+            bwd_store_row<C, C>(inst.rows, l0[lane], l1[lane], l2[lane].w, r);
         }
     }
 }
@@ -978,13 +939,13 @@ void gsr_launch_composite_bwd(hipStream_t s, int channels, GsrCam cam, const uin
                               const uint32_t* tile_order, GsrStream stream, const float* background,
                               const float* vpixels, const uint32_t* n_contrib, const float* final_T, GsrInst inst,
                               uint32_t split_len, bool color_only, bool accurate) {
-    dim3 grid(cam.grid_x * cam.grid_y), block(256 / GSR_BWD_PPL);
+    dim3 grid(cam.grid_x * cam.grid_y), block(64);
     Bg bg = make_bg(background, channels);
     GsrTierLists none{};
     none.split_len = split_len;
     const bool bg0 = bg_is_zero(bg);
 #define LAUNCH_K(CC, ZZ, VV, AA)                                                                                       \
-    hipLaunchKernelGGL((composite_bwd_kernel<CC, GSR_BWD_PPL, false, ZZ, VV, AA>), grid, block, 0, s, cam.width, cam.height, \
+    hipLaunchKernelGGL((composite_bwd_kernel<CC, ZZ, VV, AA>), grid, block, 0, s, cam.width, cam.height,               \
                        cam.grid_x, tile_start, tile_order, stream, bg, vpixels, n_contrib, final_T, inst, none)
     // accurate: the ACC instantiations (libm exp, IEEE division: gsr_config.grad_precision) — the general-background kernels only
 #define LAUNCH2(CC, ZZ) do { if (accurate) LAUNCH_K(CC, false, CC, true); else LAUNCH_K(CC, ZZ, CC, false); } while (0)
@@ -1013,19 +974,6 @@ void gsr_launch_composite_bwd_listed(hipStream_t s, int channels, GsrCam cam, co
     const uint32_t n_listed = tiers.n_big + tiers.n_mid8 + tiers.n_mid4;
     if (n_listed == 0) return;
     Bg bg = make_bg(background, channels);
-    // GSR_BWD_LONG=0: round 4's form (four waves per tile by pixel strips) for A/B runs; default: the list split along its length
-    static const bool by_strips = [] { const char* e = getenv("GSR_BWD_LONG"); return e && e[0] == '0'; }();
-    if (by_strips) {
-        dim3 grid(n_listed), block(256);
-#define LAUNCH(CC)                                                                                                 \
-        hipLaunchKernelGGL((composite_bwd_kernel<CC, 1, true, false>), grid, block, 0, s, cam.width, cam.height, cam.grid_x,  \
-                           tile_start, (const uint32_t*)nullptr, stream, bg, vpixels, n_contrib, final_T, inst, tiers)
-        if (channels == 3) LAUNCH(3);
-        else if (channels == 5) LAUNCH(5);
-        else LAUNCH(8);
-#undef LAUNCH
-        return;
-    }
     dim3 grid(n_listed * LONG_SEGS), block(64);
     const bool bg0 = bg_is_zero(bg);
     float2* st = reinterpret_cast<float2*>(long_state);

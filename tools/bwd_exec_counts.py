@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Execution counts of composite_bwd_kernel<3, 4, false>'s code paths on ONE view (default: config 3), measured from the
+"""Execution counts of composite_bwd_kernel<3, false>'s code paths on ONE view (default: config 3), measured from the
 library's own lists on the GPU box (torch is only the calculator): how many instances the back-to-front walk stages,
 how many survive the row-mask ballot, how many 16x4 pixel groups they visit, in how many of those at least one lane is
 active (the `if (active)` block runs), how many instances reach the wave reduction, how many flush rows are written.

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Instruction budget of composite_bwd_kernel<3, 4, false> from its ISA (round-2 verdict item 4-i).
+"""Instruction budget of composite_bwd_kernel<3, false> from its ISA (round-2 verdict item 4-i).
 
 Compiles composite.hip to an ISA listing exactly as the Makefile does (hipcc -S --cuda-device-only, same flags), splits the
 kernel into basic blocks (tools/isa_loop.py), assigns every block a ROLE from its content and position, multiplies its VALU
@@ -36,7 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from isa_loop import blocks, cost  # noqa: E402
 
-KERNEL = "composite_bwd_kernelILi3ELi4ELb0ELb0E"  # <C = 3, PPL = 4, LISTED = false, BG0 = false>: the kernel the :rgb launch takes
+KERNEL = "composite_bwd_kernelILi3ELb0ELi3ELb0E"  # <C = 3, BG0 = false, VC = 3, ACC = false>: the kernel the :rgb launch takes
 N_SIMD = 1024
 
 
