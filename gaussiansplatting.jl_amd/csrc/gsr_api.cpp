@@ -44,10 +44,24 @@ int fail(int code, const char* fmt, ...) {
                         hipGetErrorString(e_), __FILE__, __LINE__);                                          \
     } while (0)
 
+// GSR_DEBUG_FILL=nan | big (debugging, read at every allocation): each new allocation of a buffer marked `fill_ok` is filled
+// with the 32-bit word 0xFFFFFFFF (a NaN) or 0x7F7F7F7F (3.4e38, finite: NaN hides behind comparisons), so that a kernel
+// that reads a float it never wrote shows up in the result instead of reading the zeros of fresh pages.  0 = unset.
+uint32_t debug_fill_word() {
+    const char* e = getenv("GSR_DEBUG_FILL");
+    if (!e) return 0u;
+    if (!strcmp(e, "nan")) return 0xFFFFFFFFu;
+    if (!strcmp(e, "big")) return 0x7F7F7F7Fu;
+    return 0u;
+}
+
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;  // bytes
     uint32_t regrowths = 0;  // reallocations of a buffer that already existed (each is a device synchronisation)
+    // GSR_DEBUG_FILL may fill it: floats only, none of which ever becomes an address, a loop bound or a branch that leaves the
+    // allocation (set in gsr_create; index / key / count / mask buffers never are: garbage there is a wild address)
+    bool fill_ok = false;
     // grow-only, like the reference's scratch (rasterizer.jl:275-278,340-343)
     int ensure(size_t bytes, float slack = 1.0f) {
         if (bytes <= cap) return GSR_OK;
@@ -65,6 +79,13 @@ struct DevBuf {
         want = (want + 255) & ~(size_t)255;
         HIPCHK(hipMalloc(&p, want));
         cap = want;
+        if (fill_ok) {
+            if (const uint32_t w = debug_fill_word()) {
+                // synchronised: the library's kernels also run on its own non-blocking aux_stream
+                HIPCHK(hipMemsetD32((hipDeviceptr_t)p, (int)w, want / 4));
+                HIPCHK(hipDeviceSynchronize());
+            }
+        }
         return GSR_OK;
     }
     int release() {
@@ -567,6 +588,16 @@ int gsr_create(const gsr_config* cfg, gsr_handle** out) {
                       &h->s1, &h->s2, &h->s3, &h->big_scratch, &h->rows, &h->vmean2d, &h->d0, &h->d1,
                       &h->d2, &h->partial, &h->keys_compact, &h->big_list, &h->long_state, &h->overflow_fill, &h->dbg_flag};
     for (DevBuf* b : list) h->all[h->n_all++] = b;
+    // GSR_DEBUG_FILL candidates (DevBuf::fill_ok), each read only as float data:
+    h->rows.fill_ok = true;        // GsrInst gradient rows (float4): summed by pergauss_bwd, copied out by gsr_buffer
+    h->vmean2d.fill_ok = true;     // gstate.∇means_2d (float2): written for every Gaussian, read by gsr_update_stats behind radii > 0
+    h->final_T.fill_ok = true;     // final transmittance per pixel: a factor of the backward, never a bound (n_contrib is)
+    h->gnormal.fill_ok = true;     // per-Gaussian normals (float4): feature values of the :rgbdn stream
+    h->d0.fill_ok = true;          // SSIM loss head's ∂map/∂µ1 plane
+    h->d1.fill_ok = true;          // ... ∂map/∂σ1²
+    h->d2.fill_ok = true;          // ... ∂map/∂σ12
+    h->partial.fill_ok = true;     // per-workgroup (Σ|x-y|, Σssim) pairs summed by the loss finisher
+    h->long_state.fill_ok = true;  // (T, A) float2 per pixel and segment of the long-list backward
     const size_t P = (size_t)cfg->width * cfg->height, T = (size_t)h->n_tiles;
     int rc = GSR_OK;
     if ((rc = h->ranges.ensure(2 * T * 4)) || (rc = h->n_contrib.ensure(P * 4)) || (rc = h->final_T.ensure(P * 4)) ||

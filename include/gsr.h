@@ -164,7 +164,8 @@ typedef struct gsr_camera {
  * `covisibilities`, `uncertainties` of rasterize (rasterizer.jl:265-266). */
 typedef struct gsr_aux {
     uint8_t* covisibilities; /* device (N) Bool, set to 1 where T > 0.5, never cleared; or NULL */
-    float* uncertainties;    /* device (W,H); or NULL */
+    float* uncertainties;    /* device (W,H); or NULL.  Fully overwritten: the sum of alpha·T over the splats the pixel blends
+                              * (render.jl:65,109,128); all zeros when the view renders no instance (n_rendered = 0) */
     /* `rast.gstate.radii` (states.jl:12, Int32 (N)) — read by the densification strategy right after
      * the step (strategy.jl:85-86).  When non-NULL the forward writes the radii THERE instead of into
      * handle-owned memory, so the caller's own GeometryState stays truthful; the array must stay valid
@@ -251,7 +252,9 @@ typedef struct gsr_grads {
  * with the flag set is GSR_E_INVALID_ARG instead of silently dropped depth / normal gradients.  What it cannot see is a term
  * added to that buffer in place afterwards: GSR_CHECK_COLOR_COTANGENT=1 in the environment makes every flagged backward
  * reduce |vpixels[3:]| first (one pass over the image + a host wait — debugging only) and fail with GSR_E_INVALID_ARG when it
- * is not exactly zero. */
+ * is not exactly zero.  (Likewise a debugging switch, read at every allocation of handle scratch: GSR_DEBUG_FILL=nan / big fills
+ * each new allocation of the handle's float-only buffers with the word 0xFFFFFFFF / 0x7F7F7F7F, so that a kernel that reads a
+ * float it never wrote cannot pass on the zeros of fresh pages; index, key and count buffers are never filled.) */
 #define GSR_GRADS_COLOR_COTANGENT 0x1u
 
 typedef struct gsr_handle gsr_handle;

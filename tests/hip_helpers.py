@@ -95,3 +95,71 @@ def blend_boundary_pixels(st, opacities, W, H, ulps=4, with_ids=False):
             blends = (sig >= 0) & (alpha >= 0.5 / 255.0) & px[None]
             touched.update(int(i) for i in ids[blends.reshape(len(ids), -1).any(1)])
     return (mask, owners, touched) if with_ids else mask
+
+
+def compare_forward(st, run, img, opacities=None):
+    geo = {k: v.cpu().numpy() for k, v in run.rast.geometry().items()}
+    radii = run.rast.radii.cpu().numpy()
+    assert np.array_equal(radii, st.radii), "radii must match exactly"
+    vis = st.radii > 0
+    assert run.rast.stats.n_visible == int(vis.sum())
+    assert run.rast.stats.n_rendered == st.n_rendered
+    for name, ref in (("means2d", st.means2d), ("conics", st.conics), ("depths", st.depths), ("rgbs", st.rgbs)):
+        assert frac_bad(geo[name][vis], ref[vis], 1e-6, 1e-7) == 0.0, name
+    cb = geo["clamped_bits"][vis]
+    ref_bits = (st.clamped[vis].astype(np.int32) * np.array([1, 2, 4])).sum(1)
+    assert np.array_equal(cb, ref_bits)
+    rect = geo["rect"].astype(np.int64)
+    tiles = (rect[:, 2] - rect[:, 0]) * (rect[:, 3] - rect[:, 1])
+    assert np.array_equal(tiles[vis], st.tiles_touched[vis]), "tile counts per Gaussian must match exactly"
+    assert not st.tiles_touched[~vis].any()  # records of culled Gaussians are stale, as in the reference
+    if st.normals is not None:
+        assert frac_bad(geo["normals"][vis], st.normals[vis], 1e-6, 1e-7) == 0.0
+    if st.n_rendered > 0:
+        assert np.array_equal(run.rast.ranges.cpu().numpy().astype(np.uint32), st.ranges)
+        assert np.array_equal(run.rast.values_sorted.cpu().numpy().astype(np.uint32), st.values_sorted)
+    im = img.cpu().numpy()
+    assert im.shape == st.image.shape
+    T = run.rast.accum_alpha.cpu().numpy()
+    nc = run.rast.n_contrib.cpu().numpy().astype(np.uint32)
+    # (the last contributor moves by one where the saturation test T' < 1e-4 is decided by the last bits of T:
+    #  one such pixel is already more than 1e-3 of a 25 x 32 image)
+    sat = (nc != st.n_contrib).reshape(im.shape[:2])
+    assert sat.sum() <= max(1, 1e-3 * nc.size)
+    if opacities is not None and im.shape[0] * im.shape[1] < 20000:
+        # (one pixel of a small image is already more than the 1e-4 outlier fraction: pixels with a pair ON the blend-test
+        #  boundary, where the decision is the last bit of an exp, do not count — hip_helpers.blend_boundary_pixels — and
+        #  neither does the at most one pixel whose walk stopped one entry apart, fuzz sweep case 14113)
+        edge = blend_boundary_pixels(st, opacities, im.shape[1], im.shape[0])
+        keep = ~(edge | sat)
+        # a handful of pixels, not a tenth of the image (round-3 verdict / ADVICE: the measured worst case of 9 000 fuzzed
+        # scenes was 17 of 1 634 pixels = 1.04 %, under 50 763 splats per pixel)
+        assert (~keep).sum() <= max(4, 0.02 * keep.size), ((~keep).sum(), keep.size)
+        assert frac_bad(im[keep], st.image[keep], 0.0, 1e-4) <= 1e-4
+        assert frac_bad(T[keep], st.accum_alpha[keep], 0.0, 1e-4) <= 1e-4
+        fmax = float(max(1.0, np.abs(st.image).max()))
+        if edge.any():
+            # ... and what is excluded may only differ by ONE flipped pair: its blend weight is alpha·T <= 1/255 (+ the
+            # renormalisation of what lies behind it), times the largest feature value
+            assert np.abs(im[edge] - st.image[edge]).max() <= 2.0 / 255.0 * fmax
+            assert np.abs(T[edge] - st.accum_alpha[edge]).max() <= 2.0 / 255.0
+        if (sat & ~edge).any():
+            # ... or by the ONE entry blended on one side only: at most the transmittance the other side stopped at
+            left = float((1.0 - np.minimum(T, st.accum_alpha.reshape(T.shape))[sat & ~edge]).max())
+            assert np.abs(im[sat & ~edge] - st.image[sat & ~edge]).max() <= 2.0 * (left + 1e-4) * fmax
+            assert np.abs(T[sat & ~edge] - st.accum_alpha.reshape(T.shape)[sat & ~edge]).max() <= 2.0 * (left + 1e-4)
+    else:
+        assert frac_bad(im, st.image, 0.0, 1e-4) <= 1e-4, np.abs(im - st.image).max()
+        assert frac_bad(T, st.accum_alpha, 0.0, 1e-4) <= 1e-4
+
+
+def compare_backward(g, out, vis):
+    vm, vs, vo, vsc, vr, vR, vt = [None if o is None else o.cpu().numpy() for o in out]
+    assert rel_l2(vm, g.vmeans) <= 1e-4
+    assert rel_l2(vs, g.vshs) <= 1e-4
+    assert rel_l2(vo.reshape(-1), g.vopacities) <= 1e-4
+    assert rel_l2(vsc, g.vscales) <= 1e-4
+    assert rel_l2(vr, g.vrots) <= 1e-4
+    # culled Gaussians: exact zeros
+    assert not vm[~vis].any() and not vs[~vis].any() and not vsc[~vis].any() and not vr[~vis].any()
+    return vR, vt
