@@ -596,7 +596,7 @@ int gsr_create(const gsr_config* cfg, gsr_handle** out) {
     h->d0.fill_ok = true;          // SSIM loss head's ∂map/∂µ1 plane
     h->d1.fill_ok = true;          // ... ∂map/∂σ1²
     h->d2.fill_ok = true;          // ... ∂map/∂σ12
-    h->partial.fill_ok = true;     // per-workgroup (Σ|x-y|, Σssim) pairs summed by the loss finisher
+    h->partial.fill_ok = true;     // per-wave (Σ|x-y|, Σssim) pairs summed by the loss finisher
     h->long_state.fill_ok = true;  // (T, A) float2 per pixel and segment of the long-list backward
     const size_t P = (size_t)cfg->width * cfg->height, T = (size_t)h->n_tiles;
     int rc = GSR_OK;
@@ -1092,6 +1092,7 @@ int gsr_ssim_forward(int W, int H, int CH, int B, const float* img, const float*
     if (!img || !ref || !ssim_map) return fail(GSR_E_INVALID_ARG, "null SSIM array");
     if (train && (!dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12)) return fail(GSR_E_INVALID_ARG, "train needs the 3 partial maps");
     if ((size_t)CH * B > 65535) return fail(GSR_E_INVALID_ARG, "CH*B too large");
+    if ((size_t)W * H > 0xFFFFFFFFull) return fail(GSR_E_INVALID_ARG, "SSIM plane too large");  // 32-bit offsets inside a plane
     (g_ssim_exact.load(std::memory_order_relaxed) ? gsr_launch_ssim_fwd_exact : gsr_launch_ssim_fwd_fast)((hipStream_t)stream, W, H, CH, B, img, ref, C1, C2, train,
                                                                           ssim_map, dm_dmu1, dm_dsigma1_sq, dm_dsigma12);
     HIPCHK(hipGetLastError());
@@ -1105,6 +1106,7 @@ int gsr_ssim_backward(int W, int H, int CH, int B, const float* img, const float
     if (!img || !ref || !dL_dmap || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg)
         return fail(GSR_E_INVALID_ARG, "null SSIM array");
     if ((size_t)CH * B > 65535) return fail(GSR_E_INVALID_ARG, "CH*B too large");
+    if ((size_t)W * H > 0xFFFFFFFFull) return fail(GSR_E_INVALID_ARG, "SSIM plane too large");  // 32-bit offsets inside a plane
     (g_ssim_exact.load(std::memory_order_relaxed) ? gsr_launch_ssim_bwd_exact : gsr_launch_ssim_bwd_fast)((hipStream_t)stream, W, H, CH, B, img, ref, dL_dmap, dm_dmu1,
                                                                           dm_dsigma1_sq, dm_dsigma12, dL_dimg);
     HIPCHK(hipGetLastError());
@@ -1117,13 +1119,14 @@ int gsr_loss_l1_ssim(gsr_handle* h, const float* image, const float* target, flo
     hipStream_t s = (hipStream_t)stream;
     const int W = h->cfg.width, H = h->cfg.height, C = h->cfg.mode;
     const size_t P = (size_t)W * H;
-    int rc;
-    if ((rc = h->d0.ensure(3 * P * 4)) || (rc = h->d1.ensure(3 * P * 4)) || (rc = h->d2.ensure(3 * P * 4)) ||
-        (rc = h->partial.ensure((size_t)h->n_tiles * 3 * 2 * 4)))
-        return rc;
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;  // fused_ssim.jl:374
+    if (P * C > 0xFFFFFFFFull) return fail(GSR_E_INVALID_ARG, "image too large for the loss head");  // 32-bit offsets inside it
     // ONE decision for the forward and the pullback of this call, from the handle (ABI 5) or the process default
     const int exact = ssim_exact_of(h);
+    int rc;
+    if ((rc = h->d0.ensure(3 * P * 4)) || (rc = h->d1.ensure(3 * P * 4)) || (rc = h->d2.ensure(3 * P * 4)) ||
+        (rc = h->partial.ensure((exact ? gsr_loss_partial_pairs_exact : gsr_loss_partial_pairs_fast)(W, H) * 2 * 4)))
+        return rc;
+    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;  // fused_ssim.jl:374
     StageScope sc9(h->prof, ST_LOSS_FWD, s);
     (exact ? gsr_launch_loss_fwd_exact : gsr_launch_loss_fwd_fast)(s, W, H, C, image, target, C1, C2, h->d0.as<float>(),
                                                                           h->d1.as<float>(), h->d2.as<float>(), h->partial.as<float>());

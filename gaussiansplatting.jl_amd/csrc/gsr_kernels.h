@@ -221,7 +221,8 @@ void gsr_launch_ply_rows(hipStream_t s, bool pack, long long n, int kr, float* p
                                    float C2, int train, float* ssim_map, float* d0, float* d1, float* d2);             \
     void gsr_launch_ssim_bwd_##SUF(hipStream_t s, int W, int H, int CH, int B, const float* img, const float* ref,      \
                                    const float* dL_dmap, const float* d0, const float* d1, const float* d2, float* dL_dimg); \
-    /* fused loss head: image (C,W,H) vs target (W,H,3); partial: [3T][2] per-workgroup sum|x-y|, sum ssim */          \
+    /* fused loss head: image (C,W,H) vs target (W,H,3); partial: [gsr_loss_partial_pairs][2] per-wave sum|x-y|, sum ssim */ \
+    size_t gsr_loss_partial_pairs_##SUF(int W, int H);                                                                 \
     void gsr_launch_loss_fwd_##SUF(hipStream_t s, int W, int H, int C, const float* image, const float* target, float C1, \
                                    float C2, float* d0, float* d1, float* d2, float* partial);                         \
     void gsr_launch_loss_bwd_##SUF(hipStream_t s, int W, int H, int C, const float* image, const float* target, float lambda, \

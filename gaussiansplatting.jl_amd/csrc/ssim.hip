@@ -2,11 +2,15 @@
 // Reference behaviour: src/fused_ssim.jl:34-371 (kernels), :373-424 (host wrappers),
 // src/training.jl:656,684-694 (L = (1-λ)·L1 + λ·(1 - mean SSIM)); SURVEY.md A.12.
 //
-// 16x16 output tile + 5-pixel halo staged in LDS, separable 11-tap Gaussian:
-// horizontal pass into LDS, vertical pass in registers.  Accumulation order follows the
-// reference (symmetric pairs d = 1..5 with weight GAUSS[5-d], centre tap last).  grid.z enumerates
-// (channel, batch) planes for the generic entry points; the loss head loops the three channels inside
-// one workgroup, as the reference does.
+// Strips, not tiles: one wave owns 54 output columns (lane = column, 5 halo lanes on each side) and walks down a strip of
+// rows.  Per input row the horizontal 11x1 goes through a per-wave LDS row (one 8-byte write, 10 8-byte reads per lane, no
+// workgroup barrier: the waves of a workgroup are independent); its results enter a ring of the last 11 rows held in
+// registers, and the vertical 1x11 of output row r is evaluated over the ring when row r + 5 has arrived.  The statistics
+// travel as float2 pairs ((x, y), (x², y²), (d0, d1)): packed fp32 instructions, two per issue slot.  Rows are requested
+// from memory AHEAD rows before they are filtered.  Accumulation order follows the reference (symmetric pairs d = 1..5 with
+// weight GAUSS[5-d], centre tap last).  One channel plane per wave: grid.z enumerates (channel, batch) planes for the generic
+// entry points, the loss head puts the three channel waves of a strip into one workgroup (they read the same lines of the
+// channel-interleaved image).  The strip height is chosen per launch (ssim_strip_h).  DESIGN.md §4, §4.2.
 //
 // This file is compiled TWICE into the library (csrc/Makefile):
 //   SSIM_EXACT = 1, -ffp-contract=off: every fp32 operation as written, IEEE divisions — the maps are
@@ -29,27 +33,33 @@
 namespace {
 
 constexpr int HALO = 5;
-constexpr int SH_DIM = GSR_TILE + 2 * HALO;  // 26
-// LDS row strides (floats): a ds_read_b32 is served in two groups of 32 lanes = two tile rows of
-// 16 lanes, so a row stride of 16 (mod 32) puts the two rows on disjoint banks.
-constexpr int IN_STRIDE = 48, HC_STRIDE = 16;
+// The strip shape; the series that chose these values is in DESIGN.md §4.2 and profiles/ssim_strips/knobs.txt
+constexpr int STRIP_W = 64 - 2 * HALO;  // 54 output columns per wave
+constexpr int AHEAD = 3;                // rows requested from memory before the row being filtered
+constexpr int MIN_WAVES = 4;            // waves per SIMD the register allocation has to leave room for
+constexpr int RING = 2 * HALO + 1;      // 11 rows of horizontal results live in registers
+constexpr int LOSS_STRIPS = 1;          // loss head: strips per workgroup (x 3 channel waves); planar entry points: 4 waves
+constexpr int ROW_LDS = 64 + 2 * HALO;  // a wave's row buffer, padded so that the halo lanes read inside it
 
 __constant__ float GAUSS[11] = {0.001028380123898387f, 0.0075987582094967365f, 0.036000773310661316f,
                                 0.10936068743467331f,  0.21300552785396576f,   0.26601171493530273f,
                                 0.21300552785396576f,  0.10936068743467331f,   0.036000773310661316f,
                                 0.0075987582094967365f, 0.001028380123898387f};
 
+typedef float v2f __attribute__((ext_vector_type(2)));  // two statistics per lane: the packed fp32 instructions of gfx950
+
+// A source hands out a plane (64-bit, once per wave), a row's offset inside it (wave-uniform: scalar arithmetic) and a lane's
+// byte offset inside the row, so that a load is `scalar base + 32-bit lane offset` with no 64-bit lane arithmetic.  Offsets
+// inside a plane are 32-bit: the entry points refuse images of 2^32 elements or more.
 // (W,H,CH,B) planar arrays, x fastest (fused_ssim.jl:27-31)
 struct PlanarSrc {
     const float* img;
     const float* ref;
     int W, H;
-    __device__ __forceinline__ float x(int gx, int gy, int plane) const {
-        return img[(size_t)gx + (size_t)W * gy + (size_t)W * H * plane];
-    }
-    __device__ __forceinline__ float y(int gx, int gy, int plane) const {
-        return ref[(size_t)gx + (size_t)W * gy + (size_t)W * H * plane];
-    }
+    __device__ __forceinline__ const float* xplane(int plane) const { return img + (size_t)W * H * plane; }
+    __device__ __forceinline__ const float* yplane(int plane) const { return ref + (size_t)W * H * plane; }
+    __device__ __forceinline__ unsigned xrow(int gy) const { return (unsigned)W * (unsigned)gy; }
+    __device__ __forceinline__ unsigned xlane(int gx) const { return 4u * (unsigned)gx; }
 };
 // rasterizer output (C,W,H) channel-fastest vs target (W,H,3): folds
 // `features[1:3,:,:]` + `permutedims` (training.jl:656,684-685) into the loads
@@ -57,165 +67,216 @@ struct RasterSrc {
     const float* image;
     const float* target;
     int W, H, C;
-    __device__ __forceinline__ float x(int gx, int gy, int plane) const {
-        return image[(size_t)C * ((size_t)gx + (size_t)W * gy) + plane];
-    }
-    __device__ __forceinline__ float y(int gx, int gy, int plane) const {
-        return target[(size_t)gx + (size_t)W * gy + (size_t)W * H * plane];
-    }
+    __device__ __forceinline__ const float* xplane(int plane) const { return image + plane; }
+    __device__ __forceinline__ const float* yplane(int plane) const { return target + (size_t)W * H * plane; }
+    __device__ __forceinline__ unsigned xrow(int gy) const { return (unsigned)(C * W) * (unsigned)gy; }
+    __device__ __forceinline__ unsigned xlane(int gx) const { return 4u * (unsigned)(C * gx); }
 };
 
-// Workgroup id -> tile, XCD-aware: workgroups are dealt round-robin to the 8 XCDs (one L2 each).
-// Tiles that share halo rows and columns should share an L2, so XCD x gets the x-th contiguous
-// eighth of the tiles (raster order) instead of every 8th tile.  Grid: (8 * ceil(tiles / 8), 1, planes).
-__device__ __forceinline__ bool ssim_tile_of_block(int W, int H, int& tx0, int& ty0) {
-    const int gx = (W + GSR_TILE - 1) / GSR_TILE, gy = (H + GSR_TILE - 1) / GSR_TILE;
-    const int n = gx * gy, per = (n + 7) / 8;
-    const int t = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-    if ((int)(blockIdx.x >> 3) >= per || t >= n) return false;
-    tx0 = (t % gx) * GSR_TILE;
-    ty0 = (t / gx) * GSR_TILE;
+// element at byte offset `lane_off` of the row that starts `row` elements into `plane`
+template <class T>
+__device__ __forceinline__ T& at(T* plane, unsigned row, unsigned lane_off) {
+    return *(T*)((char*)(plane + row) + lane_off);
+}
+template <class T>
+__device__ __forceinline__ const T& at(const T* plane, unsigned row, unsigned lane_off) {
+    return *(const T*)((const char*)(plane + row) + lane_off);
+}
+
+// A wave's strip.  Workgroups are dealt round-robin to the 8 XCDs (one L2 each).  Neighbouring strips share 10 of 64
+// columns and 10 input rows, so XCD x gets the x-th contiguous eighth of the strip groups (raster order) instead of every
+// 8th group.  Grid: (8 * ceil(groups / 8), 1, planes) with groups = ceil(strips / SPB); a workgroup is NPL * SPB independent
+// waves (NPL channel planes of SPB strips: nothing to synchronise between them).
+struct Strip {
+    int x0, y0, rows;  // first output column, first output row, output rows (< strip_h in the last strip row)
+};
+template <int NPL, int SPB>
+__device__ __forceinline__ bool strip_of_wave(int W, int H, int strip_h, int wv, Strip& st) {
+    const int nsx = (W + STRIP_W - 1) / STRIP_W, nsy = (H + strip_h - 1) / strip_h;
+    const int n = nsx * nsy, groups = (n + SPB - 1) / SPB, per = (groups + 7) / 8;
+    const int g = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    const int s = g * SPB + wv / NPL;
+    if ((int)(blockIdx.x >> 3) >= per || g >= groups || s >= n) return false;
+    st.x0 = (s % nsx) * STRIP_W;
+    st.y0 = (s / nsx) * strip_h;
+    st.rows = min(strip_h, H - st.y0);
     return true;
 }
 
-__device__ __forceinline__ float block_sum(float v, float* red /*[4]*/) {
+// Orders a wave's own LDS writes before its other lanes' reads (and the reads before the next row's writes).  The LDS
+// serves one wave's instructions in order, so this only has to hold the compiler: no instruction, no workgroup barrier.
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
-    return r;
+    return v;
 }
 
-// fused_ssim.jl:34-238.  LOSS: additionally reduce Σ|x-y| and Σssim into partial[0..1].
-// NCH = channel planes handled per workgroup (the reference loops channels inside the
-// workgroup, fused_ssim.jl:52; the loss head uses 3 so that the three channels of a pixel —
-// adjacent floats of the (C,W,H) image — are fetched and written by the same workgroup).
-template <class Src, bool LOSS, int NCH>
-__global__ __launch_bounds__(256) void ssim_fwd_kernel(Src src, int W, int H, float C1, float C2, int train,
-                                                       float* __restrict__ ssim_map, float* __restrict__ d0,
-                                                       float* __restrict__ d1, float* __restrict__ d2,
-                                                       float* __restrict__ partial) {
-    __shared__ float sx[SH_DIM][IN_STRIDE], sy[SH_DIM][IN_STRIDE];
-    __shared__ float hc[5][SH_DIM][HC_STRIDE];
-    __shared__ float red[4];
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    int x0, y0;
-    const bool live = ssim_tile_of_block(W, H, x0, y0);
-    float l1 = 0.0f, sv = 0.0f;
-    if (!live) {  // padding workgroup of the XCD-aware grid: contributes zero partials
-        if (LOSS && tid == 0) { partial[2 * ((size_t)blockIdx.x + (size_t)gridDim.x * blockIdx.z)] = 0.0f; partial[2 * ((size_t)blockIdx.x + (size_t)gridDim.x * blockIdx.z) + 1] = 0.0f; }
+// a·b + c·d.  The contracted build fuses a·b into the add and rounds c·d, which is what the compiler has made of this
+// expression in the default build since it exists; left to itself it picks the other product when the operands come out
+// of float2 pairs, and the default build's results would move in the last bit (a training run then takes another path).
+__device__ __forceinline__ float sum_of_products(float a, float b, float c, float d) {
+#if SSIM_EXACT
+    return a * b + c * d;
+#else
+    return __builtin_fmaf(a, b, c * d);
+#endif
+}
+
+// 1x11 over the ring of horizontal results, input row in slot j just arrived: output row = slot j - 5, symmetric pairs
+// d = 1..5, centre tap last (the reference's order, fused_ssim.jl:160-190: what keeps the exact build bit-identical to the
+// oracle; scattering each new row into eleven pending outputs is another order).  j is static after the unroll.
+template <class T>
+__device__ __forceinline__ T ring_vertical(const T (&h)[RING], int j) {
+    T a = 0;
+#pragma unroll
+    for (int d = 1; d <= HALO; d++) a += (h[(j + HALO + 1 + RING - d) % RING] + h[(j + HALO + 1 + d) % RING]) * GAUSS[HALO - d];
+    a += h[(j + HALO + 1) % RING] * GAUSS[HALO];
+    return a;
+}
+
+// fused_ssim.jl:34-238.  LOSS: additionally reduce Σ|x-y| and Σssim into one partial pair per wave.
+// Lane = column (gx = x0 - 5 + lane), the wave walks down its strip's rows + 5 above and below.  Per input row: horizontal
+// 11x1 through the wave's LDS row (one 8-byte write, ten 8-byte reads per lane), result into slot `row % 11` of a register ring; when row
+// r + 5 has arrived, output row r is the 1x11 over the ring.  The row loop is unrolled 11 times so that every ring index
+// is static (a `break` in it defeats the unroll and sends the ring to scratch: guard the body instead).
+template <class Src, bool LOSS, int NPL, int SPB>
+__global__ __launch_bounds__(64 * NPL * SPB, MIN_WAVES) void ssim_fwd_kernel(Src src, int W, int H, int strip_h, float C1, float C2, int train,
+                                                                 float* __restrict__ ssim_map, float* __restrict__ d0,
+                                                                 float* __restrict__ d1, float* __restrict__ d2,
+                                                                 float* __restrict__ partial) {
+    constexpr int NW = NPL * SPB;
+    __shared__ v2f rowbuf[NW][ROW_LDS];  // (x, y) of the wave's current row
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    Strip st;
+    if (!strip_of_wave<NPL, SPB>(W, H, strip_h, wv, st)) {  // padding wave of the XCD-aware grid: contributes a zero pair
+        if (LOSS && lane == 0) { partial[2 * ((size_t)blockIdx.x * NW + wv)] = 0.0f; partial[2 * ((size_t)blockIdx.x * NW + wv) + 1] = 0.0f; }
         return;
     }
-  for (int ch = 0; ch < NCH; ch++) {
-    const int plane = blockIdx.z * NCH + ch;
-    if (ch > 0) __syncthreads();  // previous channel's LDS tiles fully consumed
-    for (int f = tid; f < SH_DIM * SH_DIM; f += 256) {
-        const int ly = f / SH_DIM, lx = f - ly * SH_DIM;
-        const int gx = x0 + lx - HALO, gy = y0 + ly - HALO;
-        const bool in = gx >= 0 && gx < W && gy >= 0 && gy < H;
-        sx[ly][lx] = in ? src.x(gx, gy, plane) : 0.0f;
-        sy[ly][lx] = in ? src.y(gx, gy, plane) : 0.0f;
-    }
-    __syncthreads();
-    // horizontal 11x1: rows ty and ty+16
-    for (int r = ty; r < SH_DIM; r += GSR_TILE) {
-        const int cx = tx + HALO;
-        float s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
+    const int plane = blockIdx.z * NPL + wv % NPL;
+    v2f* buf = rowbuf[wv];
+    if (lane < HALO) { buf[lane] = v2f{0.0f, 0.0f}; buf[64 + HALO + lane] = v2f{0.0f, 0.0f}; }
+    const int gx = st.x0 - HALO + lane, cx = lane + HALO;
+    const bool col_in = gx >= 0 && gx < W;
+    const bool own = lane >= HALO && lane < 64 - HALO && gx < W;  // this lane's column is an output of this strip
+    const int nrows = st.rows + 2 * HALO;                         // input rows: rr = 0 is image row y0 - 5
+    const int gxc = min(max(gx, 0), W - 1);
+    const unsigned xo = src.xlane(gxc), yo = 4u * (unsigned)gxc;
+    const float* xp = src.xplane(plane);
+    const float* yp = src.yplane(plane);
+    const size_t po = (size_t)W * H * plane;  // this wave's plane of the planar outputs
+    // Straight-line loads from a clamped address, the value untouched until its row is filtered (rows and columns
+    // outside the image become zeros then): a load under a branch, or a select right behind it, makes
+    // the wave wait for the row it has just requested, and the rows in flight are gone.
+    auto fetch = [&](int rr) {
+        const int gyc = min(max(st.y0 - HALO + rr, 0), H - 1);
+        return v2f{at(xp, src.xrow(gyc), xo), at(yp, (unsigned)W * (unsigned)gyc, yo)};
+    };
+    v2f nxt[AHEAD];  // rows in flight: a wave that waits for each row's load lives in memory latency
 #pragma unroll
-        for (int d = 1; d <= HALO; d++) {
-            const float w = GAUSS[HALO - d];
-            const float Xl = sx[r][cx - d], Yl = sy[r][cx - d], Xr = sx[r][cx + d], Yr = sy[r][cx + d];
-            s0 += (Xl + Xr) * w;
-            s1 += (Xl * Xl + Xr * Xr) * w;
-            s2 += (Yl + Yr) * w;
-            s3 += (Yl * Yl + Yr * Yr) * w;
-            s4 += (Xl * Yl + Xr * Yr) * w;
-        }
-        const float Xc = sx[r][cx], Yc = sy[r][cx], wc = GAUSS[HALO];
-        s0 += Xc * wc; s1 += Xc * Xc * wc; s2 += Yc * wc; s3 += Yc * Yc * wc; s4 += Xc * Yc * wc;
-        hc[0][r][tx] = s0; hc[1][r][tx] = s1; hc[2][r][tx] = s2; hc[3][r][tx] = s3; hc[4][r][tx] = s4;
-    }
-    __syncthreads();
-    // vertical 1x11 + SSIM
-    const int px = x0 + tx, py = y0 + ty;
-    const bool in = px < W && py < H;
-    float o[5];
-    {
-        const int cy = ty + HALO;
+    for (int i = 0; i < AHEAD; i++) nxt[i] = fetch(i);
+    v2f hm[RING], hq[RING];  // horizontal results of the last 11 rows: (Σx, Σy), (Σx², Σy²)
+    float hc[RING];          // ... Σxy
+    float l1 = 0.0f, sv = 0.0f;
+    for (int base = 0; base < nrows; base += RING) {
 #pragma unroll
-        for (int k = 0; k < 5; k++) {
-            float a = 0;
+        for (int j = 0; j < RING; j++) {
+            const int rr = base + j;
+            if (rr < nrows) {
+                const int gy = st.y0 - HALO + rr;
+                const v2f XY = col_in && gy >= 0 && gy < H ? nxt[0] : v2f{0.0f, 0.0f};  // outside the image: zeros
 #pragma unroll
-            for (int d = 1; d <= HALO; d++) a += (hc[k][cy - d][tx] + hc[k][cy + d][tx]) * GAUSS[HALO - d];
-            a += hc[k][cy][tx] * GAUSS[HALO];
-            o[k] = a;
-        }
-    }
-    if (in) {
-        const float mu1 = o[0], mu2 = o[2];
-        const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2;
-        const float sigma1_sq = o[1] - mu1_sq, sigma2_sq = o[3] - mu2_sq, sigma12 = o[4] - mu1 * mu2;
-        const float A = mu1_sq + mu2_sq + C1, Bv = sigma1_sq + sigma2_sq + C2;
-        const float Cv = 2.0f * mu1 * mu2 + C1, Dv = 2.0f * sigma12 + C2;
-        const size_t oi = (size_t)px + (size_t)W * py + (size_t)W * H * plane;
+                for (int i = 0; i + 1 < AHEAD; i++) nxt[i] = nxt[i + 1];
+                nxt[AHEAD - 1] = fetch(rr + AHEAD);
+                buf[cx] = XY;
+                wave_sync();
+                v2f m = 0, q = 0;
+                float c = 0;
+#pragma unroll
+                for (int d = 1; d <= HALO; d++) {
+                    const float w = GAUSS[HALO - d];
+                    const v2f L = buf[cx - d], R = buf[cx + d];
+                    m += (L + R) * w;
+                    q += (L * L + R * R) * w;
+                    c += sum_of_products(L.x, L.y, R.x, R.y) * w;
+                }
+                wave_sync();
+                const float wc = GAUSS[HALO];
+                m += XY * wc; q += XY * XY * wc; c += XY.x * XY.y * wc;
+                hm[j] = m; hq[j] = q; hc[j] = c;
+                if (LOSS && own && rr >= HALO && rr < nrows - HALO) l1 += fabsf(XY.x - XY.y);
+                if (rr >= 2 * HALO) {  // output row rr - 10 of the strip is complete
+                    const v2f om = ring_vertical(hm, j), oq = ring_vertical(hq, j);
+                    const float o[5] = {om.x, oq.x, om.y, oq.y, ring_vertical(hc, j)};
+                    if (own) {
+                        const int py = st.y0 + rr - 2 * HALO;
+                        const float mu1 = o[0], mu2 = o[2];
+                        const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2;
+                        const float sigma1_sq = o[1] - mu1_sq, sigma2_sq = o[3] - mu2_sq, sigma12 = o[4] - mu1 * mu2;
+                        const float A = mu1_sq + mu2_sq + C1, Bv = sigma1_sq + sigma2_sq + C2;
+                        const float Cv = 2.0f * mu1 * mu2 + C1, Dv = 2.0f * sigma12 + C2;
+                        const unsigned orow = (unsigned)W * (unsigned)py;
 #if SSIM_EXACT
-        const float val = (Cv * Dv) / (A * Bv);
-        if (!LOSS) ssim_map[oi] = val;
-        if (train) {
-            d0[oi] = ((mu2 * 2.0f * Dv) / (A * Bv) - (mu2 * 2.0f * Cv) / (A * Bv) -
-                      (mu1 * 2.0f * Cv * Dv) / (A * A * Bv) + (mu1 * 2.0f * Cv * Dv) / (A * Bv * Bv));
-            d1[oi] = (-Cv * Dv) / (A * Bv * Bv);
-            d2[oi] = (2.0f * Cv) / (A * Bv);
-        }
+                        const float val = (Cv * Dv) / (A * Bv);
+                        if (!LOSS) at(ssim_map + po, orow, yo) = val;
+                        if (train) {
+                            at(d0 + po, orow, yo) = ((mu2 * 2.0f * Dv) / (A * Bv) - (mu2 * 2.0f * Cv) / (A * Bv) -
+                                      (mu1 * 2.0f * Cv * Dv) / (A * A * Bv) + (mu1 * 2.0f * Cv * Dv) / (A * Bv * Bv));
+                            at(d1 + po, orow, yo) = (-Cv * Dv) / (A * Bv * Bv);
+                            at(d2 + po, orow, yo) = (2.0f * Cv) / (A * Bv);
+                        }
 #else
-        // the same four quotients (fused_ssim.jl:219-233) over two reciprocals: 1/(AB) = rA·rB, 1/(A²B) = rA·rAB, 1/(AB²) = rB·rAB
-        const float rA = __builtin_amdgcn_rcpf(A), rB = __builtin_amdgcn_rcpf(Bv), rAB = rA * rB;
-        const float val = (Cv * Dv) * rAB;
-        if (!LOSS) ssim_map[oi] = val;
-        if (train) {
-            d0[oi] = 2.0f * (mu2 * (Dv - Cv) * rAB + mu1 * val * (rB - rA));
-            d1[oi] = -val * rB;
-            d2[oi] = 2.0f * Cv * rAB;
-        }
+                        // the same four quotients (fused_ssim.jl:219-233) over two reciprocals: 1/(AB) = rA·rB, 1/(A²B) = rA·rAB, 1/(AB²) = rB·rAB
+                        const float rA = __builtin_amdgcn_rcpf(A), rB = __builtin_amdgcn_rcpf(Bv), rAB = rA * rB;
+                        const float val = (Cv * Dv) * rAB;
+                        if (!LOSS) at(ssim_map + po, orow, yo) = val;
+                        if (train) {
+                            at(d0 + po, orow, yo) = 2.0f * (mu2 * (Dv - Cv) * rAB + mu1 * val * (rB - rA));
+                            at(d1 + po, orow, yo) = -val * rB;
+                            at(d2 + po, orow, yo) = 2.0f * Cv * rAB;
+                        }
 #endif
-        if (LOSS) {
-            sv += val;
-            l1 += fabsf(sx[ty + HALO][tx + HALO] - sy[ty + HALO][tx + HALO]);
+                        if (LOSS) sv += val;
+                    }
+                }
+            }
         }
     }
-  }
     if (LOSS) {
-        // one partial pair per workgroup; 24k workgroups hammering two words with atomics
+        // one partial pair per wave; thousands of waves hammering two words with atomics
         // serialise at ~12 ns each (MI355X_MICROARCH.md "fanin")
-        const float a = block_sum(l1, red), b = block_sum(sv, red);
-        if (tid == 0) {
-            const size_t blk = (size_t)blockIdx.x + (size_t)gridDim.x * blockIdx.z;
-            partial[2 * blk] = a;
-            partial[2 * blk + 1] = b;
+        const float a = wave_sum(l1), b = wave_sum(sv);
+        if (lane == 0) {
+            const size_t pair = (size_t)blockIdx.x * NW + wv;
+            partial[2 * pair] = a;
+            partial[2 * pair + 1] = b;
         }
     }
 }
 
-// The scalar loss (training.jl:656,684-694) from the per-workgroup partial sums the forward kernel left: the work of
+// The scalar loss (training.jl:656,684-694) from the per-wave partial sums the forward kernel left: the work of
 // ONE workgroup, done by an extra workgroup of the backward launch (a launch of its own was 4 us during which the
 // whole GPU waited).  Fixed summation order: bit-reproducible.
-__device__ __forceinline__ void loss_finish_body(const float* __restrict__ partial, int n_blocks, float lambda,
+template <int NT>
+__device__ __forceinline__ void loss_finish_body(const float* __restrict__ partial, int n_pairs, float lambda,
                                                  float inv_count, float* __restrict__ loss_out) {
-    __shared__ float red[2][4];
+    __shared__ float red[2][NT / 64];
     float a = 0.0f, b = 0.0f;
-    for (int i = threadIdx.x; i < n_blocks; i += 256) {
+    for (int i = threadIdx.x; i < n_pairs; i += NT) {
         const float2 p = reinterpret_cast<const float2*>(partial)[i];
         a += p.x; b += p.y;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
+    a = wave_sum(a); b = wave_sum(b);
     if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
     __syncthreads();
     if (threadIdx.x == 0) {
         a = 0.0f; b = 0.0f;
-        for (int w = 0; w < 4; w++) { a += red[0][w]; b += red[1][w]; }
+        for (int w = 0; w < NT / 64; w++) { a += red[0][w]; b += red[1][w]; }
         const float l1 = a * inv_count;
         const float s = 1.0f - b * inv_count;
         loss_out[0] = (1.0f - lambda) * l1 + lambda * s;
@@ -224,113 +285,171 @@ __device__ __forceinline__ void loss_finish_body(const float* __restrict__ parti
 
 // fused_ssim.jl:241-371.  LOSS: dL_dmap is the constant -λ/(3P) (pullback of
 // λ·(1-mean(map))), the L1 pullback is added, output goes to the (C,W,H) rasterizer layout.
-template <class Src, bool LOSS, int NCH>
-__global__ __launch_bounds__(256) void ssim_bwd_kernel(Src src, int W, int H, const float* __restrict__ dL_dmap,
-                                                       float chain_const, float l1_scale,
-                                                       const float* __restrict__ d0, const float* __restrict__ d1,
-                                                       const float* __restrict__ d2, float* __restrict__ out,
-                                                       int outC, const float* __restrict__ partial, int n_partial,
-                                                       float lambda, float inv_count, float* __restrict__ loss_out) {
-    __shared__ float sd[3][SH_DIM][IN_STRIDE];
-    __shared__ float hc[3][SH_DIM][HC_STRIDE];
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+// Same strip walk as the forward with three maps instead of five statistics.
+template <class Src, bool LOSS, int NPL, int SPB>
+__global__ __launch_bounds__(64 * NPL * SPB, MIN_WAVES) void ssim_bwd_kernel(Src src, int W, int H, int strip_h, const float* __restrict__ dL_dmap,
+                                                                 float chain_const, float l1_scale,
+                                                                 const float* __restrict__ d0, const float* __restrict__ d1,
+                                                                 const float* __restrict__ d2, float* __restrict__ out,
+                                                                 int outC, const float* __restrict__ partial, int n_partial,
+                                                                 float lambda, float inv_count, float* __restrict__ loss_out) {
+    constexpr int NW = NPL * SPB;
+    __shared__ v2f rowbuf01[NW][ROW_LDS];  // chained (d0, d1) of the wave's current row
+    __shared__ float rowbuf2[NW][ROW_LDS];  // ... d2
     if (LOSS && blockIdx.x == gridDim.x - 1) {  // the extra workgroup of the loss head's launch
-        loss_finish_body(partial, n_partial, lambda, inv_count, loss_out);
+        loss_finish_body<64 * NW>(partial, n_partial, lambda, inv_count, loss_out);
         return;
     }
-    int x0, y0;
-    if (!ssim_tile_of_block(W, H, x0, y0)) return;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    Strip st;
+    if (!strip_of_wave<NPL, SPB>(W, H, strip_h, wv, st)) return;
+    const int ch = wv % NPL, plane = blockIdx.z * NPL + ch;
     const size_t P = (size_t)W * H;
-    float gout[NCH];
-  for (int ch = 0; ch < NCH; ch++) {
-    const int plane = blockIdx.z * NCH + ch;
-    gout[ch] = 0.0f;
-    if (ch > 0) __syncthreads();
-    for (int f = tid; f < SH_DIM * SH_DIM; f += 256) {
-        const int ly = f / SH_DIM, lx = f - ly * SH_DIM;
-        const int gx = x0 + lx - HALO, gy = y0 + ly - HALO;
-        const bool in = gx >= 0 && gx < W && gy >= 0 && gy < H;
-        const size_t gi = (size_t)gx + (size_t)W * gy + P * plane;
-        const float chain = in ? (LOSS ? chain_const : dL_dmap[gi]) : 0.0f;
-        sd[0][ly][lx] = (in ? d0[gi] : 0.0f) * chain;
-        sd[1][ly][lx] = (in ? d1[gi] : 0.0f) * chain;
-        sd[2][ly][lx] = (in ? d2[gi] : 0.0f) * chain;
+    v2f* b01 = rowbuf01[wv];
+    float* b2 = rowbuf2[wv];
+    if (lane < HALO) {
+        b01[lane] = v2f{0.0f, 0.0f}; b2[lane] = 0.0f;
+        b01[64 + HALO + lane] = v2f{0.0f, 0.0f}; b2[64 + HALO + lane] = 0.0f;
     }
-    __syncthreads();
-    for (int r = ty; r < SH_DIM; r += GSR_TILE) {
-        const int cx = tx + HALO;
+    const int gx = st.x0 - HALO + lane, cx = lane + HALO;
+    const bool col_in = gx >= 0 && gx < W;
+    const bool own = lane >= HALO && lane < 64 - HALO && gx < W;
+    const int nrows = st.rows + 2 * HALO;
+    const int gxc = min(max(gx, 0), W - 1);
+    const unsigned xo = src.xlane(gxc), yo = 4u * (unsigned)gxc;
+    const float* xp = src.xplane(plane);
+    const float* yp = src.yplane(plane);
+    const size_t po = P * plane;  // this wave's plane of the planar maps
+    struct Row { v2f a01; float a2, chain, p1, p2; };  // derivative maps, dL/dmap of input row rr; x, y of the output row rr - 10
+    auto fetch = [&](int rr) {  // straight-line loads from clamped addresses, values untouched until consumed, as in the forward
+        const int gy = st.y0 - HALO + rr;
+        const int gyc = min(max(gy, 0), H - 1), gyo = min(max(gy - HALO, 0), H - 1);
+        const unsigned ro = (unsigned)W * (unsigned)gyc;
+        Row r;
+        r.a01 = v2f{at(d0 + po, ro, yo), at(d1 + po, ro, yo)};
+        r.a2 = at(d2 + po, ro, yo);
+        r.chain = LOSS ? chain_const : at(dL_dmap + po, ro, yo);
+        r.p1 = at(xp, src.xrow(gyo), xo);
+        r.p2 = at(yp, (unsigned)W * (unsigned)gyo, yo);
+        return r;
+    };
+    Row nr[AHEAD];
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float a = 0;
+    for (int i = 0; i < AHEAD; i++) nr[i] = fetch(i);
+    v2f h01[RING];
+    float h2[RING];
+    for (int base = 0; base < nrows; base += RING) {
 #pragma unroll
-            for (int d = 1; d <= HALO; d++) a += (sd[k][r][cx - d] + sd[k][r][cx + d]) * GAUSS[HALO - d];
-            a += sd[k][r][cx] * GAUSS[HALO];
-            hc[k][r][tx] = a;
-        }
-    }
-    __syncthreads();
-    const int px = x0 + tx, py = y0 + ty;
-    if (px < W && py < H) {
-        const int cy = ty + HALO;
-        float s[3];
+        for (int j = 0; j < RING; j++) {
+            const int rr = base + j;
+            if (rr < nrows) {
+                const int gy = st.y0 - HALO + rr;
+                const bool in = col_in && gy >= 0 && gy < H;  // outside the image: zeros
+                Row r = nr[0];
+                r.chain = in ? r.chain : 0.0f;
+                r.a01 = (in ? r.a01 : v2f{0.0f, 0.0f}) * r.chain;
+                r.a2 = (in ? r.a2 : 0.0f) * r.chain;
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float a = 0;
+                for (int i = 0; i + 1 < AHEAD; i++) nr[i] = nr[i + 1];
+                nr[AHEAD - 1] = fetch(rr + AHEAD);
+                b01[cx] = r.a01; b2[cx] = r.a2;
+                wave_sync();
+                v2f s01 = 0;
+                float s2 = 0;
 #pragma unroll
-            for (int d = 1; d <= HALO; d++) a += (hc[k][cy - d][tx] + hc[k][cy + d][tx]) * GAUSS[HALO - d];
-            a += hc[k][cy][tx] * GAUSS[HALO];
-            s[k] = a;
-        }
-        const float p1 = src.x(px, py, plane), p2 = src.y(px, py, plane);
-        float g = s[0] + 2.0f * p1 * s[1] + p2 * s[2];
-        if (LOSS) {
-            const float df = p1 - p2;
-            g = g + l1_scale * (df > 0.0f ? 1.0f : (df < 0.0f ? -1.0f : 0.0f));
-            gout[ch] = g;
-        } else {
-            out[(size_t)px + (size_t)W * py + P * plane] = g;
-        }
-    }
-  }
-    if (LOSS) {
-        const int px = x0 + tx, py = y0 + ty;
-        if (px < W && py < H) {
-            float* o = out + (size_t)outC * ((size_t)px + (size_t)W * py) + (size_t)blockIdx.z * NCH;
-#pragma unroll
-            for (int ch = 0; ch < NCH; ch++) o[ch] = gout[ch];  // adjacent floats of one pixel
-            // the loss head only sees features[1:3]: the other channels of vpixels (C > 3) get their zeros here, with
-            // the pixel's colour cotangent (a launch of its own for them was 17 us in :rgbd mode)
-            for (int c = NCH; c < outC; c++) o[c] = 0.0f;
+                for (int d = 1; d <= HALO; d++) {
+                    const float w = GAUSS[HALO - d];
+                    s01 += (b01[cx - d] + b01[cx + d]) * w;
+                    s2 += (b2[cx - d] + b2[cx + d]) * w;
+                }
+                wave_sync();
+                h01[j] = s01 + r.a01 * GAUSS[HALO];
+                h2[j] = s2 + r.a2 * GAUSS[HALO];
+                if (rr >= 2 * HALO) {
+                    const v2f v01 = ring_vertical(h01, j);
+                    const float s[3] = {v01.x, v01.y, ring_vertical(h2, j)};
+                    if (own) {
+                        const int py = st.y0 + rr - 2 * HALO;
+                        const float p1 = r.p1, p2 = r.p2;
+                        float g = s[0] + 2.0f * p1 * s[1] + p2 * s[2];
+                        if (LOSS) {
+                            const float df = p1 - p2;
+                            g = g + l1_scale * (df > 0.0f ? 1.0f : (df < 0.0f ? -1.0f : 0.0f));
+                            float* o = &at(out + ch, (unsigned)(outC * W) * (unsigned)py, 4u * (unsigned)(outC * gxc));
+                            o[0] = g;
+                            // the loss head only sees features[1:3]: the other channels of vpixels (C > 3) get their zeros
+                            // here, from the last colour channel's wave (a launch of its own for them was 17 us in :rgbd mode)
+                            if (ch == NPL - 1)
+                                for (int c = 1; c <= outC - NPL; c++) o[c] = 0.0f;
+                        } else {
+                            at(out + po, (unsigned)W * (unsigned)py, yo) = g;
+                        }
+                    }
+                }
+            }
         }
     }
 }
 
 }  // namespace
 
-static dim3 ssim_grid(int W, int H, int planes) {
-    const int n = ((W + GSR_TILE - 1) / GSR_TILE) * ((H + GSR_TILE - 1) / GSR_TILE);
-    return dim3(8 * ((n + 7) / 8), 1, planes);
+// Strip height of a launch.  A wave's cost is 10 halo rows plus its output rows (a halo row costs about 0.4 of an output row:
+// it has no vertical pass), the kernels are VALU-bound once there is a wave to hide another's loads, and a 1080p image is
+// only a few waves per SIMD: what counts is the number of waves the fullest SIMD gets, times a wave's cost.  Pick the height
+// that minimises it; at least three waves per SIMD, so that loads and the LDS round trip of one hide behind the others.
+static int ssim_strip_h(int W, int H, int planes) {
+    static const int n_simd = [] {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+            cus = 256;
+        return 4 * cus;
+    }();
+    const long cols = (long)((W + STRIP_W - 1) / STRIP_W) * planes;
+    int best = 8;
+    long best_cost = -1;
+    for (int h = 8; h <= 64; h++) {
+        const long waves = cols * ((H + h - 1) / h);
+        const long per_simd = (waves + n_simd - 1) / n_simd;
+        const long cost = (per_simd < 3 ? 3 : per_simd) * (h + 4);
+        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = h; }
+    }
+    return best;
+}
+
+template <int SPB>
+static dim3 ssim_grid(int W, int H, int strip_h, int planes) {
+    const int n = ((W + STRIP_W - 1) / STRIP_W) * ((H + strip_h - 1) / strip_h);
+    const int groups = (n + SPB - 1) / SPB;
+    return dim3(8 * ((groups + 7) / 8), 1, planes);
+}
+
+// pairs of `partial` the loss head's forward writes: one per wave of its launch
+size_t SSIM_NAME(gsr_loss_partial_pairs)(int W, int H) {
+    return (size_t)ssim_grid<LOSS_STRIPS>(W, H, ssim_strip_h(W, H, 3), 1).x * 3 * LOSS_STRIPS;
 }
 
 void SSIM_NAME(gsr_launch_ssim_fwd)(hipStream_t s, int W, int H, int CH, int B, const float* img, const float* ref, float C1,
                          float C2, int train, float* ssim_map, float* d0, float* d1, float* d2) {
     PlanarSrc src{img, ref, W, H};
-    hipLaunchKernelGGL((ssim_fwd_kernel<PlanarSrc, false, 1>), ssim_grid(W, H, CH * B), dim3(256), 0, s, src, W, H, C1,
-                       C2, train, ssim_map, d0, d1, d2, (float*)nullptr);
+    const int sh = ssim_strip_h(W, H, CH * B);
+    hipLaunchKernelGGL((ssim_fwd_kernel<PlanarSrc, false, 1, 4>), ssim_grid<4>(W, H, sh, CH * B), dim3(256), 0, s, src, W, H, sh,
+                       C1, C2, train, ssim_map, d0, d1, d2, (float*)nullptr);
 }
 
 void SSIM_NAME(gsr_launch_ssim_bwd)(hipStream_t s, int W, int H, int CH, int B, const float* img, const float* ref,
                          const float* dL_dmap, const float* d0, const float* d1, const float* d2, float* dL_dimg) {
     PlanarSrc src{img, ref, W, H};
-    hipLaunchKernelGGL((ssim_bwd_kernel<PlanarSrc, false, 1>), ssim_grid(W, H, CH * B), dim3(256), 0, s, src, W, H,
+    const int sh = ssim_strip_h(W, H, CH * B);
+    hipLaunchKernelGGL((ssim_bwd_kernel<PlanarSrc, false, 1, 4>), ssim_grid<4>(W, H, sh, CH * B), dim3(256), 0, s, src, W, H, sh,
                        dL_dmap, 0.0f, 0.0f, d0, d1, d2, dL_dimg, 0, (const float*)nullptr, 0, 0.0f, 0.0f, (float*)nullptr);
 }
 
 void SSIM_NAME(gsr_launch_loss_fwd)(hipStream_t s, int W, int H, int C, const float* image, const float* target, float C1,
                          float C2, float* d0, float* d1, float* d2, float* partial) {
     RasterSrc src{image, target, W, H, C};
-    hipLaunchKernelGGL((ssim_fwd_kernel<RasterSrc, true, 3>), ssim_grid(W, H, 1), dim3(256), 0, s, src, W, H, C1, C2, 1,
-                       (float*)nullptr, d0, d1, d2, partial);
+    const int sh = ssim_strip_h(W, H, 3);
+    hipLaunchKernelGGL((ssim_fwd_kernel<RasterSrc, true, 3, LOSS_STRIPS>), ssim_grid<LOSS_STRIPS>(W, H, sh, 1),
+                       dim3(64 * 3 * LOSS_STRIPS), 0, s, src, W, H, sh, C1, C2, 1, (float*)nullptr, d0, d1, d2, partial);
 }
 
 void SSIM_NAME(gsr_launch_loss_bwd)(hipStream_t s, int W, int H, int C, const float* image, const float* target, float lambda,
@@ -339,10 +458,11 @@ void SSIM_NAME(gsr_launch_loss_bwd)(hipStream_t s, int W, int H, int C, const fl
     RasterSrc src{image, target, W, H, C};
     const float count = 3.0f * (float)W * (float)H;
     const float inv_count = 1.0f / count;
-    dim3 g = ssim_grid(W, H, 1);
-    const int n_partial = (int)(g.x * g.y * g.z);  // one pair per workgroup of the forward launch
-    g.x += 1;                                      // + the workgroup that finishes the scalar loss
-    hipLaunchKernelGGL((ssim_bwd_kernel<RasterSrc, true, 3>), g, dim3(256), 0, s, src, W, H,
+    const int sh = ssim_strip_h(W, H, 3);
+    dim3 g = ssim_grid<LOSS_STRIPS>(W, H, sh, 1);
+    const int n_partial = (int)(g.x * 3 * LOSS_STRIPS);  // one pair per wave of the forward launch
+    g.x += 1;                                            // + the workgroup that finishes the scalar loss
+    hipLaunchKernelGGL((ssim_bwd_kernel<RasterSrc, true, 3, LOSS_STRIPS>), g, dim3(64 * 3 * LOSS_STRIPS), 0, s, src, W, H, sh,
                        (const float*)nullptr, -lambda * inv_count, (1.0f - lambda) * inv_count, d0, d1, d2, vpixels,
                        C, partial, n_partial, lambda, inv_count, loss_out);
 }
