@@ -187,7 +187,9 @@ EXPORTS = ["gsr_create", "gsr_destroy", "gsr_release_scene_buffers", "gsr_memory
            "gsr_densify_grad_mean", "gsr_densify_mask", "gsr_compose_rows", "gsr_split_transform", "gsr_reset_opacity", "gsr_morton_codes",
            "gsr_ply_pack_rows", "gsr_ply_unpack_rows", "gsr_count_nonfinite",
            "gsr_bilateral_scratch_bytes", "gsr_bilateral_tv_scratch_bytes", "gsr_bilateral_slice_forward",
-           "gsr_bilateral_slice_backward", "gsr_bilateral_tv", "gsr_bilateral_adam_tail"] + POLICY_EXPORTS
+           "gsr_bilateral_slice_backward", "gsr_bilateral_tv", "gsr_bilateral_adam_tail",
+           "gsr_normal_loss_scratch_bytes", "gsr_normal_loss_forward", "gsr_normal_loss_backward",
+           "gsr_flatten_loss_scratch_bytes", "gsr_flatten_loss"] + POLICY_EXPORTS
 
 _lib = None
 
@@ -274,6 +276,13 @@ def load():
     lib.gsr_bilateral_tv.argtypes = [i32, i32, i32, i32, vp, f32, vp, vp, vp, sz, vp]
     lib.gsr_bilateral_adam_tail.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, i32, f32, f32, C.c_uint32, f32, f32, f32,
                                             vp, vp, sz, vp]
+    lib.gsr_normal_loss_scratch_bytes.argtypes = [i32, i32]
+    lib.gsr_normal_loss_scratch_bytes.restype = sz
+    lib.gsr_normal_loss_forward.argtypes = [i32, i32, i32, vp, C.POINTER(CameraS), f32, vp, vp, vp, vp, sz, vp]
+    lib.gsr_normal_loss_backward.argtypes = [i32, i32, i32, vp, C.POINTER(CameraS), f32, vp, vp, sz, vp]
+    lib.gsr_flatten_loss_scratch_bytes.argtypes = [i32]
+    lib.gsr_flatten_loss_scratch_bytes.restype = sz
+    lib.gsr_flatten_loss.argtypes = [i32, i32, vp, f32, vp, vp, vp, sz, vp]
     lib.gsr_stream_triad.argtypes = [vp, vp, vp, C.c_size_t, f32, vp]
     lib.gsr_ssim_precision.argtypes = [i32]
     lib.gsr_preprocess_form.argtypes = [i32]

@@ -1473,6 +1473,67 @@ int gsr_bilateral_adam_tail(int32_t n_images, int32_t gx, int32_t gy, int32_t gz
     return GSR_OK;
 }
 
+// ---- geometry regularisation (geometry.hip; src/geometry_regularization.jl) ----
+namespace {
+int check_normal_loss_frame(int32_t W, int32_t H, int32_t C) {
+    if (W < 1 || H < 1 || (int64_t)W * H > 0x7FFFFFFF / 8) return fail(GSR_E_INVALID_ARG, "image size %d x %d", W, H);
+    if (C != 8) return fail(GSR_E_INVALID_ARG, "C = %d: the depth-normal loss reads a :rgbdn frame (8 channels)", C);
+    return GSR_OK;
+}
+int check_normal_loss_camera(const gsr_camera* cam) {
+    if (!cam) return fail(GSR_E_INVALID_ARG, "null camera");
+    if (!(cam->focal[0] > 0.0f) || !(cam->focal[1] > 0.0f)) return fail(GSR_E_INVALID_ARG, "focal lengths must be positive");
+    return GSR_OK;
+}
+}  // namespace
+
+size_t gsr_normal_loss_scratch_bytes(int32_t W, int32_t H) {
+    if (W < 1 || H < 1) return 0;
+    return gsr_normal_loss_scratch_floats(W, H) * sizeof(float);
+}
+
+int gsr_normal_loss_forward(int32_t W, int32_t H, int32_t C, const float* image, const gsr_camera* cam, float weight,
+                            float* loss_out, float* stats_out, float* weights_out, void* scratch, size_t scratch_bytes,
+                            void* stream) {
+    int rc;
+    if ((rc = check_normal_loss_frame(W, H, C)) || (rc = check_normal_loss_camera(cam))) return rc;
+    if (!image || !loss_out || !stats_out || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
+    const size_t need = gsr_normal_loss_scratch_bytes(W, H);
+    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the depth-normal loss needs %zu", scratch_bytes, need);
+    gsr_launch_normal_loss_fwd((hipStream_t)stream, W, H, image, cam->focal, cam->principal, weight, loss_out, stats_out,
+                               weights_out, (float*)scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_normal_loss_backward(int32_t W, int32_t H, int32_t C, const float* image, const gsr_camera* cam, float weight,
+                             float* vpixels, const void* scratch, size_t scratch_bytes, void* stream) {
+    int rc;
+    if ((rc = check_normal_loss_frame(W, H, C)) || (rc = check_normal_loss_camera(cam))) return rc;
+    if (!image || !vpixels || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
+    if (image == vpixels) return fail(GSR_E_INVALID_ARG, "vpixels must not be the image");
+    const size_t need = gsr_normal_loss_scratch_bytes(W, H);
+    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the depth-normal loss needs %zu", scratch_bytes, need);
+    gsr_launch_normal_loss_bwd((hipStream_t)stream, W, H, image, cam->focal, cam->principal, weight, vpixels,
+                               (const float*)scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+size_t gsr_flatten_loss_scratch_bytes(int32_t n) { return gsr_flatten_loss_scratch_floats(n) * sizeof(float); }
+
+int gsr_flatten_loss(int32_t n, int32_t scale_dims, const float* scales_raw, float weight, float* loss_out, float* vscales,
+                     void* scratch, size_t scratch_bytes, void* stream) {
+    if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
+    if (scale_dims != 1 && scale_dims != 3) return fail(GSR_E_INVALID_ARG, "scale_dims = %d: 1 (isotropic) or 3", scale_dims);
+    if (!loss_out || (n > 0 && (!scales_raw || !scratch))) return fail(GSR_E_INVALID_ARG, "null array");
+    const size_t need = gsr_flatten_loss_scratch_bytes(n);
+    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the flatten loss needs %zu", scratch_bytes, need);
+    gsr_launch_flatten_loss((hipStream_t)stream, n, scale_dims, scales_raw, weight, loss_out, vscales, (float*)scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
 int gsr_densify_grad_mean(int64_t n, const float* accum, const float* denom, float* grad_out, void* stream) {
     if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
     if (n == 0) return GSR_OK;

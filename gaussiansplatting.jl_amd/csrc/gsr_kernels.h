@@ -250,3 +250,13 @@ void gsr_launch_bilateral_tv(hipStream_t s, int n, int gx, int gy, int gz, const
 void gsr_launch_bilateral_adam_tail(hipStream_t s, int n, int gx, int gy, int gz, float* grids, float* mu, float* nu,
                                     const float* vgrid, int view, const gsr::BilateralTv& tv, const gsr::AdamHyper& h,
                                     float* tv_loss_out, float* partial);
+
+// ---- geometry.hip (compiled with -ffp-contract=off): depth-normal consistency and flatten losses ----
+size_t gsr_normal_loss_scratch_floats(int W, int H);
+void gsr_launch_normal_loss_fwd(hipStream_t s, int W, int H, const float* image, const float* focal, const float* principal,
+                                float weight, float* loss_out, float* stats_out, float* weights_out, float* scratch);
+void gsr_launch_normal_loss_bwd(hipStream_t s, int W, int H, const float* image, const float* focal, const float* principal,
+                                float weight, float* vpixels, const float* scratch);
+size_t gsr_flatten_loss_scratch_floats(int64_t n);
+void gsr_launch_flatten_loss(hipStream_t s, int n, int scale_dims, const float* scales, float weight, float* loss_out,
+                             float* vscales, float* scratch);

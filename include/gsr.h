@@ -628,6 +628,47 @@ GSR_API int gsr_bilateral_adam_tail(int32_t n_images, int32_t gx, int32_t gy, in
                                     float beta1, float beta2, float eps, float* tv_loss_out, void* scratch,
                                     size_t scratch_bytes, void* stream);
 
+/* Geometry regularisation of :rgbdn training (src/geometry_regularization.jl; switched on by `use_normal_loss`, used by
+ * `step!`, training.jl:625-733): the only producer of a cotangent on the depth, alpha and normal channels.  The frame is
+ * the rasterizer's :rgbdn image (8,W,H): channels 0-2 rgb, 3 blended depth D, 4 alpha, 5-7 the blended normal; C must
+ * be 8.  The pixel rays are computed in the kernels from cam->focal and cam->principal by the fp32 expression of
+ * `pixel_rays` (geometry_regularization.jl:53-62); nothing else of `cam` is read.  All array pointers device.  Every
+ * result is run-to-run bit-identical: no float atomics anywhere; nothing is read back by the host.
+ *
+ * gsr_normal_loss_forward  : weight · depth_normal_consistency_loss (geometry_regularization.jl:87-183) into *loss_out,
+ *                            (Σw, count) of the valid centres into stats_out[0..1], and, unless weights_out is NULL, the
+ *                            detached weight map (W,H) (0 on the border and on invalid centres).  The "too little
+ *                            evidence" gate (count < 64 or Σw < 16; W <= 2 or H <= 2) is applied on the device: loss 0.
+ *                            Every decision of the validity mask is the reference's fp32 expression.  One intended
+ *                            deviation: a centre with w = 0 contributes exactly nothing, also when its stencil holds
+ *                            NaN / Inf (the reference's `sum(w .* (1 .- cosθ))` would turn NaN on 0 · NaN).
+ *                            scratch: gsr_normal_loss_scratch_bytes(W, H) bytes; the backward of the same image reads it.
+ * gsr_normal_loss_backward : ADDS weight · ∂loss/∂(D, alpha, normal) onto channels 3..7 of vpixels (8,W,H); channels 0..2
+ *                            are not touched, pixels that receive nothing are not written, a gated view adds nothing.  So
+ *                            the loss head's zeros, or another depth term, compose with it.  `scratch` is the one
+ *                            gsr_normal_loss_forward filled for the same image, camera and (any) weight: the gate and the
+ *                            normaliser are read from it on the device.  vpixels must not be the image.  A vpixels this
+ *                            was added onto must NOT go to gsr_backward with GSR_GRADS_COLOR_COTANGENT.
+ * gsr_flatten_loss         : weight · flatten_loss(scales) (geometry_regularization.jl:197-211) = weight · mean_i
+ *                            exp(min_j scales_raw[j, i]) into *loss_out (0 for n = 0); scales_raw (scale_dims, N), raw
+ *                            (pre-exp), scale_dims 1 or 3.  Unless vscales is NULL, the gradient w.r.t. the ACTIVATED
+ *                            scale — the constant weight / n on the first axis that holds the minimum (the reference's
+ *                            cumsum tie-break; row 0 for scale_dims = 1) — is ADDED onto vscales (3,N), the array
+ *                            gsr_backward wrote: gsr_prologue_backward / gsr_trainer_tail_step then yield the reference's
+ *                            weight · exp(s) / n on the raw scale.  The fused gsr_backward_trainer_tail never
+ *                            materialises ∇scales: steps with the regulariser on run gsr_backward + gsr_flatten_loss +
+ *                            gsr_trainer_tail_step.  scratch: gsr_flatten_loss_scratch_bytes(n) bytes (may be NULL for
+ *                            n = 0). */
+GSR_API size_t gsr_normal_loss_scratch_bytes(int32_t W, int32_t H);
+GSR_API int gsr_normal_loss_forward(int32_t W, int32_t H, int32_t C, const float* image, const gsr_camera* cam, float weight,
+                                    float* loss_out, float* stats_out, float* weights_out, void* scratch,
+                                    size_t scratch_bytes, void* stream);
+GSR_API int gsr_normal_loss_backward(int32_t W, int32_t H, int32_t C, const float* image, const gsr_camera* cam, float weight,
+                                     float* vpixels, const void* scratch, size_t scratch_bytes, void* stream);
+GSR_API size_t gsr_flatten_loss_scratch_bytes(int32_t n);
+GSR_API int gsr_flatten_loss(int32_t n, int32_t scale_dims, const float* scales_raw, float weight, float* loss_out,
+                             float* vscales, void* scratch, size_t scratch_bytes, void* stream);
+
 /* New: the SH-coefficient gradient of a batch of views from the factored
  * per-view colour cotangents written by gsr_backward (gsr_grads.vcolors):
  *   vshs[:, k, i] = Σ_v basis_k(normalize(means[:, i] - camera_centers[:, v])) * vcolors_all[:, i, v]

@@ -423,4 +423,86 @@ function bilateral_adam_tail!(bgrid, ∇grid_view, view::Integer; tv_weight::Flo
     return tv
 end
 
+# ---- geometry regularisation (src/geometry_regularization.jl; `use_normal_loss`, training.jl:625-733) ----
+
+# the kernels read focal and principal only (the rays of `pixel_rays`)
+function _camera_only(camera::Camera)
+    K = camera.intrinsics
+    R = SMatrix{3, 3, Float32}(camera.w2c[1:3, 1:3]); t = SVector{3, Float32}(camera.w2c[1:3, 4])
+    return GsrCamera(Tuple(R), Tuple(t), Tuple(K.focal), Tuple(K.principal), Tuple(camera.camera_center),
+        dptr(nothing), dptr(nothing))
+end
+
+function _normal_loss_scratch(w, h)
+    nb = ccall((:gsr_normal_loss_scratch_bytes, LIB), Csize_t, (Int32, Int32), w, h)
+    return AMDGPU.zeros(UInt8, max(Int(nb), 4))
+end
+
+# weight · depth_normal_consistency_loss (geometry_regularization.jl:87-183) of the (8,W,H) :rgbdn frame `image`
+# (channel 4 = blended depth, 5 = alpha, 6:8 = the blended normal, 1-based) on gsr_normal_loss_forward: a device scalar;
+# the rays are computed in the kernel from `camera`, the "too little evidence" gate is applied on the device.
+# Returns (loss, scratch): `scratch` is what depth_normal_loss_backward! of the same image reads.
+function depth_normal_loss(image::ROCArray{Float32, 3}, camera::Camera; weight::Float32 = 0.05f0,
+        scratch = _normal_loss_scratch(size(image, 2), size(image, 3)))
+    loss = AMDGPU.zeros(Float32, 1); stats = AMDGPU.zeros(Float32, 2)
+    check(ccall((:gsr_normal_loss_forward, LIB), Cint,
+        (Int32, Int32, Int32, Ptr{Float32}, Ref{GsrCamera}, Cfloat, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid},
+         Csize_t, Ptr{Cvoid}),
+        size(image, 2), size(image, 3), size(image, 1), dptr(image), _camera_only(camera), weight, dptr(loss), dptr(stats),
+        dptr(nothing), Ptr{Cvoid}(UInt(pointer(scratch))), Csize_t(length(scratch)), hipstream()))
+    return loss, scratch
+end
+
+# ADDS weight · ∂loss/∂(depth, alpha, normal) onto channels 4:8 of `vpixels` (8,W,H) in place (gsr_normal_loss_backward):
+# no float atomics, run-to-run bit-identical.  A `vpixels` this was added onto must go to the backward WITHOUT
+# `color_cotangent = true`.
+function depth_normal_loss_backward!(vpixels::ROCArray{Float32, 3}, image::ROCArray{Float32, 3}, camera::Camera, scratch;
+        weight::Float32 = 0.05f0)
+    size(vpixels) == size(image) || error("vpixels must have the image's size")
+    check(ccall((:gsr_normal_loss_backward, LIB), Cint,
+        (Int32, Int32, Int32, Ptr{Float32}, Ref{GsrCamera}, Cfloat, Ptr{Float32}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        size(image, 2), size(image, 3), size(image, 1), dptr(image), _camera_only(camera), weight, dptr(vpixels),
+        Ptr{Cvoid}(UInt(pointer(scratch))), Csize_t(length(scratch)), hipstream()))
+    return vpixels
+end
+
+function ChainRulesCore.rrule(::typeof(depth_normal_loss), image::ROCArray{Float32, 3}, camera::Camera;
+        weight::Float32 = 0.05f0)
+    loss, scratch = depth_normal_loss(image, camera; weight)
+    function _depth_normal_loss_pullback(Δ)
+        ∇image = AMDGPU.zeros(Float32, size(image))
+        depth_normal_loss_backward!(∇image, image, camera, scratch; weight)
+        δ = unthunk(Δ)[1]
+        return NoTangent(), ∇image .* δ, NoTangent()
+    end
+    return (loss, scratch), _depth_normal_loss_pullback
+end
+
+# weight · flatten_loss(scales) (geometry_regularization.jl:197-211) over the raw (3,N) / (1,N) scales as a device
+# scalar (gsr_flatten_loss); with `vscales` (3,N) — the ∇scales gsr_backward wrote, w.r.t. the ACTIVATED scale — the
+# constant weight / N is added onto it on each Gaussian's first minimal axis.  The fused backward_trainer_tail! has no
+# gradient arrays: steps with the regulariser on run ∇rasterize + flatten_loss!(...; vscales) + trainer_tail_step!.
+function flatten_loss!(scales::ROCArray{Float32, 2}; weight::Float32 = 0.005f0, vscales = nothing)
+    n = size(scales, 2)
+    loss = AMDGPU.zeros(Float32, 1)
+    nb = ccall((:gsr_flatten_loss_scratch_bytes, LIB), Csize_t, (Int32,), n)
+    scratch = AMDGPU.zeros(UInt8, max(Int(nb), 4))
+    check(ccall((:gsr_flatten_loss, LIB), Cint,
+        (Int32, Int32, Ptr{Float32}, Cfloat, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        n, size(scales, 1), dptr(scales), weight, dptr(loss), dptr(vscales), Ptr{Cvoid}(UInt(pointer(scratch))),
+        Csize_t(length(scratch)), hipstream()))
+    return loss
+end
+
+function ChainRulesCore.rrule(::typeof(flatten_loss!), scales::ROCArray{Float32, 2}; weight::Float32 = 0.005f0)
+    loss = flatten_loss!(scales; weight)
+    function _flatten_loss_pullback(Δ)
+        v = AMDGPU.zeros(Float32, 3, size(scales, 2))
+        flatten_loss!(scales; weight, vscales = v)
+        δ = unthunk(Δ)[1]
+        return NoTangent(), v[1:size(scales, 1), :] .* exp.(scales) .* δ   # the prologue's pullback: ∂exp(s)/∂s
+    end
+    return loss, _flatten_loss_pullback
+end
+
 end # module
