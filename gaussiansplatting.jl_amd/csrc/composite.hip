@@ -521,12 +521,17 @@ __global__ __launch_bounds__(64, GSR_BWD_MINWAVES) void composite_bwd_kernel(int
             for (int c = 0; c < VC; c++) col[c] = 0.0f;
             unsigned long long any_active = 0ull;
             const uint32_t rowbits = __builtin_amdgcn_readfirstlane(__float_as_uint(c2.w)) >> (ROWS * wave);
+            // The footprint bits of the four pixel groups (readfirstlane of the already-uniform bits: tells the compiler that the
+            // group skip below, and everything that merges behind it — the ballot accumulator —, is scalar; without it the test and
+            // `any_active` were VALU).  All four HERE, in the block that reads the mask: there the readfirstlane folds into an
+            // s_and; written at the skip itself, the ones of groups 2 and 3 sat in later blocks and stayed instructions — the
+            // mask copied to a VGPR and read back, 3 VALU instructions per instance (composite_bwd 669 -> 648 us).
+            int group_bits[PPL];
+#pragma unroll
+            for (int q = 0; q < PPL; q++) group_bits[q] = __builtin_amdgcn_readfirstlane((int)((rowbits >> (4 * q)) & 0xFu));
 #pragma unroll
             for (int q = 0; q < PPL; q++) {
-                // pixel rows 4q..4q+3 of this wave: untouched by the splat's footprint -> wave-uniform skip
-                // (readfirstlane of the already-uniform bits: tells the compiler that this branch, and everything that
-                // merges behind it — the ballot accumulator —, is scalar; without it the test and `any_active` were VALU)
-                if (__builtin_amdgcn_readfirstlane((int)((rowbits >> (4 * q)) & 0xFu)) == 0) continue;
+                if (group_bits[q] == 0) continue;  // pixel rows 4q..4q+3 of this wave: untouched by the footprint -> wave-uniform skip
                 const float fyq = FY_REBUILD ? fy[0] + (float)(4 * q) : fy[FY_REBUILD ? 0 : q];
                 const float dy = a.y - fyq, dy2 = __fmul_rn(dy, dy);
                 const float sigma = sigma_of(sx, b.x, dy, dy2);

@@ -83,6 +83,14 @@ KERNEL(k_readlane, asm volatile("v_readlane_b32 s20, %0, 3\n v_readlane_b32 s21,
                                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : : "s20", "s21", "s22", "s23");)
 KERNEL(k_mov, asm volatile("v_mov_b32 %0, %4\n v_mov_b32 %1, %4\n v_mov_b32 %2, %4\n v_mov_b32 %3, %4"
                            : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(c));)
+// the zero-fill forms of composite_bwd_kernel's per-instance accumulator clears: an inline-constant v_mov_b32, and the 64-bit
+// move that clears a register pair (DESIGN.md §4.2 "accumulator clears")
+KERNEL(k_mov_zero, asm volatile("v_mov_b32 %0, 0\n v_mov_b32 %1, 0\n v_mov_b32 %2, 0\n v_mov_b32 %3, 0"
+                                : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));)
+KERNEL(k_mov_b64, asm volatile("v_mov_b64 %0, %4\n v_mov_b64 %1, %4\n v_mov_b64 %2, %4\n v_mov_b64 %3, %4"
+                               : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3) : "v"(cc));)
+KERNEL(k_mov_b64_zero, asm volatile("v_mov_b64 %0, 0\n v_mov_b64 %1, 0\n v_mov_b64 %2, 0\n v_mov_b64 %3, 0"
+                                    : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3));)
 KERNEL(k_salu_mix, asm volatile("v_mul_f32 %0, %0, %4\n s_and_b64 s[20:21], s[20:21], exec\n v_mul_f32 %1, %1, %4\n s_or_b64 s[22:23], s[22:23], exec"
                                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(c) : "s20", "s21", "s22", "s23");)
 KERNEL(k_fma_dep, asm volatile("v_fma_f32 %0, %0, %4, %4\n v_fma_f32 %0, %0, %4, %4\n v_fma_f32 %0, %0, %4, %4\n v_fma_f32 %0, %0, %4, %4"
@@ -107,7 +115,8 @@ int main() {
         {"1 exp + 3 mul", k_exp_mul3}, {"v_cndmask (sgpr mask)", k_cndmask}, {"v_cmp_le_f32 -> vcc", k_cmp_vcc},
         {"v_cmp_le_f32 -> sgpr pair", k_cmp_sgpr}, {"v_cmp_le_u32 -> vcc", k_cmp_u32}, {"1 cmp + 3 mul", k_cmp_mul3},
         {"v_add_f32_dpp row_ror", k_dpp}, {"v_permlane32_swap", k_swap32}, {"v_readlane_b32", k_readlane},
-        {"2 mul + 2 salu", k_salu_mix}, {"v_fma dependent chain", k_fma_dep}, {"v_mul dependent chain", k_mul_dep}};
+        {"2 mul + 2 salu", k_salu_mix}, {"v_fma dependent chain", k_fma_dep}, {"v_mul dependent chain", k_mul_dep},
+        {"v_mov_b32 v, 0", k_mov_zero}, {"v_mov_b64 (vgpr pair)", k_mov_b64}, {"v_mov_b64 v[n:n+1], 0", k_mov_b64_zero}};
     const int max_blocks = cus * 4 * 8;
     float* out;
     unsigned long long* cyc;
@@ -134,7 +143,7 @@ int main() {
         printf("  %-28s wall %6.3f  cyc %6.3f   eff. clock %4.2f GHz  (%.3f ms)\n", c.name, ms * 1e-3 * clk / instr_per_simd,
                med / instr_per_simd, med / (ms * 1e-3) / 1e9, ms);
     };
-    for (int wps : {1, 2, 4, 8}) {  // waves per SIMD
+    for (int wps : {1, 2, 4, 6, 8}) {  // waves per SIMD (6: composite_bwd_kernel's :rgb occupancy)
         printf("--- %d wave(s) per SIMD: cycles per wave64 instruction per SIMD\n", wps);
         for (auto& c : cases) run(c, wps, 0);
     }
