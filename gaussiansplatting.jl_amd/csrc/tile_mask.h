@@ -4,51 +4,47 @@
 #include <stdint.h>
 
 // Conservative footprint masks of an instance inside its 16x16 tile.
-//   bits 0..15  row mask: bit r is set unless NO pixel of row r of the tile can reach
-//               alpha >= 1/255 (render.jl:95), i.e. unless the ellipse {sigma <= ln(255*opacity)}
-//               misses the row's pixel centres;
-//   bits 16..19 quadrant mask: bit 16 + 2*qy + qx for the 8x8 quadrant (qx, qy), from the same
-//               per-row x-intervals tested against the quadrant's columns.
+//   bits 0..15  row mask: bit r is set unless NO pixel of row r of the tile can pass the kernels' blend test
+//               bits(sigma) < X (blend_threshold_bits below: alpha >= 1/255, render.jl:95);
+//   bits 16..19 quadrant mask: bit 16 + 2*qy + qx for the 8x8 quadrant (qx, qy): some row of the quadrant's eight can pass
+//               the test inside the quadrant's eight columns.
 // The composite kernels use them only to skip work; every surviving (pixel, splat) pair still
 // runs the exact test, so the slack below never changes a result.
-__device__ __forceinline__ uint32_t instance_row_mask(const float4 g0, const float4 g1, int X0, int Y0) {
-    const float mx = g0.x, my = g0.y, a = g0.z, b = g0.w, c = g1.x, o = g1.y;
-    const float tau = __logf(255.0f * o) + 2e-3f;  // sigma <= tau  <=>  alpha >= 1/255 (with slack)
-    if (!(tau >= 0.0f)) return 0u;                  // opacity < 1/255: never blended
-    if (!(a > 0.0f)) return 0xFFFFFu;               // degenerate conic: no culling
-    // dx = mx - px: whole tile [X0, X0+15], left half [X0, X0+7], right half [X0+8, X0+15].
-    // A row's x-interval is centre(dy) +- hw(dy) with centre = -b*dy/a, hw = sqrt(disc)/a,
-    // disc = (b^2 - a*c)*dy^2 + 2*a*tau.  One slack for all rows of the instance — 0.01 px + 1e-4 of
-    // the largest |centre| + hw any row can have, on top of tau's 2e-3; fp32 rounding of these
-    // expressions is ~1e-5 px — is folded into the thresholds.
-    const float inv_a = 1.0f / a;
-    const float k0 = 2.0f * a * tau, k2 = b * b - a * c;
+//
+// A row is tested once per half (dx = mx - px: left half [mx - X0 - 7, mx - X0], right half [mx - X0 - 15, mx - X0 - 8]):
+// sigma is a convex parabola in dx, so its minimum over a column range sits at the vertex -(b/a)·dy clamped to the range,
+// and the half is flagged when that minimum is at most the threshold,
+//     s = sigma(x*, dy) - ts < 0,    x* = med3(-(b/a)·dy, lo, hi),    ts = S + 2e-3 + 4e-6·M,    S = float(X - 1):
+// S is the largest sigma that passes the test, and M = ha·Xm² + |b|·Xm·Ym + hc·Ym² (Xm, Ym: the largest |dx|, |dy| of the
+// tile's pixel centres) bounds every term of either evaluation of sigma — fp32 leaves a few ulps (6e-8) of it in the kernels'
+// sigma and in s.  An error d of the vertex (the hardware reciprocal's ulp) moves the minimum by a·d²/2: second order.
+// No sqrt, no compare, no select and no branch per row: mul / fma / v_med3_f32, and the sign bit of s shifted into the
+// half's 16-bit mask by one v_alignbit_b32 (rows walked 15 -> 0; a row the parabola misses shifts in a 0).
+__device__ __forceinline__ uint32_t instance_row_mask(const float4 g0, const float4 g1, uint32_t X, int X0, int Y0) {
+    const float mx = g0.x, my = g0.y, a = g0.z, b = g0.w, c = g1.x;
+    const float ha = 0.5f * a, hc = 0.5f * c;
+    const float l_hi = mx - (float)X0, l_lo = mx - (float)(X0 + 7);         // the kernels' own dx at the halves' end columns
+    const float r_hi = mx - (float)(X0 + 8), r_lo = mx - (float)(X0 + 15);
     const float dy0 = my - (float)Y0;
-    const float dymax = fmaxf(fabsf(dy0), fabsf(dy0 - 15.0f));
-    const float slack = 0.01f + 1e-4f * (fabsf(b) * inv_a * dymax + __fsqrt_rn(k0) * inv_a);
-    const float dx_hi = mx - (float)X0;
-    const float t_lo = dx_hi - 15.0f - slack;   // hi >= t_lo  <=> reaches the tile's last column
-    const float t_hi = dx_hi + slack;           // lo <= t_hi  <=> reaches the tile's first column
-    const float t_left = dx_hi - 7.0f - slack;  // hi >= t_left  (with lo <= t_hi): left half
-    const float t_right = dx_hi - 8.0f + slack; // lo <= t_right (with hi >= t_lo): right half
-    const float thr = -1e-3f * (k0 + (b * b + fabsf(a * c)) * dymax * dymax);  // numerically on the boundary: keep
-    uint32_t m = 0;
+    const float xm = fmaxf(fabsf(l_hi), fabsf(r_lo)), ym = fmaxf(fabsf(dy0), fabsf(dy0 - 15.0f));
+    const float M = ha * (xm * xm) + fabsf(b) * (xm * ym) + hc * (ym * ym);
+    const float ts = __uint_as_float(X - 1u) + 2e-3f + 4e-6f * M;
+    const float nboa = -b * __builtin_amdgcn_rcpf(a);
+    uint32_t ml = 0, mr = 0;
 #pragma unroll
-    for (int r = 0; r < 16; r++) {
+    for (int r = 15; r >= 0; r--) {
         const float dy = dy0 - (float)r;
-        const float disc = k2 * (dy * dy) + k0;
-        if (disc > thr) {
-            const float hw = __fsqrt_rn(fmaxf(disc, 0.0f)) * inv_a;
-            const float centre = -(b * dy) * inv_a;
-            const float lo = centre - hw, hi = centre + hw;
-            if (hi >= t_lo && lo <= t_hi) {
-                const uint32_t qrow = r < 8 ? 16u : 18u;
-                m |= 1u << r;
-                if (hi >= t_left) m |= 1u << qrow;
-                if (lo <= t_right) m |= 1u << (qrow + 1);
-            }
-        }
+        const float v = nboa * dy, bdy = b * dy;
+        const float k = __fmaf_rn(dy, hc * dy, -ts);
+        const float xl = __builtin_amdgcn_fmed3f(v, l_lo, l_hi), xr = __builtin_amdgcn_fmed3f(v, r_lo, r_hi);
+        const float sl = __fmaf_rn(xl, __fmaf_rn(ha, xl, bdy), k), sr = __fmaf_rn(xr, __fmaf_rn(ha, xr, bdy), k);
+        ml = __builtin_amdgcn_alignbit(ml, __float_as_uint(sl), 31);  // (ml << 1) | sign(sl)
+        mr = __builtin_amdgcn_alignbit(mr, __float_as_uint(sr), 31);
     }
+    uint32_t m = (ml | mr) | ((ml & 0xFFu) ? 1u << 16 : 0u) | ((mr & 0xFFu) ? 1u << 17 : 0u) |
+                 ((ml & 0xFF00u) ? 1u << 18 : 0u) | ((mr & 0xFF00u) ? 1u << 19 : 0u);
+    if (!(a > 0.0f)) m = 0xFFFFFu;  // degenerate conic: no culling
+    if (X == 0u) m = 0u;            // not even sigma = +0 passes (opacity < 1/255): never blended
     return m;
 }
 

@@ -46,7 +46,7 @@ __device__ __forceinline__ InstanceVals instance_vals_of(const InstanceRaw& r, i
     const uint32_t dense = (x1 - x0) * (y1 - y0) <= GSR_DENSE_RECT;
     const uint32_t rank = dense ? (uint32_t)__popc(__float_as_uint(rec.q3.w) & ((1u << (k & 31u)) - 1u)) : k;
     const uint32_t slot = r.bpre + __float_as_uint(rec.q2.w) + rank;
-    const uint32_t mask_bits = instance_row_mask(rec.q0, rec.q1, X0, Y0);
+    const uint32_t mask_bits = instance_row_mask(rec.q0, rec.q1, __float_as_uint(rec.q3.z), X0, Y0);
     // (:rgb, CH == 3: the blend-test threshold in place of the depth, which only the :rgbd / :rgbdn features use;
     //  otherwise in v3.w)
     const float X = rec.q3.z;  // (bit pattern)
