@@ -20,6 +20,7 @@
 #include "gsr_kernels.h"
 #include "tile_mask.h"
 #include "tile_sort_device.h"
+#include "wave_reduce.h"
 
 namespace {
 
@@ -32,12 +33,7 @@ using gsr_sort::wave_sort_and_emit;
 // barriers per array instead of four per 1024 elements (this kernel sits before the host sync).
 __device__ __forceinline__ uint32_t block_exclusive_scan_1024(uint32_t v, uint32_t* wave_sums, uint32_t& total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
+    const uint32_t x = gsr::wave_inclusive_scan(v, lane);
     __syncthreads();  // wave_sums free for reuse
     if (lane == 63) wave_sums[wave] = x;
     __syncthreads();
@@ -81,12 +77,7 @@ __device__ __forceinline__ void tile_order_body(int n_tiles, const uint32_t* __r
     }
     __syncthreads();
     const uint32_t v = hist[tid];
-    uint32_t x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
+    const uint32_t x = gsr::wave_inclusive_scan(v, lane);
     if (lane == 63) wave_sums[wave] = x;
     __syncthreads();
     uint32_t wave_off = 0;

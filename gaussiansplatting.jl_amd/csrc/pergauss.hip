@@ -206,6 +206,89 @@ __device__ __forceinline__ void gaussian_normal(const M33& Rw, const M33& Rg, co
 }
 
 // ---------------------------------------------------------------------------------
+// The FLATTENED walk of preprocess_kernel's binning (both forms).  In scene order a wave's slowest lane has 13.6 pair
+// requests at config 3 and the average lane 3.9 — a per-lane walk runs at 28 % lane efficiency.  Instead every lane
+// announces its count, an owner table in LDS maps item -> lane (wave-local, no barrier), and the wave works its ~250 items
+// off 64 at a time, each lane fetching its item's Gaussian with ds_bpermute.  One item = one aligned tile pair of one rect
+// row = (at most) one 64-bit atomic on the pair's counter word.
+// ---------------------------------------------------------------------------------
+// Pairs are aligned on the LINEAR tile index t = y * grid_x + x: a row of w tiles starting on an even t holds ceil(w / 2) of
+// them, on an odd t floor(w / 2) + 1; on grids of odd width the rows of a rect alternate between the two.
+struct RowPairs {
+    int pa, pb;  // pairs in the rect's rows 0, 2, 4 ... and in its rows 1, 3, 5 ...
+    __device__ __forceinline__ int per_two_rows() const { return pa + pb; }
+    __device__ __forceinline__ int in_rows(int h) const { return ((h + 1) >> 1) * pa + (h >> 1) * pb; }
+};
+// t0: linear index of the rect's first tile, w: its width in tiles
+__device__ __forceinline__ RowPairs row_pairs(int t0, int w, int grid_x) {
+    const int t0b = t0 + grid_x;
+    return {((t0 + w - 1) >> 1) - (t0 >> 1) + 1, ((t0b + w - 1) >> 1) - (t0b >> 1) + 1};
+}
+// multiplier of the small division q / ppr = (q * mul) >> 8 (q < 16, ppr <= 16: exact); 0 for a lane without items
+__device__ __forceinline__ uint32_t pair_div_mul(int ppr) { return ppr > 0 ? (256u + (uint32_t)ppr - 1u) / (uint32_t)ppr : 0u; }
+
+// "Announce": lane `lane` owns `cnt` items.  Scan the counts over the wave, fill the wave's owner table (item -> lane) and make
+// it visible to the wave.  Returns the index of this lane's first item; ftotal = the wave's item count.
+__device__ __forceinline__ uint32_t announce_items(uint8_t* own /* the wave's table */, int cnt, int lane, uint32_t& ftotal) {
+    const uint32_t x = gsr::wave_inclusive_scan((uint32_t)cnt, lane);
+    const uint32_t fpre = x - (uint32_t)cnt;
+    ftotal = __shfl(x, 63);
+    for (int k = 0; k < cnt; k++) own[fpre + k] = (uint8_t)lane;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    return fpre;
+}
+
+// One decoded item.  The owner lane packs its rect as rlo = x0 | y0 << 16 and rhi = x1 | pair_div_mul(pairs per two rows) << 16
+// (BANDED: y0 = the first row inside the band, and bits 26..31 of rhi = the mask bit of the clipped rect's first tile,
+// (y0 - rect's y0) * w <= 32).
+struct FlatItem {
+    int src;            // owner lane
+    uint32_t t;         // the pair's even tile (linear index; may lie left of the rect)
+    int xe, y;          // ... and its tile coordinates
+    bool va, vb;        // the even / odd tile belongs to the rect (both false on a lane past the last item)
+    uint32_t kka, kkb;  // their bits in the emitted mask (row-major tile index inside the FULL rect, mod 32)
+};
+// item number `itu` of the wave's ftotal (> 0) items; every lane of the wave runs every trip — a ds_bpermute reads zero from
+// a lane that is switched off
+template <bool BANDED>
+__device__ __forceinline__ FlatItem flat_item(const uint8_t* own, uint32_t itu, uint32_t ftotal, uint32_t fpre, uint32_t rlo,
+                                              uint32_t rhi, int grid_x) {
+    FlatItem f;
+    const bool on = itu < ftotal;
+    const uint32_t it = on ? itu : ftotal - 1u;
+    f.src = own[it];
+    const uint32_t q = it - __shfl(fpre, f.src);
+    const uint32_t lo = __shfl(rlo, f.src), hi = __shfl(rhi, f.src), skb = BANDED ? hi >> 26 : 0u;
+    const int x0 = (int)(lo & 0xFFFFu), y0 = (int)(lo >> 16), x1 = (int)(hi & 0xFFFFu);
+    const int w = x1 - x0, t0 = y0 * grid_x + x0;
+    const RowPairs rp = row_pairs(t0, w, grid_x);
+    const int r2 = (int)((q * (BANDED ? (hi >> 16) & 0x3FFu : hi >> 16)) >> 8), rem = (int)q - r2 * rp.per_two_rows();  // (q < 16: exact)
+    const int row = 2 * r2 + (rem >= rp.pa ? 1 : 0), pc = rem - (rem >= rp.pa ? rp.pa : 0);
+    f.y = y0 + row;
+    const int te = (((t0 + row * grid_x) >> 1) + pc) << 1;
+    f.xe = te - f.y * grid_x;
+    f.t = (uint32_t)te;
+    f.va = on && f.xe >= x0;
+    f.vb = on && f.xe + 1 < x1;
+    f.kka = (skb + (uint32_t)(row * w + (f.xe - x0))) & 31u;
+    f.kkb = (skb + (uint32_t)(row * w + (f.xe + 1 - x0))) & 31u;
+    return f;
+}
+
+// The footprint tests of an item's two tiles on the owner's (broadcast) floats: exact-cull mode — a tile none of whose pixels
+// can reach alpha >= 1/255 gets no instance (the reference keeps it and skips it pixel by pixel, render.jl:95).
+__device__ __forceinline__ void item_may_touch(const GsrCam& cam, const FlatItem& f, const float m2[2], const float conic[3],
+                                               float tau, uint32_t& c0, uint32_t& c1) {
+    const float smx = __shfl(m2[0], f.src), smy = __shfl(m2[1], f.src);
+    const float sa = __shfl(conic[0], f.src), sb = __shfl(conic[1], f.src), sc = __shfl(conic[2], f.src);
+    const float stau = __shfl(tau, f.src);
+    c0 = 0u; c1 = 0u;
+    if (f.va) c0 = (!cam.exact_cull || tile_may_touch(smx, smy, sa, sb, sc, stau, f.xe * GSR_TILE, f.y * GSR_TILE)) ? 1u : 0u;
+    if (f.vb) c1 = (!cam.exact_cull || tile_may_touch(smx, smy, sa, sb, sc, stau, (f.xe + 1) * GSR_TILE, f.y * GSR_TILE)) ? 1u : 0u;
+}
+
+// ---------------------------------------------------------------------------------
 // preprocess: project! (projection.jl:69-129) + spherical_harmonics!
 // (spherical_harmonics.jl:12-17,41-74) + count_tiles_per_gaussian! (utils.jl:131-141),
 // and the per-tile occupancy histogram that replaces cumsum!/duplicate/sort-by-tile.
@@ -383,125 +466,55 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
     // and stores its (depth bits << 32 | id) key there — the counters end up holding the
     // reference's per-tile counts, and no separate count / scan / scatter pass over the
     // instances exists.  Horizontally adjacent tiles are consecutive 32-bit counters, so an
-    // aligned pair is served by ONE 64-bit atomic; up to 8 are kept in flight before their
-    // keys are stored (a returning device-scope atomic is a ~2 us round trip to the memory
-    // side).  A position >= bin_cap is not stored: the host sees max count > capacity in the
-    // scan's totals, grows the bins and repeats the pass (first view / a much denser view).
-    // exact-cull mode: a tile none of whose pixels can reach alpha >= 1/255 gets no
-    // instance (the reference keeps it and skips it pixel by pixel, render.jl:95).
+    // aligned pair is served by ONE 64-bit atomic; two rounds of them are kept in flight per
+    // lane before their keys are stored (a returning device-scope atomic is a ~2 us round trip
+    // to the memory side).  A position >= bin_cap is not stored: the host sees max count >
+    // capacity in the scan's totals, grows the bins and repeats the pass (first view / a much
+    // denser view).
 #ifdef GSR_PRE_NO_BINNING
     // (A/B builds only — tools/experiments/r06_preprocess_floor.py: projection + SH + records without any instance, the floor under
     //  every re-formed binning)
     if (!SCATTER) { area = 0u; rmax[0] = rmin[0]; rmax[1] = rmin[1]; }
 #endif
-    const uint64_t key = ((uint64_t)__float_as_uint(mc_z) << 32) | (uint32_t)i;
-    // the rect's aligned tile pairs in row-major order: visit(even tile index, bit 0: even tile emitted, bit 1: odd tile)
-    // (rects of more than EMIT_COOP tiles are emitted by the whole wave below)
-    auto walk = [&](auto&& visit, bool set_emitted) {
-        uint32_t kk = 0u;
-        for (int y = rmin[1]; y < rmax[1]; y++) {
-            int x = rmin[0];
-            while (x < rmax[0]) {
-                const int t = y * cam.grid_x + x;
-                const bool odd = t & 1;
-                const bool pair = !odd && x + 1 < rmax[0];
-                uint32_t c0, c1 = 0u;
-                if (!set_emitted && area <= 32u) {  // the second walk of the AGG form: the first one's results
-                    c0 = (emitted >> (kk & 31u)) & 1u;
-                    if (pair) c1 = (emitted >> ((kk + 1u) & 31u)) & 1u;
-                } else {
-                    c0 = (!cam.exact_cull || tile_may_touch(m2[0], m2[1], conic[0], conic[1], conic[2], tau, x * GSR_TILE,
-                                                            y * GSR_TILE)) ? 1u : 0u;
-                    if (pair)
-                        c1 = (!cam.exact_cull || tile_may_touch(m2[0], m2[1], conic[0], conic[1], conic[2], tau,
-                                                               (x + 1) * GSR_TILE, y * GSR_TILE)) ? 1u : 0u;
-                }
-                // (bit kk = the rect's row-major tile index: the walk visits the tiles in exactly that order; only read
-                //  back when area <= DENSE_RECT)
-                if (set_emitted) emitted |= (c0 | (c1 << 1)) << (kk & 31u);
-                kk += pair ? 2u : 1u;
-                if (c0 | c1) visit((uint32_t)(t & ~1) /* aligned pair */, odd ? (c0 << 1) : (c0 | (c1 << 1)));
-                x += pair ? 2 : 1;
-            }
-        }
-    };
-    // FLATTENED walks (both forms, below).  In
-    // scene order a wave's slowest lane has 13.6 pair requests at config 3 and the average lane 3.9 — a per-lane walk runs at
-    // 28 % lane efficiency.  Instead every lane announces its count, an owner table in LDS maps item -> lane (wave-local, no
-    // barrier), and the wave works its ~250 items off 64 at a time, each lane fetching its item's Gaussian with ds_bpermute.
-    // Gaussians of more than FLAT_MAX requests (1 %) join the wave-cooperative path below, which then also leaves their
-    // emitted mask.
+    // Rects of at most EMIT_COOP tiles take the flattened walks (flat_item above); Gaussians of more than FLAT_MAX requests
+    // (1 %) join the wave-cooperative path below, which then also leaves their emitted mask.
     constexpr int FLAT_MAX = 16;
-#ifdef GSR_NO_FLAT
-    const bool flat = false;  // (A/B builds: the per-lane walks)
-#else
-    const bool flat = true;
-#endif
     __shared__ uint8_t own_tab[NT / 64][64 * FLAT_MAX];
     __shared__ uint32_t emit_tab[NT / 64][64];
+    const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int rw_ = rmax[0] - rmin[0];
     int fcnt = 0, fppr = 0;          // this lane's pair requests in the flattened walks, pairs per TWO rows of its rect
     bool coop_small = false;         // ... or too many of them: with the wave-cooperative path
-    if (flat && visible && area <= EMIT_COOP) {
-        // pairs are aligned on the LINEAR tile index t = y * grid_x + x: a row starting on an even t holds ceil(w / 2) of them, on
-        // an odd t floor(w / 2) + 1; on grids of odd width the rows of a rect alternate between the two (fppr = their sum)
-        const int w = rmax[0] - rmin[0], h = rmax[1] - rmin[1];
-        const int t0 = rmin[1] * cam.grid_x + rmin[0], t0b = t0 + cam.grid_x;
-        const int pa = ((t0 + w - 1) >> 1) - (t0 >> 1) + 1, pb = ((t0b + w - 1) >> 1) - (t0b >> 1) + 1;
-        fppr = pa + pb;
-        fcnt = ((h + 1) >> 1) * pa + (h >> 1) * pb;
+    if (visible && area <= EMIT_COOP) {
+        const RowPairs rp = row_pairs(rmin[1] * cam.grid_x + rmin[0], rw_, cam.grid_x);
+        fppr = rp.per_two_rows();
+        fcnt = rp.in_rows(rmax[1] - rmin[1]);
         if (fcnt > FLAT_MAX) { fcnt = 0; coop_small = true; }
     }
-    const bool walks = visible && area <= EMIT_COOP && !flat;
-    if (!AGG && flat) {
-        // the direct form with its walk flattened over the lanes: an item = one pair request = (at most) one returning global
-        // atomic; two rounds of items in flight per lane
-        const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        uint32_t x = (uint32_t)fcnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(x, off);
-            if (ln >= off) x += y;
-        }
-        const uint32_t fpre = x - (uint32_t)fcnt, ftotal = __shfl(x, 63);
-        for (int k = 0; k < fcnt; k++) own_tab[wv][fpre + k] = (uint8_t)ln;
+    unsigned long long* tc64 = reinterpret_cast<unsigned long long*>(tile_count);
+    if (!AGG) {
+        // the direct form: an item = one pair request = (at most) one returning global atomic; two rounds of items in flight
+        // per lane
         emit_tab[wv][ln] = 0u;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        uint32_t ftotal;
+        const uint32_t fpre = announce_items(own_tab[wv], fcnt, ln, ftotal);
         const uint32_t rlo = (uint32_t)rmin[0] | ((uint32_t)rmin[1] << 16);
-        const uint32_t rhi = (uint32_t)rmax[0] | ((fppr > 0 ? (256u + (uint32_t)fppr - 1u) / (uint32_t)fppr : 0u) << 16);
-        unsigned long long* tc64 = reinterpret_cast<unsigned long long*>(tile_count);
+        const uint32_t rhi = (uint32_t)rmax[0] | (pair_div_mul(fppr) << 16);
         constexpr int INFL = 2;
         for (uint32_t base = 0; base < ftotal; base += 64u * INFL) {
             uint32_t tt[INFL], cc[INFL], zz[INFL], ss[INFL];
             unsigned long long old[INFL];
 #pragma unroll
             for (int u = 0; u < INFL; u++) {
-                const uint32_t itu = base + 64u * (uint32_t)u + (uint32_t)ln;
-                const bool on = itu < ftotal;
-                const uint32_t it = on ? itu : ftotal - 1u;
-                const int src = own_tab[wv][it];
-                const uint32_t q = it - __shfl(fpre, src);
-                const uint32_t lo = __shfl(rlo, src), hi = __shfl(rhi, src);
-                const float smx = __shfl(m2[0], src), smy = __shfl(m2[1], src);
-                const float sa = __shfl(conic[0], src), sb = __shfl(conic[1], src), sc = __shfl(conic[2], src);
-                const float stau = __shfl(tau, src);
-                zz[u] = __shfl(__float_as_uint(mc_z), src);
-                ss[u] = (uint32_t)src;
-                const int x0 = (int)(lo & 0xFFFFu), y0 = (int)(lo >> 16), x1 = (int)(hi & 0xFFFFu);
-                const int w = x1 - x0, t0 = y0 * cam.grid_x + x0, t0b = t0 + cam.grid_x;
-                const int pa = ((t0 + w - 1) >> 1) - (t0 >> 1) + 1, pb = ((t0b + w - 1) >> 1) - (t0b >> 1) + 1;
-                const int r2 = (int)((q * (hi >> 16)) >> 8), rem = (int)q - r2 * (pa + pb);   // (q < 16: the multiply-shift is exact)
-                const int row = 2 * r2 + (rem >= pa ? 1 : 0), pc = rem - (rem >= pa ? pa : 0), y = y0 + row;
-                const int te = (((t0 + row * cam.grid_x) >> 1) + pc) << 1, xe = te - y * cam.grid_x;  // the pair's even tile (may lie left of the rect)
-                const bool va = on && xe >= x0, vb = on && xe + 1 < x1;
-                const uint32_t kka = (uint32_t)(row * w + (xe - x0)) & 31u, kkb = (uint32_t)(row * w + (xe + 1 - x0)) & 31u;
-                tt[u] = (uint32_t)te;
-                uint32_t c0 = 0u, c1 = 0u;
-                if (va) c0 = (!cam.exact_cull || tile_may_touch(smx, smy, sa, sb, sc, stau, xe * GSR_TILE, y * GSR_TILE)) ? 1u : 0u;
-                if (vb) c1 = (!cam.exact_cull || tile_may_touch(smx, smy, sa, sb, sc, stau, (xe + 1) * GSR_TILE, y * GSR_TILE)) ? 1u : 0u;
+                const FlatItem f = flat_item<false>(own_tab[wv], base + 64u * (uint32_t)u + (uint32_t)ln, ftotal, fpre, rlo, rhi, cam.grid_x);
+                zz[u] = __shfl(__float_as_uint(mc_z), f.src);
+                ss[u] = (uint32_t)f.src;
+                tt[u] = f.t;
+                uint32_t c0, c1;
+                item_may_touch(cam, f, m2, conic, tau, c0, c1);
                 cc[u] = c0 | (c1 << 1);
                 if (cc[u]) {
-                    atomicOr(&emit_tab[wv][src], (c0 << kka) | (c1 << kkb));
+                    atomicOr(&emit_tab[wv][f.src], (c0 << f.kka) | (c1 << f.kkb));
                     old[u] = atomicAdd(tc64 + (tt[u] >> 1), (unsigned long long)c0 | ((unsigned long long)c1 << 32));
                 }
             }
@@ -517,34 +530,6 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
         if (fcnt > 0) emitted = emit_tab[wv][ln];
-    } else if (!AGG) {
-        constexpr int PEND = 8;
-        uint32_t pend_t[PEND], pend_c[PEND];
-        int np = 0;
-        auto flush = [&]() {
-            unsigned long long old[PEND];
-#pragma unroll
-            for (int k = 0; k < PEND; k++)
-                if (k < np)
-                    old[k] = atomicAdd(reinterpret_cast<unsigned long long*>(tile_count + pend_t[k]),
-                                       (unsigned long long)(pend_c[k] & 1u) | ((unsigned long long)(pend_c[k] >> 1) << 32));
-#pragma unroll
-            for (int k = 0; k < PEND; k++)
-                if (k < np) {
-                    const uint32_t p0 = (uint32_t)old[k], p1 = (uint32_t)(old[k] >> 32);
-                    if ((pend_c[k] & 1u) && p0 < bin_cap) bins[(size_t)pend_t[k] * bin_cap + p0] = key;
-                    if ((pend_c[k] & 2u) && p1 < bin_cap) bins[(size_t)(pend_t[k] + 1) * bin_cap + p1] = key;
-                }
-            np = 0;
-        };
-        if (walks) {
-            walk([&](uint32_t t, uint32_t c) {
-                pend_t[np] = t;
-                pend_c[np] = c;  // bit 0: even tile, bit 1: odd tile
-                if (++np == PEND) flush();
-            }, true);
-            flush();
-        }
     } else {
         // AGGREGATING form, in horizontal BANDS of the tile grid (round 5: n_bands == 1 is round 4's kernel).  The counter words of
         // a 4K grid do not fit the LDS three times per CU; the words of HALF the grid do — so the workgroup runs its two walks
@@ -552,85 +537,48 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
         // positions (a rect's rows are walked band by band instead of in one go; the emitted mask is indexed by the row inside the
         // FULL rect).  What the LDS buys on a large grid is not fewer global atomics (a 512-Gaussian workgroup hits mostly distinct
         // words there) but (a) their address order and (b) no same-address serialisation: a hot tile's instances meet in LDS first
-        // (dense scenes: 1 % of a 4K grid at 50 x density took the direct form 1.9 ms).  Both walks are FLATTENED over the lanes
-        // of the wave: every lane announces its count, an owner table in LDS maps item -> lane (wave-local, no barrier), and the
-        // wave works its items off 64 at a time, each lane fetching its item's Gaussian with ds_bpermute.  Gaussians of more than
-        // FLAT_MAX requests (1 %) join the wave-cooperative path below, which then also leaves their emitted mask.
-        const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        // (dense scenes: 1 % of a 4K grid at 50 x density took the direct form 1.9 ms).
         const bool flat_lane = fcnt > 0;  // this lane's rect takes the flattened walks
-        const int rw_ = rmax[0] - rmin[0];
         emit_tab[wv][ln] = SCATTER ? emitted : 0u;  // SCATTER replays the record's mask; else the first walk's tests fill it
-        unsigned long long* tc64 = reinterpret_cast<unsigned long long*>(tile_count);
+        // an item's two instances as the emitted mask has them (SCATTER's restricted pass: a tile whose list fits its bin takes
+        // no position here)
+        auto replay = [&](const FlatItem& f, uint32_t& c0, uint32_t& c1) {
+            const uint32_t em = emit_tab[wv][f.src];
+            c0 = f.va ? (em >> f.kka) & 1u : 0u; c1 = f.vb ? (em >> f.kkb) & 1u : 0u;
+            if (SCATTER && only_above) {
+                if (c0) c0 = tile_start[f.t + 1u] - tile_start[f.t] > only_above ? 1u : 0u;
+                if (c1) c1 = tile_start[f.t + 2u] - tile_start[f.t + 1u] > only_above ? 1u : 0u;
+            }
+        };
         for (int band = 0; band < (BANDED ? n_bands : 1); band++) {
             const int yb0 = BANDED ? band * band_rows : 0, yb1 = BANDED ? min(cam.grid_y, yb0 + band_rows) : cam.grid_y;
             const int wbase = BANDED ? (yb0 * cam.grid_x) >> 1 : 0;
             const int wcount = BANDED ? ((yb1 * cam.grid_x - 1) >> 1) - wbase + 1 : n_words;
             if (BANDED && band > 0) __syncthreads();  // the previous band's second walk has taken its positions
             for (int w = threadIdx.x; w < wcount; w += NT) agg[w] = (AggWord)0;
-            // this lane's rect clipped to the band: pairs are aligned on the LINEAR tile index t = y * grid_x + x — a row starting
-            // on an even t holds ceil(w / 2) of them, on an odd t floor(w / 2) + 1; on grids of odd width the rows alternate
+            // this lane's rect clipped to the band
             const int yc0 = BANDED ? max(rmin[1], yb0) : rmin[1], yc1 = BANDED ? min(rmax[1], yb1) : rmax[1];
             int bcnt = BANDED ? 0 : fcnt, bppr = BANDED ? 0 : fppr;
             if (BANDED && flat_lane && yc1 > yc0) {
-                const int h = yc1 - yc0, t0 = yc0 * cam.grid_x + rmin[0], t0b = t0 + cam.grid_x;
-                const int pa = ((t0 + rw_ - 1) >> 1) - (t0 >> 1) + 1, pb = ((t0b + rw_ - 1) >> 1) - (t0b >> 1) + 1;
-                bppr = pa + pb;
-                bcnt = ((h + 1) >> 1) * pa + (h >> 1) * pb;
+                const RowPairs rp = row_pairs(yc0 * cam.grid_x + rmin[0], rw_, cam.grid_x);
+                bppr = rp.per_two_rows();
+                bcnt = rp.in_rows(yc1 - yc0);
             }
-            uint32_t x = (uint32_t)bcnt;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t y = __shfl_up(x, off);
-                if (ln >= off) x += y;
-            }
-            const uint32_t fpre = x - (uint32_t)bcnt, ftotal = __shfl(x, 63);
-            for (int k = 0; k < bcnt; k++) own_tab[wv][fpre + k] = (uint8_t)ln;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            uint32_t ftotal;
+            const uint32_t fpre = announce_items(own_tab[wv], bcnt, ln, ftotal);
             const uint32_t rlo = (uint32_t)rmin[0] | ((uint32_t)yc0 << 16);
-            // pairs per two rect rows, and the multiplier of the small division q / ppr = (q * fmul) >> 8 (q < 16, ppr <= 16: exact)
-            // (bits 26..31: the mask bit of the clipped rect's first tile, (yc0 - y0) * w <= 32 — zero when there is ONE band)
-            const uint32_t rhi = (uint32_t)rmax[0] | ((bppr > 0 ? (256u + (uint32_t)bppr - 1u) / (uint32_t)bppr : 0u) << 16) |
+            const uint32_t rhi = (uint32_t)rmax[0] | (pair_div_mul(bppr) << 16) |
                                  (BANDED ? (uint32_t)((yc0 - rmin[1]) * rw_) << 26 : 0u);
-            // one item = one aligned tile pair of one rect row: decode (every lane of the wave runs every trip — a ds_bpermute
-            // reads zero from a lane that is switched off)
-#define GSR_AGG_ITEM()                                                                                                          \
-                const bool on = base + (uint32_t)ln < ftotal;                                                                   \
-                const uint32_t it = on ? base + (uint32_t)ln : ftotal - 1u;                                                     \
-                const int src = own_tab[wv][it];                                                                                \
-                const uint32_t q = it - __shfl(fpre, src);                                                                      \
-                const uint32_t lo = __shfl(rlo, src), hi = __shfl(rhi, src), skb = BANDED ? hi >> 26 : 0u;                       \
-                const int x0 = (int)(lo & 0xFFFFu), y0 = (int)(lo >> 16), x1 = (int)(hi & 0xFFFFu);                             \
-                const int w = x1 - x0, t0 = y0 * cam.grid_x + x0, t0b = t0 + cam.grid_x;                                        \
-                const int pa = ((t0 + w - 1) >> 1) - (t0 >> 1) + 1, pb = ((t0b + w - 1) >> 1) - (t0b >> 1) + 1;                 \
-                const int r2 = (int)((q * ((hi >> 16) & 0x3FFu)) >> 8), rem = (int)q - r2 * (pa + pb); /* (q < 16: exact) */    \
-                const int row = 2 * r2 + (rem >= pa ? 1 : 0), pc = rem - (rem >= pa ? pa : 0), y = y0 + row;                    \
-                /* the pair's even tile (may lie left of the rect) */                                                           \
-                const int te = (((t0 + row * cam.grid_x) >> 1) + pc) << 1, xe = te - y * cam.grid_x;                            \
-                const bool va = on && xe >= x0, vb = on && xe + 1 < x1;                                                         \
-                const uint32_t kka = (skb + (uint32_t)(row * w + (xe - x0))) & 31u, kkb = (skb + (uint32_t)(row * w + (xe + 1 - x0))) & 31u; \
-                const uint32_t t = (uint32_t)te;
             __syncthreads();  // agg zeroed
+            // first walk: count per word
             for (uint32_t base = 0; base < ftotal; base += 64u) {
-                GSR_AGG_ITEM()
-                uint32_t c0 = 0u, c1 = 0u;
-                if (SCATTER) {
-                    const uint32_t em = emit_tab[wv][src];
-                    c0 = va ? (em >> kka) & 1u : 0u; c1 = vb ? (em >> kkb) & 1u : 0u;
-                    if (only_above) {  // (restricted pass: a tile whose list fits its bin takes no position here)
-                        if (c0) c0 = tile_start[t + 1u] - tile_start[t] > only_above ? 1u : 0u;
-                        if (c1) c1 = tile_start[t + 2u] - tile_start[t + 1u] > only_above ? 1u : 0u;
-                    }
-                } else {
-                    const float smx = __shfl(m2[0], src), smy = __shfl(m2[1], src);
-                    const float sa = __shfl(conic[0], src), sb = __shfl(conic[1], src), sc = __shfl(conic[2], src);
-                    const float stau = __shfl(tau, src);
-                    if (va) c0 = (!cam.exact_cull || tile_may_touch(smx, smy, sa, sb, sc, stau, xe * GSR_TILE, y * GSR_TILE)) ? 1u : 0u;
-                    if (vb) c1 = (!cam.exact_cull || tile_may_touch(smx, smy, sa, sb, sc, stau, (xe + 1) * GSR_TILE, y * GSR_TILE)) ? 1u : 0u;
-                }
+                const FlatItem f = flat_item<BANDED>(own_tab[wv], base + (uint32_t)ln, ftotal, fpre, rlo, rhi, cam.grid_x);
+                uint32_t c0, c1;
+                if (SCATTER) replay(f, c0, c1);
+                else item_may_touch(cam, f, m2, conic, tau, c0, c1);
                 if (c0 | c1) {
-                    if (!SCATTER) atomicOr(&emit_tab[wv][src], (c0 << kka) | (c1 << kkb));
-                    atomicAdd(&agg[(t >> 1) - (uint32_t)wbase], agg_inc(c0, c1));
+                    if (!SCATTER) atomicOr(&emit_tab[wv][f.src], (c0 << f.kka) | (c1 << f.kkb));
+                    atomicAdd(&agg[(f.t >> 1) - (uint32_t)wbase], agg_inc(c0, c1));
                 }
             }
             __syncthreads();
@@ -661,29 +609,24 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
             if (SCATTER || bin_cap > 0u) {
                 // second walk: the same items, the tests replayed from the emitted mask, every instance takes its position
                 for (uint32_t base = 0; base < ftotal; base += 64u) {
-                    GSR_AGG_ITEM()
-                    const uint32_t em = emit_tab[wv][src];
-                    const uint32_t zb = __shfl(__float_as_uint(mc_z), src);
-                    uint32_t c0 = va ? (em >> kka) & 1u : 0u, c1 = vb ? (em >> kkb) & 1u : 0u;
-                    if (SCATTER && only_above) {
-                        if (c0) c0 = tile_start[t + 1u] - tile_start[t] > only_above ? 1u : 0u;
-                        if (c1) c1 = tile_start[t + 2u] - tile_start[t + 1u] > only_above ? 1u : 0u;
-                    }
+                    const FlatItem f = flat_item<BANDED>(own_tab[wv], base + (uint32_t)ln, ftotal, fpre, rlo, rhi, cam.grid_x);
+                    const uint32_t zb = __shfl(__float_as_uint(mc_z), f.src);
+                    uint32_t c0, c1;
+                    replay(f, c0, c1);
                     if (c0 | c1) {
-                        const AggWord old = atomicAdd(&agg[(t >> 1) - (uint32_t)wbase], agg_inc(c0, c1));
-                        const uint64_t skey = ((uint64_t)zb << 32) | (uint32_t)(blockIdx.x * NT + (threadIdx.x & ~63) + src);
+                        const AggWord old = atomicAdd(&agg[(f.t >> 1) - (uint32_t)wbase], agg_inc(c0, c1));
+                        const uint64_t skey = ((uint64_t)zb << 32) | (uint32_t)(blockIdx.x * NT + (threadIdx.x & ~63) + f.src);
                         const uint32_t p0 = agg_lo(old), p1 = agg_hi(old);
                         if (SCATTER) {
-                            if (c0) bins[tile_start[t] + p0] = skey;
-                            if (c1) bins[tile_start[t + 1u] + p1] = skey;
+                            if (c0) bins[tile_start[f.t] + p0] = skey;
+                            if (c1) bins[tile_start[f.t + 1u] + p1] = skey;
                         } else {
-                            if (c0 && p0 < bin_cap) bins[(size_t)t * bin_cap + p0] = skey;
-                            if (c1 && p1 < bin_cap) bins[(size_t)(t + 1) * bin_cap + p1] = skey;
+                            if (c0 && p0 < bin_cap) bins[(size_t)f.t * bin_cap + p0] = skey;
+                            if (c1 && p1 < bin_cap) bins[(size_t)(f.t + 1) * bin_cap + p1] = skey;
                         }
                     }
                 }
             }
-#undef GSR_AGG_ITEM
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -738,12 +681,7 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wave0 = wave & ~3;
         // gradient-row slots of this Gaussian: one per emitted tile (small rects), one per tile of the rect otherwise
         const uint32_t slots = area <= DENSE_RECT ? (uint32_t)__popc(emitted) : area;
-        uint32_t x = slots;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            uint32_t y = __shfl_up(x, off);
-            if (lane >= off) x += y;
-        }
+        const uint32_t x = gsr::wave_inclusive_scan(slots, lane);
         const unsigned long long vm = __ballot(visible);
         // (high half: the visible Gaussians whose rect holds at least one tile — the reference's instance count is > 0 iff any)
         const unsigned long long am = __ballot(visible && area > 0u);
@@ -810,6 +748,42 @@ __device__ __forceinline__ void tail_sh_group(const gsr::TailState& TS, int i0, 
         element(e, t, m, v);
         th[e] = t; mu[e] = m; nu[e] = v;
     }
+}
+
+// The ∇shs rows of the cnt Gaussians of a workgroup starting at i0 (K3 = 3 K floats each): a lane's row is 12 K bytes apart
+// from its neighbour's, so storing it directly is 3 K store instructions of 64 different cache lines each; the workgroup's
+// slice is contiguous and goes out element-major as coalesced float4.  value(il, j): float j of the row of Gaussian il
+// (0-based inside the workgroup), read from LDS.
+template <class Value>
+__device__ __forceinline__ void store_sh_rows(float* __restrict__ vshs, int i0, int cnt, int K3, Value value) {
+    const uint32_t inv = (1u << 20) / (uint32_t)K3 + 1u;  // e / K3 == (e * inv) >> 20 for e < 2^20 / K3 (K3 <= 48, e < 256 K3)
+    float* __restrict__ dst = vshs + (size_t)i0 * K3;
+    const int total = cnt * K3;
+    auto element = [&](int e) {
+        const int il = (int)(((uint32_t)e * inv) >> 20);
+        return value(il, e - il * K3);
+    };
+    const int total4 = (((uintptr_t)dst & 15) == 0) ? total >> 2 : 0;
+    for (int f = threadIdx.x; f < total4; f += 256)
+        reinterpret_cast<float4*>(dst)[f] = make_float4(element(4 * f), element(4 * f + 1), element(4 * f + 2), element(4 * f + 3));
+    for (int e = 4 * total4 + threadIdx.x; e < total; e += 256) dst[e] = element(e);
+}
+
+// ∇unnorm_quat2rot (render.jl:335-366): vR = the rotation matrix cotangent, qn = the normalised quaternion (w, x, y, z),
+// inv_norm = 1 / |q|.  One expression tree for the float64 chain and for the reference's fp32 chain.
+template <class T>
+__device__ __forceinline__ void unnorm_quat2rot_bwd(const T (&vR)[3][3], const T (&qn)[4], T inv_norm, float vq_out[4]) {
+    const T w = qn[0], x = qn[1], y = qn[2], z = qn[3];
+#define V(i_, j_) vR[(i_) - 1][(j_) - 1]
+    T vqn[4];
+    vqn[0] = T(2) * (x * (V(3, 2) - V(2, 3)) + y * (V(1, 3) - V(3, 1)) + z * (V(2, 1) - V(1, 2)));
+    vqn[1] = T(2) * (T(-2) * x * (V(2, 2) + V(3, 3)) + y * (V(2, 1) + V(1, 2)) + z * (V(3, 1) + V(1, 3)) + w * (V(3, 2) - V(2, 3)));
+    vqn[2] = T(2) * (x * (V(2, 1) + V(1, 2)) - T(2) * y * (V(1, 1) + V(3, 3)) + z * (V(3, 2) + V(2, 3)) + w * (V(1, 3) - V(3, 1)));
+    vqn[3] = T(2) * (x * (V(3, 1) + V(1, 3)) + y * (V(3, 2) + V(2, 3)) - T(2) * z * (V(1, 1) + V(2, 2)) + w * (V(2, 1) - V(1, 2)));
+#undef V
+    const T dq = vqn[0] * qn[0] + vqn[1] * qn[1] + vqn[2] * qn[2] + vqn[3] * qn[3];
+#pragma unroll
+    for (int k = 0; k < 4; k++) vq_out[k] = (float)((vqn[k] - dq * qn[k]) * inv_norm);
 }
 
 // ---------------------------------------------------------------------------------
@@ -894,18 +868,8 @@ __device__ __forceinline__ void scales_rots_bwd_f64(const GsrCam& cam, const M33
 #pragma unroll
         for (int r = 0; r < 3; r++) vRq[r][c] = vM[r][c] * s[c] + (double)vRg.m[r][c];
     }
-    // ∇unnorm_quat2rot (render.jl:335-366)
-#define V(i_, j_) vRq[(i_) - 1][(j_) - 1]
-    double vqn[4];
-    vqn[0] = 2.0 * (x * (V(3, 2) - V(2, 3)) + y * (V(1, 3) - V(3, 1)) + z * (V(2, 1) - V(1, 2)));
-    vqn[1] = 2.0 * (-2.0 * x * (V(2, 2) + V(3, 3)) + y * (V(2, 1) + V(1, 2)) + z * (V(3, 1) + V(1, 3)) + w * (V(3, 2) - V(2, 3)));
-    vqn[2] = 2.0 * (x * (V(2, 1) + V(1, 2)) - 2.0 * y * (V(1, 1) + V(3, 3)) + z * (V(3, 2) + V(2, 3)) + w * (V(1, 3) - V(3, 1)));
-    vqn[3] = 2.0 * (x * (V(3, 1) + V(1, 3)) + y * (V(3, 2) + V(2, 3)) - 2.0 * z * (V(1, 1) + V(2, 2)) + w * (V(2, 1) - V(1, 2)));
-#undef V
     const double qn[4] = {w, x, y, z};
-    const double dq = vqn[0] * w + vqn[1] * x + vqn[2] * y + vqn[3] * z;
-#pragma unroll
-    for (int k = 0; k < 4; k++) vq_out[k] = (float)((vqn[k] - dq * qn[k]) * inv_norm);
+    unnorm_quat2rot_bwd<double>(vRq, qn, inv_norm, vq_out);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1219,20 +1183,7 @@ __global__ __launch_bounds__(256, GSR_PGB_MINWAVES) void pergauss_bwd_kernel(int
 #pragma unroll
                 for (int c = 0; c < 3; c++)
                     vs[c] = Rg.m[0][c] * vM.m[0][c] + Rg.m[1][c] * vM.m[1][c] + Rg.m[2][c] * vM.m[2][c];
-                const float w = qn[0], x = qn[1], y = qn[2], z = qn[3];
-#define V(i_, j_) vRq.m[(i_) - 1][(j_) - 1]
-                float vqn[4];
-                vqn[0] = 2.0f * (x * (V(3, 2) - V(2, 3)) + y * (V(1, 3) - V(3, 1)) + z * (V(2, 1) - V(1, 2)));
-                vqn[1] = 2.0f * (-2.0f * x * (V(2, 2) + V(3, 3)) + y * (V(2, 1) + V(1, 2)) + z * (V(3, 1) + V(1, 3)) +
-                                 w * (V(3, 2) - V(2, 3)));
-                vqn[2] = 2.0f * (x * (V(2, 1) + V(1, 2)) - 2.0f * y * (V(1, 1) + V(3, 3)) + z * (V(3, 2) + V(2, 3)) +
-                                 w * (V(1, 3) - V(3, 1)));
-                vqn[3] = 2.0f * (x * (V(3, 1) + V(1, 3)) + y * (V(3, 2) + V(2, 3)) - 2.0f * z * (V(1, 1) + V(2, 2)) +
-                                 w * (V(2, 1) - V(1, 2)));
-#undef V
-                float dq = vqn[0] * qn[0] + vqn[1] * qn[1] + vqn[2] * qn[2] + vqn[3] * qn[3];
-#pragma unroll
-                for (int k = 0; k < 4; k++) vq[k] = (vqn[k] - dq * qn[k]) * inv_norm;
+                unnorm_quat2rot_bwd<float>(vRq.m, qn, inv_norm, vq);
             }
             if constexpr (FUSED) {
 #pragma unroll
@@ -1258,20 +1209,14 @@ __global__ __launch_bounds__(256, GSR_PGB_MINWAVES) void pergauss_bwd_kernel(int
             float b[16];
             sh_basis<DEG>(dir, b);
             constexpr int NB = (DEG + 1) * (DEG + 1);
-            if constexpr (FUSED) {
-                f_nb = NB;
-#pragma unroll
-                for (int c = 0; c < 3; c++) f_vc[c] = vc[c];
-#pragma unroll
-                for (int k = 0; k < NB; k++) f_b[k] = b[k];
-            } else if (vcolors) {
+            if (!FUSED && vcolors) {
                 // factored form for the multi-view exchange: ∇shs of a view is the outer product
                 // basis(dir) x vc, so 3 floats per Gaussian travel instead of 3K (sh_grad_views_kernel
                 // rebuilds Σ_views on every rank)
                 vcolors[3 * i] = vc[0]; vcolors[3 * i + 1] = vc[1]; vcolors[3 * i + 2] = vc[2];
             } else {
-                // ∇shs = basis x vc is stored by the whole workgroup below (coalesced float4 rows instead of 48
-                // dword stores 192 bytes apart per lane)
+                // ∇shs = basis x vc is stored (FUSED: applied) by the whole workgroup below (coalesced float4 rows instead
+                // of 48 dword stores 192 bytes apart per lane)
                 f_nb = NB;
 #pragma unroll
                 for (int c = 0; c < 3; c++) f_vc[c] = vc[c];
@@ -1350,19 +1295,10 @@ __global__ __launch_bounds__(256, GSR_PGB_MINWAVES) void pergauss_bwd_kernel(int
     if constexpr (!FUSED) {
         if (!vcolors) {
             __syncthreads();
-            const uint32_t inv = (1u << 20) / (uint32_t)K3 + 1u;  // e / K3 == (e * inv) >> 20 for e < 2^20 / K3 (K3 <= 48, e < 256 K3)
-            float* __restrict__ dst = vshs + (size_t)i0 * K3;
-            const int total = cnt * K3;
-            auto value = [&](int e) {
-                const int il = (int)(((uint32_t)e * inv) >> 20);
-                const int j = e - il * K3;
+            store_sh_rows(vshs, i0, cnt, K3, [&](int il, int j) {
                 const int k = j / 3, c = j - 3 * k;
                 return k < tail_nb[il] ? tail_b[il][k] * tail_vc[il][c] : 0.0f;
-            };
-            const int total4 = (((uintptr_t)dst & 15) == 0) ? total >> 2 : 0;
-            for (int f = threadIdx.x; f < total4; f += 256)
-                reinterpret_cast<float4*>(dst)[f] = make_float4(value(4 * f), value(4 * f + 1), value(4 * f + 2), value(4 * f + 3));
-            for (int e = 4 * total4 + threadIdx.x; e < total; e += 256) dst[e] = value(e);
+            });
         }
     }
     if constexpr (FUSED) {
@@ -1427,27 +1363,15 @@ __global__ __launch_bounds__(256) void sh_grad_views_kernel(int n, int K, int n_
                 for (int c = 0; c < 3; c++) acc[3 * k + c] = acc[3 * k + c] + b[k] * vc[c];
         }
     }
-    // The rows leave through LDS: a lane's 3K floats are 12K bytes apart from its neighbour's, so storing them
-    // directly is 3K store instructions of 64 different cache lines each; the workgroup's slice is contiguous and
-    // goes out as coalesced float4 (same lesson as pergauss_bwd's ∇shs store).
+    // The rows leave through LDS (store_sh_rows; same lesson as pergauss_bwd's ∇shs store).
     __shared__ float stage[256 * (3 * NB + 1)];  // odd stride: conflict-free
     constexpr int ST = 3 * NB + 1;
 #pragma unroll
     for (int k = 0; k < 3 * NB; k++) stage[threadIdx.x * ST + k] = acc[k];
     __syncthreads();
-    const int i0 = blockIdx.x * 256, cnt = min(256, n - i0), K3 = 3 * K;
-    float* __restrict__ dst = vshs + (size_t)i0 * K3;
-    const int total = cnt * K3;
-    const uint32_t inv = (1u << 20) / (uint32_t)K3 + 1u;  // e / K3 == (e * inv) >> 20 for e < 2^20 / K3 (K3 <= 48, e < 256 K3)
-    auto value = [&](int e) {
-        const int il = (int)(((uint32_t)e * inv) >> 20);
-        const int j = e - il * K3;
-        return j < 3 * NB ? stage[il * ST + j] : 0.0f;  // bands above the active degree: zeros
-    };
-    const int total4 = (((uintptr_t)dst & 15) == 0) ? total >> 2 : 0;
-    for (int f = threadIdx.x; f < total4; f += 256)
-        reinterpret_cast<float4*>(dst)[f] = make_float4(value(4 * f), value(4 * f + 1), value(4 * f + 2), value(4 * f + 3));
-    for (int e = 4 * total4 + threadIdx.x; e < total; e += 256) dst[e] = value(e);
+    const int i0 = blockIdx.x * 256;
+    // (bands above the active degree: zeros)
+    store_sh_rows(vshs, i0, min(256, n - i0), 3 * K, [&](int il, int j) { return j < 3 * NB ? stage[il * ST + j] : 0.0f; });
 }
 
 // The multi-GPU trainer step made self-contained (training.jl:768-779): after the exchange of the
@@ -1535,6 +1459,22 @@ void gsr_launch_update_stats(hipStream_t s, int n, const int32_t* radii, const f
 namespace {
 using AggPlan = gsr_agg::Plan;
 inline AggPlan agg_plan(int grid_x, int grid_y, uint32_t max_pos) { return gsr_agg::plan(grid_x, grid_y, max_pos); }
+
+// Run-time values that select a kernel instantiation: f gets them as integral constants (a generic lambda takes `auto d`
+// and reads `constexpr int DEG = d;`).
+template <class F>
+inline void dispatch_degree(int degree, F&& f) {
+    switch (degree) {
+        case 0: f(std::integral_constant<int, 0>{}); break;
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        default: f(std::integral_constant<int, 3>{}); break;
+    }
+}
+template <class F>
+inline void dispatch_bool(bool b, F&& f) {
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
 }  // namespace
 
 // `agg`: the aggregating form (else the direct one) — WHICH is gsr_policy.cpp's decision (gsr_policy_begin_view: the handle's
@@ -1551,28 +1491,25 @@ int gsr_launch_preprocess(hipStream_t s, int n, int K, int degree, int channels,
     const int n_words = (n_tiles + 2) / 2;
     const AggPlan pl = agg_plan(cam.grid_x, cam.grid_y, bin_cap);
     const uint32_t* no_start = nullptr;
-    const dim3 agg_grid((n + kAggThreads - 1) / kAggThreads), agg_block(kAggThreads);
-#define LAUNCH_AGG(D, W, B)                                                                                                 \
-    hipLaunchKernelGGL((preprocess_kernel<D, kAggThreads, W, false, B>), agg_grid, agg_block, pl.lds, s, n, K, channels,    \
-                       means, scales, r4, opac, shs, cam, geom, tile_count, n_visible, bins, bin_cap, n_words, no_start,    \
-                       pl.n_bands, pl.band_rows)
-#define LAUNCH(D)                                                                                                           \
-    do {                                                                                                                    \
-        if (agg && pl.n_bands > 1) { if (pl.w32) LAUNCH_AGG(D, true, true); else LAUNCH_AGG(D, false, true); }              \
-        else if (agg) { if (pl.w32) LAUNCH_AGG(D, true, false); else LAUNCH_AGG(D, false, false); }                         \
-        else                                                                                                                \
-            hipLaunchKernelGGL((preprocess_kernel<D, 0, false, false, false>), dim3((n + 255) / 256), dim3(256), 0, s, n, K, \
-                               channels, means, scales, r4, opac, shs, cam, geom, tile_count, n_visible, bins, bin_cap,     \
-                               n_words, no_start, 1, cam.grid_y);                                                           \
-    } while (0)
-    switch (degree) {
-        case 0: LAUNCH(0); break;
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        default: LAUNCH(3); break;
-    }
-#undef LAUNCH
-#undef LAUNCH_AGG
+    dispatch_degree(degree, [&](auto d) {
+        constexpr int DEG = d;
+        if (!agg) {
+            hipLaunchKernelGGL((preprocess_kernel<DEG, 0, false, false, false>), dim3((n + 255) / 256), dim3(256), 0, s, n, K,
+                               channels, means, scales, r4, opac, shs, cam, geom, tile_count, n_visible, bins, bin_cap,
+                               n_words, no_start, 1, cam.grid_y);
+            return;
+        }
+        dispatch_bool(pl.w32, [&](auto w) {
+            constexpr bool W32 = w;
+            dispatch_bool(pl.n_bands > 1, [&](auto b) {
+                constexpr bool BANDED = b;
+                hipLaunchKernelGGL((preprocess_kernel<DEG, kAggThreads, W32, false, BANDED>),
+                                   dim3((n + kAggThreads - 1) / kAggThreads), dim3(kAggThreads), pl.lds, s, n, K, channels,
+                                   means, scales, r4, opac, shs, cam, geom, tile_count, n_visible, bins, bin_cap, n_words,
+                                   no_start, pl.n_bands, pl.band_rows);
+            });
+        });
+    });
     return gsr_agg::form_code(agg, pl);
 }
 
@@ -1590,13 +1527,15 @@ void gsr_launch_emit_compact(hipStream_t s, int n, GsrCam cam, GsrGeom geom, con
     const dim3 grid((n + kAggThreads - 1) / kAggThreads), block(kAggThreads);
     const float* nf = nullptr;
     const float4* nq = nullptr;
-#define LAUNCH_SC(W, B)                                                                                                            \
-    hipLaunchKernelGGL((preprocess_kernel<0, kAggThreads, W, true, B>), grid, block, pl.lds, s, n, 0, 3, nf, nf, nq, nf, nf, cam,  \
-                       geom, tile_fill, (uint32_t*)nullptr, keys, only_above, n_words, tile_start, pl.n_bands, pl.band_rows)
-    if (pl.n_bands > 1) { if (pl.w32) LAUNCH_SC(true, true); else LAUNCH_SC(false, true); }
-    else if (pl.w32) LAUNCH_SC(true, false);
-    else LAUNCH_SC(false, false);
-#undef LAUNCH_SC
+    dispatch_bool(pl.w32, [&](auto w) {
+        constexpr bool W32 = w;
+        dispatch_bool(pl.n_bands > 1, [&](auto b) {
+            constexpr bool BANDED = b;
+            hipLaunchKernelGGL((preprocess_kernel<0, kAggThreads, W32, true, BANDED>), grid, block, pl.lds, s, n, 0, 3, nf,
+                               nf, nq, nf, nf, cam, geom, tile_fill, (uint32_t*)nullptr, keys, only_above, n_words, tile_start,
+                               pl.n_bands, pl.band_rows);
+        });
+    });
 }
 
 void gsr_launch_pergauss_bwd(hipStream_t s, int n, int K, int degree, int channels, const float* means,
@@ -1608,18 +1547,14 @@ void gsr_launch_pergauss_bwd(hipStream_t s, int n, int K, int degree, int channe
     const float4* r4 = reinterpret_cast<const float4*>(rots);
     float4* vr4 = reinterpret_cast<float4*>(vrots);
     const gsr::TailState none{};
-#define LAUNCH_C(D, F32)                                                                                              \
-    hipLaunchKernelGGL((pergauss_bwd_kernel<D, false, F32>), grid, block, 0, s, n, K, channels, means, scales, r4, shs, \
-                       cam, geom, inst, vmean2d, vmeans, vshs, vopac, vscales, vr4, vR, vt, vcolors, none)
-#define LAUNCH(D) do { if (fp32_chain) LAUNCH_C(D, true); else LAUNCH_C(D, false); } while (0)
-    switch (degree) {
-        case 0: LAUNCH(0); break;
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        default: LAUNCH(3); break;
-    }
-#undef LAUNCH
-#undef LAUNCH_C
+    dispatch_degree(degree, [&](auto d) {
+        constexpr int DEG = d;
+        dispatch_bool(fp32_chain, [&](auto f) {
+            constexpr bool F32 = f;
+            hipLaunchKernelGGL((pergauss_bwd_kernel<DEG, false, F32>), grid, block, 0, s, n, K, channels, means, scales, r4,
+                               shs, cam, geom, inst, vmean2d, vmeans, vshs, vopac, vscales, vr4, vR, vt, vcolors, none);
+        });
+    });
 }
 
 void gsr_launch_pergauss_bwd_tail(hipStream_t s, int n, int K, int degree, int channels, GsrCam cam, GsrGeom geom,
@@ -1627,20 +1562,16 @@ void gsr_launch_pergauss_bwd_tail(hipStream_t s, int n, int K, int degree, int c
     if (n <= 0) return;
     dim3 grid((n + 255) / 256), block(256);
     const float4* r4 = reinterpret_cast<const float4*>(S.rots);
-#define LAUNCH_C(D, F32)                                                                                              \
-    hipLaunchKernelGGL((pergauss_bwd_kernel<D, true, F32>), grid, block, 0, s, n, K, channels, S.points, S.scales_act, \
-                       r4, (const float*)nullptr, cam, geom, inst, vmean2d, (float*)nullptr, (float*)nullptr,       \
-                       (float*)nullptr, (float*)nullptr, (float4*)nullptr, (float*)nullptr, (float*)nullptr,        \
-                       (float*)nullptr, S)
-#define LAUNCH(D) do { if (fp32_chain) LAUNCH_C(D, true); else LAUNCH_C(D, false); } while (0)
-    switch (degree) {
-        case 0: LAUNCH(0); break;
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        default: LAUNCH(3); break;
-    }
-#undef LAUNCH
-#undef LAUNCH_C
+    float* const no_f = nullptr;
+    dispatch_degree(degree, [&](auto d) {
+        constexpr int DEG = d;
+        dispatch_bool(fp32_chain, [&](auto f) {
+            constexpr bool F32 = f;
+            hipLaunchKernelGGL((pergauss_bwd_kernel<DEG, true, F32>), grid, block, 0, s, n, K, channels, S.points,
+                               S.scales_act, r4, (const float*)nullptr, cam, geom, inst, vmean2d, no_f, no_f, no_f, no_f,
+                               (float4*)nullptr, no_f, no_f, no_f, S);
+        });
+    });
 }
 
 void gsr_launch_sh_views_tail(hipStream_t s, int n, int K, int degree, int n_views, const float* centers,
@@ -1648,27 +1579,19 @@ void gsr_launch_sh_views_tail(hipStream_t s, int n, int K, int degree, int n_vie
                               const float* vrot, const gsr::TailState& S) {
     if (n <= 0) return;
     dim3 grid((n + 255) / 256), block(256);
-#define LAUNCH(D) hipLaunchKernelGGL(sh_views_tail_kernel<D>, grid, block, 0, s, n, K, n_views, centers, vc_all, vmeans, \
-                                     vopac_act, vscales_act, vrot, S)
-    switch (degree) {
-        case 0: LAUNCH(0); break;
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        default: LAUNCH(3); break;
-    }
-#undef LAUNCH
+    dispatch_degree(degree, [&](auto d) {
+        constexpr int DEG = d;
+        hipLaunchKernelGGL(sh_views_tail_kernel<DEG>, grid, block, 0, s, n, K, n_views, centers, vc_all, vmeans, vopac_act,
+                           vscales_act, vrot, S);
+    });
 }
 
 void gsr_launch_sh_grad_views(hipStream_t s, int n, int K, int degree, int n_views, const float* centers,
                               const float* means, const float* vc_all, float* vshs) {
     if (n <= 0) return;
     dim3 grid((n + 255) / 256), block(256);
-#define LAUNCH(D) hipLaunchKernelGGL(sh_grad_views_kernel<D>, grid, block, 0, s, n, K, n_views, centers, means, vc_all, vshs)
-    switch (degree) {
-        case 0: LAUNCH(0); break;
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        default: LAUNCH(3); break;
-    }
-#undef LAUNCH
+    dispatch_degree(degree, [&](auto d) {
+        constexpr int DEG = d;
+        hipLaunchKernelGGL(sh_grad_views_kernel<DEG>, grid, block, 0, s, n, K, n_views, centers, means, vc_all, vshs);
+    });
 }

@@ -6,6 +6,7 @@
 // expression tree as the oracle's.
 #include "gsr_kernels.h"
 #include "adam_math.h"
+#include "wave_reduce.h"
 
 namespace {
 
@@ -235,12 +236,7 @@ __global__ __launch_bounds__(1024) void findall_scan_kernel(int nb, uint32_t* __
     for (int b0 = 0; b0 < nb; b0 += 1024) {
         const int i = b0 + tid;
         const uint32_t v = i < nb ? block_count[i] : 0u;
-        uint32_t x = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(x, off);
-            if (lane >= off) x += y;
-        }
+        const uint32_t x = gsr::wave_inclusive_scan(v, lane);
         if (lane == 63) wave_sums[wave] = x;
         __syncthreads();
         uint32_t woff = 0;

@@ -19,6 +19,17 @@
 
 namespace gsr {
 
+// Inclusive prefix sum over the 64 lanes of a wave (six shuffle-up steps); lane 63 ends up with the wave's total.
+// `lane` = threadIdx.x & 63.  Every lane of the wave has to call it.
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    return x;
+}
+
 __device__ __forceinline__ float dpp_xor1(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
 }
