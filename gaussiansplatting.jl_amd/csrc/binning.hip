@@ -16,7 +16,6 @@
 // through HBM twice (8 B key out, 8 B key in) instead of ~8 passes x 12 B.  The bins are
 // sized for the part's 288 GB of HBM: capacity = the longest list seen so far with slack,
 // unused slots are never read.
-#include <cstdlib>
 #include "gsr_kernels.h"
 #include "tile_mask.h"
 #include "tile_sort_device.h"
@@ -95,7 +94,7 @@ __device__ __forceinline__ void tile_order_body(int n_tiles, const uint32_t* __r
 // (the whole GPU waits for them: 26 us as two launches, scan then order):
 //   block 0: exclusive scan of the tile counts -> tile_start, D, longest list, tier lists
 //   block 1: exclusive scan of the per-block rect-area sums -> bpre, slot total, visible count
-//   block 2: tile launch order (order == NULL: skipped)
+//   block 2: tile launch order
 // Whichever of blocks 0 / 1 finishes second (ticket in totals[7], left at zero) hands the totals to the host.
 __global__ __launch_bounds__(1024) void tile_scan_kernel(int n_tiles, const uint32_t* __restrict__ tile_count,
                                                          uint32_t* __restrict__ tile_start,
@@ -112,7 +111,7 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(int n_tiles, const uint
     __shared__ uint32_t big_fill, mid8_fill, mid4_fill;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (blockIdx.x == 2) {
-        if (order) tile_order_body(n_tiles, tile_count, order, hist, wave_sums);
+        tile_order_body(n_tiles, tile_count, order, hist, wave_sums);
         return;
     }
     if (blockIdx.x == 0) {
@@ -221,36 +220,6 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(int n_tiles, const uint
 }
 
 // ---- per-tile sort ----
-// Bitonic network over `m` (power of two) keys held in `buf` (LDS or global scratch).
-__device__ __forceinline__ void bitonic_sort(uint64_t* buf, uint32_t m, int tid, int nthreads) {
-    for (uint32_t k = 2; k <= m; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t t = tid; t < (m >> 1); t += nthreads) {
-                const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const uint32_t ixj = i | j;
-                const uint64_t a = buf[i], b = buf[ixj];
-                const bool up = (i & k) == 0;
-                if ((a > b) == up) {
-                    buf[i] = b;
-                    buf[ixj] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-template <int CH, int NT>
-__device__ __forceinline__ void sort_and_emit(uint64_t* buf, uint32_t m, uint32_t n, uint32_t start, int tid,
-                                              int X0, int Y0,
-                                              const uint64_t* __restrict__ keys, const GsrGeom& geom,
-                                              const GsrStream& stream, uint32_t* __restrict__ values_sorted) {
-    for (uint32_t i = tid; i < m; i += NT) buf[i] = i < n ? keys[i] : ~0ull;  // keys = this tile's bin / compact segment
-    __syncthreads();
-    if (m > 1) bitonic_sort(buf, m, tid, NT);
-    for (uint32_t i = tid; i < n; i += NT) emit_instance<CH>(buf[i], start + i, X0, Y0, geom, stream, values_sorted);
-}
-
 // Where a tile's unsorted keys are.  bin_cap == 0: compact layout, the keys of tile t sit at bins[tile_start[t] ...) (count ->
 // scan -> scatter; memory O(D) whatever the skew).  bin_cap > 0: the tile's fixed-capacity bin — unless the list is longer than
 // the capacity (round 5: the bin then holds only its first arrivals): the restricted scatter pass has put the complete list at
@@ -262,34 +231,15 @@ __device__ __forceinline__ const uint64_t* tile_keys(const uint64_t* __restrict_
 }
 
 // Tier launches over the tile lists the scan wrote, for the lists the main pass (tile_sort_wave_kernel, below) leaves:
-// CAP = 4096 keys with 512 threads (32 KB of LDS), CAP = 8192 with 1024 threads (64 KB); lists beyond 8192 belong to
-// tile_sort_big_kernel.  Tiers that are empty (the host knows the counts) are not launched.
-// The keys come from tile_keys() above.
-template <int CH, int CAP, int NT>
-__global__ __launch_bounds__(NT) void tile_sort_kernel(const uint32_t* __restrict__ tile_start,
-                                                       const uint32_t* __restrict__ tier_list,
-                                                       const uint64_t* __restrict__ bins, uint32_t bin_cap,
-                                                       const uint64_t* __restrict__ overflow, int grid_x,
-                                                       GsrGeom geom, GsrStream stream,
-                                                       uint32_t* __restrict__ values_sorted) {
-    __shared__ uint64_t skeys[CAP];
-    const int tile = (int)tier_list[blockIdx.x], tid = threadIdx.x;
-    const uint32_t start = tile_start[tile], end = tile_start[tile + 1];
-    const uint32_t n = end - start;
-    if (n == 0 || n > (uint32_t)CAP) return;
-    const int X0 = (tile % grid_x) * GSR_TILE, Y0 = (tile / grid_x) * GSR_TILE;
-    const uint64_t* __restrict__ keys = tile_keys(bins, bin_cap, overflow, tile, start, n);
-    uint32_t m = 1;
-    while (m < n) m <<= 1;
-    sort_and_emit<CH, NT>(skeys, m, n, start, tid, X0, Y0, keys, geom, stream, values_sorted);
-}
-
-// Round 5: the tier kernels above run a bitonic NETWORK in LDS — 78 barrier steps for 4096 keys — and a trained-like scene with
-// longer lists has hundreds of such tiles (in-plane splat size 12 px at 1 M / 1080p: tile_sort 0.18 ms, as much as the fused
-// forward).  Here every wave sorts a run of 1024 keys IN REGISTERS (the main pass's network: no LDS traffic for the keys, no
-// barrier) and the RUNS runs are merged through LDS: log2(RUNS) passes in which every thread finds its 16 outputs by merge path
-// (a binary search over two sorted runs) and merges them sequentially.  Runs are padded to 1024 with +inf, so every merge is of
-// two full runs; passes stop as soon as one run holds every real key.  Keys are unique: the same total order as everywhere.
+// RUNS = 4 for lists of up to 4096 keys (256 threads, 32 KB of LDS), RUNS = 8 up to 8192 (512 threads, 64 KB); lists beyond
+// 8192 belong to the big_* kernels.  Tiers that are empty (the host knows the counts) are not launched.  The keys come from
+// tile_keys() above.
+// A trained-like scene with longer lists has hundreds of such tiles (in-plane splat size 12 px at 1 M / 1080p), and a bitonic
+// network in LDS takes 78 barrier steps for 4096 keys (round 5: tile_sort 0.18 ms, as much as the fused forward).  Here every
+// wave sorts a run of 1024 keys IN REGISTERS (the main pass's network: no LDS traffic for the keys, no barrier) and the RUNS
+// runs are merged through LDS: log2(RUNS) passes in which every thread finds its 16 outputs by merge path (a binary search over
+// two sorted runs) and merges them sequentially.  Runs are padded to 1024 with +inf, so every merge is of two full runs; passes
+// stop as soon as one run holds every real key.  Keys are unique: the same total order as everywhere.
 template <int CH, int RUNS>
 __global__ __launch_bounds__(64 * RUNS) void tile_sort_runs_kernel(const uint32_t* __restrict__ tile_start,
                                                                    const uint32_t* __restrict__ tier_list,
@@ -352,8 +302,8 @@ __global__ __launch_bounds__(64) void tile_sort_wave_kernel(const uint32_t* __re
     wave_sort_and_emit<CH>(ids, n, start, lane, X0, Y0, keys, geom, stream, values_sorted);
 }
 
-// ---- lists beyond the LDS capacity: chunked LDS sort + merge passes (one 1024-thread workgroup per listed tile) ----
-// Phase 1 sorts runs of GSR_SORT_LDS_CAP keys in LDS (the same bitonic network) into slab A; phase 2 merges runs
+// ---- lists beyond the LDS capacity: chunked LDS sort + merge passes ----
+// Phase 1 sorts runs of GSR_SORT_LDS_CAP keys in LDS (big_chunk_kernel) into slab A; phase 2 merges runs
 // pairwise, ping-ponging between the tile's two global slabs: the merge-path split of every 4096-key output block is
 // found by a parallel binary search, then each block's two input pieces are staged in LDS (coalesced), every thread
 // merges its 4 outputs from LDS and the block is stored coalesced — ceil(log2(n / 8192)) passes of n keys instead of
@@ -417,17 +367,16 @@ __device__ __forceinline__ bool big_item(const uint32_t* __restrict__ prefix, ui
     return true;
 }
 
-// NET = false (default): the chunk is sorted as eight register runs of 1024 keys + three merge-path passes through LDS
-// (tile_sort_device.h: sort_runs_lds, 512 threads) — the bitonic network's 91 barrier steps took 77 us per chunk, on the critical
-// path of a view whose longest list is tens of thousands of keys; NET = true: that network (GSR_SORT_TIERS_NETWORK=1, A/B runs).
-template <bool NET>
-__global__ __launch_bounds__(NET ? BIG_THREADS : 512) void big_chunk_kernel(const uint32_t* __restrict__ tile_start,
-                                                                const uint32_t* __restrict__ big_list, uint32_t n_big,
-                                                                const uint32_t* __restrict__ plan,
-                                                                const uint64_t* __restrict__ bins, uint32_t bin_cap,
-                                                                const uint64_t* __restrict__ overflow,
-                                                                uint64_t* __restrict__ scratch, size_t slab_stride) {
-    constexpr uint32_t NT = NET ? BIG_THREADS : 512;
+// The chunk is sorted as eight register runs of 1024 keys + three merge-path passes through LDS (tile_sort_device.h:
+// sort_runs_lds, 512 threads) — a bitonic network's 91 barrier steps took 77 us per chunk, on the critical path of a view whose
+// longest list is tens of thousands of keys.
+__global__ __launch_bounds__(512) void big_chunk_kernel(const uint32_t* __restrict__ tile_start,
+                                                        const uint32_t* __restrict__ big_list, uint32_t n_big,
+                                                        const uint32_t* __restrict__ plan,
+                                                        const uint64_t* __restrict__ bins, uint32_t bin_cap,
+                                                        const uint64_t* __restrict__ overflow,
+                                                        uint64_t* __restrict__ scratch, size_t slab_stride) {
+    constexpr uint32_t NT = 512;
     __shared__ uint64_t skeys[GSR_SORT_LDS_CAP];
     uint32_t b, c;
     if (!big_item(plan, n_big, blockIdx.x, b, c)) return;
@@ -436,16 +385,8 @@ __global__ __launch_bounds__(NET ? BIG_THREADS : 512) void big_chunk_kernel(cons
     const uint64_t* __restrict__ keys = tile_keys(bins, bin_cap, overflow, tile, start, n);
     uint64_t* slab0 = scratch + (size_t)(2 * b) * slab_stride;
     const uint32_t c0 = c * GSR_SORT_LDS_CAP, cn = min((uint32_t)GSR_SORT_LDS_CAP, n - c0);
-    if (NET) {
-        uint32_t m = 1;
-        while (m < cn) m <<= 1;
-        for (uint32_t i = tid; i < m; i += NT) skeys[i] = i < cn ? keys[c0 + i] : ~0ull;
-        __syncthreads();
-        if (m > 1) bitonic_sort(skeys, m, tid, NT);
-    } else {
-        static_assert(GSR_SORT_LDS_CAP == 8192, "eight runs of 1024 keys");
-        gsr_sort::sort_runs_lds<8>(skeys, cn, tid, keys + c0);
-    }
+    static_assert(GSR_SORT_LDS_CAP == 8192, "eight runs of 1024 keys");
+    gsr_sort::sort_runs_lds<8>(skeys, cn, tid, keys + c0);
     for (uint32_t i = tid; i < cn; i += NT) slab0[c0 + i] = skeys[i];
 }
 
@@ -523,21 +464,12 @@ __global__ __launch_bounds__(256) void fill_background_kernel(size_t n_pixels, i
     n_contrib[p] = 0u;
 }
 
-__global__ void tile_order_identity_kernel(int n_tiles, uint32_t* __restrict__ order) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_tiles) order[i] = (uint32_t)i;
-}
-
 void gsr_launch_tile_scan(hipStream_t s, int n_tiles, const uint32_t* tile_count, uint32_t* tile_start,
                           uint32_t* totals, int n_blocks, const uint32_t* bsum, uint32_t* bpre,
                           const uint32_t* bvis, uint32_t* big_list, uint32_t* host_mirror, uint32_t seq,
                           uint32_t* order) {
-    // GSR_TILE_ORDER=raster: row-major launch order (A/B measurements only; outputs are the same)
-    static const bool raster = [] { const char* e = getenv("GSR_TILE_ORDER"); return e && e[0] == 'r'; }();
-    if (raster)
-        hipLaunchKernelGGL(tile_order_identity_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, s, n_tiles, order);
     hipLaunchKernelGGL(tile_scan_kernel, dim3(3), dim3(1024), 0, s, n_tiles, tile_count, tile_start, totals,
-                       n_blocks, bsum, bpre, bvis, big_list, host_mirror, seq, raster ? nullptr : order);
+                       n_blocks, bsum, bpre, bvis, big_list, host_mirror, seq, order);
 }
 
 void gsr_launch_tile_sort(hipStream_t s, int passes, int n_tiles, int grid_x, int channels, const uint32_t* tile_start,
@@ -547,14 +479,9 @@ void gsr_launch_tile_sort(hipStream_t s, int passes, int n_tiles, int grid_x, in
                           GsrStream stream, uint32_t* values_sorted, uint32_t* ranges, const uint32_t* totals,
                           uint32_t cap_instances, uint32_t first4, uint32_t first8) {
     // (first4 / first8: the leading tiles of the two mid tier lists that gsr_launch_tile_sort_mid has already sorted)
-    // GSR_SORT_TIERS_NETWORK=1: round 2's LDS bitonic network for the (1024, 8192] tiers (A/B runs); default: register runs + merges
-    static const bool net = [] { const char* e = getenv("GSR_SORT_TIERS_NETWORK"); return e && e[0] == '1'; }();
 #define LAUNCH_RUNS(CC, RUNSV, GRID, LIST)                                                                        \
     hipLaunchKernelGGL((tile_sort_runs_kernel<CC, RUNSV>), dim3(GRID), dim3(64 * RUNSV), 0, s, tile_start, LIST, bins, \
                        bin_cap, overflow_keys, grid_x, geom, stream, values_sorted, 0u, (const uint32_t*)nullptr, 0u, 0)
-#define LAUNCH(CC, CAPV, NTV, GRID, LIST)                                                                        \
-    hipLaunchKernelGGL((tile_sort_kernel<CC, CAPV, NTV>), dim3(GRID), dim3(NTV), 0, s, tile_start, LIST, bins,    \
-                       bin_cap, overflow_keys, grid_x, geom, stream, values_sorted)
     // lists beyond the LDS sort: plan -> chunk sorts -> merge passes -> emit, one workgroup per chunk / 4096-key block
     // (the plan lives behind the 2 n_big slabs; grids are upper bounds from the longest list, surplus workgroups leave at once)
     uint32_t* const plan = reinterpret_cast<uint32_t*>(big_scratch + (size_t)2 * n_big * slab_stride);
@@ -563,10 +490,8 @@ void gsr_launch_tile_sort(hipStream_t s, int passes, int n_tiles, int grid_x, in
 #define LAUNCH_BIG(CC)                                                                                            \
     do {                                                                                                          \
         hipLaunchKernelGGL(big_plan_kernel, dim3(1), dim3(1024), 0, s, tile_start, tier_lists, n_big, plan);      \
-        if (net) hipLaunchKernelGGL(big_chunk_kernel<true>, dim3(chunks_ub), dim3(BIG_THREADS), 0, s, tile_start, tier_lists, \
-                                    n_big, plan, bins, bin_cap, overflow_keys, big_scratch, slab_stride);           \
-        else hipLaunchKernelGGL(big_chunk_kernel<false>, dim3(chunks_ub), dim3(512), 0, s, tile_start, tier_lists, n_big, \
-                                plan, bins, bin_cap, overflow_keys, big_scratch, slab_stride);                      \
+        hipLaunchKernelGGL(big_chunk_kernel, dim3(chunks_ub), dim3(512), 0, s, tile_start, tier_lists, n_big, plan, \
+                           bins, bin_cap, overflow_keys, big_scratch, slab_stride);                               \
         int cur = 0;                                                                                              \
         for (uint32_t L = GSR_SORT_LDS_CAP; L < slab_stride; L <<= 1, cur ^= 1)                                   \
             hipLaunchKernelGGL(big_merge_kernel, dim3(blocks_ub), dim3(BIG_THREADS), 0, s, tile_start, tier_lists, n_big, \
@@ -580,15 +505,12 @@ void gsr_launch_tile_sort(hipStream_t s, int passes, int n_tiles, int grid_x, in
                            tile_count, bins, bin_cap, grid_x, geom, stream, values_sorted, ranges, totals,          \
                            cap_instances, n_tiles);                                                                 \
     if (passes & GSR_SORT_PASS_TIERS) {                                                                           \
-        if (n_mid4 > first4) { if (net) LAUNCH(CC, 4096, 512, n_mid4 - first4, tier_lists + 2 * (size_t)n_tiles + first4); \
-                               else LAUNCH_RUNS(CC, 4, n_mid4 - first4, tier_lists + 2 * (size_t)n_tiles + first4); }        \
-        if (n_mid8 > first8) { if (net) LAUNCH(CC, GSR_SORT_LDS_CAP, 1024, n_mid8 - first8, tier_lists + (size_t)n_tiles + first8); \
-                               else LAUNCH_RUNS(CC, 8, n_mid8 - first8, tier_lists + (size_t)n_tiles + first8); }            \
+        if (n_mid4 > first4) LAUNCH_RUNS(CC, 4, n_mid4 - first4, tier_lists + 2 * (size_t)n_tiles + first4);      \
+        if (n_mid8 > first8) LAUNCH_RUNS(CC, 8, n_mid8 - first8, tier_lists + (size_t)n_tiles + first8);          \
         if (n_big > 0) LAUNCH_BIG(CC);                                                                            \
     }
     if (channels > 5) { ALL(8) } else if (channels > 3) { ALL(5) } else { ALL(3) }
 #undef ALL
-#undef LAUNCH
 #undef LAUNCH_RUNS
 #undef LAUNCH_BIG
 }

@@ -324,10 +324,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void s
 // [7..8] v mean2d, [9] v depth (C>=5), [10..12] v normal (C==8)
 template <int C> struct AccRow { static constexpr int N = C == 3 ? 9 : (C == 5 ? 10 : 13); static constexpr int STRIDE = N | 1; };
 
-#ifndef GSR_BWD_MINWAVES
-#define GSR_BWD_MINWAVES 1
-#endif
-
 // ACC — the backward's per-pixel arithmetic in its ACCURATE form (round 6; gsr_config.grad_precision = GSR_GRAD_ACCURATE /
 // GSR_GRAD_FP32_REFERENCE): libm-accurate expf instead of v_exp_f32 on the rounded product sigma x log2(e), IEEE division
 // instead of v_rcp_f32 for T / (1 - alpha) — what the reference's Julia source means by `exp` and `/` (render.jl:236-259).
@@ -393,14 +389,14 @@ __device__ __forceinline__ void bwd_zero_rows(float4* rows, const GsrStream stre
 // gradients too): the pixels' cotangent state, the colour·v dot product and the reduction are the :rgb kernel's; the stream, the
 // blend thresholds and the row layout stay the mode's.
 template <int C, bool BG0, int VC = C, bool ACC = false>
-__global__ __launch_bounds__(64, GSR_BWD_MINWAVES) void composite_bwd_kernel(int W, int H, int grid_x,
-                                                                const uint32_t* __restrict__ tile_start,
-                                                                const uint32_t* __restrict__ tile_order,
-                                                                GsrStream stream, Bg bg,
-                                                                const float* __restrict__ vpixels,
-                                                                const uint32_t* __restrict__ n_contrib,
-                                                                const float* __restrict__ final_T, GsrInst inst,
-                                                                GsrTierLists tiers) {
+__global__ __launch_bounds__(64, 1) void composite_bwd_kernel(int W, int H, int grid_x,
+                                                 const uint32_t* __restrict__ tile_start,
+                                                 const uint32_t* __restrict__ tile_order,
+                                                 GsrStream stream, Bg bg,
+                                                 const float* __restrict__ vpixels,
+                                                 const uint32_t* __restrict__ n_contrib,
+                                                 const float* __restrict__ final_T, GsrInst inst,
+                                                 GsrTierLists tiers) {
     static_assert(VC == C || VC == 3, "all channels, or colour only");
     constexpr int NA = AccRow<VC>::N, ST = AccRow<VC>::STRIDE;
     // one wave64 per tile, four pixels per lane, 64 splats staged per batch.  (The wave index, the per-wave slab and mask
@@ -882,10 +878,8 @@ __global__ __launch_bounds__(64) void composite_bwd_long_kernel(int W, int H, in
     }
 }
 
-// exactly zero (either sign) in every channel: the kernels' BG0 specialisation; GSR_NO_BG0=1 disables it (A/B runs)
+// exactly zero (either sign) in every channel: the kernels' BG0 specialisation
 bool bg_is_zero(const Bg& b) {
-    static const bool off = [] { const char* e = getenv("GSR_NO_BG0"); return e && e[0] == '1'; }();
-    if (off) return false;
     for (int c = 0; c < 8; c++)
         if (b.v[c] != 0.0f) return false;
     return true;

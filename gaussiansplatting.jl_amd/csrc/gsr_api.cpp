@@ -572,17 +572,11 @@ int gsr_create(const gsr_config* cfg, gsr_handle** out) {
     // (8 192 tiles = 131 072 pixels wide: one row of the tile grid must fit the aggregating binning's LDS band, pergauss.hip)
     if (h->grid_x > 8192 || h->grid_y > 65535) { delete h; return fail(GSR_E_INVALID_ARG, "resolution too large"); }
     h->n_tiles = h->grid_x * h->grid_y;
-    // the handle's policies: configuration (constructor fields, then the A/B environment knobs) and the view-history state
+    // the handle's policies: configuration (constructor fields, then the tuner's process default) and the view-history state
     gsr_policy_config_init(&h->pcfg, cfg->width, cfg->height, cfg->bins_budget_bytes, -1 /* resolved per view: process default */);
     gsr_policy_state_init(&h->pol);
-    {
-        const auto env_u32 = [](const char* name, uint32_t dflt) { const char* e = getenv(name); return e ? (uint32_t)atoi(e) : dflt; };
-        const char* tun = getenv("GSR_FORM_TUNER");  // the DEFAULT of handles that do not say (0 = off)
-        h->pcfg.form_tuner = cfg->form_tuner == GSR_TUNER_ON ? 1 : cfg->form_tuner == GSR_TUNER_OFF ? 0 : !(tun && tun[0] == '0');
-        h->pcfg.beside_max_tiles = env_u32("GSR_TIERS_BESIDE_MAX", h->pcfg.beside_max_tiles);      // 0 = never hold the fused launch
-        h->pcfg.bwd_split_max_tiles = env_u32("GSR_BWD_SPLIT_TILES", h->pcfg.bwd_split_max_tiles);
-        h->pcfg.agg_max_bands = (int32_t)env_u32("GSR_AGG_MAX_BANDS", (uint32_t)h->pcfg.agg_max_bands);
-    }
+    const char* tun = getenv("GSR_FORM_TUNER");  // the DEFAULT of handles that do not say (0 = off)
+    h->pcfg.form_tuner = cfg->form_tuner == GSR_TUNER_ON ? 1 : cfg->form_tuner == GSR_TUNER_OFF ? 0 : !(tun && tun[0] == '0');
     DevBuf* list[] = {&h->ranges, &h->n_contrib, &h->final_T, &h->tile_count, &h->tile_start, &h->tile_order, &h->totals,
                       &h->geo, &h->gnormal, &h->radii, &h->bsum, &h->bpre, &h->bvis, &h->bins, &h->values_sorted, &h->s0,
                       &h->s1, &h->s2, &h->s3, &h->big_scratch, &h->rows, &h->vmean2d, &h->d0, &h->d1,
@@ -778,8 +772,7 @@ int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, floa
     if (C > 3) cap_instances = std::min<uint64_t>(cap_instances, h->s3.cap / 16);
     cap_instances = std::min<uint64_t>(cap_instances, 0xFFFFFFFFull);
     if (fwd_only) cap_instances = 0xFFFFFFFFull;  // nothing is stored per instance: no capacity to respect
-    static const bool no_fused = [] { const char* e = getenv("GSR_NO_FUSED_FWD"); return e && e[0] == '1'; }();  // A/B only
-    const bool spec = use_bins && cap_instances > 0 && !no_fused;
+    const bool spec = use_bins && cap_instances > 0;
     // TIER TILES (lists beyond the fused launch's 1024 instances) are walked by their own launch, four single-wave workgroups per
     // tile, and that walk is a latency chain: 0.4 ms for one 32 k-instance tile and its neighbours, 0.15 ms for the few hundred
     // tiles of 1-4 k instances of a trained-like scene — it belongs BESIDE the fused launch, not behind it.  What does not work,
@@ -793,8 +786,7 @@ int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, floa
     // tiles the fused launch is HELD until the host has the counts and the tier sorts have run (mostly idle GPU: 0.04-0.2 ms),
     // and then goes out together with the walk, which takes the handle's second stream at raised wave priority.  Hot tile
     // (32 k) 2.08 -> 1.80 ms, trained-like 3 M / 1440p 2.19 -> 2.10, dense 4K 7.81 -> 7.70; a view without tier tiles is not
-    // touched.  (GSR_TIERS_BESIDE_MAX: hold only when the previous view had at most that many tier tiles — A/B runs; 0 = never:
-    // gsr_policy_config.beside_max_tiles.)
+    // touched.  (gsr_policy_config.beside_max_tiles: hold only when the previous view had at most that many tier tiles; 0 = never.)
     const bool hold_fused = spec && plan.hold_fused;
     const auto launch_fused = [&](hipStream_t fs) {
         StageScope sc3(h->prof, ST_SORT_COMPOSITE_FWD, fs);
@@ -812,19 +804,15 @@ int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, floa
     // go out NOW, behind the scan, with grids guessed from the previous view and the scan's totals checked on the device
     // (gsr_launch_tile_sort_mid); what the guess missed — and every list beyond 8192, whose chain needs host-sized scratch — is
     // sorted after the read-back.  Not for forward-only renders (whose stream buffers are not sized by cap_instances).
-    // GSR_SPEC_TIER_SORTS=0: A/B.
-    static const bool spec_tiers_on = [] { const char* e = getenv("GSR_SPEC_TIER_SORTS"); return !(e && e[0] == '0'); }();
     // (the guesses are the policy's: gsr_view_plan.spec_mid4 / spec_mid8; what is not launched is zeroed for gsr_policy_end_view)
-    if (!(hold_fused && spec_tiers_on && !fwd_only)) plan.spec_mid4 = plan.spec_mid8 = 0u;
+    if (!(hold_fused && !fwd_only)) plan.spec_mid4 = plan.spec_mid8 = 0u;
     const uint32_t spec4 = plan.spec_mid4, spec8 = plan.spec_mid8;
-    {
-        if (spec4 | spec8) {
-            StageScope scs(h->prof, ST_SORT, s, /*extra=*/true);  // (the stage's time; the call after the read-back counts the launch)
-            gsr_launch_tile_sort_mid(s, h->n_tiles, h->grid_x, C, h->tile_start.as<uint32_t>(), h->bins.as<uint64_t>(), bin_cap_view,
-                                     spec4, spec8, h->big_list.as<uint32_t>(), geom_of(h), stream_of(h),
-                                     h->values_sorted.as<uint32_t>(), totals, (uint32_t)cap_instances);
-            scs.close();
-        }
+    if (spec4 | spec8) {
+        StageScope scs(h->prof, ST_SORT, s, /*extra=*/true);  // (the stage's time; the call after the read-back counts the launch)
+        gsr_launch_tile_sort_mid(s, h->n_tiles, h->grid_x, C, h->tile_start.as<uint32_t>(), h->bins.as<uint64_t>(), bin_cap_view,
+                                 spec4, spec8, h->big_list.as<uint32_t>(), geom_of(h), stream_of(h),
+                                 h->values_sorted.as<uint32_t>(), totals, (uint32_t)cap_instances);
+        scs.close();
     }
     if ((rc = wait_totals(h, seq, s))) return rc;
     // What this view turned out to be — bins / overflow tiles / compact; whether the fused launch covers it; where the tier
@@ -933,8 +921,7 @@ int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, floa
         }
         StageScope sc5(h->prof, ST_COMPOSITE_FWD, ws);
         // after the fused launch only the tiles of the tier lists are left; otherwise every tile
-        static const bool walk_prio = [] { const char* e = getenv("GSR_WALK_PRIO"); return !(e && e[0] == '0'); }();  // A/B only
-        const GsrTierLists tiers{h->big_list.as<uint32_t>(), (uint32_t)h->n_tiles, n_big, n_mid8, n_mid4, beside && walk_prio ? 1u : 0u};
+        const GsrTierLists tiers{h->big_list.as<uint32_t>(), (uint32_t)h->n_tiles, n_big, n_mid8, n_mid4, beside ? 1u : 0u};
         gsr_launch_composite_fwd(ws, C, k, h->tile_start.as<uint32_t>(), fused_done ? nullptr : h->tile_order.as<uint32_t>(),
                                  stream_of(h), in->background, image_out, h->n_contrib.as<uint32_t>(), h->final_T.as<float>(),
                                  h->values_sorted.as<uint32_t>(), aux ? aux->covisibilities : nullptr,
@@ -961,10 +948,8 @@ int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, floa
 // ~20 % more work per instance, so when long tiles are plentiful they stay with the main launch.
 static int launch_composite_bwd(gsr_handle* h, hipStream_t s, int C, const GsrCam& k, const float* background,
                                 const float* vpixels, bool color_only) {
-    // (A/B knob: GSR_BWD_COLOR_ONLY=1 treats EVERY cotangent as the loss head's — valid only where it is)
-    static const bool force_color_only = [] { const char* e = getenv("GSR_BWD_COLOR_ONLY"); return e && e[0] == '1'; }();
-    color_only = (color_only || force_color_only) && C > 3;
-    // which tiers leave the main launch: gsr_policy_bwd_split (GSR_BWD_SPLIT_TILES overrides its limit for A/B runs)
+    color_only = color_only && C > 3;
+    // which tiers leave the main launch: gsr_policy_bwd_split (its limit: gsr_policy_config.bwd_split_max_tiles)
     gsr_bwd_split sp;
     gsr_policy_bwd_split(&h->pcfg, h->pol.tier_n[0], h->pol.tier_n[1], h->pol.tier_n[2], &sp);
     // (the accurate per-pixel arithmetic exists for the one-wave-per-tile kernel only: such a handle splits nothing)
@@ -989,18 +974,40 @@ static int launch_composite_bwd(gsr_handle* h, hipStream_t s, int C, const GsrCa
     return GSR_OK;
 }
 
-int gsr_backward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, const float* vpixels,
-                 const gsr_grads* g, void* stream_v) {
-    int rc = check_inputs(h, in, cam);
-    if (rc) return rc;
-    if (!vpixels || !g) return fail(GSR_E_INVALID_ARG, "null vpixels / grads");
+// What both backward entry points ask of the handle's last forward (`entry`: the entry point's name, for the messages).
+static int check_backward_state(const gsr_handle* h, const gsr_inputs* in, const char* entry) {
     if (!h->fwd_valid || h->last_n != in->n)
-        return fail(GSR_E_STATE, "gsr_backward without a matching gsr_forward on this handle");
+        return fail(GSR_E_STATE, "%s without a matching gsr_forward on this handle", entry);
     if (h->fwd_only)
         return fail(GSR_E_STATE, "the handle's last forward was GSR_FORWARD_ONLY: it kept no backward state");
     if (h->inputs_consumed)
         return fail(GSR_E_STATE, "the inputs of the handle's last forward were updated in place by "
                     "gsr_backward_trainer_tail; run gsr_forward again");
+    return GSR_OK;
+}
+
+// ... and what both do once their arguments are checked: ∇means_2d goes to the caller's array or the handle's scratch, a
+// cotangent declared colour-only is checked where asked (GSR_CHECK_COLOR_COTANGENT), the compositing backward runs as its stage.
+static int composite_bwd_stage(gsr_handle* h, hipStream_t s, const gsr_inputs* in, const gsr_camera* cam, const float* vpixels,
+                               float* vmeans2d, uint32_t flags, GsrCam* k) {
+    int rc;
+    if (!vmeans2d && (rc = h->vmean2d.ensure((size_t)in->n * 8, 1.25f))) return rc;
+    h->vmean2d_cur = vmeans2d ? reinterpret_cast<float2*>(vmeans2d) : h->vmean2d.as<float2>();
+    const bool color_only = (flags & GSR_GRADS_COLOR_COTANGENT) != 0u;
+    if (color_only && (rc = check_color_cotangent(h, vpixels, s))) return rc;
+    *k = make_cam(h, cam);
+    StageScope sc(h->prof, ST_COMPOSITE_BWD, s);
+    if (h->last_D > 0 && (rc = launch_composite_bwd(h, s, h->cfg.mode, *k, in->background, vpixels, color_only))) return rc;
+    sc.close();
+    return GSR_OK;
+}
+
+int gsr_backward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, const float* vpixels,
+                 const gsr_grads* g, void* stream_v) {
+    int rc = check_inputs(h, in, cam);
+    if (rc) return rc;
+    if (!vpixels || !g) return fail(GSR_E_INVALID_ARG, "null vpixels / grads");
+    if ((rc = check_backward_state(h, in, "gsr_backward"))) return rc;
     if ((g->flags & ~GSR_GRADS_COLOR_COTANGENT) != 0u || g->reserved != 0u) return fail(GSR_E_INVALID_ARG, "unknown gsr_grads.flags / reserved bits");
     if (g->forward_generation != 0 && g->forward_generation != h->generation)
         return fail(GSR_E_STATE, "gsr_backward for forward #%llu, but the handle's last forward is #%llu (another "
@@ -1013,8 +1020,6 @@ int gsr_backward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, con
     hipStream_t s = (hipStream_t)stream_v;
     const int C = h->cfg.mode, n = in->n;
     if (n == 0) return GSR_OK;
-    if (!g->vmeans2d && (rc = h->vmean2d.ensure((size_t)n * 8, 1.25f))) return rc;
-    h->vmean2d_cur = g->vmeans2d ? reinterpret_cast<float2*>(g->vmeans2d) : h->vmean2d.as<float2>();
     // (the gradient rows need no memset: composite_bwd writes the row of every emitted instance,
     // pergauss_bwd skips the slots of culled tiles; only the 12 pose-gradient floats are accumulated into)
     if (g->vR) {
@@ -1023,12 +1028,8 @@ int gsr_backward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, con
         HIPCHK(hipMemsetAsync(g->vt, 0, 3 * 4, s));
         sc6.close();
     }
-    const bool color_only = (g->flags & GSR_GRADS_COLOR_COTANGENT) != 0u;
-    if (color_only && (rc = check_color_cotangent(h, vpixels, s))) return rc;
-    GsrCam k = make_cam(h, cam);
-    StageScope sc7(h->prof, ST_COMPOSITE_BWD, s);
-    if (h->last_D > 0 && (rc = launch_composite_bwd(h, s, C, k, in->background, vpixels, color_only))) return rc;
-    sc7.close();
+    GsrCam k;
+    if ((rc = composite_bwd_stage(h, s, in, cam, vpixels, g->vmeans2d, g->flags, &k))) return rc;
     StageScope sc8(h->prof, ST_PERGAUSS_BWD, s);
     gsr_launch_pergauss_bwd(s, n, in->n_coeffs, in->sh_degree, C, in->means, in->scales, in->rotations, in->shs, k,
                             geom_of(h), inst_of(h), h->vmean2d_cur, g->vmeans, g->vshs, g->vopacities,
@@ -1235,6 +1236,25 @@ int gsr_prologue_backward(int32_t n, int32_t k_rest, int32_t scale_dims, const f
     return GSR_OK;
 }
 
+// Adam's step size with both debiasing factors folded in (Kingma & Ba §2); current_step counts from 1
+static float adam_lr_t(float lr, float beta1, float beta2, uint32_t current_step) {
+    const float t = (float)current_step;
+    return lr * sqrtf(1.0f - powf(beta2, t)) / (1.0f - powf(beta1, t));
+}
+
+// lr_t of the trainer's six groups, after checking their arrays and counters; rest_empty: the scene has no features_rest
+// (group 2), whose arrays are then not looked at (training.jl:770)
+static int tail_lr_t(float* const theta[6], float* const mu[6], float* const nu[6], const float lr[6],
+                     const uint32_t current_step[6], float beta1, float beta2, bool rest_empty, float lr_t[6]) {
+    for (int g = 0; g < 6; g++) {
+        if (g == 2 && rest_empty) { lr_t[g] = 0.0f; continue; }
+        if (!theta[g] || !mu[g] || !nu[g]) return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
+        if (current_step[g] == 0) return fail(GSR_E_INVALID_ARG, "group %d: current_step counts from 1", g);
+        lr_t[g] = adam_lr_t(lr[g], beta1, beta2, current_step[g]);
+    }
+    return GSR_OK;
+}
+
 int gsr_adam_step(const gsr_adam_group* groups, int32_t n_groups, float beta1, float beta2, float eps, void* stream) {
     if (n_groups < 0 || n_groups > GSR_ADAM_MAX_GROUPS || (n_groups > 0 && !groups))
         return fail(GSR_E_INVALID_ARG, "n_groups must be in [0, %d]", GSR_ADAM_MAX_GROUPS);
@@ -1248,9 +1268,8 @@ int gsr_adam_step(const gsr_adam_group* groups, int32_t n_groups, float beta1, f
         if (a.count == 0) continue;  // training.jl:770 `isempty(θᵢ) && continue`
         if (!a.theta || !a.grad || !a.mu || !a.nu) return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
         if (a.current_step == 0) return fail(GSR_E_INVALID_ARG, "group %d: current_step counts from 1", g);
-        const float t = (float)a.current_step;
         theta[m] = a.theta; grad[m] = a.grad; mu[m] = a.mu; nu[m] = a.nu; count[m] = a.count;
-        lr_t[m] = a.lr * sqrtf(1.0f - powf(beta2, t)) / (1.0f - powf(beta1, t));  // debiasing, Kingma & Ba §2
+        lr_t[m] = adam_lr_t(a.lr, beta1, beta2, a.current_step);
         m++;
     }
     if (m == 0) return GSR_OK;
@@ -1271,13 +1290,8 @@ int gsr_trainer_tail_step(int32_t n, int32_t k_rest, int32_t scale_dims, const g
     if (!grads->vmeans || !grads->vshs || !grads->vopacities || !grads->vscales || !grads->vrotations)
         return fail(GSR_E_INVALID_ARG, "null gradient");
     float lr_t[6];
-    for (int g = 0; g < 6; g++) {
-        if (g == 2 && k_rest == 0) { lr_t[g] = 0.0f; continue; }  // empty features_rest (training.jl:770)
-        if (!theta[g] || !mu[g] || !nu[g]) return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
-        if (current_step[g] == 0) return fail(GSR_E_INVALID_ARG, "group %d: current_step counts from 1", g);
-        const float t = (float)current_step[g];
-        lr_t[g] = lr[g] * sqrtf(1.0f - powf(beta2, t)) / (1.0f - powf(beta1, t));
-    }
+    int rc = tail_lr_t(theta, mu, nu, lr, current_step, beta1, beta2, /*rest_empty=*/k_rest == 0, lr_t);
+    if (rc) return rc;
     const float* gr[5] = {grads->vmeans, grads->vshs, grads->vopacities, grads->vscales, grads->vrotations};
     gsr_launch_trainer_tail((hipStream_t)stream, n, k_rest, scale_dims, gr, theta, mu, nu, lr_t, beta1, beta2, eps, shs,
                             opacities_act, scales_act);
@@ -1290,13 +1304,7 @@ int gsr_backward_trainer_tail(gsr_handle* h, const gsr_inputs* in, const gsr_cam
     int rc = check_inputs(h, in, cam);
     if (rc) return rc;
     if (!vpixels || !st) return fail(GSR_E_INVALID_ARG, "null vpixels / tail state");
-    if (!h->fwd_valid || h->last_n != in->n)
-        return fail(GSR_E_STATE, "gsr_backward_trainer_tail without a matching gsr_forward on this handle");
-    if (h->fwd_only)
-        return fail(GSR_E_STATE, "the handle's last forward was GSR_FORWARD_ONLY: it kept no backward state");
-    if (h->inputs_consumed)
-        return fail(GSR_E_STATE, "the inputs of the handle's last forward were updated in place by "
-                    "gsr_backward_trainer_tail; run gsr_forward again");
+    if ((rc = check_backward_state(h, in, "gsr_backward_trainer_tail"))) return rc;
     if ((st->flags & ~GSR_GRADS_COLOR_COTANGENT) != 0u || st->reserved != 0u) return fail(GSR_E_INVALID_ARG, "unknown gsr_tail_state.flags / reserved bits");
     if (st->forward_generation != 0 && st->forward_generation != h->generation)
         return fail(GSR_E_STATE, "gsr_backward_trainer_tail for forward #%llu, but the handle's last forward is #%llu",
@@ -1305,13 +1313,8 @@ int gsr_backward_trainer_tail(gsr_handle* h, const gsr_inputs* in, const gsr_cam
     const int n = in->n, K = in->n_coeffs;
     if (n == 0) return GSR_OK;
     float lr_t[6];
-    for (int g = 0; g < 6; g++) {
-        if (g == 2 && K == 1) { lr_t[g] = 0.0f; continue; }  // empty features_rest (training.jl:770)
-        if (!st->theta[g] || !st->mu[g] || !st->nu[g]) return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
-        if (st->current_step[g] == 0) return fail(GSR_E_INVALID_ARG, "group %d: current_step counts from 1", g);
-        const float t = (float)st->current_step[g];
-        lr_t[g] = st->lr[g] * sqrtf(1.0f - powf(st->beta2, t)) / (1.0f - powf(st->beta1, t));
-    }
+    if ((rc = tail_lr_t(st->theta, st->mu, st->nu, st->lr, st->current_step, st->beta1, st->beta2, /*rest_empty=*/K == 1, lr_t)))
+        return rc;
     // the kernel reads its inputs through the trainer's arrays and updates them in place
     if (in->means != st->theta[0] || in->rotations != st->theta[5] || in->shs != st->shs ||
         in->opacities != st->opacities_act || in->scales != st->scales_act)
@@ -1320,14 +1323,8 @@ int gsr_backward_trainer_tail(gsr_handle* h, const gsr_inputs* in, const gsr_cam
     if (((uintptr_t)st->theta[5] & 15) != 0) return fail(GSR_E_INVALID_ARG, "rotations must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream_v;
     const int C = h->cfg.mode;
-    if (!st->vmeans2d && (rc = h->vmean2d.ensure((size_t)n * 8, 1.25f))) return rc;
-    h->vmean2d_cur = st->vmeans2d ? reinterpret_cast<float2*>(st->vmeans2d) : h->vmean2d.as<float2>();
-    const bool color_only = (st->flags & GSR_GRADS_COLOR_COTANGENT) != 0u;
-    if (color_only && (rc = check_color_cotangent(h, vpixels, s))) return rc;
-    GsrCam k = make_cam(h, cam);
-    StageScope sc11(h->prof, ST_COMPOSITE_BWD, s);
-    if (h->last_D > 0 && (rc = launch_composite_bwd(h, s, C, k, in->background, vpixels, color_only))) return rc;
-    sc11.close();
+    GsrCam k;
+    if ((rc = composite_bwd_stage(h, s, in, cam, vpixels, st->vmeans2d, st->flags, &k))) return rc;
     StageScope sc12(h->prof, ST_PERGAUSS_BWD, s);
     const gsr::TailState S = gsr_make_tail_state(st->theta, st->mu, st->nu, lr_t, st->beta1, st->beta2, st->eps,
                                                  st->scale_dims, st->shs, st->opacities_act, st->scales_act);
@@ -1464,8 +1461,7 @@ int gsr_bilateral_adam_tail(int32_t n_images, int32_t gx, int32_t gy, int32_t gz
     if (current_step == 0) return fail(GSR_E_INVALID_ARG, "current_step counts from 1");
     const size_t need = gsr_bilateral_tv_scratch_bytes(n_images);
     if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the tail needs %zu", scratch_bytes, need);
-    const float t = (float)current_step;
-    const float lr_t = lr * sqrtf(1.0f - powf(beta2, t)) / (1.0f - powf(beta1, t));  // as gsr_adam_step
+    const float lr_t = adam_lr_t(lr, beta1, beta2, current_step);
     const gsr::AdamHyper h{lr_t, beta1, beta2, 1.0f - beta1, 1.0f - beta2, eps};
     gsr_launch_bilateral_adam_tail((hipStream_t)stream, n_images, gx, gy, gz, grids, mu, nu, vgrid_view, view,
                                    bilateral_tv_consts(n_images, gx, gy, gz, tv_weight), h, tv_loss_out, (float*)scratch);
@@ -1680,13 +1676,8 @@ int gsr_sh_grad_from_views_tail(int32_t n, int32_t n_coeffs, int32_t sh_degree, 
     if (st->scale_dims != 1 && st->scale_dims != 3) return fail(GSR_E_INVALID_ARG, "scale_dims must be 1 or 3");
     if (!st->shs || !st->opacities_act || !st->scales_act) return fail(GSR_E_INVALID_ARG, "null activated copy");
     float lr_t[6];
-    for (int g = 0; g < 6; g++) {
-        if (g == 2 && n_coeffs == 1) { lr_t[g] = 0.0f; continue; }  // empty features_rest (training.jl:770)
-        if (!st->theta[g] || !st->mu[g] || !st->nu[g]) return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
-        if (st->current_step[g] == 0) return fail(GSR_E_INVALID_ARG, "group %d: current_step counts from 1", g);
-        const float t = (float)st->current_step[g];
-        lr_t[g] = st->lr[g] * sqrtf(1.0f - powf(st->beta2, t)) / (1.0f - powf(st->beta1, t));
-    }
+    int rc = tail_lr_t(st->theta, st->mu, st->nu, st->lr, st->current_step, st->beta1, st->beta2, /*rest_empty=*/n_coeffs == 1, lr_t);
+    if (rc) return rc;
     const gsr::TailState S = gsr_make_tail_state(st->theta, st->mu, st->nu, lr_t, st->beta1, st->beta2, st->eps,
                                                  st->scale_dims, st->shs, st->opacities_act, st->scales_act);
     gsr_launch_sh_views_tail((hipStream_t)stream, n, n_coeffs, sh_degree, n_views, camera_centers, vcolors_all, small->vmeans,

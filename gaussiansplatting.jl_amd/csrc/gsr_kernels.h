@@ -58,12 +58,8 @@ struct GsrStream {
 // per-Gaussian kernel sums them in a fixed order (deterministic gradients).
 //   row = 4 x float4: {v r, v g, v b, v opacity}, {v conic a,b,c, v depth}, {v mean2d x,y, v normal x,y}, {v normal z,-,-,-}
 // segments a long tile list is cut into by the list-parallel backward (composite_bwd_long_kernel)
-#ifndef GSR_BWD_LONG_SEGS
 #define GSR_BWD_LONG_SEGS 32
-#endif
-#ifndef GSR_ROW_F4
 #define GSR_ROW_F4(C) ((C) > 3 ? 4 : 3)  // float4s per gradient row: 48 bytes in :rgb mode (9 floats used), 64 otherwise
-#endif
 struct GsrInst {
     float4* rows;  // D_slots x 4 float4, zero-filled per backward
 };

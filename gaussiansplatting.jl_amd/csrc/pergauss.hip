@@ -11,9 +11,6 @@
 // kernels are HBM-bound (192 B of SH per Gaussian), the extra VALU ops are free.
 #include "gsr_kernels.h"
 #include <type_traits>
-#ifndef GSR_PGB_MINWAVES
-#define GSR_PGB_MINWAVES 1
-#endif
 #include "tile_mask.h"
 #include "wave_reduce.h"
 #include "adam_math.h"
@@ -471,11 +468,6 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
     // to the memory side).  A position >= bin_cap is not stored: the host sees max count >
     // capacity in the scan's totals, grows the bins and repeats the pass (first view / a much
     // denser view).
-#ifdef GSR_PRE_NO_BINNING
-    // (A/B builds only — tools/experiments/r06_preprocess_floor.py: projection + SH + records without any instance, the floor under
-    //  every re-formed binning)
-    if (!SCATTER) { area = 0u; rmax[0] = rmin[0]; rmax[1] = rmin[1]; }
-#endif
     // Rects of at most EMIT_COOP tiles take the flattened walks (flat_item above); Gaussians of more than FLAT_MAX requests
     // (1 %) join the wave-cooperative path below, which then also leaves their emitted mask.
     constexpr int FLAT_MAX = 16;
@@ -892,7 +884,7 @@ __device__ __forceinline__ void scales_rots_bwd_f64(const GsrCam& cam, const M33
 // expression trees instead of the float64 chain — reference-parity runs; a template parameter, not a branch, so
 // that the default kernels are round 5's register for register.
 template <int DEG, bool FUSED, bool F32CHAIN = false>
-__global__ __launch_bounds__(256, GSR_PGB_MINWAVES) void pergauss_bwd_kernel(int n, int K, int channels, const float* __restrict__ means,
+__global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int channels, const float* __restrict__ means,
                                                            const float* __restrict__ scales,
                                                            const float4* __restrict__ rots,
                                                            const float* __restrict__ shs, GsrCam cam, GsrGeom geom,

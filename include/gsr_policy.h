@@ -128,9 +128,8 @@ typedef struct gsr_bwd_split {
     uint32_t split_len;              /* lists longer than this are split (8192 / 4096 / 1024); 0xFFFFFFFF: none */
 } gsr_bwd_split;
 
-/* Defaults: tuner on, hold for any number of tier tiles, split up to 256 tiles, one band.  Environment overrides of the
- * library (GSR_FORM_TUNER, GSR_TIERS_BESIDE_MAX, GSR_BWD_SPLIT_TILES, GSR_AGG_MAX_BANDS: A/B runs) are applied by gsr_create,
- * not here. */
+/* Defaults: tuner on, hold for any number of tier tiles, split up to 256 tiles, one band.  The library's one environment override
+ * (GSR_FORM_TUNER, the tuner's default of handles that do not say) is applied by gsr_create, not here. */
 GSR_API void gsr_policy_config_init(gsr_policy_config* cfg, int32_t width, int32_t height, uint64_t bins_budget_bytes,
                                     int32_t preprocess_form);
 GSR_API void gsr_policy_state_init(gsr_policy_state* st);
