@@ -17,6 +17,7 @@
 // sized for the part's 288 GB of HBM: capacity = the longest list seen so far with slack,
 // unused slots are never read.
 #include "gsr_kernels.h"
+#include "gsr_dispatch.h"
 #include "tile_mask.h"
 #include "tile_sort_device.h"
 #include "wave_reduce.h"
@@ -95,7 +96,7 @@ __device__ __forceinline__ void tile_order_body(int n_tiles, const uint32_t* __r
 //   block 0: exclusive scan of the tile counts -> tile_start, D, longest list, tier lists
 //   block 1: exclusive scan of the per-block rect-area sums -> bpre, slot total, visible count
 //   block 2: tile launch order
-// Whichever of blocks 0 / 1 finishes second (ticket in totals[7], left at zero) hands the totals to the host.
+// Whichever of blocks 0 / 1 finishes second (ticket in totals[GSR_TOTAL_SEQ], left at zero) hands the totals to the host.
 __global__ __launch_bounds__(1024) void tile_scan_kernel(int n_tiles, const uint32_t* __restrict__ tile_count,
                                                          uint32_t* __restrict__ tile_start,
                                                          uint32_t* __restrict__ totals, int n_blocks,
@@ -161,11 +162,11 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(int n_tiles, const uint
             uint32_t m = 0, b = 0;
             for (int w = 0; w < 16; w++) { m = red[0][w] > m ? red[0][w] : m; b += red[1][w]; }
             tile_start[n_tiles] = total;
-            totals[0] = total;  // D
-            totals[1] = m;      // longest list
-            totals[2] = b;      // #tiles over GSR_SORT_LDS_CAP (listed in big_list; they get two global-scratch slabs each)
-            totals[3] = mid4_fill;  // #tiles with a list in (1024, 4096]
-            totals[6] = mid8_fill;  // #tiles with a list in (4096, 8192]
+            totals[GSR_TOTAL_D] = total;
+            totals[GSR_TOTAL_MAX_LIST] = m;
+            totals[GSR_TOTAL_BIG] = b;  // (listed in big_list; they get two global-scratch slabs each)
+            totals[GSR_TOTAL_MID4] = mid4_fill;
+            totals[GSR_TOTAL_MID8] = mid8_fill;
         }
     } else {
         // Gaussian blocks: per-block sums of tile-rect areas -> bpre (Gaussian-major instance-slot
@@ -199,21 +200,21 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(int n_tiles, const uint
         if (tid == 0) {
             uint32_t v = 0, any = 0;
             for (int w = 0; w < 16; w++) { v += red[2][w] & 0x7FFFFFFFu; any |= red[2][w] & 0x80000000u; }
-            totals[4] = v | any;  // visible Gaussians; bit 31: one of them has a non-empty tile rect (the reference's D > 0)
-            totals[5] = total;  // sum of tile-rect areas = number of Gaussian-major instance slots (gradient rows)
+            totals[GSR_TOTAL_VISIBLE] = v | any;
+            totals[GSR_TOTAL_SLOTS] = total;
         }
     }
     if (tid == 0) {
         __threadfence();  // this block's totals before its ticket
-        if (atomicAdd(&totals[7], 1u) == 1u) {
-            totals[7] = 0u;  // ready for the next view
+        if (atomicAdd(&totals[GSR_TOTAL_SEQ], 1u) == 1u) {
+            totals[GSR_TOTAL_SEQ] = 0u;  // ready for the next view
             if (host_mirror) {
                 // The host's copy, written straight into its pinned (fine-grained) memory: the seven totals, then the
                 // sequence number of this forward with system-scope release — the host spins on that word.  A D2H copy
                 // packet + an event record here cost an 8 us bubble on the stream (rocprofv3 kernel trace).
 #pragma unroll
-                for (int k = 0; k < 7; k++) host_mirror[k] = __hip_atomic_load(&totals[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&host_mirror[7], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                for (int k = 0; k < GSR_TOTAL_SEQ; k++) host_mirror[k] = __hip_atomic_load(&totals[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&host_mirror[GSR_TOTAL_SEQ], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
     }
@@ -246,16 +247,16 @@ __global__ __launch_bounds__(64 * RUNS) void tile_sort_runs_kernel(const uint32_
                                                                    const uint64_t* __restrict__ bins, uint32_t bin_cap,
                                                                    const uint64_t* __restrict__ overflow, int grid_x,
                                                                    GsrGeom geom, GsrStream stream,
-                                                                   uint32_t* __restrict__ values_sorted, uint32_t first,
+                                                                   uint32_t* __restrict__ values_sorted,
                                                                    const uint32_t* __restrict__ totals, uint32_t cap_instances,
                                                                    int count_slot) {
     constexpr int NT = 64 * RUNS, CAP = 1024 * RUNS;
     __shared__ uint64_t buf[CAP];
-    const uint32_t slot = first + blockIdx.x;
+    const uint32_t slot = blockIdx.x;
     // totals != NULL: launched behind the scan BEFORE the host has the counts (gsr_launch_tile_sort_mid): the grid is a guess.
     // A view that needs more instances than the buffers hold, or whose bins overflowed, is left alone (the host, which sees
     // the same totals, sorts it after growing / scattering); a workgroup beyond the tier's real count leaves.
-    if (totals && (totals[0] > cap_instances || totals[1] > bin_cap || slot >= totals[count_slot])) return;
+    if (totals && (totals[GSR_TOTAL_D] > cap_instances || totals[GSR_TOTAL_MAX_LIST] > bin_cap || slot >= totals[count_slot])) return;
     const int tile = (int)tier_list[slot], tid = threadIdx.x;
     const uint32_t start = tile_start[tile], end = tile_start[tile + 1];
     const uint32_t n = end - start;
@@ -273,14 +274,8 @@ __global__ __launch_bounds__(64) void tile_sort_wave_kernel(const uint32_t* __re
                                                             const uint64_t* __restrict__ bins, uint32_t bin_cap, int grid_x,
                                                             GsrGeom geom, GsrStream stream,
                                                             uint32_t* __restrict__ values_sorted,
-                                                            uint32_t* __restrict__ ranges,
-                                                            const uint32_t* __restrict__ totals, uint32_t cap_instances,
-                                                            int n_tiles) {
+                                                            uint32_t* __restrict__ ranges, int n_tiles) {
     __shared__ uint32_t ids[1024];
-    // Launched BEFORE the host has read the instance count (totals != NULL): the output buffers hold cap_instances
-    // instances and the bins bin_cap keys — if this view needs more, every workgroup leaves without touching
-    // anything and the host, which sees the same totals, launches the pass again after growing them.
-    if (totals && (totals[0] > cap_instances || (totals[1] > bin_cap && bin_cap < 1024u))) return;
     // Workgroup id -> tile, XCD-aware (grid = 8 * ceil(T / 8)): workgroups are dealt round-robin to the 8 XCDs, each
     // with its own L2; XCD x sorts the x-th contiguous eighth of the tiles in raster order, so the record gathers of
     // neighbouring tiles (a Gaussian touches 3.6 on average) meet in one L2.
@@ -464,55 +459,48 @@ __global__ __launch_bounds__(256) void fill_background_kernel(size_t n_pixels, i
     n_contrib[p] = 0u;
 }
 
-void gsr_launch_tile_scan(hipStream_t s, int n_tiles, const uint32_t* tile_count, uint32_t* tile_start,
-                          uint32_t* totals, int n_blocks, const uint32_t* bsum, uint32_t* bpre,
-                          const uint32_t* bvis, uint32_t* big_list, uint32_t* host_mirror, uint32_t seq,
-                          uint32_t* order) {
-    hipLaunchKernelGGL(tile_scan_kernel, dim3(3), dim3(1024), 0, s, n_tiles, tile_count, tile_start, totals,
-                       n_blocks, bsum, bpre, bvis, big_list, host_mirror, seq, order);
+void gsr_launch_tile_scan(hipStream_t s, GsrTiles tiles, GsrGeom geom, int n_blocks, const uint32_t* bvis,
+                          uint32_t* host_mirror, uint32_t seq) {
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(3), dim3(1024), 0, s, tiles.n_tiles, tiles.count, tiles.start, tiles.totals,
+                       n_blocks, geom.bsum, geom.bpre, bvis, tiles.tier_lists, host_mirror, seq, tiles.order);
 }
 
-void gsr_launch_tile_sort(hipStream_t s, int passes, int n_tiles, int grid_x, int channels, const uint32_t* tile_start,
-                          uint32_t* tile_count, const uint64_t* bins, uint32_t bin_cap, const uint64_t* overflow_keys,
-                          uint32_t n_mid4, uint32_t n_mid8,
-                          uint32_t n_big, const uint32_t* tier_lists, uint64_t* big_scratch, size_t slab_stride, GsrGeom geom,
-                          GsrStream stream, uint32_t* values_sorted, uint32_t* ranges, const uint32_t* totals,
-                          uint32_t cap_instances, uint32_t first4, uint32_t first8) {
-    // (first4 / first8: the leading tiles of the two mid tier lists that gsr_launch_tile_sort_mid has already sorted)
-#define LAUNCH_RUNS(CC, RUNSV, GRID, LIST)                                                                        \
-    hipLaunchKernelGGL((tile_sort_runs_kernel<CC, RUNSV>), dim3(GRID), dim3(64 * RUNSV), 0, s, tile_start, LIST, bins, \
-                       bin_cap, overflow_keys, grid_x, geom, stream, values_sorted, 0u, (const uint32_t*)nullptr, 0u, 0)
+void gsr_launch_tile_sort(hipStream_t s, int channels, bool main_pass, GsrTiles tiles, GsrKeys keys, uint32_t n_mid4,
+                          uint32_t n_mid8, uint32_t n_big, uint32_t first4, uint32_t first8, uint64_t* big_scratch,
+                          size_t slab_stride, GsrGeom geom, GsrStream stream, uint32_t* values_sorted) {
+    const uint32_t* const lists = tiles.tier_lists;
+    const size_t T = (size_t)tiles.n_tiles;
     // lists beyond the LDS sort: plan -> chunk sorts -> merge passes -> emit, one workgroup per chunk / 4096-key block
     // (the plan lives behind the 2 n_big slabs; grids are upper bounds from the longest list, surplus workgroups leave at once)
     uint32_t* const plan = reinterpret_cast<uint32_t*>(big_scratch + (size_t)2 * n_big * slab_stride);
     const uint32_t chunks_ub = n_big * (uint32_t)((slab_stride + GSR_SORT_LDS_CAP - 1) / GSR_SORT_LDS_CAP);
     const uint32_t blocks_ub = n_big * (uint32_t)((slab_stride + BIG_OUT - 1) / BIG_OUT);
-#define LAUNCH_BIG(CC)                                                                                            \
-    do {                                                                                                          \
-        hipLaunchKernelGGL(big_plan_kernel, dim3(1), dim3(1024), 0, s, tile_start, tier_lists, n_big, plan);      \
-        hipLaunchKernelGGL(big_chunk_kernel, dim3(chunks_ub), dim3(512), 0, s, tile_start, tier_lists, n_big, plan, \
-                           bins, bin_cap, overflow_keys, big_scratch, slab_stride);                               \
-        int cur = 0;                                                                                              \
-        for (uint32_t L = GSR_SORT_LDS_CAP; L < slab_stride; L <<= 1, cur ^= 1)                                   \
-            hipLaunchKernelGGL(big_merge_kernel, dim3(blocks_ub), dim3(BIG_THREADS), 0, s, tile_start, tier_lists, n_big, \
-                               plan, big_scratch, slab_stride, L, cur);                                           \
-        hipLaunchKernelGGL((big_emit_kernel<CC>), dim3(blocks_ub), dim3(BIG_THREADS), 0, s, tile_start, tier_lists, n_big, \
-                           plan, big_scratch, slab_stride, cur, grid_x, geom, stream, values_sorted);             \
-    } while (0)
-#define ALL(CC)                                                                                                   \
-    if (passes & GSR_SORT_PASS_MAIN)                                                                              \
-        hipLaunchKernelGGL((tile_sort_wave_kernel<CC>), dim3(8 * ((n_tiles + 7) / 8)), dim3(64), 0, s, tile_start,  \
-                           tile_count, bins, bin_cap, grid_x, geom, stream, values_sorted, ranges, totals,          \
-                           cap_instances, n_tiles);                                                                 \
-    if (passes & GSR_SORT_PASS_TIERS) {                                                                           \
-        if (n_mid4 > first4) LAUNCH_RUNS(CC, 4, n_mid4 - first4, tier_lists + 2 * (size_t)n_tiles + first4);      \
-        if (n_mid8 > first8) LAUNCH_RUNS(CC, 8, n_mid8 - first8, tier_lists + (size_t)n_tiles + first8);          \
-        if (n_big > 0) LAUNCH_BIG(CC);                                                                            \
-    }
-    if (channels > 5) { ALL(8) } else if (channels > 3) { ALL(5) } else { ALL(3) }
-#undef ALL
-#undef LAUNCH_RUNS
-#undef LAUNCH_BIG
+    gsr::dispatch_channels(channels, [&](auto c) {
+        constexpr int CH = c;
+        if (main_pass)
+            hipLaunchKernelGGL((tile_sort_wave_kernel<CH>), dim3(8 * ((tiles.n_tiles + 7) / 8)), dim3(64), 0, s, tiles.start,
+                               tiles.count, keys.bins, keys.cap, tiles.grid_x, geom, stream, values_sorted, tiles.ranges,
+                               tiles.n_tiles);
+        // (first4 / first8: the leading tiles of the two mid tier lists that gsr_launch_tile_sort_mid has already sorted)
+        if (n_mid4 > first4)
+            hipLaunchKernelGGL((tile_sort_runs_kernel<CH, 4>), dim3(n_mid4 - first4), dim3(256), 0, s, tiles.start,
+                               lists + 2 * T + first4, keys.bins, keys.cap, keys.overflow, tiles.grid_x, geom, stream,
+                               values_sorted, (const uint32_t*)nullptr, 0u, 0);
+        if (n_mid8 > first8)
+            hipLaunchKernelGGL((tile_sort_runs_kernel<CH, 8>), dim3(n_mid8 - first8), dim3(512), 0, s, tiles.start,
+                               lists + T + first8, keys.bins, keys.cap, keys.overflow, tiles.grid_x, geom, stream,
+                               values_sorted, (const uint32_t*)nullptr, 0u, 0);
+        if (n_big == 0) return;
+        hipLaunchKernelGGL(big_plan_kernel, dim3(1), dim3(1024), 0, s, tiles.start, lists, n_big, plan);
+        hipLaunchKernelGGL(big_chunk_kernel, dim3(chunks_ub), dim3(512), 0, s, tiles.start, lists, n_big, plan, keys.bins,
+                           keys.cap, keys.overflow, big_scratch, slab_stride);
+        int cur = 0;
+        for (uint32_t L = GSR_SORT_LDS_CAP; L < slab_stride; L <<= 1, cur ^= 1)
+            hipLaunchKernelGGL(big_merge_kernel, dim3(blocks_ub), dim3(BIG_THREADS), 0, s, tiles.start, lists, n_big, plan,
+                               big_scratch, slab_stride, L, cur);
+        hipLaunchKernelGGL((big_emit_kernel<CH>), dim3(blocks_ub), dim3(BIG_THREADS), 0, s, tiles.start, lists, n_big, plan,
+                           big_scratch, slab_stride, cur, tiles.grid_x, geom, stream, values_sorted);
+    });
 }
 
 // The two mid tiers' sorts queued BEHIND the scan, before the host has read the counts (round 6): with a held fused launch the
@@ -521,28 +509,27 @@ void gsr_launch_tile_sort(hipStream_t s, int passes, int n_tiles, int grid_x, in
 // workgroup checks the scan's totals (tile_sort_runs_kernel).  Tiles the guess did not cover, lists beyond 8192 and views the
 // guard turned down are sorted by gsr_launch_tile_sort after the read-back (first4 / first8).  Sorting a tile twice is harmless:
 // same keys, same entries.
-void gsr_launch_tile_sort_mid(hipStream_t s, int n_tiles, int grid_x, int channels, const uint32_t* tile_start,
-                              const uint64_t* bins, uint32_t bin_cap, uint32_t grid4, uint32_t grid8, const uint32_t* tier_lists,
-                              GsrGeom geom, GsrStream stream, uint32_t* values_sorted, const uint32_t* totals,
-                              uint32_t cap_instances) {
-#define SPEC(CC)                                                                                                          \
-    do {                                                                                                                  \
-        if (grid4) hipLaunchKernelGGL((tile_sort_runs_kernel<CC, 4>), dim3(grid4), dim3(256), 0, s, tile_start,              \
-                                      tier_lists + 2 * (size_t)n_tiles, bins, bin_cap, (const uint64_t*)nullptr, grid_x, geom, \
-                                      stream, values_sorted, 0u, totals, cap_instances, 3 /* totals[3] = n_mid4 */);          \
-        if (grid8) hipLaunchKernelGGL((tile_sort_runs_kernel<CC, 8>), dim3(grid8), dim3(512), 0, s, tile_start,              \
-                                      tier_lists + (size_t)n_tiles, bins, bin_cap, (const uint64_t*)nullptr, grid_x, geom,    \
-                                      stream, values_sorted, 0u, totals, cap_instances, 6 /* totals[6] = n_mid8 */);          \
-    } while (0)
-    if (channels > 5) SPEC(8); else if (channels > 3) SPEC(5); else SPEC(3);
-#undef SPEC
+void gsr_launch_tile_sort_mid(hipStream_t s, int channels, GsrTiles tiles, GsrKeys keys, uint32_t grid4, uint32_t grid8,
+                              GsrGeom geom, GsrStream stream, uint32_t* values_sorted, uint32_t cap_instances) {
+    const uint32_t* const lists = tiles.tier_lists;
+    const size_t T = (size_t)tiles.n_tiles;
+    gsr::dispatch_channels(channels, [&](auto c) {
+        constexpr int CH = c;
+        if (grid4)
+            hipLaunchKernelGGL((tile_sort_runs_kernel<CH, 4>), dim3(grid4), dim3(256), 0, s, tiles.start, lists + 2 * T,
+                               keys.bins, keys.cap, (const uint64_t*)nullptr, tiles.grid_x, geom, stream, values_sorted,
+                               tiles.totals, cap_instances, (int)GSR_TOTAL_MID4);
+        if (grid8)
+            hipLaunchKernelGGL((tile_sort_runs_kernel<CH, 8>), dim3(grid8), dim3(512), 0, s, tiles.start, lists + T, keys.bins,
+                               keys.cap, (const uint64_t*)nullptr, tiles.grid_x, geom, stream, values_sorted, tiles.totals,
+                               cap_instances, (int)GSR_TOTAL_MID8);
+    });
 }
 
-void gsr_launch_fill_background(hipStream_t s, size_t n_pixels, int channels, const float* background, float* image,
-                                float* final_T, uint32_t* n_contrib) {
+void gsr_launch_fill_background(hipStream_t s, size_t n_pixels, int channels, GsrFrame frame) {
     if (n_pixels == 0) return;
     GsrBg8 bg{};
-    for (int c = 0; c < 3 && c < channels; c++) bg.v[c] = background ? background[c] : 0.0f;  // the colour channels (rasterizer.jl:411-414)
+    for (int c = 0; c < 3 && c < channels; c++) bg.v[c] = frame.background ? frame.background[c] : 0.0f;  // the colour channels (rasterizer.jl:411-414)
     hipLaunchKernelGGL(fill_background_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, s, n_pixels, channels, bg,
-                       image, final_T, n_contrib);
+                       frame.image, frame.final_T, frame.n_contrib);
 }

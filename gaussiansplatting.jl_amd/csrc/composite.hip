@@ -15,6 +15,7 @@
 // (wave_reduce.h), and one 64-byte gradient ROW per (tile, splat) instance leaves the
 // workgroup as plain stores; the per-Gaussian kernel sums a Gaussian's rows.
 #include "gsr_kernels.h"
+#include "gsr_dispatch.h"
 #include "wave_reduce.h"
 #include "tile_sort_device.h"
 
@@ -254,9 +255,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void s
     constexpr int CHUNK = 256;
     __shared__ uint32_t ids[1024];
     __shared__ LdsSplats<C, CHUNK> e;
-    // [0] instances, [1] longest list.  Bins of >= 1024 keys hold every list this launch takes complete whatever the longest one
+    // Bins of >= 1024 keys hold every list this launch takes complete whatever the longest one
     // is (lists beyond the capacity are tier tiles; the host scatters their keys again) — smaller bins must hold them all
-    if (totals[0] > cap_instances || (totals[1] > bin_cap && bin_cap < 1024u)) return;
+    if (totals[GSR_TOTAL_D] > cap_instances || (totals[GSR_TOTAL_MAX_LIST] > bin_cap && bin_cap < 1024u)) return;
     const int tile = (int)tile_order[blockIdx.x];  // launch order: longest lists first
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t start = tile_start[tile], end = tile_start[tile + 1];
@@ -893,65 +894,61 @@ Bg make_bg(const float* background, int channels) {
 
 }  // namespace
 
-void gsr_launch_composite_fwd(hipStream_t s, int channels, GsrCam cam, const uint32_t* tile_start,
-                              const uint32_t* tile_order, GsrStream stream, const float* background, float* image,
-                              uint32_t* n_contrib, float* final_T, const uint32_t* values_sorted, uint8_t* covis,
-                              float* uncert, const GsrTierLists* listed) {
-    // tile_order == NULL: only the tiles of *listed
-    const int n_slots = tile_order ? cam.grid_x * cam.grid_y : (int)(listed->n_big + listed->n_mid8 + listed->n_mid4);
+void gsr_launch_composite_fwd(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrStream stream, GsrFrame frame,
+                              const GsrTierLists* only_listed) {
+    const uint32_t* const tile_order = only_listed ? nullptr : tiles.order;
+    const GsrTierLists tiers = only_listed ? *only_listed : GsrTierLists{};
+    const int n_slots = tile_order ? cam.grid_x * cam.grid_y : (int)(tiers.n_big + tiers.n_mid8 + tiers.n_mid4);
     if (n_slots <= 0) return;
     dim3 grid(32 * ((n_slots + 7) / 8)), block(64);  // 8 XCD lanes x 4 strips per launch slot
-    Bg bg = make_bg(background, channels);
-    const bool aux = covis || uncert;
-    const GsrTierLists tiers = listed ? *listed : GsrTierLists{};
-#define LAUNCH(CC, AA)                                                                                             \
-    hipLaunchKernelGGL((composite_fwd_strip_kernel<CC, AA>), grid, block, 0, s, cam.width, cam.height, cam.grid_x, \
-                       tile_start, tile_order, stream, bg, image, n_contrib, final_T, values_sorted, covis, uncert, tiers)
-    if (channels == 3) { if (aux) LAUNCH(3, true); else LAUNCH(3, false); }
-    else if (channels == 5) { if (aux) LAUNCH(5, true); else LAUNCH(5, false); }
-    else { if (aux) LAUNCH(8, true); else LAUNCH(8, false); }
-#undef LAUNCH
+    Bg bg = make_bg(frame.background, channels);
+    gsr::dispatch_channels(channels, [&](auto c) {
+        constexpr int CH = c;
+        gsr::dispatch_bool(frame.covis || frame.uncert, [&](auto a) {
+            constexpr bool AUX = a;
+            hipLaunchKernelGGL((composite_fwd_strip_kernel<CH, AUX>), grid, block, 0, s, cam.width, cam.height, cam.grid_x,
+                               tiles.start, tile_order, stream, bg, frame.image, frame.n_contrib, frame.final_T,
+                               frame.values_sorted, frame.covis, frame.uncert, tiers);
+        });
+    });
 }
 
-void gsr_launch_sort_composite_fwd(hipStream_t s, int channels, GsrCam cam, const uint32_t* tile_start,
-                                   const uint32_t* tile_order, uint32_t* tile_count, const uint64_t* bins, uint32_t bin_cap,
-                                   GsrGeom geom, GsrStream stream, const float* background, float* image,
-                                   uint32_t* n_contrib, float* final_T, uint32_t* values_sorted, uint32_t* ranges,
-                                   uint8_t* covis, float* uncert, const uint32_t* totals, uint32_t cap_instances,
-                                   bool keep_backward_state) {
+void gsr_launch_sort_composite_fwd(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrKeys keys, GsrGeom geom,
+                                   GsrStream stream, GsrFrame frame, uint32_t cap_instances, bool keep_backward_state) {
     dim3 grid(cam.grid_x * cam.grid_y), block(256);
-    Bg bg = make_bg(background, channels);
-    const bool aux = covis || uncert;
-#define LAUNCH2(CC, AA, KK)                                                                                            \
-    hipLaunchKernelGGL((sort_composite_fwd_kernel<CC, AA, KK>), grid, block, 0, s, cam.width, cam.height, cam.grid_x,  \
-                       tile_start, tile_order, tile_count, bins, bin_cap, geom, stream, bg, image, n_contrib,          \
-                       final_T, values_sorted, ranges, covis, uncert, totals, cap_instances)
-#define LAUNCH(CC, AA) do { if (keep_backward_state) LAUNCH2(CC, AA, true); else LAUNCH2(CC, AA, false); } while (0)
-    if (channels == 3) { if (aux) LAUNCH(3, true); else LAUNCH(3, false); }
-    else if (channels == 5) { if (aux) LAUNCH(5, true); else LAUNCH(5, false); }
-    else { if (aux) LAUNCH(8, true); else LAUNCH(8, false); }
-#undef LAUNCH
-#undef LAUNCH2
+    Bg bg = make_bg(frame.background, channels);
+    gsr::dispatch_channels(channels, [&](auto c) {
+        constexpr int CH = c;
+        gsr::dispatch_bool(frame.covis || frame.uncert, [&](auto a) {
+            constexpr bool AUX = a;
+            gsr::dispatch_bool(keep_backward_state, [&](auto k) {
+                constexpr bool KEEP = k;
+                hipLaunchKernelGGL((sort_composite_fwd_kernel<CH, AUX, KEEP>), grid, block, 0, s, cam.width, cam.height,
+                                   cam.grid_x, tiles.start, tiles.order, tiles.count, keys.bins, keys.cap, geom, stream, bg,
+                                   frame.image, frame.n_contrib, frame.final_T, frame.values_sorted, tiles.ranges,
+                                   frame.covis, frame.uncert, tiles.totals, cap_instances);
+            });
+        });
+    });
 }
 
-void gsr_launch_composite_bwd(hipStream_t s, int channels, GsrCam cam, const uint32_t* tile_start,
-                              const uint32_t* tile_order, GsrStream stream, const float* background,
-                              const float* vpixels, const uint32_t* n_contrib, const float* final_T, GsrInst inst,
-                              uint32_t split_len, bool color_only, bool accurate) {
+void gsr_launch_composite_bwd(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrStream stream, GsrFrame frame,
+                              const float* vpixels, GsrInst inst, uint32_t split_len, bool color_only, bool accurate) {
     dim3 grid(cam.grid_x * cam.grid_y), block(64);
-    Bg bg = make_bg(background, channels);
+    Bg bg = make_bg(frame.background, channels);
     GsrTierLists none{};
     none.split_len = split_len;
     const bool bg0 = bg_is_zero(bg);
 #define LAUNCH_K(CC, ZZ, VV, AA)                                                                                       \
     hipLaunchKernelGGL((composite_bwd_kernel<CC, ZZ, VV, AA>), grid, block, 0, s, cam.width, cam.height,               \
-                       cam.grid_x, tile_start, tile_order, stream, bg, vpixels, n_contrib, final_T, inst, none)
+                       cam.grid_x, tiles.start, tiles.order, stream, bg, vpixels, frame.n_contrib, frame.final_T, inst, none)
     // accurate: the ACC instantiations (libm exp, IEEE division: gsr_config.grad_precision) — the general-background kernels only
 #define LAUNCH2(CC, ZZ) do { if (accurate) LAUNCH_K(CC, false, CC, true); else LAUNCH_K(CC, ZZ, CC, false); } while (0)
     // the zero-background kernels where they pay (table above the kernel): C == 5 and C == 8 take BG0, C == 3 never does
     // (:rgb capped at six waves with 1.25 KB of unused dynamic LDS per workgroup takes 0.738 ms: it is the code generated under
     //  the tighter register budget that is slower, not the occupancy)
 #define LAUNCH3(CC, ZZ) do { if (accurate) LAUNCH_K(CC, false, 3, true); else LAUNCH_K(CC, ZZ, 3, false); } while (0)
+    // (written out: the instantiation set is irregular on purpose — no BG0 for C == 3 or with ACC, VC = 3 only for colour-only)
     if (channels == 3) LAUNCH2(3, false);
     else if (color_only) {
         // the cotangent of the loss head (channels >= 3 are zeros): the :rgb arithmetic on the mode's stream.  (BG0 as measured
@@ -966,26 +963,21 @@ void gsr_launch_composite_bwd(hipStream_t s, int channels, GsrCam cam, const uin
 #undef LAUNCH3
 }
 
-void gsr_launch_composite_bwd_listed(hipStream_t s, int channels, GsrCam cam, const uint32_t* tile_start,
-                                     GsrTierLists tiers, GsrStream stream, const float* background,
-                                     const float* vpixels, const uint32_t* n_contrib, const float* final_T, GsrInst inst,
-                                     float* long_state) {
+void gsr_launch_composite_bwd_listed(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrTierLists tiers,
+                                     GsrStream stream, GsrFrame frame, const float* vpixels, GsrInst inst, float* long_state) {
     const uint32_t n_listed = tiers.n_big + tiers.n_mid8 + tiers.n_mid4;
     if (n_listed == 0) return;
-    Bg bg = make_bg(background, channels);
+    Bg bg = make_bg(frame.background, channels);
     dim3 grid(n_listed * LONG_SEGS), block(64);
-    const bool bg0 = bg_is_zero(bg);
     float2* st = reinterpret_cast<float2*>(long_state);
-#define LAUNCH(CC, ZZ)                                                                                                    \
-    do {                                                                                                                  \
-        hipLaunchKernelGGL((composite_bwd_long_kernel<CC, ZZ, 1>), grid, block, 0, s, cam.width, cam.height, cam.grid_x,  \
-                           tile_start, stream, bg, vpixels, n_contrib, final_T, inst, tiers, st);                         \
-        hipLaunchKernelGGL((composite_bwd_long_kernel<CC, ZZ, 2>), grid, block, 0, s, cam.width, cam.height, cam.grid_x,  \
-                           tile_start, stream, bg, vpixels, n_contrib, final_T, inst, tiers, st);                         \
-    } while (0)
-    if (channels == 3) { if (bg0) LAUNCH(3, true); else LAUNCH(3, false); }
-    else if (channels == 5) { if (bg0) LAUNCH(5, true); else LAUNCH(5, false); }
-    else if (bg0) LAUNCH(8, true);
-    else LAUNCH(8, false);
-#undef LAUNCH
+    gsr::dispatch_channels(channels, [&](auto c) {
+        constexpr int CH = c;
+        gsr::dispatch_bool(bg_is_zero(bg), [&](auto z) {
+            constexpr bool BG0 = z;
+            hipLaunchKernelGGL((composite_bwd_long_kernel<CH, BG0, 1>), grid, block, 0, s, cam.width, cam.height, cam.grid_x,
+                               tiles.start, stream, bg, vpixels, frame.n_contrib, frame.final_T, inst, tiers, st);
+            hipLaunchKernelGGL((composite_bwd_long_kernel<CH, BG0, 2>), grid, block, 0, s, cam.width, cam.height, cam.grid_x,
+                               tiles.start, stream, bg, vpixels, frame.n_contrib, frame.final_T, inst, tiers, st);
+        });
+    });
 }

@@ -258,7 +258,7 @@ struct gsr_handle {
     DevBuf rows, vmean2d;
     // loss-head scratch
     DevBuf d0, d1, d2, partial;
-    uint32_t* host_totals = nullptr;  // pinned: D, max tile count, #oversized tiles, slab ctr, n_visible, ..., [7] = sequence
+    uint32_t* host_totals = nullptr;  // pinned: the scan's totals (GsrTotal), [GSR_TOTAL_SEQ] = the forward's sequence number
     uint32_t* host_totals_dev = nullptr;  // the same words as the device addresses them
     uint32_t totals_seq = 0;
     hipStream_t aux_stream = nullptr;  // the four-wave backward of those tiles runs here, next to the main launch
@@ -308,6 +308,16 @@ GsrStream stream_of(const gsr_handle* h) {
     return GsrStream{h->s0.as<float4>(), h->s1.as<float4>(), h->s2.as<float4>(), h->s3.as<float4>()};
 }
 GsrInst inst_of(const gsr_handle* h) { return GsrInst{h->rows.as<float4>()}; }
+GsrTiles tiles_of(const gsr_handle* h) {
+    return GsrTiles{h->tile_start.as<uint32_t>(), h->tile_count.as<uint32_t>(), h->tile_order.as<uint32_t>(),
+                    h->ranges.as<uint32_t>(), h->big_list.as<uint32_t>(), h->totals.as<uint32_t>(), h->n_tiles, h->grid_x};
+}
+// the handle's fixed-capacity bins (cap == 0: preprocess only counts)
+GsrKeys bins_of(const gsr_handle* h, uint32_t cap) { return GsrKeys{h->bins.as<uint64_t>(), cap, nullptr}; }
+GsrFrame frame_of(const gsr_handle* h, const float* background, float* image, const gsr_aux* aux) {
+    return GsrFrame{background, image, h->n_contrib.as<uint32_t>(), h->final_T.as<float>(), h->values_sorted.as<uint32_t>(),
+                    aux ? aux->covisibilities : nullptr, aux ? aux->uncertainties : nullptr};
+}
 
 // CPU relax hint inside the spin phase: x86 `pause`, AArch64 `yield`, nothing elsewhere (the host side builds on any arch).
 static inline void cpu_relax() {
@@ -367,7 +377,7 @@ inline int preprocess_form_of(const gsr_handle* h) {  // -1 by scene and grid, 0
 // the stream, and a marker between two kernels is a 5 us bubble (rocprofv3 kernel trace, tools/gap_report.py).
 int wait_totals(gsr_handle* h, uint32_t seq, hipStream_t s) {
     using clk = std::chrono::steady_clock;
-    volatile uint32_t* word = h->host_totals + 7;
+    volatile uint32_t* word = h->host_totals + GSR_TOTAL_SEQ;
     if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return GSR_OK;
     const auto t0 = clk::now();
     const double expect_us = h->wait_ema_us;
@@ -596,13 +606,13 @@ int gsr_create(const gsr_config* cfg, gsr_handle** out) {
     int rc = GSR_OK;
     if ((rc = h->ranges.ensure(2 * T * 4)) || (rc = h->n_contrib.ensure(P * 4)) || (rc = h->final_T.ensure(P * 4)) ||
         (rc = h->tile_count.ensure((T + 2) * 4)) || (rc = h->tile_start.ensure((T + 1) * 4)) ||
-        (rc = h->tile_order.ensure((T + 8) * 4)) || (rc = h->totals.ensure(8 * 4)) || (rc = h->big_list.ensure((3 * T + 1) * 4))) {
+        (rc = h->tile_order.ensure((T + 8) * 4)) || (rc = h->totals.ensure(GSR_TOTAL_WORDS * 4)) || (rc = h->big_list.ensure((3 * T + 1) * 4))) {
         gsr_destroy(h);
         return rc;
     }
-    hipError_t e = hipHostMalloc((void**)&h->host_totals, 8 * sizeof(uint32_t), hipHostMallocDefault);  // fine-grained
+    hipError_t e = hipHostMalloc((void**)&h->host_totals, GSR_TOTAL_WORDS * sizeof(uint32_t), hipHostMallocDefault);  // fine-grained
     if (e == hipSuccess) {
-        memset(h->host_totals, 0, 8 * sizeof(uint32_t));
+        memset(h->host_totals, 0, GSR_TOTAL_WORDS * sizeof(uint32_t));
         e = hipHostGetDevicePointer((void**)&h->host_totals_dev, h->host_totals, 0);
     }
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking);
@@ -612,7 +622,7 @@ int gsr_create(const gsr_config* cfg, gsr_handle** out) {
         gsr_destroy(h);
         return fail(GSR_E_HIP, "pinned memory / stream / event creation failed: %s", hipGetErrorString(e));
     }
-    (void)hipMemset(h->totals.p, 0, 8 * 4);  // [7]: the scan's ticket word
+    (void)hipMemset(h->totals.p, 0, GSR_TOTAL_WORDS * 4);  // [GSR_TOTAL_SEQ]: the scan's ticket word
     (void)hipMemset(h->ranges.p, 0, 2 * T * 4);
     (void)hipMemset(h->tile_count.p, 0, (T + 2) * 4);
     *out = h;
@@ -689,24 +699,42 @@ int64_t gsr_memory_usage(const gsr_handle* h) {
     return s;
 }
 
-int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, float* image_out, const gsr_aux* aux,
-                void* stream_v, gsr_stats* stats) {
+// What the stages of one gsr_forward share (the stages below, in the order gsr_forward lists them).
+struct FwdView {
+    hipStream_t s;
+    int C, n;
+    const gsr_inputs* in; float* image_out; const gsr_aux* aux; gsr_stats* stats;  // the caller's
+    bool fwd_only;
+    GsrCam k;
+    gsr_view_plan plan;
+    gsr_view_outcome oc;
+    uint64_t cap_instances;  // what the per-instance buffers held when the view began
+    bool spec;               // launches may go out behind the scan, before the host has the counts
+    uint32_t seq;
+    uint64_t D, D_slots;     // the scan's totals, read back: D_slots >= D; == D unless exact culling dropped tiles
+    uint32_t max_tile, n_big, n_mid4, n_mid8, visible;  // visible: with the any-rect flag in bit 31
+    size_t slab_stride;      // keys per merge slab of a list beyond the LDS sort (0: none)
+};
+
+// Argument checks and per-Gaussian scratch; a call that gets through them is the handle's forward number `generation`.
+static int fwd_begin(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, float* image_out, const gsr_aux* aux,
+                     void* stream_v, gsr_stats* stats, FwdView& v) {
     int rc = check_inputs(h, in, cam);
     if (rc) return rc;
     if (!image_out) return fail(GSR_E_INVALID_ARG, "null image_out");
     if (aux && ((aux->flags & ~(uint32_t)GSR_FORWARD_ONLY) || aux->reserved))
         return fail(GSR_E_INVALID_ARG, "unknown gsr_aux.flags 0x%x / reserved 0x%x", aux->flags, aux->reserved);
-    const bool fwd_only = aux && (aux->flags & GSR_FORWARD_ONLY);
-    hipStream_t s = (hipStream_t)stream_v;
-    const int C = h->cfg.mode, n = in->n;
-    const size_t P = (size_t)h->cfg.width * h->cfg.height, T = (size_t)h->n_tiles;
+    v.in = in; v.image_out = image_out; v.aux = aux; v.stats = stats;
+    v.fwd_only = aux && (aux->flags & GSR_FORWARD_ONLY);
+    v.s = (hipStream_t)stream_v;
+    v.C = h->cfg.mode; v.n = in->n;
     h->fwd_valid = false;
     h->bwd_valid = false;
     h->inputs_consumed = false;
-    h->fwd_only = fwd_only;
+    h->fwd_only = v.fwd_only;
 
-    const size_t nn = n > 0 ? (size_t)n : 1;
-    const int n_blocks = (n + 255) / 256;
+    const size_t nn = v.n > 0 ? (size_t)v.n : 1;
+    const int n_blocks = (v.n + 255) / 256;
     const bool own_radii = !(aux && aux->radii);
     // per-Gaussian scratch: grow-only with 25 % slack, like the per-instance buffers below — a training run's densification
     // adds 5-15 % of Gaussians per round (strategy.jl:78-105), and an exact fit made EVERY round's first view reallocate all
@@ -714,15 +742,30 @@ int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, floa
     const float nslack = 1.25f;
     if ((rc = h->geo.ensure(nn * 64, nslack)) || (own_radii && (rc = h->radii.ensure(nn * 4, nslack))) ||
         (rc = h->bsum.ensure((size_t)(n_blocks + 1) * 4, nslack)) || (rc = h->bpre.ensure((size_t)(n_blocks + 1) * 4, nslack)) ||
-        (rc = h->bvis.ensure((size_t)(n_blocks + 1) * 4, nslack)) || (C > 5 && (rc = h->gnormal.ensure(nn * 16, nslack))))
+        (rc = h->bvis.ensure((size_t)(n_blocks + 1) * 4, nslack)) || (v.C > 5 && (rc = h->gnormal.ensure(nn * 16, nslack))))
         return rc;
     h->radii_cur = own_radii ? h->radii.as<int32_t>() : aux->radii;
     h->vmean2d_cur = nullptr;
     h->generation++;
     if (stats) stats->generation = h->generation;
+    v.k = make_cam(h, cam);
+    return GSR_OK;
+}
 
-    GsrCam k = make_cam(h, cam);
-    uint32_t* totals = h->totals.as<uint32_t>();
+// Sort + forward of every tile of up to 1024 instances, as ONE launch on stream fs.
+static void launch_fused(gsr_handle* h, const FwdView& v, hipStream_t fs) {
+    StageScope sc3(h->prof, ST_SORT_COMPOSITE_FWD, fs);
+    gsr_launch_sort_composite_fwd(fs, v.C, v.k, tiles_of(h), bins_of(h, v.plan.bin_cap_view), geom_of(h), stream_of(h),
+                                  frame_of(h, v.in->background, v.image_out, v.aux), (uint32_t)v.cap_instances,
+                                  /*keep_backward_state=*/!v.fwd_only);
+    sc3.close();
+}
+
+// Plan and bin: the view's plan, preprocess, the scan, and what goes out behind the scan without waiting for the host.
+static int fwd_plan_and_bin(gsr_handle* h, FwdView& v) {
+    int rc;
+    const hipStream_t s = v.s;
+    const size_t T = (size_t)h->n_tiles;
     // Binning (SURVEY.md A.5-A.7 restated per tile).  FAST mode: every tile owns a fixed-capacity key bin and preprocess drops
     // the keys straight into them — no second pass over the instances; (T+1) x capacity x 8 B, so only while that stays within
     // the bins budget.  Otherwise — a scene with a few very deep tiles, or a view that overflowed small bins — the COMPACT mode
@@ -731,17 +774,16 @@ int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, floa
     h->pcfg.preprocess_form = preprocess_form_of(h);  // the handle's pin, else the process default as of this call
     float timed_ms[GSR_TUNER_TIMED_VIEWS];
     const bool have_ms = h->pcfg.form_tuner && h->pol.tuner.phase == GSR_TUNER_TIMED_VIEWS && h->tuner_ev.read(timed_ms);
-    gsr_view_plan plan;
-    gsr_policy_begin_view(&h->pcfg, &h->pol, n, have_ms ? timed_ms : nullptr, &plan);
-    const bool use_bins = plan.bin_cap_view > 0;
-    const uint32_t bin_cap_view = plan.bin_cap_view;
+    gsr_policy_begin_view(&h->pcfg, &h->pol, v.n, have_ms ? timed_ms : nullptr, &v.plan);
+    const uint32_t bin_cap_view = v.plan.bin_cap_view;
+    const bool use_bins = bin_cap_view > 0;
     if (use_bins && (rc = h->bins.ensure((T + 1) * (size_t)bin_cap_view * 8))) return rc;
     // The tile counters are zero on entry: gsr_create clears them and the tile sort re-zeroes each
     // tile's counter as it consumes it (no memset kernel per view; the scan overwrites every total).
     // Only a pass that did not reach the sort (an error) leaves them dirty.
     if (h->tile_count_dirty) HIPCHK(hipMemsetAsync(h->tile_count.p, 0, (T + 2) * 4, s));
     h->tile_count_dirty = true;
-    int timed = plan.timed_slot;
+    int timed = v.plan.timed_slot;
     if (timed >= 0 && !h->tuner_ev.create()) {  // no clock, no tuner on this handle (the plan's form is still a valid form)
         h->pcfg.form_tuner = 0;
         h->pol.tuner.phase = 0;
@@ -749,30 +791,29 @@ int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, floa
     }
     StageScope sc1(h->prof, ST_PREPROCESS, s);
     if (timed >= 0) HIPCHK(hipEventRecord(h->tuner_ev.ev[2 * timed], s));
-    h->last_form = gsr_launch_preprocess(s, n, in->n_coeffs, in->sh_degree, C, in->means, in->scales, in->rotations,
-                                         in->opacities, in->shs, k, geom_of(h), h->tile_count.as<uint32_t>(),
-                                         h->bvis.as<uint32_t>(), h->bins.as<uint64_t>(), bin_cap_view /* 0: count only */,
-                                         h->n_tiles, /*aggregating=*/plan.form != GSR_FORM_DIRECT);
+    h->last_form = gsr_launch_preprocess(s, v.n, v.in->n_coeffs, v.in->sh_degree, v.C, v.in->means, v.in->scales,
+                                         v.in->rotations, v.in->opacities, v.in->shs, v.k, geom_of(h), tiles_of(h),
+                                         h->bvis.as<uint32_t>(), bins_of(h, bin_cap_view) /* 0: count only */,
+                                         /*aggregating=*/v.plan.form != GSR_FORM_DIRECT);
     if (timed >= 0) HIPCHK(hipEventRecord(h->tuner_ev.ev[2 * timed + 1], s));
     sc1.close();
-    const uint32_t seq = ++h->totals_seq ? h->totals_seq : ++h->totals_seq;  // never 0
+    v.seq = ++h->totals_seq ? h->totals_seq : ++h->totals_seq;  // never 0
     StageScope sc2(h->prof, ST_SCAN, s);
-    gsr_launch_tile_scan(s, h->n_tiles, h->tile_count.as<uint32_t>(), h->tile_start.as<uint32_t>(), totals,
-                         n_blocks, h->bsum.as<uint32_t>(), h->bpre.as<uint32_t>(), h->bvis.as<uint32_t>(),
-                         h->big_list.as<uint32_t>(), h->host_totals_dev, seq, h->tile_order.as<uint32_t>());
+    gsr_launch_tile_scan(s, tiles_of(h), geom_of(h), (v.n + 255) / 256, h->bvis.as<uint32_t>(), h->host_totals_dev, v.seq);
     sc2.close();
     HIPCHK(hipGetLastError());
     // the one host sync of the path: instance count D (reference: rasterizer.jl:337).  tile_scan stores the totals
     // and then this forward's sequence number into pinned host memory; no copy packet, no event on the stream.
     // Sort + forward of every tile of up to 1024 instances (nearly all of them) go out BEHIND the scan, as ONE launch,
     // without waiting for the host: the buffers have a capacity from earlier views (grow-only, 25 % slack), and the
-    // kernel itself checks the scan's totals against it.  The host's wait below then overlaps that launch instead of
+    // kernel itself checks the scan's totals against it.  The host's wait (fwd_read_back) then overlaps that launch instead of
     // idling the GPU, and inside it the HBM-bound sort of one tile shares the CU with the VALU-bound compositing of others.
     uint64_t cap_instances = std::min(std::min(h->values_sorted.cap / 4, h->s0.cap / 16), std::min(h->s1.cap / 16, h->s2.cap / 16));
-    if (C > 3) cap_instances = std::min<uint64_t>(cap_instances, h->s3.cap / 16);
+    if (v.C > 3) cap_instances = std::min<uint64_t>(cap_instances, h->s3.cap / 16);
     cap_instances = std::min<uint64_t>(cap_instances, 0xFFFFFFFFull);
-    if (fwd_only) cap_instances = 0xFFFFFFFFull;  // nothing is stored per instance: no capacity to respect
-    const bool spec = use_bins && cap_instances > 0;
+    if (v.fwd_only) cap_instances = 0xFFFFFFFFull;  // nothing is stored per instance: no capacity to respect
+    v.cap_instances = cap_instances;
+    v.spec = use_bins && cap_instances > 0;
     // TIER TILES (lists beyond the fused launch's 1024 instances) are walked by their own launch, four single-wave workgroups per
     // tile, and that walk is a latency chain: 0.4 ms for one 32 k-instance tile and its neighbours, 0.15 ms for the few hundred
     // tiles of 1-4 k instances of a trained-like scene — it belongs BESIDE the fused launch, not behind it.  What does not work,
@@ -787,152 +828,174 @@ int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, floa
     // and then goes out together with the walk, which takes the handle's second stream at raised wave priority.  Hot tile
     // (32 k) 2.08 -> 1.80 ms, trained-like 3 M / 1440p 2.19 -> 2.10, dense 4K 7.81 -> 7.70; a view without tier tiles is not
     // touched.  (gsr_policy_config.beside_max_tiles: hold only when the previous view had at most that many tier tiles; 0 = never.)
-    const bool hold_fused = spec && plan.hold_fused;
-    const auto launch_fused = [&](hipStream_t fs) {
-        StageScope sc3(h->prof, ST_SORT_COMPOSITE_FWD, fs);
-        gsr_launch_sort_composite_fwd(fs, C, k, h->tile_start.as<uint32_t>(), h->tile_order.as<uint32_t>(),
-                                      h->tile_count.as<uint32_t>(), h->bins.as<uint64_t>(), bin_cap_view, geom_of(h),
-                                      stream_of(h), in->background, image_out, h->n_contrib.as<uint32_t>(),
-                                      h->final_T.as<float>(), h->values_sorted.as<uint32_t>(), h->ranges.as<uint32_t>(),
-                                      aux ? aux->covisibilities : nullptr, aux ? aux->uncertainties : nullptr, totals,
-                                      (uint32_t)cap_instances, /*keep_backward_state=*/!fwd_only);
-        sc3.close();
-    };
-    if (spec && !hold_fused) launch_fused(s);
+    const bool hold_fused = v.spec && v.plan.hold_fused;
+    if (v.spec && !hold_fused) launch_fused(h, v, s);
     // A held fused launch waits for the tier sorts, and those for the host's read-back: 22-34 us of idle GPU per view (kernel
     // trace of the training protocol, profiles/r06/experiments/training_step_idle_time.txt).  The two mid tiers' sorts therefore
     // go out NOW, behind the scan, with grids guessed from the previous view and the scan's totals checked on the device
     // (gsr_launch_tile_sort_mid); what the guess missed — and every list beyond 8192, whose chain needs host-sized scratch — is
     // sorted after the read-back.  Not for forward-only renders (whose stream buffers are not sized by cap_instances).
     // (the guesses are the policy's: gsr_view_plan.spec_mid4 / spec_mid8; what is not launched is zeroed for gsr_policy_end_view)
-    if (!(hold_fused && !fwd_only)) plan.spec_mid4 = plan.spec_mid8 = 0u;
-    const uint32_t spec4 = plan.spec_mid4, spec8 = plan.spec_mid8;
-    if (spec4 | spec8) {
+    if (!(hold_fused && !v.fwd_only)) v.plan.spec_mid4 = v.plan.spec_mid8 = 0u;
+    if (v.plan.spec_mid4 | v.plan.spec_mid8) {
         StageScope scs(h->prof, ST_SORT, s, /*extra=*/true);  // (the stage's time; the call after the read-back counts the launch)
-        gsr_launch_tile_sort_mid(s, h->n_tiles, h->grid_x, C, h->tile_start.as<uint32_t>(), h->bins.as<uint64_t>(), bin_cap_view,
-                                 spec4, spec8, h->big_list.as<uint32_t>(), geom_of(h), stream_of(h),
-                                 h->values_sorted.as<uint32_t>(), totals, (uint32_t)cap_instances);
+        gsr_launch_tile_sort_mid(s, v.C, tiles_of(h), bins_of(h, bin_cap_view), v.plan.spec_mid4, v.plan.spec_mid8, geom_of(h),
+                                 stream_of(h), h->values_sorted.as<uint32_t>(), (uint32_t)cap_instances);
         scs.close();
     }
-    if ((rc = wait_totals(h, seq, s))) return rc;
+    return GSR_OK;
+}
+
+// gsr_stats of the view, once the scan's counts and the policy's outcome are known
+static void fill_view_stats(const gsr_handle* h, const FwdView& v, gsr_stats* st) {
+    const bool hybrid = v.oc.binning == GSR_BINNING_OVERFLOW, compact = v.oc.binning == GSR_BINNING_COMPACT;
+    st->n_rendered = (int64_t)v.D;
+    st->n_visible = (int32_t)(v.visible & 0x7FFFFFFFu);
+    st->max_tile_instances = (int32_t)v.max_tile;
+    st->compact_binning = v.oc.binning;
+    st->preprocess_form = h->last_form;
+    st->bins_bytes = (int64_t)(compact ? v.D * 8 : (uint64_t)(h->n_tiles + 1) * v.plan.bin_cap_view * 8ull + (hybrid ? v.D * 8 : 0));
+    st->bin_capacity = v.plan.bin_cap_view;
+    st->tier_tiles[0] = v.n_mid4; st->tier_tiles[1] = v.n_mid8; st->tier_tiles[2] = v.n_big;
+    st->reserved = 0;
+    fill_history(h, st);  // (again at the end: the buffers this view grows are counted there)
+}
+
+// Read-back: the one host sync, then what this view turned out to be.
+static int fwd_read_back(gsr_handle* h, FwdView& v) {
+    int rc;
+    if ((rc = wait_totals(h, v.seq, v.s))) return rc;
     // What this view turned out to be — bins / overflow tiles / compact; whether the fused launch covers it; where the tier
     // walk goes; the bins' capacity for the next view — is gsr_policy_end_view's decision on the scan's counts.
     // OVERFLOW TILES (round 5): lists longer than the bins' capacity.  Their bins hold the first bin_cap_view arrivals only
-    // (preprocess counted every instance); their complete key lists come from a scatter pass restricted to them (below), and
-    // every sort takes a tile's keys from wherever they are complete.  The rest of the view stays on the fast path.
-    const uint64_t D = h->host_totals[0];
-    const uint32_t max_tile = h->host_totals[1], n_big = h->host_totals[2];
-    const uint32_t n_mid4 = h->host_totals[3], n_mid8 = h->host_totals[6];
-    const uint64_t D_slots = h->host_totals[5];  // >= D; == D unless exact culling dropped tiles
-    gsr_view_outcome oc;
-    gsr_policy_end_view(&h->pcfg, &h->pol, &plan, (int64_t)D, max_tile, n_mid4, n_mid8, n_big, cap_instances, spec ? 1 : 0, &oc);
-    const bool hybrid = oc.binning == GSR_BINNING_OVERFLOW, compact = oc.binning == GSR_BINNING_COMPACT;
-    const bool fused_done = oc.fused_done != 0, long_tiles = oc.long_tiles != 0, beside = oc.beside != 0;
-    h->last_n = n;
-    h->last_D = (int64_t)D;
-    h->last_slots = (int64_t)D_slots;
-    h->last_compact = compact;
-    if (stats) {
-        stats->n_rendered = (int64_t)D;
-        stats->n_visible = (int32_t)(h->host_totals[4] & 0x7FFFFFFFu);
-        stats->max_tile_instances = (int32_t)max_tile;
-        stats->compact_binning = oc.binning;
-        stats->preprocess_form = h->last_form;
-        stats->bins_bytes = (int64_t)(compact ? D * 8 : (uint64_t)(T + 1) * bin_cap_view * 8ull + (hybrid ? D * 8 : 0));
-        stats->bin_capacity = bin_cap_view;
-        stats->tier_tiles[0] = n_mid4; stats->tier_tiles[1] = n_mid8; stats->tier_tiles[2] = n_big;
-        stats->reserved = 0;
-        fill_history(h, stats);  // (again at the end: the buffers this view grows are counted there)
+    // (preprocess counted every instance); their complete key lists come from a scatter pass restricted to them
+    // (fwd_sort_and_walk), and every sort takes a tile's keys from wherever they are complete.  The rest of the view stays on
+    // the fast path.
+    const uint32_t* t = h->host_totals;
+    v.D = t[GSR_TOTAL_D]; v.D_slots = t[GSR_TOTAL_SLOTS]; v.max_tile = t[GSR_TOTAL_MAX_LIST];
+    v.n_big = t[GSR_TOTAL_BIG]; v.n_mid4 = t[GSR_TOTAL_MID4]; v.n_mid8 = t[GSR_TOTAL_MID8]; v.visible = t[GSR_TOTAL_VISIBLE];
+    gsr_policy_end_view(&h->pcfg, &h->pol, &v.plan, (int64_t)v.D, v.max_tile, v.n_mid4, v.n_mid8, v.n_big, v.cap_instances,
+                        v.spec ? 1 : 0, &v.oc);
+    h->last_n = v.n;
+    h->last_D = (int64_t)v.D;
+    h->last_slots = (int64_t)v.D_slots;
+    h->last_compact = v.oc.binning == GSR_BINNING_COMPACT;
+    if (v.stats) fill_view_stats(h, v, v.stats);
+    return GSR_OK;
+}
+
+// Empty view (D == 0): nothing to sort or blend.
+static int fwd_empty_view(gsr_handle* h, const FwdView& v) {
+    const hipStream_t s = v.s;
+    const size_t P = (size_t)h->cfg.width * h->cfg.height, T = (size_t)h->n_tiles;
+    h->tile_count_dirty = false;  // every counter is zero
+    if (v.k.exact_cull && (v.visible >> 31)) {
+        // exact-cull mode dropped every instance (all of them invisible: opacities below 1/255) of a view the reference WOULD
+        // have rendered (some rect holds a tile): its pixels blend nothing and show the background, as with the reference's
+        // lists — the all-zero image below is the reference's answer to "no instance at all" only
+        gsr_launch_fill_background(s, P, v.C, frame_of(h, v.in->background, v.image_out, v.aux));
+    } else {
+        // rasterizer.jl:283,338: all-zero image, background not applied
+        HIPCHK(hipMemsetAsync(v.image_out, 0, P * v.C * 4, s));
+        HIPCHK(hipMemsetAsync(h->n_contrib.p, 0, P * 4, s));
+        HIPCHK(hipMemsetAsync(h->final_T.p, 0, P * 4, s));
     }
-    if (D == 0) {
-        h->tile_count_dirty = false;  // every counter is zero
-        if (k.exact_cull && (h->host_totals[4] >> 31)) {
-            // exact-cull mode dropped every instance (all of them invisible: opacities below 1/255) of a view the reference WOULD
-            // have rendered (some rect holds a tile): its pixels blend nothing and show the background, as with the reference's
-            // lists — the all-zero image below is the reference's answer to "no instance at all" only
-            gsr_launch_fill_background(s, P, C, in->background, image_out, h->final_T.as<float>(), h->n_contrib.as<uint32_t>());
-        } else {
-            // rasterizer.jl:283,338: all-zero image, background not applied
-            HIPCHK(hipMemsetAsync(image_out, 0, P * C * 4, s));
-            HIPCHK(hipMemsetAsync(h->n_contrib.p, 0, P * 4, s));
-            HIPCHK(hipMemsetAsync(h->final_T.p, 0, P * 4, s));
-        }
-        HIPCHK(hipMemsetAsync(h->ranges.p, 0, 2 * T * 4, s));
-        if (aux && aux->uncertainties) HIPCHK(hipMemsetAsync(aux->uncertainties, 0, P * 4, s));
-        h->fwd_valid = true;
-        return GSR_OK;
-    }
+    HIPCHK(hipMemsetAsync(h->ranges.p, 0, 2 * T * 4, s));
+    if (v.aux && v.aux->uncertainties) HIPCHK(hipMemsetAsync(v.aux->uncertainties, 0, P * 4, s));
+    h->fwd_valid = true;
+    return GSR_OK;
+}
+
+// Instance buffers: grow-only, sized by the counts just read.
+static int fwd_instance_buffers(gsr_handle* h, FwdView& v) {
+    int rc;
+    const uint64_t D = v.D;
     const float slack = 1.25f;  // instance count drifts slowly between training steps
-    // forward-only and everything composited by the fused launch: no per-instance storage at all (the rare paths below —
-    // tier lists, compact binning — still hand their instances over through the stream)
-    const bool need_stream = !(fwd_only && fused_done && !long_tiles);
+    // forward-only and everything composited by the fused launch: no per-instance storage at all (the rare paths of
+    // fwd_sort_and_walk — tier lists, compact binning — still hand their instances over through the stream)
+    const bool need_stream = !(v.fwd_only && v.oc.fused_done && !v.oc.long_tiles);
     if (need_stream &&
         ((rc = h->values_sorted.ensure(D * 4, slack)) ||
          (rc = h->s0.ensure(D * 16, slack)) || (rc = h->s1.ensure(D * 16, slack)) ||
-         (rc = h->s2.ensure(D * 16, slack)) || (C > 3 && (rc = h->s3.ensure(D * 16, slack)))))
+         (rc = h->s2.ensure(D * 16, slack)) || (v.C > 3 && (rc = h->s3.ensure(D * 16, slack)))))
         return rc;
-    if (!fwd_only && (rc = h->rows.ensure(D_slots * 64, slack))) return rc;
-    size_t slab_stride = 0;
-    if (n_big > 0) {  // lists beyond the LDS sort: two merge slabs per listed tile
-        slab_stride = ((size_t)max_tile + 63) & ~(size_t)63;
+    if (!v.fwd_only && (rc = h->rows.ensure(v.D_slots * 64, slack))) return rc;
+    v.slab_stride = 0;
+    if (v.n_big > 0) {  // lists beyond the LDS sort: two merge slabs per listed tile
+        v.slab_stride = ((size_t)v.max_tile + 63) & ~(size_t)63;
         // (+ the plan of the multi-workgroup sort: 2 (n_big + 1) words behind the slabs)
-        if ((rc = h->big_scratch.ensure((size_t)n_big * 2 * slab_stride * 8 + (size_t)(2 * n_big + 2) * 4 + 64))) return rc;
+        if ((rc = h->big_scratch.ensure((size_t)v.n_big * 2 * v.slab_stride * 8 + (size_t)(2 * v.n_big + 2) * 4 + 64))) return rc;
     }
+    return GSR_OK;
+}
+
+// Sort and tier walk: whatever the launches behind the scan left of the view.
+static int fwd_sort_and_walk(gsr_handle* h, const FwdView& v) {
+    int rc;
+    const hipStream_t s = v.s;
+    const size_t T = (size_t)h->n_tiles;
+    const float slack = 1.25f;
+    const bool fused_done = v.oc.fused_done != 0, beside = v.oc.beside != 0;
     // (a held fused launch that this view gives no reason to hold any longer — no tier tiles after all, or too many — goes out
     // now; one that would only find its buffers too small — the kernel checks the same totals — is not launched at all: the
     // main sort pass then re-zeroes the counters and writes the ranges, as in every view without the fused launch)
-    if (oc.launch_fused_now) launch_fused(s);
-    // what the speculative mid-tier sorts covered (gsr_policy_end_view: the kernels' own test, on the same numbers)
-    const uint32_t done4 = oc.sorted_mid4, done8 = oc.sorted_mid8;
-    if (!fused_done || long_tiles) {
-        StageScope sc4(h->prof, ST_SORT, s);
-        const uint64_t* keys = h->bins.as<uint64_t>();
-        const uint64_t* overflow_keys = nullptr;
-        uint32_t key_cap = bin_cap_view;
-        if (compact) {
-            // count -> scan -> scatter: the counters become the fill cursors of the scatter pass
-            if ((rc = h->keys_compact.ensure(D * 8, slack))) return rc;
-            HIPCHK(hipMemsetAsync(h->tile_count.p, 0, (T + 2) * 4, s));
-            gsr_launch_emit_compact(s, n, k, geom_of(h), h->tile_start.as<uint32_t>(), h->tile_count.as<uint32_t>(),
-                                    h->keys_compact.as<uint64_t>(), max_tile, /*only_above=*/0u);
-            keys = h->keys_compact.as<uint64_t>();
-            key_cap = 0;
-        } else if (hybrid) {
-            // the scatter pass restricted to the lists beyond the bins' capacity: their keys go to keys_compact at the offsets of
-            // the compact layout (the buffer is sized as for it; only those segments are touched), with fill cursors of its own
-            // (the tile counters belong to the fused launch, which re-zeroes them)
-            if ((rc = h->keys_compact.ensure(D * 8, slack)) || (rc = h->overflow_fill.ensure((T + 2) * 4))) return rc;
-            HIPCHK(hipMemsetAsync(h->overflow_fill.p, 0, (T + 2) * 4, s));
-            gsr_launch_emit_compact(s, n, k, geom_of(h), h->tile_start.as<uint32_t>(), h->overflow_fill.as<uint32_t>(),
-                                    h->keys_compact.as<uint64_t>(), max_tile, /*only_above=*/bin_cap_view);
-            overflow_keys = h->keys_compact.as<uint64_t>();
-        }
-        gsr_launch_tile_sort(s, (fused_done ? 0 : GSR_SORT_PASS_MAIN) | GSR_SORT_PASS_TIERS, h->n_tiles, h->grid_x, C,
-                             h->tile_start.as<uint32_t>(), h->tile_count.as<uint32_t>(), keys, key_cap, overflow_keys,
-                             n_mid4, n_mid8, n_big, h->big_list.as<uint32_t>(), h->big_scratch.as<uint64_t>(),
-                             slab_stride, geom_of(h), stream_of(h), h->values_sorted.as<uint32_t>(), h->ranges.as<uint32_t>(),
-                             nullptr, 0, done4, done8);
-        sc4.close();
-        // the walk of the tier tiles: beside the held fused launch (second stream, first in the queue), else behind it
-        const hipStream_t ws = beside ? h->aux_stream : s;
-        if (beside) {
-            HIPCHK(hipEventRecord(h->ev_fork, s));
-            HIPCHK(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
-        }
-        StageScope sc5(h->prof, ST_COMPOSITE_FWD, ws);
-        // after the fused launch only the tiles of the tier lists are left; otherwise every tile
-        const GsrTierLists tiers{h->big_list.as<uint32_t>(), (uint32_t)h->n_tiles, n_big, n_mid8, n_mid4, beside ? 1u : 0u};
-        gsr_launch_composite_fwd(ws, C, k, h->tile_start.as<uint32_t>(), fused_done ? nullptr : h->tile_order.as<uint32_t>(),
-                                 stream_of(h), in->background, image_out, h->n_contrib.as<uint32_t>(), h->final_T.as<float>(),
-                                 h->values_sorted.as<uint32_t>(), aux ? aux->covisibilities : nullptr,
-                                 aux ? aux->uncertainties : nullptr, &tiers);
-        sc5.close();
-        if (beside) {
-            HIPCHK(hipEventRecord(h->ev_join, h->aux_stream));
-            launch_fused(s);
-            HIPCHK(hipStreamWaitEvent(s, h->ev_join, 0));
-        }
+    if (v.oc.launch_fused_now) launch_fused(h, v, s);
+    if (fused_done && !v.oc.long_tiles) return GSR_OK;
+    StageScope sc4(h->prof, ST_SORT, s);
+    GsrKeys keys = bins_of(h, v.plan.bin_cap_view);
+    if (v.oc.binning == GSR_BINNING_COMPACT) {
+        // count -> scan -> scatter: the counters become the fill cursors of the scatter pass
+        if ((rc = h->keys_compact.ensure(v.D * 8, slack))) return rc;
+        HIPCHK(hipMemsetAsync(h->tile_count.p, 0, (T + 2) * 4, s));
+        gsr_launch_emit_compact(s, v.n, v.k, geom_of(h), h->tile_start.as<uint32_t>(), h->tile_count.as<uint32_t>(),
+                                h->keys_compact.as<uint64_t>(), v.max_tile, /*only_above=*/0u);
+        keys = GsrKeys{h->keys_compact.as<uint64_t>(), 0u, nullptr};
+    } else if (v.oc.binning == GSR_BINNING_OVERFLOW) {
+        // the scatter pass restricted to the lists beyond the bins' capacity: their keys go to keys_compact at the offsets of
+        // the compact layout (the buffer is sized as for it; only those segments are touched), with fill cursors of its own
+        // (the tile counters belong to the fused launch, which re-zeroes them)
+        if ((rc = h->keys_compact.ensure(v.D * 8, slack)) || (rc = h->overflow_fill.ensure((T + 2) * 4))) return rc;
+        HIPCHK(hipMemsetAsync(h->overflow_fill.p, 0, (T + 2) * 4, s));
+        gsr_launch_emit_compact(s, v.n, v.k, geom_of(h), h->tile_start.as<uint32_t>(), h->overflow_fill.as<uint32_t>(),
+                                h->keys_compact.as<uint64_t>(), v.max_tile, /*only_above=*/keys.cap);
+        keys.overflow = h->keys_compact.as<uint64_t>();
     }
+    // (sorted_mid4 / sorted_mid8: what the speculative mid-tier sorts covered — gsr_policy_end_view: the kernels' own test, on
+    // the same numbers)
+    gsr_launch_tile_sort(s, v.C, /*main_pass=*/!fused_done, tiles_of(h), keys, v.n_mid4, v.n_mid8, v.n_big, v.oc.sorted_mid4,
+                         v.oc.sorted_mid8, h->big_scratch.as<uint64_t>(), v.slab_stride, geom_of(h), stream_of(h),
+                         h->values_sorted.as<uint32_t>());
+    sc4.close();
+    // the walk of the tier tiles: beside the held fused launch (second stream, first in the queue), else behind it
+    const hipStream_t ws = beside ? h->aux_stream : s;
+    if (beside) {
+        HIPCHK(hipEventRecord(h->ev_fork, s));
+        HIPCHK(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
+    }
+    StageScope sc5(h->prof, ST_COMPOSITE_FWD, ws);
+    // after the fused launch only the tiles of the tier lists are left; otherwise every tile
+    const GsrTierLists tiers{h->big_list.as<uint32_t>(), (uint32_t)h->n_tiles, v.n_big, v.n_mid8, v.n_mid4, beside ? 1u : 0u};
+    gsr_launch_composite_fwd(ws, v.C, v.k, tiles_of(h), stream_of(h), frame_of(h, v.in->background, v.image_out, v.aux),
+                             fused_done ? &tiers : nullptr);
+    sc5.close();
+    if (beside) {
+        HIPCHK(hipEventRecord(h->ev_join, h->aux_stream));
+        launch_fused(h, v, s);
+        HIPCHK(hipStreamWaitEvent(s, h->ev_join, 0));
+    }
+    return GSR_OK;
+}
+
+int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, float* image_out, const gsr_aux* aux,
+                void* stream_v, gsr_stats* stats) {
+    FwdView v;
+    int rc;
+    if ((rc = fwd_begin(h, in, cam, image_out, aux, stream_v, stats, v))) return rc;
+    if ((rc = fwd_plan_and_bin(h, v))) return rc;
+    if ((rc = fwd_read_back(h, v))) return rc;
+    if (v.D == 0) return fwd_empty_view(h, v);
+    if ((rc = fwd_instance_buffers(h, v))) return rc;
+    if ((rc = fwd_sort_and_walk(h, v))) return rc;
     h->tile_count_dirty = false;  // the sort (fused or not) zeroed the counters
     HIPCHK(hipGetLastError());
     if (stats) fill_history(h, stats);
@@ -957,19 +1020,18 @@ static int launch_composite_bwd(gsr_handle* h, hipStream_t s, int C, const GsrCa
     if (accurate) { sp.n_big = sp.n_mid8 = sp.n_mid4 = 0; sp.split_len = 0xFFFFFFFFu; }
     GsrTierLists tiers{h->big_list.as<uint32_t>(), (uint32_t)h->n_tiles, sp.n_big, sp.n_mid8, sp.n_mid4, sp.split_len};
     const uint32_t n = sp.n_big + sp.n_mid8 + sp.n_mid4;
+    const GsrFrame frame = frame_of(h, background, nullptr, nullptr);
     if (n > 0) {
         // per (listed tile, list segment, pixel): the (m, c) of the segment — the first pass's hand-over to the second
         int rc = h->long_state.ensure((size_t)n * GSR_BWD_LONG_SEGS * 256 * 2 * sizeof(float));
         if (rc) return rc;
         HIPCHK(hipEventRecord(h->ev_fork, s));
         HIPCHK(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
-        gsr_launch_composite_bwd_listed(h->aux_stream, C, k, h->tile_start.as<uint32_t>(), tiers, stream_of(h), background,
-                                        vpixels, h->n_contrib.as<uint32_t>(), h->final_T.as<float>(), inst_of(h),
+        gsr_launch_composite_bwd_listed(h->aux_stream, C, k, tiles_of(h), tiers, stream_of(h), frame, vpixels, inst_of(h),
                                         h->long_state.as<float>());
         HIPCHK(hipEventRecord(h->ev_join, h->aux_stream));
     }
-    gsr_launch_composite_bwd(s, C, k, h->tile_start.as<uint32_t>(), h->tile_order.as<uint32_t>(), stream_of(h), background,
-                             vpixels, h->n_contrib.as<uint32_t>(), h->final_T.as<float>(), inst_of(h), tiers.split_len, color_only, accurate);
+    gsr_launch_composite_bwd(s, C, k, tiles_of(h), stream_of(h), frame, vpixels, inst_of(h), tiers.split_len, color_only, accurate);
     if (n > 0) HIPCHK(hipStreamWaitEvent(s, h->ev_join, 0));
     return GSR_OK;
 }

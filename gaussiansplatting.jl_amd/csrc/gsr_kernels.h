@@ -20,7 +20,7 @@ struct GsrCam {
     float near_plane, far_plane;
     int radius_clip;
     float blur_eps;
-    int exact_cull;      // GSR_FLAG_EXACT_TILE_CULL
+    int exact_cull;      // 1 = exact footprint culling (the default), 0 = the reference's lists (GSR_FLAG_REFERENCE_TILE_LISTS)
     const float* R_dev;  // optional device overrides (column-major (3,3), (3))
     const float* t_dev;
 };
@@ -61,7 +61,42 @@ struct GsrStream {
 #define GSR_BWD_LONG_SEGS 32
 #define GSR_ROW_F4(C) ((C) > 3 ? 4 : 3)  // float4s per gradient row: 48 bytes in :rgb mode (9 floats used), 64 otherwise
 struct GsrInst {
-    float4* rows;  // D_slots x 4 float4, zero-filled per backward
+    float4* rows;  // D_slots x GSR_ROW_F4 float4; never cleared: composite_bwd stores the row of every emitted instance (gsr_backward)
+};
+
+// ---- what the launchers below share: plain bundles, unpacked by each launcher into its kernel's own parameter list ----
+// The eight words tile_scan_kernel leaves in GsrTiles::totals (device) and mirrors into pinned host memory.
+enum GsrTotal {
+    GSR_TOTAL_D = 0,         // instances of the view (= tile_start[T])
+    GSR_TOTAL_MAX_LIST = 1,  // longest tile list
+    GSR_TOTAL_BIG = 2,       // tiles with a list over GSR_SORT_LDS_CAP (8192): tier_lists[0, T)
+    GSR_TOTAL_MID4 = 3,      // tiles with a list in (1024, 4096]: tier_lists[2T, 3T)
+    GSR_TOTAL_VISIBLE = 4,   // visible Gaussians; bit 31: one of them has a non-empty tile rect (the reference's D > 0)
+    GSR_TOTAL_SLOTS = 5,     // sum of tile-rect areas = Gaussian-major instance slots (gradient rows); >= D
+    GSR_TOTAL_MID8 = 6,      // tiles with a list in (4096, 8192]: tier_lists[T, 2T)
+    GSR_TOTAL_SEQ = 7,       // device: the scan's ticket (zero between launches); host mirror: the forward's sequence number
+    GSR_TOTAL_WORDS = 8
+};
+// The tile-side arrays of a view.
+struct GsrTiles {
+    uint32_t* start;       // [T + 1] exclusive scan of the counts
+    uint32_t* count;       // [T] list lengths, counted by preprocess, re-zeroed by the sort for the next view
+    uint32_t* order;       // [T] tile ids by descending list length: launch order of the compositing workgroups
+    uint32_t* ranges;      // [2 T] identify_tile_range! (utils.jl:56-78)
+    uint32_t* tier_lists;  // [3 T] written by tile_scan: [0, T) tiles with lists > 8192, [T, 2T) (4096, 8192], [2T, 3T) (1024, 4096]
+    uint32_t* totals;      // [GSR_TOTAL_WORDS]
+    int n_tiles, grid_x;
+};
+// Where a view's unsorted keys are.  cap > 0: keys of tile t at bins + t * cap — unless its list is longer than cap: the complete
+// list is then at overflow + start[t]; cap == 0: compact layout, keys of tile t at bins + start[t].
+struct GsrKeys { uint64_t* bins; uint32_t cap; const uint64_t* overflow /* or NULL */; };
+// The frame a view renders into, and what the backward reads of it.
+struct GsrFrame {
+    const float* background;  // host, 3 floats
+    float* image;             // (the backward launches do not touch it)
+    uint32_t* n_contrib; float* final_T;
+    uint32_t* values_sorted;  // sorted ids, per instance
+    uint8_t* covis; float* uncert;  // gsr_aux.covisibilities / uncertainties, or NULL
 };
 
 // ---- pergauss.hip (compiled with -ffp-contract=off: bit-reproducible fp32) ----
@@ -69,11 +104,9 @@ struct GsrInst {
 // returns the form that ran (gsr_stats.preprocess_form: 0 direct, 1 / 2 aggregating with 2 x 32 / 2 x 16-bit LDS words, 3 banded)
 int gsr_launch_preprocess(hipStream_t s, int n, int K, int degree, int channels, const float* means,
                           const float* scales, const float* rots, const float* opac, const float* shs, GsrCam cam,
-                          GsrGeom geom, uint32_t* tile_count, uint32_t* n_visible /* per 256-block */,
-                          uint64_t* bins /* (T+1) x bin_cap keys */, uint32_t bin_cap, int n_tiles, bool aggregating);
+                          GsrGeom geom, GsrTiles tiles, uint32_t* n_visible /* per 256-block */,
+                          GsrKeys keys /* (T+1) x cap keys; cap == 0: count only */, bool aggregating);
 struct GsrBg8 { float v[8]; };
-void gsr_launch_fill_background(hipStream_t s, size_t n_pixels, int channels, const float* background /* host, 3 floats */,
-                                float* image, float* final_T, uint32_t* n_contrib);
 // compact binning mode: scatter the keys to tile_start[t] + arrival rank (tile_fill zeroed by the caller).
 // only_above > 0: only the tiles whose list is LONGER than that (the lists that overflowed fixed-capacity bins) — the others'
 // segments of `keys` and their fill cursors are not touched
@@ -101,40 +134,25 @@ void gsr_launch_update_stats(hipStream_t s, int n, const int32_t* radii, const f
                              int32_t* max_radii, float* accum, float* denom);
 
 // ---- binning.hip ----
-// exclusive scan of tile_count -> tile_start[T+1]; and of the per-block
-// rect-area sums bsum[nb] -> bpre[nb];
-// totals[0] = D, totals[1] = max count, totals[2] = #tiles over GSR_SORT_LDS_CAP, totals[3] = slab counter (0)
-void gsr_launch_tile_scan(hipStream_t s, int n_tiles, const uint32_t* tile_count, uint32_t* tile_start,
-                          uint32_t* totals /* 8 words, [7] = ticket (zero between launches) */, int n_blocks,
-                          const uint32_t* bsum, uint32_t* bpre, const uint32_t* bvis,
-                          uint32_t* tier_lists /* [3 * n_tiles], see gsr_launch_tile_sort */,
-                          uint32_t* host_mirror /* pinned host, 8 words: totals[0..6] + seq, or NULL */, uint32_t seq,
-                          uint32_t* order /* [n_tiles] tile ids by descending list length: launch order of the compositing
-                                             workgroups, computed by a third workgroup of the same launch */);
-// bin_cap > 0: keys of tile t at bins + t * bin_cap; bin_cap == 0: compact layout, keys of tile t at bins + tile_start[t].
-// tier_lists (written by tile_scan): [0, T) tiles with lists > 8192, [T, 2T) lists in (4096, 8192], [2T, 3T) in (1024, 4096]
-// passes: GSR_SORT_PASS_MAIN = the T-workgroup pass over lists of up to 1024 keys (also writes `ranges` and re-zeroes the
-// counters), GSR_SORT_PASS_TIERS = the launches over the tier lists (their sizes are host-side numbers).  totals != NULL:
-// the main pass is launched before the host knows the counts and leaves everything untouched when the view needs more
-// than cap_instances instances or bin_cap keys in a bin (the host then launches it again with totals == NULL).
-#define GSR_SORT_PASS_MAIN 1
-#define GSR_SORT_PASS_TIERS 2
-void gsr_launch_tile_sort(hipStream_t s, int passes, int n_tiles, int grid_x, int channels, const uint32_t* tile_start,
-                          uint32_t* tile_count /* re-zeroed for the next view */, const uint64_t* bins, uint32_t bin_cap,
-                          const uint64_t* overflow_keys /* compact-layout keys of the lists longer than bin_cap, or NULL */,
-                          uint32_t n_mid4, uint32_t n_mid8, uint32_t n_big, const uint32_t* tier_lists,
-                          uint64_t* big_scratch /* 2 slabs of slab_stride keys per tile over 8192 */, size_t slab_stride, GsrGeom geom,
-                          GsrStream stream, uint32_t* values_sorted, uint32_t* ranges, const uint32_t* totals,
-                          uint32_t cap_instances, uint32_t first4 = 0, uint32_t first8 = 0 /* leading tiles of the mid tier
-                          lists already sorted by gsr_launch_tile_sort_mid */);
+// exclusive scan of tiles.count -> tiles.start[T+1], and of the per-block rect-area sums geom.bsum[n_blocks] -> geom.bpre;
+// tiles.totals (GsrTotal), tiles.tier_lists and tiles.order, the last by a third workgroup of the same launch
+void gsr_launch_tile_scan(hipStream_t s, GsrTiles tiles, GsrGeom geom, int n_blocks, const uint32_t* bvis,
+                          uint32_t* host_mirror /* pinned host: the totals + seq in [GSR_TOTAL_SEQ], or NULL */, uint32_t seq);
+// The sorts the fused launch (gsr_launch_sort_composite_fwd) leaves, after the host has read the scan's totals:
+// main_pass: one wave per tile over every list of up to 1024 keys — a view the fused launch did not take; it also writes
+// tiles.ranges and re-zeroes tiles.count.  Always: one launch per non-empty tier list (the counts are host-side numbers), less
+// the first4 / first8 leading tiles of the two mid tiers that gsr_launch_tile_sort_mid has already sorted.
+void gsr_launch_tile_sort(hipStream_t s, int channels, bool main_pass, GsrTiles tiles, GsrKeys keys, uint32_t n_mid4,
+                          uint32_t n_mid8, uint32_t n_big, uint32_t first4, uint32_t first8,
+                          uint64_t* big_scratch /* 2 slabs of slab_stride keys per tile over 8192 */, size_t slab_stride,
+                          GsrGeom geom, GsrStream stream, uint32_t* values_sorted);
 // the sorts of the (1024, 4096] / (4096, 8192] tiers launched BEFORE the host has the counts: grids are guesses, every workgroup
-// checks `totals` (device) — instances <= cap_instances, longest list <= bin_cap, its slot < the tier's count — else leaves
-void gsr_launch_tile_sort_mid(hipStream_t s, int n_tiles, int grid_x, int channels, const uint32_t* tile_start,
-                              const uint64_t* bins, uint32_t bin_cap, uint32_t grid4, uint32_t grid8, const uint32_t* tier_lists,
-                              GsrGeom geom, GsrStream stream, uint32_t* values_sorted, const uint32_t* totals,
-                              uint32_t cap_instances);
+// checks tiles.totals — instances <= cap_instances, longest list <= keys.cap, its slot < the tier's count — else leaves
+void gsr_launch_tile_sort_mid(hipStream_t s, int channels, GsrTiles tiles, GsrKeys keys, uint32_t grid4, uint32_t grid8,
+                              GsrGeom geom, GsrStream stream, uint32_t* values_sorted, uint32_t cap_instances);
 
 // ---- composite.hip ----
+void gsr_launch_fill_background(hipStream_t s, size_t n_pixels, int channels, GsrFrame frame);  // (defined in binning.hip)
 // Tiles whose list is longer than split_len (a tier boundary of the scan: 1024, 4096, 8192, or 0xFFFFFFFF for none)
 // are left out by gsr_launch_composite_bwd and walked by four waves each (one 16x4 pixel strip per wave) in the
 // listed launch, on a second stream.
@@ -143,30 +161,21 @@ struct GsrTierLists {  // the scan's tier lists: [0, T) lists > 8192, [T, 2T) (4
     uint32_t n_tiles, n_big, n_mid8, n_mid4;  // a tier that is not split has count 0 here
     uint32_t split_len;  // (forward launch over the lists: non-zero = its waves run at raised issue priority, beside another launch)
 };
-void gsr_launch_composite_fwd(hipStream_t s, int channels, GsrCam cam, const uint32_t* tile_start,
-                              const uint32_t* tile_order /* NULL: only the tiles of *listed */, GsrStream stream,
-                              const float* background, float* image, uint32_t* n_contrib, float* final_T,
-                              const uint32_t* values_sorted, uint8_t* covis, float* uncert,
-                              const GsrTierLists* listed /* or NULL */);
+void gsr_launch_composite_fwd(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrStream stream, GsrFrame frame,
+                              const GsrTierLists* only_listed /* NULL: every tile, in tiles.order */);
 // sort + forward of every tile in one launch (fixed-capacity bins, no list beyond 1024 instances; checked on the
 // device against the scan's totals — a view that does not qualify leaves everything untouched)
-void gsr_launch_sort_composite_fwd(hipStream_t s, int channels, GsrCam cam, const uint32_t* tile_start,
-                                   const uint32_t* tile_order, uint32_t* tile_count, const uint64_t* bins, uint32_t bin_cap,
-                                   GsrGeom geom, GsrStream stream, const float* background, float* image,
-                                   uint32_t* n_contrib, float* final_T, uint32_t* values_sorted, uint32_t* ranges,
-                                   uint8_t* covis, float* uncert, const uint32_t* totals, uint32_t cap_instances,
+void gsr_launch_sort_composite_fwd(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrKeys keys, GsrGeom geom,
+                                   GsrStream stream, GsrFrame frame, uint32_t cap_instances,
                                    bool keep_backward_state /* false (GSR_FORWARD_ONLY): the sorted stream and ids are not stored */);
-void gsr_launch_composite_bwd(hipStream_t s, int channels, GsrCam cam, const uint32_t* tile_start,
-                              const uint32_t* tile_order, GsrStream stream,
-                              const float* background, const float* vpixels, const uint32_t* n_contrib,
-                              const float* final_T, GsrInst inst,
+void gsr_launch_composite_bwd(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrStream stream, GsrFrame frame,
+                              const float* vpixels, GsrInst inst,
                               uint32_t split_len /* tiles with a longer list are left to the listed launch */,
                               bool color_only /* channels >= 3 of vpixels are zeros (the loss head's cotangent) */,
                               bool accurate /* libm exp + IEEE division per pixel (gsr_config.grad_precision); the caller then
                                                leaves EVERY tile to this launch (split_len = 0xFFFFFFFF) */);
-void gsr_launch_composite_bwd_listed(hipStream_t s, int channels, GsrCam cam, const uint32_t* tile_start,
-                                     GsrTierLists tiers, GsrStream stream, const float* background,
-                                     const float* vpixels, const uint32_t* n_contrib, const float* final_T, GsrInst inst,
+void gsr_launch_composite_bwd_listed(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrTierLists tiers,
+                                     GsrStream stream, GsrFrame frame, const float* vpixels, GsrInst inst,
                                      float* long_state /* GSR_BWD_LONG_SEGS x 512 floats per listed tile */);
 
 // ---- trainer.hip ----

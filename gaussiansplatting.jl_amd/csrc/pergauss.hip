@@ -10,7 +10,7 @@
 // the per-Gaussian floats are bit-reproducible against the CPU oracle.  These
 // kernels are HBM-bound (192 B of SH per Gaussian), the extra VALU ops are free.
 #include "gsr_kernels.h"
-#include <type_traits>
+#include "gsr_dispatch.h"
 #include "tile_mask.h"
 #include "wave_reduce.h"
 #include "adam_math.h"
@@ -1451,22 +1451,8 @@ void gsr_launch_update_stats(hipStream_t s, int n, const int32_t* radii, const f
 namespace {
 using AggPlan = gsr_agg::Plan;
 inline AggPlan agg_plan(int grid_x, int grid_y, uint32_t max_pos) { return gsr_agg::plan(grid_x, grid_y, max_pos); }
-
-// Run-time values that select a kernel instantiation: f gets them as integral constants (a generic lambda takes `auto d`
-// and reads `constexpr int DEG = d;`).
-template <class F>
-inline void dispatch_degree(int degree, F&& f) {
-    switch (degree) {
-        case 0: f(std::integral_constant<int, 0>{}); break;
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        default: f(std::integral_constant<int, 3>{}); break;
-    }
-}
-template <class F>
-inline void dispatch_bool(bool b, F&& f) {
-    if (b) f(std::true_type{}); else f(std::false_type{});
-}
+using gsr::dispatch_bool;
+using gsr::dispatch_degree;
 }  // namespace
 
 // `agg`: the aggregating form (else the direct one) — WHICH is gsr_policy.cpp's decision (gsr_policy_begin_view: the handle's
@@ -1474,20 +1460,19 @@ inline void dispatch_bool(bool b, F&& f) {
 // the form that ran (gsr_stats.preprocess_form = gsr_agg::form_code: the same number the policy announced).
 int gsr_launch_preprocess(hipStream_t s, int n, int K, int degree, int channels, const float* means,
                           const float* scales, const float* rots, const float* opac, const float* shs, GsrCam cam,
-                          GsrGeom geom, uint32_t* tile_count, uint32_t* n_visible, uint64_t* bins, uint32_t bin_cap,
-                          int n_tiles, bool agg) {
+                          GsrGeom geom, GsrTiles tiles, uint32_t* n_visible, GsrKeys keys, bool agg) {
     if (n <= 0) return 0;
     const float4* r4 = reinterpret_cast<const float4*>(rots);
     // The aggregating form keeps its counter words in LDS three times per CU: the whole grid up to ~21 500 tiles, bands of it
     // beyond (4K: two).
-    const int n_words = (n_tiles + 2) / 2;
-    const AggPlan pl = agg_plan(cam.grid_x, cam.grid_y, bin_cap);
+    const int n_words = (tiles.n_tiles + 2) / 2;
+    const AggPlan pl = agg_plan(cam.grid_x, cam.grid_y, keys.cap);
     const uint32_t* no_start = nullptr;
     dispatch_degree(degree, [&](auto d) {
         constexpr int DEG = d;
         if (!agg) {
             hipLaunchKernelGGL((preprocess_kernel<DEG, 0, false, false, false>), dim3((n + 255) / 256), dim3(256), 0, s, n, K,
-                               channels, means, scales, r4, opac, shs, cam, geom, tile_count, n_visible, bins, bin_cap,
+                               channels, means, scales, r4, opac, shs, cam, geom, tiles.count, n_visible, keys.bins, keys.cap,
                                n_words, no_start, 1, cam.grid_y);
             return;
         }
@@ -1497,7 +1482,7 @@ int gsr_launch_preprocess(hipStream_t s, int n, int K, int degree, int channels,
                 constexpr bool BANDED = b;
                 hipLaunchKernelGGL((preprocess_kernel<DEG, kAggThreads, W32, false, BANDED>),
                                    dim3((n + kAggThreads - 1) / kAggThreads), dim3(kAggThreads), pl.lds, s, n, K, channels,
-                                   means, scales, r4, opac, shs, cam, geom, tile_count, n_visible, bins, bin_cap, n_words,
+                                   means, scales, r4, opac, shs, cam, geom, tiles.count, n_visible, keys.bins, keys.cap, n_words,
                                    no_start, pl.n_bands, pl.band_rows);
             });
         });
