@@ -256,6 +256,7 @@ struct gsr_handle {
     DevBuf overflow_fill;           // fill cursors of the scatter pass restricted to the lists beyond the bins' capacity
     // backward: per-instance gradient rows + instance position map; gstate.∇means_2d
     DevBuf rows, vmean2d;
+    DevBuf pose_part;  // pose gradient: 12 partial sums per workgroup of pergauss_bwd, added in a fixed order by its finishing launch
     // loss-head scratch
     DevBuf d0, d1, d2, partial;
     uint32_t* host_totals = nullptr;  // pinned: the scan's totals (GsrTotal), [GSR_TOTAL_SEQ] = the forward's sequence number
@@ -590,7 +591,7 @@ int gsr_create(const gsr_config* cfg, gsr_handle** out) {
     DevBuf* list[] = {&h->ranges, &h->n_contrib, &h->final_T, &h->tile_count, &h->tile_start, &h->tile_order, &h->totals,
                       &h->geo, &h->gnormal, &h->radii, &h->bsum, &h->bpre, &h->bvis, &h->bins, &h->values_sorted, &h->s0,
                       &h->s1, &h->s2, &h->s3, &h->big_scratch, &h->rows, &h->vmean2d, &h->d0, &h->d1,
-                      &h->d2, &h->partial, &h->keys_compact, &h->big_list, &h->long_state, &h->overflow_fill, &h->dbg_flag};
+                      &h->d2, &h->partial, &h->keys_compact, &h->big_list, &h->long_state, &h->overflow_fill, &h->dbg_flag, &h->pose_part};
     for (DevBuf* b : list) h->all[h->n_all++] = b;
     // GSR_DEBUG_FILL candidates (DevBuf::fill_ok), each read only as float data:
     h->rows.fill_ok = true;        // GsrInst gradient rows (float4): summed by pergauss_bwd, copied out by gsr_buffer
@@ -601,6 +602,7 @@ int gsr_create(const gsr_config* cfg, gsr_handle** out) {
     h->d1.fill_ok = true;          // ... ∂map/∂σ1²
     h->d2.fill_ok = true;          // ... ∂map/∂σ12
     h->partial.fill_ok = true;     // per-wave (Σ|x-y|, Σssim) pairs summed by the loss finisher
+    h->pose_part.fill_ok = true;   // per-workgroup pose-gradient partials: every slot is stored (zeros included) before it is summed
     h->long_state.fill_ok = true;  // (T, A) float2 per pixel and segment of the long-list backward
     const size_t P = (size_t)cfg->width * cfg->height, T = (size_t)h->n_tiles;
     int rc = GSR_OK;
@@ -645,7 +647,7 @@ int gsr_destroy(gsr_handle* h) {
 int gsr_release_scene_buffers(gsr_handle* h) {
     if (!h) return fail(GSR_E_INVALID_ARG, "null handle");
     DevBuf* scene[] = {&h->geo, &h->gnormal, &h->radii, &h->bsum, &h->bpre, &h->bvis, &h->bins, &h->values_sorted, &h->s0, &h->s1,
-                       &h->s2, &h->s3, &h->big_scratch, &h->rows, &h->vmean2d, &h->keys_compact};
+                       &h->s2, &h->s3, &h->big_scratch, &h->rows, &h->vmean2d, &h->pose_part, &h->keys_compact};
     h->pol.bin_cap = 0;
     h->pol.compact_sticky = 0;
     for (DevBuf* b : scene) {
@@ -678,6 +680,7 @@ int gsr_reserve(gsr_handle* h, int64_t n_gaussians, int64_t n_instances) {
         const size_t nn = (size_t)n_gaussians, nb = (nn + 255) / 256 + 1;
         if ((rc = h->geo.ensure(nn * 64)) || (rc = h->radii.ensure(nn * 4)) || (rc = h->bsum.ensure(nb * 4)) ||
             (rc = h->bpre.ensure(nb * 4)) || (rc = h->bvis.ensure(nb * 4)) || (rc = h->vmean2d.ensure(nn * 8)) ||
+            (rc = h->pose_part.ensure(gsr_pose_partial_floats(n_gaussians) * 4)) ||
             (C > 5 && (rc = h->gnormal.ensure(nn * 16))))
             return rc;
     }
@@ -1082,20 +1085,16 @@ int gsr_backward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, con
     hipStream_t s = (hipStream_t)stream_v;
     const int C = h->cfg.mode, n = in->n;
     if (n == 0) return GSR_OK;
-    // (the gradient rows need no memset: composite_bwd writes the row of every emitted instance,
-    // pergauss_bwd skips the slots of culled tiles; only the 12 pose-gradient floats are accumulated into)
-    if (g->vR) {
-        StageScope sc6(h->prof, ST_ZERO_ACC, s);
-        HIPCHK(hipMemsetAsync(g->vR, 0, 9 * 4, s));
-        HIPCHK(hipMemsetAsync(g->vt, 0, 3 * 4, s));
-        sc6.close();
-    }
+    // (nothing is cleared and nothing is accumulated into: composite_bwd writes the row of every emitted instance, pergauss_bwd
+    // skips the slots of culled tiles, and the pose gradient goes through per-workgroup partials that are all stored, then summed
+    // in a fixed order — the "zero_acc" stage stays in the table, empty)
+    if (g->vR && (rc = h->pose_part.ensure(gsr_pose_partial_floats(n) * 4, 1.25f))) return rc;
     GsrCam k;
     if ((rc = composite_bwd_stage(h, s, in, cam, vpixels, g->vmeans2d, g->flags, &k))) return rc;
     StageScope sc8(h->prof, ST_PERGAUSS_BWD, s);
     gsr_launch_pergauss_bwd(s, n, in->n_coeffs, in->sh_degree, C, in->means, in->scales, in->rotations, in->shs, k,
                             geom_of(h), inst_of(h), h->vmean2d_cur, g->vmeans, g->vshs, g->vopacities,
-                            g->vscales, g->vrotations, g->vR, g->vt, g->vcolors,
+                            g->vscales, g->vrotations, g->vR, g->vt, h->pose_part.as<float>(), g->vcolors,
                             /*fp32_chain=*/h->cfg.grad_precision == GSR_GRAD_FP32_REFERENCE);
     sc8.close();
     HIPCHK(hipGetLastError());

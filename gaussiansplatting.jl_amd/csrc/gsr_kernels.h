@@ -112,10 +112,13 @@ struct GsrBg8 { float v[8]; };
 // segments of `keys` and their fill cursors are not touched
 void gsr_launch_emit_compact(hipStream_t s, int n, GsrCam cam, GsrGeom geom, const uint32_t* tile_start, uint32_t* tile_fill,
                              uint64_t* keys, uint32_t max_list /* longest tile list of the view */, uint32_t only_above);
+// per-workgroup partials of the pose gradient (12 floats per 256 Gaussians), summed in a fixed order by a finishing launch
+inline size_t gsr_pose_partial_floats(int64_t n) { return n <= 0 ? 0 : (size_t)((n + 255) / 256) * 12; }
 void gsr_launch_pergauss_bwd(hipStream_t s, int n, int K, int degree, int channels, const float* means,
                              const float* scales, const float* rots, const float* shs, GsrCam cam, GsrGeom geom,
                              GsrInst inst, float2* vmean2d, float* vmeans, float* vshs, float* vopac,
-                             float* vscales, float* vrots, float* vR, float* vt,
+                             float* vscales, float* vrots, float* vR, float* vt /* both or neither */,
+                             float* pose_part /* scratch of gsr_pose_partial_floats(n) floats, needed when vR is given */,
                              float* vcolors /* (3,N) or NULL: factored SH gradient instead of vshs */,
                              bool fp32_chain /* ∇scales / ∇rotations by the reference's fp32 trees (GSR_GRAD_FP32_REFERENCE) */);
 // backward epilogue = trainer tail (single-GPU step): no gradient arrays, the parameters / Adam states in S are

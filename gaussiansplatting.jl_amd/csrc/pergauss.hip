@@ -892,7 +892,7 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
                                                            float* __restrict__ vmeans,
                                                            float* __restrict__ vshs, float* __restrict__ vopac,
                                                            float* __restrict__ vscales, float4* __restrict__ vrots,
-                                                           float* __restrict__ vR_out, float* __restrict__ vt_out,
+                                                           float* __restrict__ pose_part,
                                                            float* __restrict__ vcolors, gsr::TailState TS) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     float poseR[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, poset[3] = {0, 0, 0};
@@ -1121,7 +1121,7 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
 #pragma unroll
             for (int c = 0; c < 3; c++) vmean[c] = R.m[0][c] * vmc[0] + R.m[1][c] * vmc[1] + R.m[2][c] * vmc[2];
             M33 vSigma = mul33(mul33(tr33(R), vSc), R);
-            if (vR_out) {
+            if (pose_part) {
                 M33 vR0;
 #pragma unroll
                 for (int r = 0; r < 3; r++)
@@ -1303,9 +1303,10 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
         sh_group(TS.dc, TS.dc_mu, TS.dc_nu, 3, 0, TS.h_dc);
         if (K > 1) sh_group(TS.rest, TS.rest_mu, TS.rest_nu, 3 * (K - 1), 1, TS.h_rest);
     }
-    if (vR_out) {  // projection.jl:243-256: thresholded per Gaussian, then summed
-        // wave sum -> workgroup sum in LDS -> ONE atomic per workgroup and component (the 12
-        // destinations are shared by every workgroup; per-wave atomics would serialise 4x longer)
+    if (pose_part) {  // projection.jl:243-256: thresholded per Gaussian, then summed
+        // wave sum -> workgroup sum in LDS -> the workgroup's 12 partials (∇R column-major, ∇t) to ITS slot of pose_part, zeros
+        // included (the scratch needs no clearing); pose_final_kernel adds the slots in a fixed order — float atomics onto the 12
+        // shared destinations would add in arrival order, and three workgroups already give run-to-run different last bits
         __shared__ float pose_red[4][12];
 #pragma unroll
         for (int k = 0; k < 12; k++) {
@@ -1317,10 +1318,31 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
         __syncthreads();
         if (threadIdx.x < 12) {
             const int k = threadIdx.x;
-            const float v = pose_red[0][k] + pose_red[1][k] + pose_red[2][k] + pose_red[3][k];
-            if (v != 0.0f) atomicAdd(k < 9 ? &vR_out[k] : &vt_out[k - 9], v);
+            pose_part[(size_t)blockIdx.x * 12 + k] = pose_red[0][k] + pose_red[1][k] + pose_red[2][k] + pose_red[3][k];
         }
     }
+}
+
+// ∇R (9 floats, column-major) and ∇t (3) from the per-workgroup partials of pergauss_bwd_kernel (12 floats per workgroup), summed
+// in double in an order that depends on n_part alone: ONE workgroup, thread t takes the partials t, t + 256, ... in ascending
+// order, then the 256 thread sums are added in thread order.  Writes (not accumulates into) vR / vt.
+__global__ __launch_bounds__(256) void pose_final_kernel(int n_part, const float* __restrict__ part, float* __restrict__ vR,
+                                                         float* __restrict__ vt) {
+    __shared__ double red[12][256];
+    double s[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) s[k] = 0.0;
+    for (int i = threadIdx.x; i < n_part; i += 256)
+#pragma unroll
+        for (int k = 0; k < 12; k++) s[k] += (double)part[(size_t)i * 12 + k];
+#pragma unroll
+    for (int k = 0; k < 12; k++) red[k][threadIdx.x] = s[k];
+    __syncthreads();
+    if (threadIdx.x >= 12) return;
+    const int k = threadIdx.x;
+    double t = 0.0;
+    for (int i = 0; i < 256; i++) t += red[k][i];
+    if (k < 9) vR[k] = (float)t; else vt[k - 9] = (float)t;
 }
 
 // ∇shs of a batch of views from the factored per-view colour cotangents:
@@ -1518,7 +1540,8 @@ void gsr_launch_emit_compact(hipStream_t s, int n, GsrCam cam, GsrGeom geom, con
 void gsr_launch_pergauss_bwd(hipStream_t s, int n, int K, int degree, int channels, const float* means,
                              const float* scales, const float* rots, const float* shs, GsrCam cam, GsrGeom geom,
                              GsrInst inst, float2* vmean2d, float* vmeans, float* vshs, float* vopac,
-                             float* vscales, float* vrots, float* vR, float* vt, float* vcolors, bool fp32_chain) {
+                             float* vscales, float* vrots, float* vR, float* vt, float* pose_part, float* vcolors,
+                             bool fp32_chain) {
     if (n <= 0) return;
     dim3 grid((n + 255) / 256), block(256);
     const float4* r4 = reinterpret_cast<const float4*>(rots);
@@ -1529,9 +1552,10 @@ void gsr_launch_pergauss_bwd(hipStream_t s, int n, int K, int degree, int channe
         dispatch_bool(fp32_chain, [&](auto f) {
             constexpr bool F32 = f;
             hipLaunchKernelGGL((pergauss_bwd_kernel<DEG, false, F32>), grid, block, 0, s, n, K, channels, means, scales, r4,
-                               shs, cam, geom, inst, vmean2d, vmeans, vshs, vopac, vscales, vr4, vR, vt, vcolors, none);
+                               shs, cam, geom, inst, vmean2d, vmeans, vshs, vopac, vscales, vr4, vR ? pose_part : nullptr, vcolors, none);
         });
     });
+    if (vR) hipLaunchKernelGGL(pose_final_kernel, dim3(1), dim3(256), 0, s, (int)grid.x, pose_part, vR, vt);
 }
 
 void gsr_launch_pergauss_bwd_tail(hipStream_t s, int n, int K, int degree, int channels, GsrCam cam, GsrGeom geom,
@@ -1546,7 +1570,7 @@ void gsr_launch_pergauss_bwd_tail(hipStream_t s, int n, int K, int degree, int c
             constexpr bool F32 = f;
             hipLaunchKernelGGL((pergauss_bwd_kernel<DEG, true, F32>), grid, block, 0, s, n, K, channels, S.points,
                                S.scales_act, r4, (const float*)nullptr, cam, geom, inst, vmean2d, no_f, no_f, no_f, no_f,
-                               (float4*)nullptr, no_f, no_f, no_f, S);
+                               (float4*)nullptr, no_f, no_f, S);
         });
     });
 }

@@ -163,3 +163,35 @@ def compare_backward(g, out, vis):
     # culled Gaussians: exact zeros
     assert not vm[~vis].any() and not vs[~vis].any() and not vsc[~vis].any() and not vr[~vis].any()
     return vR, vt
+
+
+def pose_grad_f64(means, shs, opac, scales, rots, cam, deg, bg, mode, st, vp):
+    """∇R (9 values, column-major like the library's and the oracle's vR) and ∇t (3) of the float64 autograd model
+    (f64_model.render_dense with R_w2c / t_w2c as leaves) on the oracle state `st`, for the cotangent `vp`.  The model detaches
+    the normal channel from the pose (projection.jl:227-229)."""
+    import f64_model as fm
+    tt = lambda a: torch.tensor(np.asarray(a, np.float64), dtype=fm.DT)  # noqa: E731
+    Rl = tt(cam.R).requires_grad_(True)  # row-major R[r][c]
+    tl = tt(cam.t).requires_grad_(True)
+    img = fm.render_dense(tt(means), tt(shs), tt(np.asarray(opac).reshape(-1)), tt(scales), tt(rots), cam, deg,
+                          np.asarray(bg, np.float32), mode, st.values_sorted, st.ranges, st.radii, R_w2c=Rl, t_w2c=tl)
+    (img * torch.tensor(np.asarray(vp), dtype=fm.DT)).sum().backward()
+    return Rl.grad.numpy().T.reshape(-1).copy(), tl.grad.numpy().reshape(-1).copy()
+
+
+def pose_distances(hip, oracle, f64=None):
+    """(rel-L2(HIP, oracle), rel-L2(oracle, f64), rel-L2(HIP, f64)) of one pose-gradient vector (vR or vt); the float64 legs are
+    None without `f64`."""
+    h, o = np.asarray(hip, np.float64).reshape(-1), np.asarray(oracle, np.float64).reshape(-1)
+    if f64 is None:
+        return rel_l2(h, o), None, None
+    f = np.asarray(f64, np.float64).reshape(-1)
+    return rel_l2(h, o), rel_l2(o, f), rel_l2(h, f)
+
+
+def pose_ok(e_ho, e_o=None, e_h=None):
+    """The pose-gradient criterion.  A pose gradient is ONE sum over every Gaussian of the view — signed terms that largely
+    cancel — so its relative error is the per-Gaussian errors amplified by Σ|terms| / |Σ terms|: HIP meets 1e-4 against the
+    oracle, or (where the float64 model was evaluated) meets 1e-4 against float64 or is no further from float64 than the fp32
+    oracle is (x 4 + 1e-4)."""
+    return e_ho <= 1e-4 or (e_h is not None and (e_h <= 1e-4 or e_h <= 4.0 * e_o + 1e-4))
