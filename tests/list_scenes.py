@@ -51,6 +51,8 @@ class ListScene:
     deg: int
     order: np.ndarray       # order[p] = Gaussian id at sorted position p, by construction (list_positions reads it back from a run)
     walls: tuple = ()       # sorted positions of the full-tile splats (walled_scene)
+    ties: int = 0           # adjacent list entries with equal depth bits (tied_tile_scene)
+    lengths: tuple = ()     # list length per tile, row-major (many_tile_scene)
 
     @property
     def args(self):
@@ -89,8 +91,9 @@ def _front(rng, n, depths, sigma_px, base_opacity, fx, pinned, deg, lo=(1.5, 1.5
     u = rng.uniform(lo[0], hi[0], n)
     v = rng.uniform(lo[1], hi[1], n)
     ju, jv = rng.uniform(-0.15, 0.15, n), rng.uniform(-0.15, 0.15, n)
-    u = np.where(pinned, np.clip(np.round(u), math.ceil(lo[0]), math.floor(hi[0])) + ju, u)
-    v = np.where(pinned, np.clip(np.round(v), math.ceil(lo[1]), math.floor(hi[1])) + jv, v)
+    # (lo, hi, cx, cy: scalars, or one value per splat — many_tile_scene)
+    u = np.where(pinned, np.clip(np.round(u), np.ceil(lo[0]), np.floor(hi[0])) + ju, u)
+    v = np.where(pinned, np.clip(np.round(v), np.ceil(lo[1]), np.floor(hi[1])) + jv, v)
     means = np.stack([(u - cx) * depths / fx, (v - cy) * depths / fx, depths], 1)
     scales = (sigma_px * depths / fx)[:, None] * rng.uniform(0.8, 1.25, (n, 3))
     rots = rng.standard_normal((n, 4))
@@ -206,6 +209,119 @@ def two_tile_scene(L, n_second, seed, deg=0):
     sc = _pack(parts, rng.permutation(n).astype(np.int64), cam, deg)
     sc.order = np.concatenate([sc.order[~second], sc.order[second]])   # the sorted ids: tile-major, then by depth
     return sc
+
+
+# List lengths of tests/test_gpu_sort_ties.py (one tile, groups 1 and 5) and the key-path cases on top of them.
+TIED_LENGTHS = (2, 64, 65, 129, 257, 513, 1024, 1025, 2049, 4096, 4097, 8192, 8193, 16385, 32769)
+TIED_GROUPS = (1, 5)
+TIED_MODE_LENGTHS = (1024, 4097, 8193)
+# tied list length -> entries of the two first views that leave bins too small for it (estimate 8 L1 + 64: 896, 1664, 8064 keys)
+TIED_BIN_FIRST_VIEWS = {1024: 100, 4097: 200, 8193: 1000}
+
+
+def tied_tile_scene(L, groups, seed, deg=0):
+    """single_tile_scene whose front shares its depths: every front Gaussian takes one of `groups` levels float32(2 + 6 (k + 0.5) /
+    groups), the level drawn per Gaussian ID, so the list order is decided by the ids wherever the depth bits are equal —
+    order = lexsort((id, depth)), the reference's "ties by ascending Gaussian id".  The camera has the identity pose: the depth
+    bits of a key are the bits of means[:, 2].  With every level in use the list has L - 1 - groups adjacent tied pairs
+    (`ties`); groups = 1 makes the whole front ONE tie, which the sort must return as ascending ids.  Backdrop, pinned
+    positions and front_parameters as in single_tile_scene."""
+    rng = np.random.default_rng([int(seed), int(L), int(groups), 0x71E])
+    cam = _camera()
+    fx = float(cam.focal[0])
+    sigma_px, base = front_parameters(L)
+    n = L - 1
+    level = rng.integers(0, groups, n)
+    depth_of_id = (2.0 + 6.0 * (level + 0.5) / groups).astype(np.float32)
+    front_order = np.lexsort((np.arange(n), depth_of_id))      # the order first, then one splat per POSITION
+    pinned = np.zeros(n, bool)
+    P = boundary_positions(L)
+    pinned[P[P < n]] = True
+    means, shs, opac, scales, rots = _front(rng, n, depth_of_id[front_order].astype(np.float64), sigma_px, base, fx, pinned, deg)
+    bm, bs, bsc, br = _full_tile(9.0, 40.0, fx, (0.8, 0.3, 0.6), deg)
+    parts = [np.concatenate([means, bm[None]]), np.concatenate([shs, bs[None]]), np.concatenate([opac, [0.9]]),
+             np.concatenate([scales, bsc[None]]), np.concatenate([rots, br[None]])]
+    sc = _pack(parts, np.concatenate([front_order, [n]]).astype(np.int64), cam, deg)
+    sc.ties = n - np.unique(level).size
+    assert np.array_equal(sc.means[:n, 2], depth_of_id)        # the levels survive the float32 pack bit for bit
+    return sc
+
+
+MANY_FAINT_ABOVE = 64   # lists beyond this many entries get the faint front (opacity 0.0042), shorter ones 0.05
+
+
+def many_tile_scene(gx, gy, lengths, seed, deg=0):
+    """A 16 gx x 16 gy image whose tile t (row-major) has a list of exactly lengths[t] entries: two_tile_scene on a grid.  Front
+    splats of sigma 1.05 px, projected centres within [6, 10] px of their tile's origin in x and y — every 3-sigma square
+    (radius 5) inside its own tile; distinct depths in [2, 8] whose ranks are dealt to the tiles at random; ids a random
+    permutation; the entries at boundary_positions(lengths[t]) of every list pinned, the last one among them, so the deepest
+    contributor of every tile is its last entry.  Opacity 0.0042 U(1, 1.5) in lists of more than MANY_FAINT_ABOVE entries, 0.05
+    U(1, 1.5) in shorter ones (a 1024-entry list at 0.05 would saturate after some 300 entries; at 0.0042 its walk ends with
+    T ~ 0.4).  Principal point in the image centre, focal length 2 W: at _camera()'s 13.9 px a splat 150 px off the axis is
+    stretched over several tiles.  No per-tile Python loop over Gaussians: one pass per DISTINCT length."""
+    lengths = np.asarray(lengths, np.int64)
+    assert lengths.shape == (gx * gy,) and (lengths >= 1).all()
+    rng = np.random.default_rng([int(seed), gx, gy, int(lengths.sum()), 0x3A9])
+    W, H = 16 * gx, 16 * gy
+    f = np.float32(2.0 * W)
+    cam = Camera(W, H, (f, f))
+    fx = float(f)
+    n = int(lengths.sum())
+    depths = _unique_depths(rng, n)
+    tile_of_rank = rng.permutation(np.repeat(np.arange(gx * gy), lengths))
+    by_pos = np.argsort(tile_of_rank, kind="stable")           # position (tile-major, then depth) -> depth rank
+    tile = tile_of_rank[by_pos]                                # == repeat(arange(T), lengths)
+    starts = np.concatenate([[0], np.cumsum(lengths)])
+    pinned = np.zeros(n, bool)
+    for Lk in np.unique(lengths):
+        pinned[(starts[:-1][lengths == Lk][:, None] + boundary_positions(int(Lk))[None, :]).reshape(-1)] = True
+    ox, oy = 16.0 * (tile % gx), 16.0 * (tile // gx)
+    base = np.where(lengths[tile] > MANY_FAINT_ABOVE, 0.0042, 0.05)
+    parts = _front(rng, n, depths[by_pos], 1.05, base, fx, pinned, deg, lo=(ox + 6.0, oy + 6.0), hi=(ox + 10.0, oy + 10.0),
+                   cx=W / 2.0, cy=H / 2.0)
+    sc = _pack(parts, rng.permutation(n).astype(np.int64), cam, deg)
+    sc.lengths = tuple(int(x) for x in lengths)
+    return sc
+
+
+# Views with more than 256 tier tiles (tests/test_gpu_tier_routing.py): (tiles in (1024, 4096], in (4096, 8192], beyond 8192) on a
+# 20 x 14 grid -> what gsr_policy_bwd_split must return for those counts on a default 320 x 224 configuration, as
+# (n_mid4, n_mid8, n_big, split_len).  Listed in the order in which each case's NEIGHBOUR follows it (the last wraps around).
+MANY_GRID = (20, 14)
+NO_SPLIT = 0xFFFFFFFF
+MANY_TILE_CASES = {(256, 0, 0): (256, 0, 0, 1024),     # the limit itself; the 1024-entry tile stays in the main launch
+                   (257, 0, 0): (0, 0, 0, NO_SPLIT),   # default main kernel on lists beyond 1024
+                   (256, 1, 0): (0, 1, 0, 4096),       # lists of 1025 .. 4096 in the main launch, 4096 included
+                   (250, 6, 1): (0, 6, 1, 4096),       # long kernel over big, then mid8, with n_mid4 = 0
+                   (0, 256, 1): (0, 0, 1, 8192),       # lists of 4097 .. 8192, 8192 included, in the main launch
+                   (0, 257, 0): (0, 0, 0, NO_SPLIT)}   # default main kernel on lists beyond 4096
+MANY_CLASSES = ("mid4", "mid8", "big", "1024", "ten")
+
+
+def many_tile_lengths(case, seed=5):
+    """(lengths, classes) of a MANY_TILE_CASES key: tier tiles at random places of the grid — the first two of a tier ON its upper
+    edge (4096, 8192), the others one past its lower edge (1025, 4097); lists beyond 8192 hold 8193 — one ordinary tile of exactly
+    1024 entries and ten entries everywhere else.  classes: MANY_CLASSES name -> tile indices."""
+    gx, gy = MANY_GRID
+    tiles = np.random.default_rng([int(seed), *case]).permutation(gx * gy)
+    lengths = np.full(gx * gy, 10, np.int64)
+    classes, k = {}, 0
+    for name, count, low, edge in (("1024", 1, 1024, 1024), ("mid4", case[0], 1025, 4096), ("mid8", case[1], 4097, 8192),
+                                   ("big", case[2], 8193, 8193)):
+        classes[name] = np.sort(tiles[k:k + count])
+        lengths[tiles[k:k + count]] = low
+        lengths[tiles[k:k + min(count, 2)]] = edge
+        k += count
+    classes["ten"] = np.sort(tiles[k:])
+    return lengths, classes
+
+
+def tile_rows(sc, tiles):
+    """Gaussian ids of the pinned entries (boundary_positions) of the given tiles' lists of a many_tile_scene."""
+    lengths = np.asarray(sc.lengths, np.int64)
+    starts = np.concatenate([[0], np.cumsum(lengths)])
+    pos = [starts[t] + boundary_positions(int(lengths[t])) for t in tiles]
+    return sc.order[np.concatenate(pos)] if pos else np.zeros(0, np.int64)
 
 
 def list_positions(st):

@@ -38,24 +38,28 @@ def tier_name(L):
     return "<= 1024" if L <= 1024 else "(1024, 4096]" if L <= 4096 else "(4096, 8192]" if L <= 8192 else "> 8192"
 
 
-def reference(orc, kind, L, stop=None, mode="rgb", bg=BG, second=0):
-    """Scene, oracle forward, cotangent and oracle gradients of a case: computed once, shared, never modified."""
-    key = (kind, L, stop, mode, bg, second)
+def reference_for(orc, key, build, vp_seed, mode="rgb", bg=BG, deterministic=True):
+    """Scene (build()), oracle forward, cotangent and oracle gradients of a case: computed once, shared, never modified."""
     if key not in _refs:
-        if kind == "full":
-            sc = ls.single_tile_scene(L, 7)
-        elif kind == "walled":
-            sc = ls.walled_scene(L, stop, 11)
-        else:
-            sc = ls.two_tile_scene(L, second, 13)
+        sc = build()
         st = orc.forward(*sc.args, sc.cam, sc.deg, background=bg, mode=mode)
-        vp = np.random.default_rng(1000 + L).standard_normal(st.image.shape).astype(np.float32)
-        g = orc.backward(st, vp, *sc.args, sc.cam, sc.deg, background=bg)
+        vp = np.random.default_rng(vp_seed).standard_normal(st.image.shape).astype(np.float32)
+        g = orc.backward(st, vp, *sc.args, sc.cam, sc.deg, background=bg, deterministic=deterministic)
         for a in (st.image, st.n_contrib, st.accum_alpha, st.values_sorted,
                   g.vmeans, g.vshs, g.vopacities, g.vscales, g.vrots):
             a.setflags(write=False)
         _refs[key] = Ref(sc, st, vp, g)
     return _refs[key]
+
+
+def reference(orc, kind, L, stop=None, mode="rgb", bg=BG, second=0):
+    if kind == "full":
+        build = lambda: ls.single_tile_scene(L, 7)  # noqa: E731
+    elif kind == "walled":
+        build = lambda: ls.walled_scene(L, stop, 11)  # noqa: E731
+    else:
+        build = lambda: ls.two_tile_scene(L, second, 13)  # noqa: E731
+    return reference_for(orc, (kind, L, stop, mode, bg, second), build, 1000 + L, mode, bg)
 
 
 def hip_run(pkg, ref, mode="rgb", bg=BG, **kw):
@@ -208,20 +212,21 @@ def test_early_stop(pkg, orc, L, stop, precision):
 
 
 # ---- e. the key bins filled to the last slot, and one key more ----
-def _bins_walk(pkg, orc, L1, kind, delta, second=0):
+def _bins_walk(pkg, orc, L1, kind, delta, second=0, third=None):
     """Two views of L1 entries settle the bins' capacity `cap` (read from gsr_stats, equal to gsr_bins_capacity_after); the
     third view brings a list of cap + delta keys.  One handle per delta: the capacity grows after every view whose list + 25 %
-    exceeds it (gsr_policy_end_view), so on one handle only the first probe would meet the capacity it was aimed at."""
+    exceeds it (gsr_policy_end_view), so on one handle only the first probe would meet the capacity it was aimed at.
+    third = (Ref, L3, family): the third view (and the one after it) shows this scene of L3 > cap entries instead (delta is ignored)."""
     W = 32 if second else 16
     lib = pkg._lib.load()
     ref = reference(orc, kind, L1, second=second)
     run = hip_run(pkg, ref)
 
     def view(L):
-        r = reference(orc, kind, L, second=second)
+        r, family = (third[0], third[2]) if third and L == third[1] else (reference(orc, kind, L, second=second), None)
         show(r, run)
         check_forward(r, run, L, second)
-        check_backward(r, run, L, family="bin capacity, two tiles" if second else "bin capacity", second=second)
+        check_backward(r, run, L, family=family or ("bin capacity, two tiles" if second else "bin capacity"), second=second)
         return run.rast.stats
 
     s1 = view(L1)
@@ -230,6 +235,9 @@ def _bins_walk(pkg, orc, L1, kind, delta, second=0):
     s2 = view(L1)
     cap = int(s2.bin_capacity)
     assert cap == lib.gsr_bins_capacity_after(L1 + second, L1, W, 16, 0, first_cap) and s2.compact_binning == 0
+    if third:
+        assert L1 != third[1] > cap
+        delta = third[1] - cap
     s = view(cap + delta)
     assert int(s.bin_capacity) == cap
     if delta <= 0:
@@ -237,9 +245,10 @@ def _bins_walk(pkg, orc, L1, kind, delta, second=0):
     else:
         # one key too many: bins of >= 1024 keys scatter the overflowing list a second time, smaller ones finish the view compactly
         assert s.compact_binning == (2 if cap >= 1024 else 1), (cap, s.compact_binning)
-        s = view(cap + 1)
+        L3 = third[1] if third else cap + 1
+        s = view(L3)
         assert s.compact_binning == 0, "the next view has bins that hold the list"
-        assert int(s.bin_capacity) == lib.gsr_bins_capacity_after(cap + 1 + second, cap + 1, W, 16, 0, cap) >= cap + 1
+        assert int(s.bin_capacity) == lib.gsr_bins_capacity_after(L3 + second, L3, W, 16, 0, cap) >= L3
     return cap
 
 
