@@ -189,7 +189,10 @@ EXPORTS = ["gsr_create", "gsr_destroy", "gsr_release_scene_buffers", "gsr_memory
            "gsr_bilateral_scratch_bytes", "gsr_bilateral_tv_scratch_bytes", "gsr_bilateral_slice_forward",
            "gsr_bilateral_slice_backward", "gsr_bilateral_tv", "gsr_bilateral_adam_tail",
            "gsr_normal_loss_scratch_bytes", "gsr_normal_loss_forward", "gsr_normal_loss_backward",
-           "gsr_flatten_loss_scratch_bytes", "gsr_flatten_loss"] + POLICY_EXPORTS
+           "gsr_flatten_loss_scratch_bytes", "gsr_flatten_loss",
+           "gsr_mcmc_weights", "gsr_mcmc_sample_scratch_bytes", "gsr_mcmc_sample", "gsr_mcmc_split_sampled",
+           "gsr_mcmc_relocation_params", "gsr_mcmc_relocate_rows", "gsr_mcmc_inject_noise",
+           "gsr_mcmc_regularization_scratch_bytes", "gsr_mcmc_regularization"] + POLICY_EXPORTS
 
 _lib = None
 
@@ -283,6 +286,18 @@ def load():
     lib.gsr_flatten_loss_scratch_bytes.argtypes = [i32]
     lib.gsr_flatten_loss_scratch_bytes.restype = sz
     lib.gsr_flatten_loss.argtypes = [i32, i32, vp, f32, vp, vp, vp, sz, vp]
+    u32 = C.c_uint32
+    lib.gsr_mcmc_weights.argtypes = [i64, i32, vp, vp, f32, f32, vp, vp, vp]
+    lib.gsr_mcmc_sample_scratch_bytes.argtypes = [i64]
+    lib.gsr_mcmc_sample_scratch_bytes.restype = sz
+    lib.gsr_mcmc_sample.argtypes = [i64, vp, i64, u32, vp, vp, vp, vp, sz, vp]
+    lib.gsr_mcmc_split_sampled.argtypes = [i64, i32, vp, vp, i32, f32, vp, vp, vp]
+    lib.gsr_mcmc_relocation_params.argtypes = [i64, vp, vp, vp, i32, f32, vp, vp, vp]
+    lib.gsr_mcmc_relocate_rows.argtypes = [C.POINTER(ComposeGroup), i32, i64, vp, vp, i64, vp]
+    lib.gsr_mcmc_inject_noise.argtypes = [i64, i32, vp, vp, vp, vp, f32, f32, u32, vp]
+    lib.gsr_mcmc_regularization_scratch_bytes.argtypes = [i64]
+    lib.gsr_mcmc_regularization_scratch_bytes.restype = sz
+    lib.gsr_mcmc_regularization.argtypes = [i64, i32, vp, vp, f32, f32, vp, vp, vp, vp, sz, vp]
     lib.gsr_stream_triad.argtypes = [vp, vp, vp, C.c_size_t, f32, vp]
     lib.gsr_ssim_precision.argtypes = [i32]
     lib.gsr_preprocess_form.argtypes = [i32]

@@ -146,7 +146,8 @@ def read_adam(opt, ckpt: Checkpoint, prefix: str, numel=None) -> None:
 def save_state(filename: str, gaussians, optimizers: Dict[str, object], step: int, strategy=None,
                extra_meta: Optional[Dict[str, str]] = None, bilateral_grid=None) -> None:
     """The Gaussian + optimizer part of `save_state` (training.jl:418-445).  `strategy` (a densification.DefaultStrategy):
-    its split-noise position is added as two metadata scalars (`strategy.split_seed_base`, `strategy.split_rounds`) —
+    its split-noise position is added as two metadata scalars (`strategy.split_seed_base`, `strategy.split_rounds`; an
+    mcmc.MCMCStrategy: `strategy.seed_base`, `strategy.sample_rounds`, `strategy.noise_steps` — its `state_dict()`) —
     keys the reference's reader never asks for, so the file stays a valid reference checkpoint; the reference itself draws
     split noise from the backend's RNG and has nothing to save there (densification.jl:128).
     `extra_meta`: more string scalars of the same kind — e.g. {"gsr.ssim_precision": "fast"}: the arithmetic of the loss head the
@@ -185,9 +186,13 @@ def load_state(filename: str, optimizers: Dict[str, object], strategy=None, bila
     g = read_gaussians(ckpt, "gaussians")
     for name in OPTIMIZER_NAMES:
         read_adam(optimizers[name], ckpt, f"optimizers.{name}", numel=int(np.asarray(getattr(g, name)).size))
-    if strategy is not None and "strategy.split_rounds" in ckpt.meta:
-        strategy.load_state_dict({k: ckpt.read_scalar(f"strategy.{k}") for k in ("split_seed_base", "split_rounds")})
-    if strategy is not None and all(f"strategy.{k}" in ckpt for k in STRATEGY_STATS):
+    # the strategy's scalars: DefaultStrategy's split-noise position, or whatever the strategy names in STATE_KEYS
+    # (mcmc.MCMCStrategy: its seed and its sampling / noise counters) — restored when the file carries all of them
+    keys = getattr(strategy, "STATE_KEYS", ("split_seed_base", "split_rounds"))
+    if strategy is not None and all(f"strategy.{k}" in ckpt.meta for k in keys):
+        strategy.load_state_dict({k: ckpt.read_scalar(f"strategy.{k}") for k in keys})
+    # the running statistics belong to a DefaultStrategy; a strategy without them (mcmc.MCMCStrategy) leaves them in the file
+    if strategy is not None and all(hasattr(strategy, k) and f"strategy.{k}" in ckpt for k in STRATEGY_STATS):
         import torch
         n = int(np.asarray(g.points).shape[0])
         for k in STRATEGY_STATS:

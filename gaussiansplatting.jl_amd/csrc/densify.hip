@@ -7,6 +7,8 @@
 // Compiled with -ffp-contract=off (bit-reproducible fp32 against the oracle's restatement for everything
 // except the transcendental calls exp / log / cos / sin, which differ from glibc's by ulps).
 #include "gsr_kernels.h"
+#include "quat.h"
+#include "rng.h"
 
 namespace {
 
@@ -115,18 +117,6 @@ __global__ __launch_bounds__(256) void compose_rows_kernel(ComposeGroups G, cons
     }
 }
 
-// Counter-based generator for the split noise: 32 well-mixed bits from (seed, row, draw) — integer only, so the
-// host restatement reproduces the stream bit for bit; the reference draws from the backend's device RNG
-// (`randn(Float32)`, densification.jl:128), which no implementation can reproduce.
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ float uniform01(uint32_t seed, uint32_t row, uint32_t draw) {
-    const uint32_t h = mix32(mix32(seed ^ (row * 0x9E3779B9u)) + draw * 0x85EBCA6Bu);
-    return ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
-}
-
 // The tail of densify_split! on the 2m appended rows (densification.jl:81-104,121-135):
 //   sigma = exp(scale)              (stds = repeat(exp.(gs.scales)[:, mask], 1, 2))
 //   point += R(q) * (sigma .* randn3)   (_add_split_noise!; R = unnorm_quat2rot(q), render.jl:322-333)
@@ -139,19 +129,12 @@ __global__ __launch_bounds__(256) void split_transform_kernel(long long n_new, i
     float sg[3];
     if (scale_dims == 1) { sg[0] = sg[1] = sg[2] = expf(scales[i]); }
     else { sg[0] = expf(scales[3 * i]); sg[1] = expf(scales[3 * i + 1]); sg[2] = expf(scales[3 * i + 2]); }
-    // Box-Muller: two pairs of uniforms -> three normals
-    const float u1 = uniform01(seed, (uint32_t)i, 0), u2 = uniform01(seed, (uint32_t)i, 1);
-    const float u3 = uniform01(seed, (uint32_t)i, 2), u4 = uniform01(seed, (uint32_t)i, 3);
-    const float r1 = sqrtf(-2.0f * logf(u1)), r2 = sqrtf(-2.0f * logf(u3));
-    const float two_pi = 6.2831853071795864f;
-    const float xi[3] = {sg[0] * (r1 * cosf(two_pi * u2)), sg[1] * (r1 * sinf(two_pi * u2)), sg[2] * (r2 * cosf(two_pi * u4))};
-    const float4 q4 = rots[i];
-    const float inv = 1.0f / sqrtf(q4.x * q4.x + q4.y * q4.y + q4.z * q4.z + q4.w * q4.w);
-    const float w = q4.x * inv, x = q4.y * inv, y = q4.z * inv, z = q4.w * inv;
-    const float x2 = x * x, y2 = y * y, z2 = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
-    const float R[3][3] = {{1.0f - 2.0f * (y2 + z2), 2.0f * (xy - wz), 2.0f * (xz + wy)},
-                           {2.0f * (xy + wz), 1.0f - 2.0f * (x2 + z2), 2.0f * (yz - wx)},
-                           {2.0f * (xz - wy), 2.0f * (yz + wx), 1.0f - 2.0f * (x2 + y2)}};
+    // the split noise: normals of the shared counter-based generator (rng.h), keyed by (seed, appended row)
+    float nrm[3];
+    gsr::randn3(seed, (uint32_t)i, nrm);
+    const float xi[3] = {sg[0] * nrm[0], sg[1] * nrm[1], sg[2] * nrm[2]};
+    float R[3][3];
+    gsr::unnorm_quat2rot(rots[i], R);
 #pragma unroll
     for (int r = 0; r < 3; r++)
         points[3 * i + r] = points[3 * i + r] + (R[r][0] * xi[0] + R[r][1] * xi[1] + R[r][2] * xi[2]);

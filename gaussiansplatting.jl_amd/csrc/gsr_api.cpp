@@ -1660,6 +1660,116 @@ int gsr_reset_opacity(int64_t n, float* opacities, void* stream) {
     return GSR_OK;
 }
 
+// ---- the MCMC strategy (mcmc.hip; src/mcmc.jl) ----
+static int check_mcmc_rows(int64_t n, int32_t scale_dims) {
+    if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
+    if (scale_dims != 1 && scale_dims != 3) return fail(GSR_E_INVALID_ARG, "scale_dims = %d: 1 (isotropic) or 3", scale_dims);
+    return GSR_OK;
+}
+
+int gsr_mcmc_weights(int64_t n, int32_t scale_dims, const float* opacities_raw, const float* scales_raw, float min_opacity,
+                     float log_max_scale, uint32_t* q, uint8_t* dead, void* stream) {
+    int rc;
+    if ((rc = check_mcmc_rows(n, scale_dims))) return rc;
+    if (n == 0) return GSR_OK;
+    if (!opacities_raw || !q || (dead && !scales_raw)) return fail(GSR_E_INVALID_ARG, "null array");
+    gsr_launch_mcmc_weights((hipStream_t)stream, n, scale_dims, opacities_raw, scales_raw, min_opacity, log_max_scale, q, dead);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+size_t gsr_mcmc_sample_scratch_bytes(int64_t n) { return gsr_mcmc_sample_scratch_words(n) * sizeof(uint64_t); }
+
+int gsr_mcmc_sample(int64_t n, const uint32_t* q, int64_t m, uint32_t seed, uint32_t* sampled, int32_t* counts, uint64_t* total,
+                    void* scratch, size_t scratch_bytes, void* stream) {
+    if (n < 0 || m < 0) return fail(GSR_E_INVALID_ARG, "negative count: n=%lld m=%lld", (long long)n, (long long)m);
+    if (n > 0xFFFFFFFFll || m > 0xFFFFFFFFll) return fail(GSR_E_INVALID_ARG, "rows and draws are indexed with 32 bits");
+    if (m == 0) return GSR_OK;
+    if (!total) return fail(GSR_E_INVALID_ARG, "null total");
+    if (n > 0 && (!q || !sampled || !counts || !scratch)) return fail(GSR_E_INVALID_ARG, "null array");
+    const size_t need = gsr_mcmc_sample_scratch_bytes(n);
+    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the sampler needs %zu", scratch_bytes, need);
+    if ((((uintptr_t)scratch | (uintptr_t)total) & 7) != 0) return fail(GSR_E_INVALID_ARG, "scratch and total must be 8-byte aligned");
+    gsr_launch_mcmc_sample((hipStream_t)stream, n, q, m, seed, sampled, counts, reinterpret_cast<unsigned long long*>(total),
+                           reinterpret_cast<unsigned long long*>(scratch));
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_mcmc_split_sampled(int64_t n, int32_t scale_dims, const int32_t* counts, const float* binoms, int32_t n_max,
+                           float min_opacity, float* opacities_raw, float* scales_raw, void* stream) {
+    int rc;
+    if ((rc = check_mcmc_rows(n, scale_dims))) return rc;
+    if (n_max < 1) return fail(GSR_E_INVALID_ARG, "n_max = %d: at least 1", n_max);
+    if (n == 0) return GSR_OK;
+    if (!counts || !binoms || !opacities_raw || !scales_raw) return fail(GSR_E_INVALID_ARG, "null array");
+    gsr_launch_mcmc_split_sampled((hipStream_t)stream, n, scale_dims, counts, binoms, n_max, min_opacity, opacities_raw, scales_raw);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_mcmc_relocation_params(int64_t m, const float* o, const int32_t* ratio, const float* binoms, int32_t n_max,
+                               float min_opacity, float* new_o, float* coeff, void* stream) {
+    if (m < 0) return fail(GSR_E_INVALID_ARG, "negative m");
+    if (n_max < 1) return fail(GSR_E_INVALID_ARG, "n_max = %d: at least 1", n_max);
+    if (m == 0) return GSR_OK;
+    if (!o || !ratio || !binoms || !new_o || !coeff) return fail(GSR_E_INVALID_ARG, "null array");
+    gsr_launch_mcmc_relocation_params((hipStream_t)stream, m, o, ratio, binoms, n_max, min_opacity, new_o, coeff);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_mcmc_relocate_rows(const gsr_compose_group* groups, int32_t n_groups, int64_t n, const uint32_t* dead_idx,
+                           const uint32_t* sampled_idx, int64_t m, void* stream) {
+    if (n_groups < 0 || n_groups > GSR_COMPOSE_MAX_GROUPS || (n_groups > 0 && !groups))
+        return fail(GSR_E_INVALID_ARG, "n_groups must be in [0, %d]", GSR_COMPOSE_MAX_GROUPS);
+    if (n < 0 || m < 0) return fail(GSR_E_INVALID_ARG, "negative count");
+    if (m == 0 || n == 0 || n_groups == 0) return GSR_OK;
+    if (!dead_idx || !sampled_idx) return fail(GSR_E_INVALID_ARG, "null index vector");
+    void* x[GSR_COMPOSE_MAX_GROUPS];
+    int rw[GSR_COMPOSE_MAX_GROUPS], nz[GSR_COMPOSE_MAX_GROUPS];
+    int k = 0;
+    for (int g = 0; g < n_groups; g++) {
+        if (groups[g].row_words < 0) return fail(GSR_E_INVALID_ARG, "group %d: negative row_words", g);
+        if (groups[g].row_words == 0) continue;  // an empty features_rest
+        if (!groups[g].dst) return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
+        if (groups[g].src && groups[g].src != groups[g].dst) return fail(GSR_E_INVALID_ARG, "group %d: the relocation is in place (src must be NULL or dst)", g);
+        x[k] = groups[g].dst; rw[k] = groups[g].row_words; nz[k] = groups[g].new_zero ? 1 : 0; k++;
+    }
+    if (k == 0) return GSR_OK;
+    gsr_launch_mcmc_relocate_rows((hipStream_t)stream, k, x, rw, nz, n, dead_idx, sampled_idx, m);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_mcmc_inject_noise(int64_t n, int32_t scale_dims, float* points, const float* opacities_raw, const float* scales_raw,
+                          const float* rotations, float lr, float max_kick, uint32_t seed, void* stream) {
+    int rc;
+    if ((rc = check_mcmc_rows(n, scale_dims))) return rc;
+    if (n == 0) return GSR_OK;  // mcmc.jl:292
+    if (!points || !opacities_raw || !scales_raw || !rotations) return fail(GSR_E_INVALID_ARG, "null array");
+    if (((uintptr_t)rotations & 15) != 0) return fail(GSR_E_INVALID_ARG, "rotations must be 16-byte aligned");
+    gsr_launch_mcmc_inject_noise((hipStream_t)stream, n, scale_dims, points, opacities_raw, scales_raw, rotations, lr, max_kick, seed);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+size_t gsr_mcmc_regularization_scratch_bytes(int64_t n) { return gsr_mcmc_regularization_scratch_floats(n) * sizeof(float); }
+
+int gsr_mcmc_regularization(int64_t n, int32_t scale_dims, const float* opacities_raw, const float* scales_raw, float opacity_reg,
+                            float scale_reg, float* loss_out, float* vopacities, float* vscales, void* scratch,
+                            size_t scratch_bytes, void* stream) {
+    int rc;
+    if ((rc = check_mcmc_rows(n, scale_dims))) return rc;
+    if (!loss_out || (n > 0 && (!opacities_raw || !scales_raw || !scratch))) return fail(GSR_E_INVALID_ARG, "null array");
+    const size_t need = gsr_mcmc_regularization_scratch_bytes(n);
+    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the regulariser needs %zu", scratch_bytes, need);
+    gsr_launch_mcmc_regularization((hipStream_t)stream, n, scale_dims, opacities_raw, scales_raw, opacity_reg, scale_reg, loss_out,
+                                   vopacities, vscales, (float*)scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
 int gsr_morton_codes(int64_t n, const float* points, const float* box_lo, const float* box_hi, uint64_t* codes, void* stream) {
     if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
     if (n == 0) return GSR_OK;

@@ -222,6 +222,25 @@ void gsr_launch_nonfinite_scan(hipStream_t s, int n_groups, const float* const* 
 void gsr_launch_ply_rows(hipStream_t s, bool pack, long long n, int kr, float* points, float* dc, float* rest, float* opac,
                          float* scales, float* rots, float* rows);
 
+// ---- mcmc.hip (compiled with -ffp-contract=off): the MCMC densification strategy ----
+void gsr_launch_mcmc_weights(hipStream_t s, long long n, int scale_dims, const float* opac, const float* scales, float min_opacity,
+                             float log_max_scale, uint32_t* q, uint8_t* dead);
+size_t gsr_mcmc_sample_scratch_words(long long n);  // 8-byte words
+void gsr_launch_mcmc_sample(hipStream_t s, long long n, const uint32_t* q, long long m, uint32_t seed, uint32_t* sampled,
+                            int32_t* counts, unsigned long long* total, unsigned long long* scratch);
+void gsr_launch_mcmc_split_sampled(hipStream_t s, long long n, int scale_dims, const int32_t* counts, const float* binoms, int n_max,
+                                   float min_opacity, float* opac, float* scales);
+void gsr_launch_mcmc_relocation_params(hipStream_t s, long long m, const float* o, const int32_t* ratio, const float* binoms,
+                                       int n_max, float min_opacity, float* new_o, float* coeff);
+void gsr_launch_mcmc_relocate_rows(hipStream_t s, int n_groups, void* const* x, const int* row_words, const int* new_zero,
+                                   long long n, const uint32_t* dead, const uint32_t* sampled, long long m);
+void gsr_launch_mcmc_inject_noise(hipStream_t s, long long n, int scale_dims, float* points, const float* opac, const float* scales,
+                                  const float* rots, float lr, float max_kick, uint32_t seed);
+size_t gsr_mcmc_regularization_scratch_floats(long long n);
+void gsr_launch_mcmc_regularization(hipStream_t s, long long n, int scale_dims, const float* opac, const float* scales,
+                                    float opacity_reg, float scale_reg, float* loss_out, float* vopac, float* vscales,
+                                    float* scratch);
+
 // ---- ssim.hip (compiled twice: *_exact = -ffp-contract=off + IEEE divisions, bit-exact vs the oracle; *_fast = contracted
 // multiply-adds + hardware reciprocals, the default path; gsr_ssim_precision selects) ----
 #define GSR_SSIM_DECL(SUF)                                                                                              \

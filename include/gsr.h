@@ -669,6 +669,87 @@ GSR_API size_t gsr_flatten_loss_scratch_bytes(int32_t n);
 GSR_API int gsr_flatten_loss(int32_t n, int32_t scale_dims, const float* scales_raw, float weight, float* loss_out,
                              float* vscales, void* scratch, size_t scratch_bytes, void* stream);
 
+/* The MCMC densification strategy of the reference on the device (src/mcmc.jl, `strategy = :mcmc`, src/strategy.jl:16): the
+ * number of Gaussians only grows (up to max_cap), dead Gaussians are relocated onto alive ones sampled ∝ opacity with the
+ * Eq. 9 opacity / scale correction, position noise keeps the chain exploring and an L1 on opacity and scale produces the
+ * dead Gaussians to recycle.  The host keeps the reference's control flow (post_train_step! -> relocate_gaussians! ->
+ * add_gaussians! -> inject_noise!, mcmc.jl:109-124); every per-Gaussian pass — in the reference a chain of device->host
+ * copies, host loops and re-uploads (:135-258) — is one of these launches.  All array pointers device, caller-owned; arrays
+ * in the reference's layouts (opacities (1,N), scales (scale_dims,N) with scale_dims 3, or 1 for an isotropic model,
+ * rotations (4,N), points (3,N)), raw (pre-activation) unless said otherwise.  Rows are addressed 0-based.
+ *
+ * Two intended deviations from the reference:
+ *  1. Randomness.  The reference draws from the host's `rand()` (mcmc.jl:224) and the device's `randn` (:310), which nothing
+ *     can reproduce.  Here every random number is a pure function of (seed, index, draw) of the counter-based generator
+ *     gsr_split_transform uses (a 32-bit integer mixer; uniforms and Box-Muller normals on top of it); a host restatement
+ *     reproduces its integer part bit for bit.  The caller passes a different `seed` on every round / step.
+ *  2. Multinomial sampling in integers.  The reference takes a float64 `cumsum` of the float32 opacities and
+ *     `searchsortedfirst(cw, rand()·total)` (:220-225); a parallel scan cannot match a sequential float sum bit for bit, and
+ *     one ulp flips a discrete choice.  Here the weight of row i is q_i = floor(sigmoid(opacity_i) · 2^30) as uint32 (0 for
+ *     a dead row when relocating), prefix sums are uint64 — exact, independent of the order; below 2^51 at 2 M rows —, draw
+ *     j takes r_j = mulhi64(h_j, total) with h_j 64 generator bits keyed by (seed, j), and selects the FIRST row whose
+ *     inclusive prefix is > r_j.  With the strict inequality a zero-weight row is never selected, so one scan over all N
+ *     rows replaces the reference's `alive[...]` indirection.  The distribution equals the reference's to 2^-30 per weight.
+ *
+ * gsr_mcmc_weights           : q[n], and unless `dead` is NULL dead[n] = (sigmoid(o) <= min_opacity) | (max_j scales_raw[j]
+ *                              > log_max_scale) with q = 0 on dead rows (mcmc.jl:135-140); log_max_scale =
+ *                              log(max_scale · extent) is evaluated by the host, as in the reference, so the compare needs
+ *                              no device transcendental.  dead NULL: every row is weighted (add_gaussians!, :189-190).
+ * gsr_mcmc_sample            : multinomial_sample (:220-225) + the multiplicities of split_sampled! (:237-240): scans q[n],
+ *                              writes the m draws to sampled[m], zeroes counts[n] and counts the draws into it (integer
+ *                              atomics: order-independent), and writes Σq to *total (a device 64-bit word).  total = 0
+ *                              (the reference's `total > 0 || return Int[]`): sampled is not written, counts are zeros —
+ *                              the host reads *total before it uses them.  m = 0: nothing is touched.  scratch:
+ *                              gsr_mcmc_sample_scratch_bytes(n) bytes, 8-byte aligned.
+ * gsr_mcmc_split_sampled     : split_sampled! (:232-260) in place: every row with counts[i] > 0 gets Eq. 9 with ratio =
+ *                              clamp(counts[i] + 1, 1, n_max) applied to its raw opacity and raw scales — new opacity
+ *                              inverse_sigmoid(new_o), new scale log(max(|coeff · exp(s)|, 1e-10)).  One thread per row: a
+ *                              source drawn several times is rewritten once, from its own opacity before the rewrite.
+ *                              binoms: the (n_max, n_max) table of mcmc_binom_coefficients (:79-90), row-major
+ *                              binoms[n·n_max + k] = C(n, k)·(-1)^k/√(k+1), built once by the host.
+ * gsr_mcmc_relocation_params : relocation_params (:266-280, Eq. 9 of the paper) on explicit arrays: activated opacities
+ *                              o[m] and ratio[m] (clamped to [1, n_max]) -> new_o[m], coeff[m].  The device function
+ *                              gsr_mcmc_split_sampled applies, exposed for tests: the reference's fp32 expression, summed
+ *                              `i` outer, `k` inner.
+ * gsr_mcmc_relocate_rows     : the row copies of relocate_gaussians! (:153-172), in place, for up to
+ *                              GSR_COMPOSE_MAX_GROUPS arrays of n rows in one launch.  The array is groups[g].dst
+ *                              (groups[g].src must be NULL or equal to it): x[dead_idx[j]] = x[sampled_idx[j]], j < m; for
+ *                              new_zero groups (the twelve Adam moment arrays) rows dead_idx[j] AND sampled_idx[j] become 0
+ *                              (`touched = union(sampled, dead)`).  In place is safe because dead ∩ sampled = ∅ and
+ *                              dead_idx holds no row twice; an index >= n is skipped.
+ * gsr_mcmc_inject_noise      : _inject_noise! (:306-325): points += Δ, Δ = lr / (1 + exp(min(100·sigmoid(o) - 0.5, 80))) ·
+ *                              R·diag(min(exp(2s), 1e8))·Rᵀ·ξ, rescaled to length max_kick where longer; ξ = three normals
+ *                              keyed by (seed, row).  One pass, 44 B read + 12 B written per Gaussian.  rotations must be
+ *                              16-byte aligned.
+ * gsr_mcmc_regularization    : regularization_loss (:104-107): opacity_reg · mean(sigmoid(o)) + scale_reg · mean(exp(s))
+ *                              into *loss_out (device; 0 for n = 0).  Unless NULL, the gradient w.r.t. the ACTIVATED
+ *                              values — the constants opacity_reg / n and scale_reg / (n · scale_dims) — is ADDED onto
+ *                              vopacities (1,N) and vscales (3,N), the arrays gsr_backward wrote (scale_dims = 1: row 0
+ *                              only — the prologue pullback sums the three tiled rows), exactly as gsr_flatten_loss does:
+ *                              gsr_prologue_backward / gsr_trainer_tail_step then yield the raw gradients.  The fused
+ *                              gsr_backward_trainer_tail cannot take it: steps with a non-zero regulariser run
+ *                              gsr_backward + gsr_mcmc_regularization + gsr_trainer_tail_step.  Fixed summation order, no
+ *                              float atomics.  scratch: gsr_mcmc_regularization_scratch_bytes(n) bytes (may be NULL for
+ *                              n = 0). */
+GSR_API int gsr_mcmc_weights(int64_t n, int32_t scale_dims, const float* opacities_raw, const float* scales_raw,
+                             float min_opacity, float log_max_scale, uint32_t* q, uint8_t* dead, void* stream);
+GSR_API size_t gsr_mcmc_sample_scratch_bytes(int64_t n);
+GSR_API int gsr_mcmc_sample(int64_t n, const uint32_t* q, int64_t m, uint32_t seed, uint32_t* sampled, int32_t* counts,
+                            uint64_t* total, void* scratch, size_t scratch_bytes, void* stream);
+GSR_API int gsr_mcmc_split_sampled(int64_t n, int32_t scale_dims, const int32_t* counts, const float* binoms, int32_t n_max,
+                                   float min_opacity, float* opacities_raw, float* scales_raw, void* stream);
+GSR_API int gsr_mcmc_relocation_params(int64_t m, const float* o, const int32_t* ratio, const float* binoms, int32_t n_max,
+                                       float min_opacity, float* new_o, float* coeff, void* stream);
+GSR_API int gsr_mcmc_relocate_rows(const gsr_compose_group* groups, int32_t n_groups, int64_t n, const uint32_t* dead_idx,
+                                   const uint32_t* sampled_idx, int64_t m, void* stream);
+GSR_API int gsr_mcmc_inject_noise(int64_t n, int32_t scale_dims, float* points, const float* opacities_raw,
+                                  const float* scales_raw, const float* rotations, float lr, float max_kick, uint32_t seed,
+                                  void* stream);
+GSR_API size_t gsr_mcmc_regularization_scratch_bytes(int64_t n);
+GSR_API int gsr_mcmc_regularization(int64_t n, int32_t scale_dims, const float* opacities_raw, const float* scales_raw,
+                                    float opacity_reg, float scale_reg, float* loss_out, float* vopacities, float* vscales,
+                                    void* scratch, size_t scratch_bytes, void* stream);
+
 /* New: the SH-coefficient gradient of a batch of views from the factored
  * per-view colour cotangents written by gsr_backward (gsr_grads.vcolors):
  *   vshs[:, k, i] = Σ_v basis_k(normalize(means[:, i] - camera_centers[:, v])) * vcolors_all[:, i, v]

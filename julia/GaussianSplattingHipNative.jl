@@ -505,4 +505,142 @@ function ChainRulesCore.rrule(::typeof(flatten_loss!), scales::ROCArray{Float32,
     return loss, _flatten_loss_pullback
 end
 
+# ---- MCMCStrategy on the device (src/mcmc.jl; include/gsr.h: gsr_mcmc_*) ----
+# The reference's relocate_gaussians! / add_gaussians! / split_sampled! / multinomial_sample are chains of device->host
+# copies, host loops and re-uploads (mcmc.jl:135-258); here every per-Gaussian pass is one launch.  Two intended deviations
+# (include/gsr.h): random numbers come from the library's counter-based generator (the caller passes a fresh `seed` per draw
+# / step), and the multinomial draw runs on integer weights floor(sigmoid(o)·2^30) with exact UInt64 prefix sums.  Row
+# indices stay 0-based on the device (`sampled`, `dead`): they only ever go back into the library.  Mirrored 1:1 by the
+# tested Python (gaussiansplatting.jl_amd/mcmc.py).
+struct GsrComposeGroup; src::Ptr{Cvoid}; dst::Ptr{Cvoid}; row_words::Int32; new_zero::Int32; end
+
+# q (UInt32, N) and, unless `dead` is nothing, the dead mask (UInt8, N) of mcmc.jl:135-140
+function mcmc_weights!(q, dead, opacities, scales; min_opacity::Float32 = 0f0, log_max_scale::Float32 = 0f0)
+    n = size(opacities, 2)
+    check(ccall((:gsr_mcmc_weights, LIB), Cint,
+        (Int64, Int32, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, Ptr{UInt32}, Ptr{UInt8}, Ptr{Cvoid}),
+        n, size(scales, 1), dptr(opacities), dptr(scales), min_opacity, log_max_scale, dptr(UInt32, q), dptr(UInt8, dead), hipstream()))
+    return q
+end
+
+# multinomial_sample (mcmc.jl:220-225) + the multiplicities of split_sampled! (:237-240): (sampled, counts, total) on the device
+function mcmc_sample(q, m::Integer, seed::UInt32)
+    n = length(q)
+    sampled = AMDGPU.zeros(UInt32, m)
+    counts = AMDGPU.zeros(Int32, n)
+    total = AMDGPU.zeros(UInt64, 1)
+    nb = ccall((:gsr_mcmc_sample_scratch_bytes, LIB), Csize_t, (Int64,), n)
+    scratch = AMDGPU.zeros(UInt64, max(Int(nb) ÷ 8, 1))
+    check(ccall((:gsr_mcmc_sample, LIB), Cint,
+        (Int64, Ptr{UInt32}, Int64, UInt32, Ptr{UInt32}, Ptr{Int32}, Ptr{UInt64}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        n, dptr(UInt32, q), m, seed, dptr(UInt32, sampled), dptr(Int32, counts), dptr(UInt64, total),
+        Ptr{Cvoid}(UInt(pointer(scratch))), nb, hipstream()))
+    return sampled, counts, total
+end
+
+_binoms(strategy) = ROCArray(permutedims(strategy.binoms))   # the library reads binoms[n·n_max + k]: row-major
+
+# split_sampled! (mcmc.jl:232-260) in place on every row with counts > 0
+function mcmc_split_sampled!(strategy, gs, counts, binoms = _binoms(strategy))
+    check(ccall((:gsr_mcmc_split_sampled, LIB), Cint,
+        (Int64, Int32, Ptr{Int32}, Ptr{Float32}, Int32, Cfloat, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+        size(gs.points, 2), size(gs.scales, 1), dptr(Int32, counts), dptr(binoms), strategy.n_max, strategy.min_opacity,
+        dptr(gs.opacities), dptr(gs.scales), hipstream()))
+    return
+end
+
+# relocation_params (mcmc.jl:266-280) on device arrays of activated opacities and Int32 ratios
+function mcmc_relocation_params(strategy, o, ratio, binoms = _binoms(strategy))
+    new_o, coeff = similar(o), similar(o)
+    check(ccall((:gsr_mcmc_relocation_params, LIB), Cint,
+        (Int64, Ptr{Float32}, Ptr{Int32}, Ptr{Float32}, Int32, Cfloat, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+        length(o), dptr(o), dptr(Int32, ratio), dptr(binoms), strategy.n_max, strategy.min_opacity, dptr(new_o), dptr(coeff), hipstream()))
+    return new_o, coeff
+end
+
+_row_words(x) = Int32(length(x) ÷ size(x, ndims(x)))
+_mcmc_arrays(gs) = (gs.points, gs.features_dc, gs.features_rest, gs.scales, gs.rotations, gs.opacities)
+_mcmc_opts(o) = (o.points, o.features_dc, o.features_rest, o.scales, o.rotations, o.opacities)
+
+# the row copies of relocate_gaussians! (mcmc.jl:153-172), in place: x[:, dead] = x[:, sampled]; the moments of both are zeroed
+function mcmc_relocate_rows!(gs, optimizers, dead, sampled)
+    groups = GsrComposeGroup[]
+    vp(x) = Ptr{Cvoid}(UInt(pointer(x)))
+    foreach(_mcmc_arrays(gs), _mcmc_opts(optimizers)) do x, opt
+        isempty(x) && return
+        rw = _row_words(x)
+        push!(groups, GsrComposeGroup(C_NULL, vp(x), rw, 0), GsrComposeGroup(C_NULL, vp(opt.μ[1]), rw, 1),
+              GsrComposeGroup(C_NULL, vp(opt.ν[1]), rw, 1))
+    end
+    gs.ids ≡ nothing || push!(groups, GsrComposeGroup(C_NULL, vp(gs.ids), 1, 0))
+    check(ccall((:gsr_mcmc_relocate_rows, LIB), Cint,
+        (Ptr{GsrComposeGroup}, Int32, Int64, Ptr{UInt32}, Ptr{UInt32}, Int64, Ptr{Cvoid}),
+        groups, length(groups), size(gs.points, 2), dptr(UInt32, dead), dptr(UInt32, sampled), length(dead), hipstream()))
+    return
+end
+
+# inject_noise! (mcmc.jl:288-325); `seed` must differ from step to step
+function mcmc_inject_noise!(strategy, gs, points_lr::Float32, seed::UInt32; extent::Float32)
+    n = size(gs.points, 2)
+    n == 0 && return
+    check(ccall((:gsr_mcmc_inject_noise, LIB), Cint,
+        (Int64, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, UInt32, Ptr{Cvoid}),
+        n, size(gs.scales, 1), dptr(gs.points), dptr(gs.opacities), dptr(gs.scales), dptr(gs.rotations),
+        points_lr * strategy.noise_lr, 0.5f0 * strategy.max_scale * extent, seed, hipstream()))
+    return
+end
+
+# regularization_loss (mcmc.jl:104-107) as a device scalar; with vopacities (1,N) / vscales (3,N) — what ∇rasterize wrote,
+# w.r.t. the ACTIVATED values — its gradient is added onto them: steps with the regulariser on run ∇rasterize +
+# mcmc_regularization!(...; vopacities, vscales) + trainer_tail_step! (the fused backward_trainer_tail! has no gradient arrays)
+function mcmc_regularization!(strategy, opacities, scales; vopacities = nothing, vscales = nothing)
+    n = size(opacities, 2)
+    loss = AMDGPU.zeros(Float32, 1)
+    nb = ccall((:gsr_mcmc_regularization_scratch_bytes, LIB), Csize_t, (Int64,), n)
+    scratch = AMDGPU.zeros(UInt8, max(Int(nb), 4))
+    check(ccall((:gsr_mcmc_regularization, LIB), Cint,
+        (Int64, Int32, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        n, size(scales, 1), dptr(opacities), dptr(scales), strategy.opacity_reg, strategy.scale_reg, dptr(loss), dptr(vopacities),
+        dptr(vscales), Ptr{Cvoid}(UInt(pointer(scratch))), Csize_t(length(scratch)), hipstream()))
+    return loss
+end
+
+# Sketch of post_train_step! (mcmc.jl:109-124) on these entry points — the control flow of the reference, the tested form of
+# which is mcmc.py's post_train_step.  `seeds` yields a fresh UInt32 per call (Python: (seed_base, counter) mixed as
+# DefaultStrategy.next_split_seed does, separate counters for sampling and noise).  Appending the sampled rows is
+# `append_gaussians!` of the reference on `gs.x[:, sampled .+ 1]`, or one gsr_compose_rows launch.
+function mcmc_post_train_step!(strategy, gs, optimizers, seeds; step::Int, extent::Float32, points_lr::Float32)
+    refining = strategy.start_refine < step < strategy.stop_refine && step % strategy.refine_every == 0
+    if refining
+        n = size(gs.points, 2)
+        q, dead_mask = AMDGPU.zeros(UInt32, n), AMDGPU.zeros(UInt8, n)
+        mcmc_weights!(q, dead_mask, gs.opacities, gs.scales; min_opacity = strategy.min_opacity,
+                      log_max_scale = log(strategy.max_scale * extent))
+        dead = UInt32.(findall(!iszero, dead_mask) .- 1)                      # read-back 1: the number of dead rows
+        if 0 < length(dead) < n
+            sampled, counts, total = mcmc_sample(q, length(dead), seeds())
+            if Array(total)[1] > 0                                             # read-back 2
+                mcmc_split_sampled!(strategy, gs, counts)
+                mcmc_relocate_rows!(gs, optimizers, dead, sampled)
+            end
+        end
+        n_new = min(strategy.max_cap, floor(Int, strategy.grow_factor * n)) - n
+        if n_new > 0
+            mcmc_weights!(q, nothing, gs.opacities, gs.scales)
+            sampled, counts, total = mcmc_sample(q, n_new, seeds())
+            if Array(total)[1] > 0
+                mcmc_split_sampled!(strategy, gs, counts)
+                ids = Int.(Array(sampled)) .+ 1
+                GaussianSplatting.append_gaussians!(gs, optimizers;
+                    new_points = gs.points[:, ids], new_features_dc = gs.features_dc[:, :, ids],
+                    new_features_rest = isempty(gs.features_rest) ? gs.features_rest : gs.features_rest[:, :, ids],
+                    new_scales = gs.scales[:, ids], new_rotations = gs.rotations[:, ids], new_opacities = gs.opacities[:, ids],
+                    new_ids = gs.ids ≡ nothing ? nothing : gs.ids[ids])
+            end
+        end
+    end
+    mcmc_inject_noise!(strategy, gs, points_lr, seeds(); extent)
+    return refining
+end
+
 end # module

@@ -12,6 +12,10 @@ ground-truth scene:
     ∇rasterize + NU.step! x 6 (training.jl:768-779)  gsr_backward_trainer_tail   (or gsr_backward + gsr_trainer_tail_step)
     post_train_step! (strategy.jl:78-105)            gsr_update_stats + densification.py (gsr_densify_* / gsr_compose_rows)
 
+With `Protocol.strategy = "mcmc"` (src/mcmc.jl) the step adds `regularization_loss` (mcmc.jl:104-107) to the loss — its gradient
+joins ∇opacities / ∇scales between gsr_backward and gsr_trainer_tail_step, so the step runs the unfused tail — and
+post_train_step! is mcmc.py's (gsr_mcmc_*: relocation + growth on refine steps, position noise on every step).
+
 Used by tests/test_gpu_train_protocol.py (reduced size: oracle-chain parity of the first steps, PSNR, checkpoint -> resume bit
 identity, the handle's view-history assertions), by bench.py's `train_protocol` section (full size, the reference's 500 + 1000
 steps) and by tools/record_train_history.py.  numpy + torch + the package; NO oracle import (the oracle twin of the chain
@@ -68,6 +72,8 @@ class Protocol:
     sh_ramp_interval: int = 1000      # training.jl:584: `trainer.step % 1000 == 0 && gs.sh_degree < gs.max_sh_degree`
     fused_tail: bool = True           # gsr_backward_trainer_tail; False: gsr_backward + gsr_trainer_tail_step
     spatial_reorder: bool = False     # (not in the reference) Morton re-sort at the end of a densification round
+    strategy: str = "default"         # "default": DefaultStrategy (above); "mcmc": MCMCStrategy (src/mcmc.jl)
+    mcmc: dict = field(default_factory=dict)   # keyword arguments of mcmc.MCMCStrategy that differ from the reference's defaults
     bins_budget_bytes: int = 0
     grad_precision: str = None        # None: the library default (∇scales / ∇rotations through the float64 chain); "fp32_reference":
                                       # the reference's own fp32 expression trees (what an oracle-chain comparison runs with: an
@@ -203,11 +209,17 @@ class Harness:
         lrs = dict(points=p.lr_points_start * self.extent, features_dc=p.lr_feature, features_rest=p.lr_feature / 20.0,
                    opacities=p.lr_opacities, scales=p.lr_scales, rotations=p.lr_rotations)          # training.jl:233-239
         self.opts = {k: O.Adam(getattr(self.gs, k), lrs[k], eps=1e-15) for k in GROUPS}
-        self.strategy = Dz.DefaultStrategy(self.gs, dense_percent=p.dense_percent, densify_from_iter=p.densify_from_iter,
-                                           densify_until_iter=p.densify_until_iter, densification_interval=p.densification_interval,
-                                           densify_grad_threshold=p.densify_grad_threshold,
-                                           opacity_reset_interval=p.opacity_reset_interval, min_opacity=p.min_opacity, seed=p.seed,
-                                           spatial_reorder=p.spatial_reorder)
+        if p.strategy not in ("default", "mcmc"):
+            raise ValueError(f"strategy = {p.strategy!r}: 'default' or 'mcmc'")
+        self.is_mcmc = p.strategy == "mcmc"
+        if self.is_mcmc:
+            self.strategy = pkg.mcmc.MCMCStrategy(seed=p.seed, **p.mcmc)
+        else:
+            self.strategy = Dz.DefaultStrategy(self.gs, dense_percent=p.dense_percent, densify_from_iter=p.densify_from_iter,
+                                               densify_until_iter=p.densify_until_iter, densification_interval=p.densification_interval,
+                                               densify_grad_threshold=p.densify_grad_threshold,
+                                               opacity_reset_interval=p.opacity_reset_interval, min_opacity=p.min_opacity, seed=p.seed,
+                                               spatial_reorder=p.spatial_reorder)
         self.step_no, self.sh_degree = 0, 0
         self.act = None          # (shs, opacities_act, scales_act) of the current raw arrays, or None: run the prologue
         self.losses = []         # device scalars, one per step
@@ -275,12 +287,17 @@ class Harness:
         loss, vp = self.pkg.fused_ssim.l1_ssim_loss(rast, img, self.targets[v], p.lambda_dssim)
         self.losses.append(loss)
         color = p.mode != "rgb"   # the loss head's own cotangent: zeros above the colour channels (training.jl:656,684-685)
-        if p.fused_tail:
+        # the MCMC regulariser's gradient joins ∇opacities / ∇scales, which the fused tail never materialises (mcmc.jl:104-107)
+        reg = self.is_mcmc and (self.strategy.opacity_reg != 0.0 or self.strategy.scale_reg != 0.0)
+        if p.fused_tail and not reg:
             O.fused_backward_tail_step(rast, vp, self.opts, self.raw(), shs, oa, sa, cam, self.sh_degree, self.bg,
                                        forward_generation=int(st.generation), color_cotangent=color)
         else:
             vm, vsh, vo, vsc, vr, _, _ = rast.backward_raw(vp, gs.points, shs, oa, sa, gs.rotations, cam, self.sh_degree, self.bg,
                                                            forward_generation=int(st.generation), color_cotangent=color)
+            if reg:
+                self.losses[-1] = loss + self.pkg.mcmc.regularization_loss(self.strategy, gs.opacities, gs.scales, vopacities=vo,
+                                                                           vscales=vsc)
             O.trainer_tail_step(self.opts, self.raw(), dict(vmeans=vm, vshs=vsh, vopacities=vo, vscales=vsc, vrot=vr), shs, oa, sa)
         self.post_train_step(step)
         return v
@@ -289,6 +306,17 @@ class Harness:
         """post_train_step! (strategy.jl:78-105) — densification.post_train_step with the split seed drawn HERE, so that an
         oracle twin of the chain can be handed the same seed."""
         s, Dz, torch = self.strategy, self.Dz, self.torch
+        if self.is_mcmc:
+            n0, t0 = len(self.gs), None
+            if s.refining(step):
+                torch.cuda.synchronize()     # (so that host_ms below is the refine round, not the queue in front of it)
+                t0 = time.perf_counter()
+            if self.pkg.mcmc.post_train_step(s, self.gs, self.opts, self.rast, step, self.extent):
+                self.prologue()   # a refine round rewrote raw opacities / scales (and may have appended rows)
+                torch.cuda.synchronize()
+                ms = 1e3 * (time.perf_counter() - t0)
+                self.densify_log.append(dict(step=step, n_before=n0, n_after=len(self.gs), host_ms=round(ms, 3)))
+            return
         if step > s.densify_until_iter:
             return
         will_densify = step >= s.densify_from_iter and step % s.densification_interval == 0
