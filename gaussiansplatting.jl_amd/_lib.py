@@ -104,6 +104,10 @@ class ComposeGroup(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_words", C.c_int32), ("new_zero", C.c_int32)]
 
 
+class DepthAnchorS(C.Structure):  # gsr_depth_anchor
+    _fields_ = [("a", C.c_float), ("b", C.c_float), ("floor", C.c_float), ("disparity", C.c_float), ("p_far", C.c_float)]
+
+
 COMPOSE_MAX_GROUPS = 24
 DENSIFY_CLONE, DENSIFY_SPLIT, DENSIFY_PRUNE = 0, 1, 2
 
@@ -190,6 +194,7 @@ EXPORTS = ["gsr_create", "gsr_destroy", "gsr_release_scene_buffers", "gsr_memory
            "gsr_bilateral_slice_backward", "gsr_bilateral_tv", "gsr_bilateral_adam_tail",
            "gsr_normal_loss_scratch_bytes", "gsr_normal_loss_forward", "gsr_normal_loss_backward",
            "gsr_flatten_loss_scratch_bytes", "gsr_flatten_loss",
+           "gsr_depth_loss_scratch_bytes", "gsr_depth_target", "gsr_depth_loss_forward", "gsr_depth_loss_backward",
            "gsr_mcmc_weights", "gsr_mcmc_sample_scratch_bytes", "gsr_mcmc_sample", "gsr_mcmc_split_sampled",
            "gsr_mcmc_relocation_params", "gsr_mcmc_relocate_rows", "gsr_mcmc_inject_noise",
            "gsr_mcmc_regularization_scratch_bytes", "gsr_mcmc_regularization"] + POLICY_EXPORTS
@@ -286,6 +291,12 @@ def load():
     lib.gsr_flatten_loss_scratch_bytes.argtypes = [i32]
     lib.gsr_flatten_loss_scratch_bytes.restype = sz
     lib.gsr_flatten_loss.argtypes = [i32, i32, vp, f32, vp, vp, vp, sz, vp]
+    lib.gsr_depth_loss_scratch_bytes.argtypes = [i32, i32]
+    lib.gsr_depth_loss_scratch_bytes.restype = sz
+    lib.gsr_depth_target.argtypes = [i32, i32, vp, C.POINTER(DepthAnchorS), f32, vp, vp, vp, vp]
+    lib.gsr_depth_loss_forward.argtypes = [i32, i32, i32, vp, vp, C.POINTER(DepthAnchorS), f32, f32, f32, vp, vp, vp, vp, vp,
+                                           vp, sz, vp]
+    lib.gsr_depth_loss_backward.argtypes = [i32, i32, i32, vp, vp, C.POINTER(DepthAnchorS), f32, f32, f32, vp, vp, sz, vp]
     u32 = C.c_uint32
     lib.gsr_mcmc_weights.argtypes = [i64, i32, vp, vp, f32, f32, vp, vp, vp]
     lib.gsr_mcmc_sample_scratch_bytes.argtypes = [i64]

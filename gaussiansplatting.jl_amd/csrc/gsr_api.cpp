@@ -1591,6 +1591,66 @@ int gsr_flatten_loss(int32_t n, int32_t scale_dims, const float* scales_raw, flo
     return GSR_OK;
 }
 
+// ---- anchored depth supervision (depth.hip; src/depth_supervision.jl) ----
+namespace {
+int check_depth_loss_args(int32_t W, int32_t H, int32_t C, const gsr_depth_anchor* anchor, float qstep) {
+    if (W < 1 || H < 1 || (int64_t)W * H > 0x7FFFFFFF / 8) return fail(GSR_E_INVALID_ARG, "image size %d x %d", W, H);
+    if (C != 5 && C != 8) return fail(GSR_E_INVALID_ARG, "C = %d: the depth loss reads a :rgbd (5) or :rgbdn (8) frame", C);
+    if (!anchor) return fail(GSR_E_INVALID_ARG, "null anchor");
+    if (!std::isfinite(anchor->a) || !std::isfinite(anchor->b) || !(anchor->floor > 0.0f) || !std::isfinite(anchor->floor) ||
+        !(anchor->p_far >= 0.0f) || !std::isfinite(anchor->p_far))
+        return fail(GSR_E_INVALID_ARG, "anchor: a and b must be finite, floor > 0, p_far >= 0");
+    if (!(qstep >= 0.0f) || !std::isfinite(qstep)) return fail(GSR_E_INVALID_ARG, "qstep must be finite and >= 0");
+    return GSR_OK;
+}
+}  // namespace
+
+size_t gsr_depth_loss_scratch_bytes(int32_t W, int32_t H) {
+    if (W < 1 || H < 1) return 0;
+    return gsr_depth_loss_scratch_size(W, H);
+}
+
+int gsr_depth_target(int32_t W, int32_t H, const float* prior, const gsr_depth_anchor* anchor, float qstep, float* target_out,
+                     float* half_band_out, uint8_t* flags_out, void* stream) {
+    int rc;
+    if ((rc = check_depth_loss_args(W, H, 5, anchor, qstep))) return rc;
+    if (!prior) return fail(GSR_E_INVALID_ARG, "null array");
+    gsr_launch_depth_target((hipStream_t)stream, W, H, prior, &anchor->a, qstep, target_out, half_band_out, flags_out);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_depth_loss_forward(int32_t W, int32_t H, int32_t C, const float* image, const float* prior, const gsr_depth_anchor* anchor,
+                           float qstep, float lambda_grad, float weight, float* loss_out, float* stats_out, float* target_out,
+                           float* half_band_out, uint8_t* flags_out, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc;
+    if ((rc = check_depth_loss_args(W, H, C, anchor, qstep))) return rc;
+    if (!image || !prior || !loss_out || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
+    if ((uintptr_t)scratch % 16) return fail(GSR_E_INVALID_ARG, "scratch must be 16-byte aligned");
+    const size_t need = gsr_depth_loss_scratch_bytes(W, H);
+    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the depth loss needs %zu", scratch_bytes, need);
+    gsr_launch_depth_loss_fwd((hipStream_t)stream, W, H, C, image, prior, &anchor->a, qstep, lambda_grad, weight, loss_out,
+                              stats_out, target_out, half_band_out, flags_out, scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_depth_loss_backward(int32_t W, int32_t H, int32_t C, const float* image, const float* prior, const gsr_depth_anchor* anchor,
+                            float qstep, float lambda_grad, float weight, float* vpixels, const void* scratch, size_t scratch_bytes,
+                            void* stream) {
+    int rc;
+    if ((rc = check_depth_loss_args(W, H, C, anchor, qstep))) return rc;
+    if (!image || !prior || !vpixels || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
+    if (image == vpixels) return fail(GSR_E_INVALID_ARG, "vpixels must not be the image");
+    if ((uintptr_t)scratch % 16) return fail(GSR_E_INVALID_ARG, "scratch must be 16-byte aligned");
+    const size_t need = gsr_depth_loss_scratch_bytes(W, H);
+    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the depth loss needs %zu", scratch_bytes, need);
+    // prior, anchor and qstep are the forward's: what they determine per pixel is in the records the forward left in scratch
+    gsr_launch_depth_loss_bwd((hipStream_t)stream, W, H, C, image, lambda_grad, weight, vpixels, scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
 int gsr_densify_grad_mean(int64_t n, const float* accum, const float* denom, float* grad_out, void* stream) {
     if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
     if (n == 0) return GSR_OK;

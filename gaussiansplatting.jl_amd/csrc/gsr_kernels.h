@@ -287,3 +287,13 @@ void gsr_launch_normal_loss_bwd(hipStream_t s, int W, int H, const float* image,
 size_t gsr_flatten_loss_scratch_floats(int64_t n);
 void gsr_launch_flatten_loss(hipStream_t s, int n, int scale_dims, const float* scales, float weight, float* loss_out,
                              float* vscales, float* scratch);
+
+// ---- depth.hip (compiled with -ffp-contract=off): anchored depth supervision; `anchor` = the 5 floats of gsr_depth_anchor ----
+size_t gsr_depth_loss_scratch_size(int W, int H);
+void gsr_launch_depth_target(hipStream_t s, int W, int H, const float* prior, const float* anchor, float qstep, float* target_out,
+                             float* half_band_out, uint8_t* flags_out);
+void gsr_launch_depth_loss_fwd(hipStream_t s, int W, int H, int C, const float* image, const float* prior, const float* anchor,
+                               float qstep, float lambda_grad, float weight, float* loss_out, float* stats_out, float* target_out,
+                               float* half_band_out, uint8_t* flags_out, void* scratch);
+void gsr_launch_depth_loss_bwd(hipStream_t s, int W, int H, int C, const float* image, float lambda_grad, float weight,
+                               float* vpixels, const void* scratch);

@@ -669,6 +669,47 @@ GSR_API size_t gsr_flatten_loss_scratch_bytes(int32_t n);
 GSR_API int gsr_flatten_loss(int32_t n, int32_t scale_dims, const float* scales_raw, float weight, float* loss_out,
                              float* vscales, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Anchored depth supervision of :rgbd / :rgbdn training (src/depth_supervision.jl:406-536; switched on by `use_depth_loss`,
+ * used by `step!`, training.jl:604-620,709-718): `depth_target` and `ssi_depth_loss` on the device.  The frame is the
+ * rasterizer's image (C,W,H), C = 5 (:rgbd) or 8 (:rgbdn): channel 3 is the blended depth D, channel 4 alpha; nothing else
+ * of a record is read.  `prior` is the (W,H) relative depth prior, `anchor` its per-camera affine alignment (DepthAnchor,
+ * depth_supervision.jl:51-57; `disparity` > 0 selects the inverse-depth model), `qstep` the quantisation step of the
+ * prior's encoding.  The target, the deadband half-width and the masks are built in the kernels from `prior` and `anchor`:
+ *   affine = a·t + b (a multiply, then an add);  valid = isfinite(t) & t > 0 & affine > 0;
+ *   target = min(affine, 1/floor) (disparity) or 1/(affine + floor) (depth);  half_band = 0.5·qstep·|a| (· target² in the
+ *   depth model);  far_extrap = target < p_far
+ * every decision in the reference's fp32 expression.  All array pointers device; nothing is read back by the host; no
+ * float atomics anywhere: every result is run-to-run bit-identical.
+ *
+ * Intended deviation from the reference: a pixel with w = 0 (invalid, or clamp(alpha,0,1) <= 1e-3) contributes exactly
+ * nothing to the loss, to σ and to the gradients, also when its D or its prior is NaN / Inf — it is selected out, not
+ * multiplied by zero (the reference's `sum(w .* ...)` would turn NaN on 0 · NaN).  The same holds for a forward-difference
+ * pair whose min(w_s, w_s') = 0.  A non-finite alpha counts as 0, in Σα and as a weight.
+ *
+ * gsr_depth_target         : the maps alone: target_out (W,H), half_band_out (W,H), flags_out (W,H) bytes with bit 0 =
+ *                            valid and bit 1 = far_extrap; each may be NULL.
+ * gsr_depth_loss_forward   : weight · ssi_depth_loss into *loss_out = weight · (data + lambda_grad · (grad_x + grad_y)) /
+ *                            max(Σα, 1); unless NULL, stats_out[0..3] = (Σα, Σw_supported, μ, σ) (Σα before the max) and
+ *                            the three maps as above.  scratch: gsr_depth_loss_scratch_bytes(W, H) bytes, 16-byte aligned
+ *                            (a header, per-tile partials and a 16-byte record per pixel); the backward reads it.
+ * gsr_depth_loss_backward  : ADDS weight · ∂loss/∂(D, alpha) onto channels 3 and 4 of vpixels (C,W,H); σ, the weights and
+ *                            Σα are detached, as in the reference.  Channels 0..2 (and 5..7 for C = 8) are not touched, a
+ *                            pixel that receives nothing is not written: the loss head's zeros and the depth-normal term
+ *                            compose with it.  `scratch` is the one gsr_depth_loss_forward filled for the same image,
+ *                            prior, anchor and qstep (lambda_grad and weight may differ).  vpixels must not be the image.
+ *                            A vpixels this was added onto must NOT go to gsr_backward with GSR_GRADS_COLOR_COTANGENT. */
+typedef struct gsr_depth_anchor { float a, b, floor, disparity, p_far; } gsr_depth_anchor;
+GSR_API size_t gsr_depth_loss_scratch_bytes(int32_t W, int32_t H);
+GSR_API int gsr_depth_target(int32_t W, int32_t H, const float* prior, const gsr_depth_anchor* anchor, float qstep,
+                             float* target_out, float* half_band_out, uint8_t* flags_out, void* stream);
+GSR_API int gsr_depth_loss_forward(int32_t W, int32_t H, int32_t C, const float* image, const float* prior,
+                                   const gsr_depth_anchor* anchor, float qstep, float lambda_grad, float weight, float* loss_out,
+                                   float* stats_out, float* target_out, float* half_band_out, uint8_t* flags_out, void* scratch,
+                                   size_t scratch_bytes, void* stream);
+GSR_API int gsr_depth_loss_backward(int32_t W, int32_t H, int32_t C, const float* image, const float* prior,
+                                    const gsr_depth_anchor* anchor, float qstep, float lambda_grad, float weight, float* vpixels,
+                                    const void* scratch, size_t scratch_bytes, void* stream);
+
 /* The MCMC densification strategy of the reference on the device (src/mcmc.jl, `strategy = :mcmc`, src/strategy.jl:16): the
  * number of Gaussians only grows (up to max_cap), dead Gaussians are relocated onto alive ones sampled ∝ opacity with the
  * Eq. 9 opacity / scale correction, position noise keeps the chain exploring and an L1 on opacity and scale produces the

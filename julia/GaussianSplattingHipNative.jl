@@ -505,6 +505,72 @@ function ChainRulesCore.rrule(::typeof(flatten_loss!), scales::ROCArray{Float32,
     return loss, _flatten_loss_pullback
 end
 
+# ---- anchored depth supervision (src/depth_supervision.jl:406-536; `use_depth_loss`, training.jl:604-620,709-718) ----
+
+# gsr_depth_anchor: the fields of the reference's DepthAnchor, in its order
+struct GsrDepthAnchor; a::Float32; b::Float32; floor::Float32; disparity::Float32; p_far::Float32; end
+GsrDepthAnchor(anchor) = GsrDepthAnchor(anchor.a, anchor.b, anchor.floor, anchor.disparity, anchor.p_far)
+
+function _depth_loss_scratch(w, h)
+    nb = ccall((:gsr_depth_loss_scratch_bytes, LIB), Csize_t, (Int32, Int32), w, h)
+    return AMDGPU.zeros(UInt8, max(Int(nb), 16))
+end
+
+# `depth_target` on the device: (target, half_band, flags) of the (W,H) prior; flags: bit 0 valid, bit 1 far_extrap
+function depth_target(anchor, prior::ROCArray{Float32, 2}, qstep::Float32)
+    target = similar(prior); half_band = similar(prior); flags = AMDGPU.zeros(UInt8, size(prior))
+    check(ccall((:gsr_depth_target, LIB), Cint,
+        (Int32, Int32, Ptr{Float32}, Ref{GsrDepthAnchor}, Cfloat, Ptr{Float32}, Ptr{Float32}, Ptr{UInt8}, Ptr{Cvoid}),
+        size(prior, 1), size(prior, 2), dptr(prior), GsrDepthAnchor(anchor), qstep, dptr(target), dptr(half_band),
+        Ptr{UInt8}(UInt(pointer(flags))), hipstream()))
+    return target, half_band, flags
+end
+
+# weight · ssi_depth_loss of the (C,W,H) frame `image` (C = 5 or 8; channel 4 = blended depth, 5 = alpha, 1-based) against
+# the target built in the kernel from `prior` (W,H) and `anchor`: a device scalar (gsr_depth_loss_forward).
+# Returns (loss, scratch): `scratch` is what depth_loss_backward! of the same image reads.
+function depth_loss(image::ROCArray{Float32, 3}, prior::ROCArray{Float32, 2}, anchor, qstep::Float32; weight::Float32,
+        λ_grad::Float32 = 1f0, scratch = _depth_loss_scratch(size(image, 2), size(image, 3)))
+    loss = AMDGPU.zeros(Float32, 1); stats = AMDGPU.zeros(Float32, 4)
+    check(ccall((:gsr_depth_loss_forward, LIB), Cint,
+        (Int32, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Ref{GsrDepthAnchor}, Cfloat, Cfloat, Cfloat, Ptr{Float32},
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{UInt8}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        size(image, 2), size(image, 3), size(image, 1), dptr(image), dptr(prior), GsrDepthAnchor(anchor), qstep, λ_grad,
+        weight, dptr(loss), dptr(stats), dptr(nothing), dptr(nothing), Ptr{UInt8}(0), Ptr{Cvoid}(UInt(pointer(scratch))),
+        Csize_t(length(scratch)), hipstream()))
+    return loss, scratch
+end
+
+# ADDS weight · ∂ssi_depth_loss/∂(depth, alpha) onto channels 4:5 of `vpixels` (C,W,H) in place (gsr_depth_loss_backward):
+# no float atomics, run-to-run bit-identical.  A `vpixels` this was added onto must go to the backward WITHOUT
+# `color_cotangent = true`.
+function depth_loss_backward!(vpixels::ROCArray{Float32, 3}, image::ROCArray{Float32, 3}, prior::ROCArray{Float32, 2},
+        anchor, qstep::Float32, scratch; weight::Float32, λ_grad::Float32 = 1f0)
+    size(vpixels) == size(image) || error("vpixels must have the image's size")
+    check(ccall((:gsr_depth_loss_backward, LIB), Cint,
+        (Int32, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Ref{GsrDepthAnchor}, Cfloat, Cfloat, Cfloat, Ptr{Float32},
+         Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        size(image, 2), size(image, 3), size(image, 1), dptr(image), dptr(prior), GsrDepthAnchor(anchor), qstep, λ_grad,
+        weight, dptr(vpixels), Ptr{Cvoid}(UInt(pointer(scratch))), Csize_t(length(scratch)), hipstream()))
+    return vpixels
+end
+
+function ChainRulesCore.rrule(::typeof(depth_loss), image::ROCArray{Float32, 3}, prior::ROCArray{Float32, 2}, anchor,
+        qstep::Float32; weight::Float32, λ_grad::Float32 = 1f0)
+    loss, scratch = depth_loss(image, prior, anchor, qstep; weight, λ_grad)
+    function _depth_loss_pullback(Δ)
+        ∇image = AMDGPU.zeros(Float32, size(image))
+        depth_loss_backward!(∇image, image, prior, anchor, qstep, scratch; weight, λ_grad)
+        δ = unthunk(Δ)[1]
+        return NoTangent(), ∇image .* δ, NoTangent(), NoTangent(), NoTangent()
+    end
+    return (loss, scratch), _depth_loss_pullback
+end
+
+# weight · final_scale^clamp(step / steps, 0, 1): the decay of the term's weight over training
+depth_weight(step; weight::Float32 = 2f0, final_scale::Float32 = 0.02f0, steps = 30_000) =
+    weight * final_scale^clamp(Float32(step) / Float32(steps), 0f0, 1f0)
+
 # ---- MCMCStrategy on the device (src/mcmc.jl; include/gsr.h: gsr_mcmc_*) ----
 # The reference's relocate_gaussians! / add_gaussians! / split_sampled! / multinomial_sample are chains of device->host
 # copies, host loops and re-uploads (mcmc.jl:135-258); here every per-Gaussian pass is one launch.  Two intended deviations
