@@ -55,6 +55,23 @@ uint32_t debug_fill_word() {
     return 0u;
 }
 
+// GSR_DEBUG_GUARD=1 (debugging, read at every allocation): every handle buffer is allocated kGuardBytes longer than asked for and
+// the extra bytes — right behind `cap`, which stays what it would have been, so that nothing the library derives from a
+// capacity moves — are filled with a guard word.  gsr_debug_check_guards (and every free of such a buffer) compares them: a
+// kernel that stores past the end of a handle buffer is named instead of silently corrupting the neighbouring allocation.
+bool debug_guard_on() {
+    const char* e = getenv("GSR_DEBUG_GUARD");
+    return e && e[0] == '1' && !e[1];
+}
+constexpr size_t kGuardBytes = 4096;
+struct GuardDamage {  // the first damaged guard seen on a handle (remembered across the free of its buffer)
+    bool set = false;
+    const char* name = "";
+    size_t offset = 0;   // bytes past cap
+    uint32_t word = 0;   // what was found there
+    uint32_t expect = 0;
+};
+
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;  // bytes
@@ -62,6 +79,31 @@ struct DevBuf {
     // GSR_DEBUG_FILL may fill it: floats only, none of which ever becomes an address, a loop bound or a branch that leaves the
     // allocation (set in gsr_create; index / key / count / mask buffers never are: garbage there is a wild address)
     bool fill_ok = false;
+    // GSR_DEBUG_GUARD: the name the check reports; whether THIS allocation carries a guard; the word of a buffer that is not
+    // fill_ok (those get 0x7F7F7F7F).  By the rule above an index / count buffer's guard holds a small valid value: 1 — one
+    // instance, offset 1, tile-list range [1, 1), radius 1, a 64-bit key of tile 0 — and unlike 0 it differs from what a
+    // stray clear would leave.  The three buffers whose words are ids that need not have a second element (tile ids of a
+    // one-tile image, Gaussian ids of a one-Gaussian scene) get 0 (set in gsr_create).
+    const char* name = "?";
+    bool guarded = false;
+    uint32_t guard_word = 1u;
+    GuardDamage* damage = nullptr;
+    uint32_t guard_value() const { return fill_ok ? 0x7F7F7F7Fu : guard_word; }
+    // Compares the guard with its word (synchronises the device); the first difference is remembered in *damage.
+    int check_guard() {
+        if (!p || !guarded || !damage) return GSR_OK;
+        static thread_local uint32_t host[kGuardBytes / 4];
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(host, (const char*)p + cap, kGuardBytes, hipMemcpyDeviceToHost));
+        const uint32_t w = guard_value();
+        for (size_t i = 0; i < kGuardBytes / 4; i++) {
+            if (host[i] != w) {
+                if (!damage->set) *damage = GuardDamage{true, name, i * 4, host[i], w};
+                break;
+            }
+        }
+        return GSR_OK;
+    }
     // grow-only, like the reference's scratch (rasterizer.jl:275-278,340-343)
     int ensure(size_t bytes, float slack = 1.0f) {
         if (bytes <= cap) return GSR_OK;
@@ -72,26 +114,40 @@ struct DevBuf {
             // training run grows; 288 GB of HBM are there to be used, a hipFree + hipMalloc synchronises the device
             if (slack > 1.0f) want = std::max(want, cap + cap / 2);
             regrowths++;
+            if (int rc = check_guard()) return rc;
             HIPCHK(hipFree(p));
             p = nullptr;
             cap = 0;
+            guarded = false;
         }
         want = (want + 255) & ~(size_t)255;
-        HIPCHK(hipMalloc(&p, want));
+        const bool guard = debug_guard_on();
+        HIPCHK(hipMalloc(&p, want + (guard ? kGuardBytes : 0)));
         cap = want;
+        guarded = guard;
+        bool wrote = false;
         if (fill_ok) {
             if (const uint32_t w = debug_fill_word()) {
                 // synchronised: the library's kernels also run on its own non-blocking aux_stream
                 HIPCHK(hipMemsetD32((hipDeviceptr_t)p, (int)w, want / 4));
-                HIPCHK(hipDeviceSynchronize());
+                wrote = true;
             }
         }
+        if (guard) {
+            HIPCHK(hipMemsetD32((hipDeviceptr_t)((char*)p + want), (int)guard_value(), kGuardBytes / 4));
+            wrote = true;
+        }
+        if (wrote) HIPCHK(hipDeviceSynchronize());
         return GSR_OK;
     }
     int release() {
-        if (p) HIPCHK(hipFree(p));
+        if (p) {
+            if (int rc = check_guard()) return rc;
+            HIPCHK(hipFree(p));
+        }
         p = nullptr;
         cap = 0;
+        guarded = false;
         return GSR_OK;
     }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
@@ -282,6 +338,7 @@ struct gsr_handle {
 
     DevBuf* all[40];
     int n_all = 0;
+    GuardDamage guard_damage;  // GSR_DEBUG_GUARD: the first damaged guard of any buffer of `all`, freed ones included
 };
 
 namespace {
@@ -592,7 +649,20 @@ int gsr_create(const gsr_config* cfg, gsr_handle** out) {
                       &h->geo, &h->gnormal, &h->radii, &h->bsum, &h->bpre, &h->bvis, &h->bins, &h->values_sorted, &h->s0,
                       &h->s1, &h->s2, &h->s3, &h->big_scratch, &h->rows, &h->vmean2d, &h->d0, &h->d1,
                       &h->d2, &h->partial, &h->keys_compact, &h->big_list, &h->long_state, &h->overflow_fill, &h->dbg_flag, &h->pose_part};
-    for (DevBuf* b : list) h->all[h->n_all++] = b;
+    static const char* const names[] = {"ranges", "n_contrib", "final_T", "tile_count", "tile_start", "tile_order", "totals",
+                                        "geo", "gnormal", "radii", "bsum", "bpre", "bvis", "bins", "values_sorted", "s0",
+                                        "s1", "s2", "s3", "big_scratch", "rows", "vmean2d", "d0", "d1",
+                                        "d2", "partial", "keys_compact", "big_list", "long_state", "overflow_fill", "dbg_flag", "pose_part"};
+    static_assert(sizeof(names) / sizeof(names[0]) == sizeof(list) / sizeof(list[0]), "one name per buffer");
+    for (DevBuf* b : list) {
+        b->name = names[h->n_all];
+        b->damage = &h->guard_damage;
+        h->all[h->n_all++] = b;
+    }
+    // GSR_DEBUG_GUARD words (DevBuf::guard_word): ids whose range may be {0} get 0
+    h->tile_order.guard_word = 0u;     // tile ids
+    h->big_list.guard_word = 0u;       // tile ids of the tier lists
+    h->values_sorted.guard_word = 0u;  // Gaussian ids
     // GSR_DEBUG_FILL candidates (DevBuf::fill_ok), each read only as float data:
     h->rows.fill_ok = true;        // GsrInst gradient rows (float4): summed by pergauss_bwd, copied out by gsr_buffer
     h->vmean2d.fill_ok = true;     // gstate.∇means_2d (float2): written for every Gaussian, read by gsr_update_stats behind radii > 0
@@ -692,6 +762,17 @@ int gsr_reserve(gsr_handle* h, int64_t n_gaussians, int64_t n_instances) {
             (rc = h->s2.ensure(D * 16)) || (C > 3 && (rc = h->s3.ensure(D * 16))) || (rc = h->rows.ensure(D * 64 + D * 32)))
             return rc;
     }
+    return GSR_OK;
+}
+
+int gsr_debug_check_guards(gsr_handle* h) {
+    if (!h) return fail(GSR_E_INVALID_ARG, "null handle");
+    for (int i = 0; i < h->n_all; i++)
+        if (int rc = h->all[i]->check_guard()) return rc;
+    const GuardDamage& d = h->guard_damage;
+    if (d.set)
+        return fail(GSR_E_STATE, "guard behind handle buffer '%s' is damaged: byte offset %zu past its capacity holds the word "
+                                 "0x%08x (guard word 0x%08x)", d.name, d.offset, d.word, d.expect);
     return GSR_OK;
 }
 

@@ -254,7 +254,12 @@ typedef struct gsr_grads {
  * reduce |vpixels[3:]| first (one pass over the image + a host wait — debugging only) and fail with GSR_E_INVALID_ARG when it
  * is not exactly zero.  (Likewise a debugging switch, read at every allocation of handle scratch: GSR_DEBUG_FILL=nan / big fills
  * each new allocation of the handle's float-only buffers with the word 0xFFFFFFFF / 0x7F7F7F7F, so that a kernel that reads a
- * float it never wrote cannot pass on the zeros of fresh pages; index, key and count buffers are never filled.) */
+ * float it never wrote cannot pass on the zeros of fresh pages; index, key and count buffers are never filled.  And
+ * GSR_DEBUG_GUARD=1, read at the same place: every handle buffer is allocated 4 KiB longer than its capacity and the extra
+ * bytes hold a guard word — 0x7F7F7F7F behind the float-only buffers, a small valid value (1, or 0 behind lists of ids)
+ * behind index, key and count buffers; capacities, gsr_memory_usage and every result are unchanged.  The guards are compared
+ * whenever such a buffer is freed and by gsr_debug_check_guards below: a kernel that stores past the end of a handle buffer
+ * is named.  Costs nothing when unset.) */
 #define GSR_GRADS_COLOR_COTANGENT 0x1u
 
 typedef struct gsr_handle gsr_handle;
@@ -267,6 +272,11 @@ GSR_API int gsr_destroy(gsr_handle* h);
 GSR_API int gsr_release_scene_buffers(gsr_handle* h);
 /* memory_usage(rast) — rasterizer.jl:127-134 (device bytes owned by the handle). */
 GSR_API int64_t gsr_memory_usage(const gsr_handle* h);
+/* Debugging (no reference counterpart; a new function, no struct change: GSR_ABI_VERSION stays).  Synchronises the device and
+ * compares the guard behind every buffer the handle owns, plus what was found when a guarded buffer was freed (regrowth,
+ * gsr_release_scene_buffers).  GSR_OK, or GSR_E_STATE with gsr_last_error_string() naming the buffer, the first damaged byte
+ * offset past its capacity and the word found there.  Handles created without GSR_DEBUG_GUARD=1 have no guards: GSR_OK. */
+GSR_API int gsr_debug_check_guards(gsr_handle* h);
 /* New in ABI 6 (no reference counterpart: the reference reallocates its states whenever the model or the instance count grew,
  * rasterizer.jl:275-278,340-343).  Pre-size the handle's grow-only scratch for views of up to n_gaussians Gaussians and
  * n_instances tile instances, so that the forwards that follow allocate nothing — a reallocation inside gsr_forward is a hipFree
