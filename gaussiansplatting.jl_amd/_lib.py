@@ -330,6 +330,19 @@ def load():
     return lib
 
 
+def stream():
+    """The current torch stream, as the hipStream_t argument of an entry point."""
+    import torch  # lazily, as in load(): modules with a host-only part import this one without torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def ptr(t, empty_is_null=False):
+    """A tensor's address as a pointer argument; None -> NULL, and with `empty_is_null` so does a tensor of no elements."""
+    if t is None or (empty_is_null and t.numel() == 0):
+        return None
+    return C.c_void_p(t.data_ptr())
+
+
 def check(rc: int):
     if rc != 0:
         raise GsrError(rc, load().gsr_last_error_string().decode())

@@ -9,8 +9,6 @@ Layouts: all grids are one (n, 12, gz, gy, gx) tensor ≙ the reference's (gx, g
 (12, gz, gy, gx); images are (H, W, C) ≙ (C, W, H), C = 3, 5 or 8 (the rasterizer's modes)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -19,10 +17,6 @@ from . import fused_ssim
 from .optim import Adam
 
 GRID_SIZE = (16, 16, 8)  # bilateral_grid_size (utils.jl:60): (x, y, guidance)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def lr_exp_scheduler(lr_start: float, lr_end: float, steps: int):
@@ -85,7 +79,7 @@ def slice_forward(image: torch.Tensor, grid: torch.Tensor, out: torch.Tensor = N
         raise ValueError("out must have the image's shape and device")
     with torch.cuda.device(image.device):
         L.check(L.load().gsr_bilateral_slice_forward(W, H, Cc, image.data_ptr(), grid.data_ptr(), gx, gy, gz, out.data_ptr(),
-                                                     _stream()))
+                                                     L.stream()))
     return out
 
 
@@ -109,7 +103,7 @@ def slice_backward(image: torch.Tensor, grid: torch.Tensor, vout: torch.Tensor, 
     buf = _scratch(_SCRATCH if scratch is None else scratch, "slice", nb, image.device)
     with torch.cuda.device(image.device):
         L.check(lib.gsr_bilateral_slice_backward(W, H, Cc, image.data_ptr(), grid.data_ptr(), gx, gy, gz, vout.data_ptr(),
-                                                 vimage.data_ptr(), vgrid.data_ptr(), buf.data_ptr(), buf.numel(), _stream()))
+                                                 vimage.data_ptr(), vgrid.data_ptr(), buf.data_ptr(), buf.numel(), L.stream()))
     return vimage, vgrid
 
 
@@ -124,7 +118,7 @@ def tv(grids: torch.Tensor, weight: float = 1.0, grad: bool = False, scratch: di
     buf = _scratch(_SCRATCH if scratch is None else scratch, "tv", int(lib.gsr_bilateral_tv_scratch_bytes(n)), grids.device)
     with torch.cuda.device(grids.device):
         L.check(lib.gsr_bilateral_tv(n, gx, gy, gz, grids.data_ptr(), float(weight), loss.data_ptr(),
-                                     None if g is None else g.data_ptr(), buf.data_ptr(), buf.numel(), _stream()))
+                                     None if g is None else g.data_ptr(), buf.data_ptr(), buf.numel(), L.stream()))
     return (loss, g) if grad else loss
 
 
@@ -222,7 +216,7 @@ class BilateralGrid:
             L.check(lib.gsr_bilateral_adam_tail(n, gx, gy, gz, self.grids.data_ptr(), o.mu.data_ptr(), o.nu.data_ptr(),
                                                 self.vgrid.data_ptr(), int(view), float(tv_weight), o.lr, o.current_step + 1,
                                                 o.beta1, o.beta2, o.eps, self.tv_term.data_ptr(), buf.data_ptr(), buf.numel(),
-                                                _stream()))
+                                                L.stream()))
         o.current_step += 1  # committed after validation and a successful launch
         self.vgrid_view = None
         return self.tv_term

@@ -14,6 +14,7 @@
 // slab; a second kernel sums, per grid entry, the slabs of the <= 4 cells x chunks that touch it in a fixed order.
 #include "gsr_kernels.h"
 #include "adam_math.h"
+#include "block_reduce.h"
 
 #include <algorithm>
 
@@ -262,16 +263,6 @@ __global__ __launch_bounds__(256) void slice_bwd_sum_kernel(int gx, int gy, int 
 }
 
 // ---- total variation (bilateral_grid.jl:106-119) and the fused Adam tail ----
-__device__ __forceinline__ float block_sum256(float v, float* red) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    const int t = threadIdx.x;
-    __syncthreads();
-    if ((t & 63) == 0) red[t >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // One workgroup per (image, coefficient) slab of gx*gy*gz floats, staged in LDS: the TV gradient reads neighbours of
 // the values BEFORE the update, so the Adam tail can update the slab in place.  partial[slab][3]: the slab's sums of
 // squared forward differences along x, y, z.
@@ -312,9 +303,9 @@ __global__ __launch_bounds__(256) void tv_slab_kernel(int gx, int gy, int gz, fl
             mu[k] = m; nu[k] = v;
         }
     }
-    sx = block_sum256(sx, red);
-    sy = block_sum256(sy, red);
-    sz = block_sum256(sz, red);
+    sx = gsr::block_sum(sx, red);
+    sy = gsr::block_sum(sy, red);
+    sz = gsr::block_sum(sz, red);
     if (t == 0) {
         partial[sid * 3 + 0] = sx;
         partial[sid * 3 + 1] = sy;
@@ -331,7 +322,7 @@ __global__ __launch_bounds__(256) void tv_final_kernel(int n_slabs, const float*
 #pragma unroll
         for (int a = 0; a < 3; a++) s[a] += partial[(size_t)i * 3 + a];
 #pragma unroll
-    for (int a = 0; a < 3; a++) s[a] = block_sum256(s[a], red);
+    for (int a = 0; a < 3; a++) s[a] = gsr::block_sum(s[a], red);
     if (threadIdx.x == 0) *loss_out = tv.weight * (((s[0] / tv.nx + s[1] / tv.ny) + s[2] / tv.nz) / tv.n12);
 }
 

@@ -25,6 +25,7 @@
 // counts as 0 in Σα.  No float atomics anywhere; every result is run-to-run bit-identical; every scratch word that is
 // read was written by an earlier pass of the same call.
 #include "gsr_kernels.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -57,16 +58,6 @@ __device__ __forceinline__ float deadband(float r, float half) {
 }
 __device__ __forceinline__ float geman_mcclure(float x) { const float x2 = x * x; return 0.5f * x2 / (1.0f + x2); }
 __device__ __forceinline__ float geman_mcclure_d(float x) { const float q = 1.0f + x * x; return x / (q * q); }
-
-// fixed-order sum over the 256 threads of a workgroup; thread 0 holds the result
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 // the target maps alone (`depth_target`): one thread per pixel
 __global__ __launch_bounds__(THREADS) void depth_target_kernel(size_t n, const float* __restrict__ prior, Anchor an, float qstep,
@@ -119,17 +110,19 @@ __global__ __launch_bounds__(THREADS) void depth_stats_kernel(int W, int H, int 
         }
         rec[i] = r;
     }
-    s_a = block_sum(s_a, red);
-    s_w = block_sum(s_w, red);
-    s_wp = block_sum(s_wp, red);
-    s_wpp = block_sum(s_wpp, red);
+    s_a = gsr::block_sum<double>(s_a, red);
+    s_w = gsr::block_sum<double>(s_w, red);
+    s_wp = gsr::block_sum<double>(s_wp, red);
+    s_wpp = gsr::block_sum<double>(s_wpp, red);
     if (threadIdx.x == 0) {
         double* p = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * N_STAT;
         p[0] = s_a; p[1] = s_w; p[2] = s_wp; p[3] = s_wpp;
     }
 }
 
-// N sums of the partials (n_partial rows of N doubles): each thread its rows in index order, then a tree over the threads
+// N sums of the partials (n_partial rows of N doubles): each thread its rows in index order, then a tree over the threads.
+// The one TREE-ordered final pass: every other one is gsr::sum_partials (block_reduce.h), which adds the 256 thread sums
+// serially.  The two orders round double sums differently, so folding this one into it would move the loss, μ and σ.
 template <int N>
 __device__ __forceinline__ void sum_partials(int n_partial, const double* __restrict__ partial, double (*red)[THREADS], double* s) {
 #pragma unroll
@@ -219,9 +212,9 @@ __global__ __launch_bounds__(THREADS) void depth_loss_kernel(int W, int H, const
         const float hy = pair_x(c, sr[(ly + 1) * SW + lx], iscale, w);
         if (w > 0.0f) s_y += (double)(w * geman_mcclure(hy));
     }
-    s_d = block_sum(s_d, red);
-    s_x = block_sum(s_x, red);
-    s_y = block_sum(s_y, red);
+    s_d = gsr::block_sum<double>(s_d, red);
+    s_x = gsr::block_sum<double>(s_x, red);
+    s_y = gsr::block_sum<double>(s_y, red);
     if (threadIdx.x == 0) {
         double* p = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * N_LOSS;
         p[0] = s_d; p[1] = s_x; p[2] = s_y;

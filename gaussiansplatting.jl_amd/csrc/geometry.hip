@@ -18,6 +18,7 @@
 // The fused gsr_backward_trainer_tail never materialises ∇scales, so it cannot take the flatten gradient: steps with the
 // regulariser on run gsr_backward + gsr_flatten_loss (adds onto vscales) + gsr_trainer_tail_step.
 #include "gsr_kernels.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -113,16 +114,6 @@ __device__ __forceinline__ float centre_eval(const float* se, const float* sa, i
     return fminf(fmaxf(a_c, 0.0f), 1.0f);
 }
 
-// fixed-order sum over the 256 threads of a workgroup; every thread gets the result
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // ---- forward: one workgroup per tile -> partial[wg] = (Σ w(1-cos), Σ w, count) ----
 __global__ __launch_bounds__(THREADS) void normal_fwd_kernel(int W, int H, const float* __restrict__ image, Rays rays,
                                                              float* __restrict__ weights_out, float* __restrict__ partial) {
@@ -149,9 +140,9 @@ __global__ __launch_bounds__(THREADS) void normal_fwd_kernel(int W, int H, const
         }
         if (weights_out) weights_out[(size_t)y * W + x] = w;
     }
-    s_loss = block_sum(s_loss, red);
-    s_w = block_sum(s_w, red);
-    s_n = block_sum(s_n, red);
+    s_loss = gsr::block_sum(s_loss, red);
+    s_w = gsr::block_sum(s_w, red);
+    s_n = gsr::block_sum(s_n, red);
     if (threadIdx.x == 0) {
         float* p = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
         p[0] = s_loss; p[1] = s_w; p[2] = s_n;
@@ -163,19 +154,9 @@ __global__ __launch_bounds__(THREADS) void normal_fwd_kernel(int W, int H, const
 __global__ __launch_bounds__(THREADS) void normal_final_kernel(int n_partial, const float* __restrict__ partial, float weight,
                                                                float* loss_out, float* stats_out, float* head) {
     __shared__ double red[3][THREADS];
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < n_partial; i += THREADS)
-#pragma unroll
-        for (int a = 0; a < 3; a++) s[a] += (double)partial[(size_t)i * 3 + a];
-#pragma unroll
-    for (int a = 0; a < 3; a++) red[a][threadIdx.x] = s[a];
-    __syncthreads();
+    double s[3];
+    gsr::sum_partials<3>(n_partial, partial, red, s);
     if (threadIdx.x != 0) return;
-    for (int a = 0; a < 3; a++) {
-        double t = 0.0;
-        for (int i = 0; i < THREADS; i++) t += red[a][i];
-        s[a] = t;
-    }
     const float sum_w = (float)s[1], count = (float)s[2];
     const bool enough = count >= MIN_COUNT && sum_w >= MIN_WEIGHT;
     const double norm = s[1] > 1.0 ? s[1] : 1.0;
@@ -257,20 +238,16 @@ __global__ __launch_bounds__(THREADS) void flatten_kernel(int n, int sd, const f
         sum += expf(m);
         if (vscales) vscales[(size_t)i * 3 + arg] += grad;
     }
-    sum = block_sum(sum, red);
+    sum = gsr::block_sum(sum, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(THREADS) void flatten_final_kernel(int n_partial, const float* __restrict__ partial, float weight,
                                                                 int n, float* loss_out) {
-    __shared__ double red[THREADS];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n_partial; i += THREADS) s += (double)partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
+    __shared__ double red[1][THREADS];
+    double t;
+    gsr::sum_partials<1>(n_partial, partial, red, &t);
     if (threadIdx.x != 0) return;
-    double t = 0.0;
-    for (int i = 0; i < THREADS; i++) t += red[i];
     *loss_out = n > 0 ? weight * (float)(t / (double)n) : 0.0f;
 }
 

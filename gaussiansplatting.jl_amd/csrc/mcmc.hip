@@ -8,6 +8,7 @@
 // Compiled with -ffp-contract=off, like densify.hip: the fp32 expression trees are the reference's, only the transcendental
 // calls (exp / log / pow / cos / sin) differ from a host libm by ulps.
 #include "gsr_kernels.h"
+#include "block_reduce.h"
 #include "quat.h"
 #include "rng.h"
 
@@ -43,15 +44,6 @@ __global__ __launch_bounds__(256) void mcmc_weights_kernel(long long n, int sd, 
 // one-workgroup scan of the block sums, per-block prefixes.  A thread owns 4 consecutive rows.
 constexpr int MS_BLOCK = 1024;
 
-__device__ __forceinline__ u64 wave_inclusive_scan_u64(u64 x, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u64 y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    return x;
-}
-
 __device__ __forceinline__ u64 load_rows4(long long n, const uint32_t* __restrict__ q, long long first, uint32_t (&v)[4]) {
     u64 s = 0;
 #pragma unroll
@@ -68,7 +60,7 @@ __global__ __launch_bounds__(256) void mcmc_block_sum_kernel(long long n, const 
     uint32_t v[4];
     const u64 s = load_rows4(n, q, (long long)blockIdx.x * MS_BLOCK + 4 * threadIdx.x, v);
     const int lane = threadIdx.x & 63;
-    const u64 x = wave_inclusive_scan_u64(s, lane);
+    const u64 x = gsr::wave_inclusive_scan(s, lane);
     if (lane == 63) wsum[threadIdx.x >> 6] = x;
     __syncthreads();
     if (threadIdx.x == 0) block_sum[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
@@ -76,26 +68,7 @@ __global__ __launch_bounds__(256) void mcmc_block_sum_kernel(long long n, const 
 
 __global__ __launch_bounds__(1024) void mcmc_scan_blocks_kernel(int nb, u64* __restrict__ block_sum /* in: sums, out: exclusive offsets */,
                                                                 u64* __restrict__ total) {
-    __shared__ u64 wave_sums[16];
-    __shared__ u64 carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += 1024) {
-        const int i = b0 + tid;
-        const u64 v = i < nb ? block_sum[i] : 0ull;
-        const u64 x = wave_inclusive_scan_u64(v, lane);
-        if (lane == 63) wave_sums[wave] = x;
-        __syncthreads();
-        u64 woff = 0;
-        for (int w = 0; w < wave; w++) woff += wave_sums[w];
-        const u64 excl = carry_s + woff + x - v;
-        if (i < nb) block_sum[i] = excl;
-        __syncthreads();
-        if (tid == 1023) carry_s = excl + v;
-        __syncthreads();
-    }
-    if (tid == 0) *total = carry_s;
+    gsr::block_scan_carry(nb, block_sum, total);
 }
 
 __global__ __launch_bounds__(256) void mcmc_prefix_kernel(long long n, const uint32_t* __restrict__ q,
@@ -105,7 +78,7 @@ __global__ __launch_bounds__(256) void mcmc_prefix_kernel(long long n, const uin
     const long long first = (long long)blockIdx.x * MS_BLOCK + 4 * threadIdx.x;
     const u64 s = load_rows4(n, q, first, v);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 x = wave_inclusive_scan_u64(s, lane);
+    const u64 x = gsr::wave_inclusive_scan(s, lane);
     if (lane == 63) wsum[wave] = x;
     __syncthreads();
     u64 run = block_off[blockIdx.x] + x - s;
@@ -294,17 +267,11 @@ __global__ __launch_bounds__(256) void mcmc_noise_kernel(long long n, int sd, fl
 // pullback sums the three tiled rows).  partial[wg] = (Σ sigmoid, Σ exp) of the workgroup's chunk, summed in a fixed order.
 constexpr int RG_PER = 8, RG_CHUNK = 256 * RG_PER;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;  // lane 0
-}
-
 __global__ __launch_bounds__(256) void mcmc_reg_kernel(long long n, int sd, const float* __restrict__ opac,
                                                        const float* __restrict__ scales, float grad_o, float grad_s,
                                                        float* __restrict__ vopac, float* __restrict__ vscales,
                                                        float* __restrict__ partial) {
-    __shared__ float red[2][4];
+    __shared__ float red[4];
     float so = 0.0f, ss = 0.0f;
     const long long ns = n * sd, n3 = 3 * n;
 #pragma unroll
@@ -317,28 +284,21 @@ __global__ __launch_bounds__(256) void mcmc_reg_kernel(long long n, int sd, cons
         if (e < ns) ss += expf(scales[e]);
         if (vscales && e < n3 && (sd == 3 || e % 3 == 0)) vscales[e] = vscales[e] + grad_s;
     }
-    so = wave_sum(so);
-    ss = wave_sum(ss);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = so; red[1][threadIdx.x >> 6] = ss; }
-    __syncthreads();
+    so = gsr::block_sum(so, red);
+    ss = gsr::block_sum(ss, red);
     if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-        partial[2 * blockIdx.x + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+        partial[2 * blockIdx.x] = so;
+        partial[2 * blockIdx.x + 1] = ss;
     }
 }
 
 __global__ __launch_bounds__(256) void mcmc_reg_final_kernel(int n_partial, const float* __restrict__ partial, long long n, int sd,
                                                              float opacity_reg, float scale_reg, float* loss_out) {
     __shared__ double red[2][256];
-    double so = 0.0, ss = 0.0;
-    for (int i = threadIdx.x; i < n_partial; i += 256) { so += (double)partial[2 * i]; ss += (double)partial[2 * i + 1]; }
-    red[0][threadIdx.x] = so;
-    red[1][threadIdx.x] = ss;
-    __syncthreads();
+    double t[2];  // (Σ sigmoid, Σ exp)
+    gsr::sum_partials<2>(n_partial, partial, red, t);
     if (threadIdx.x != 0) return;
-    double to = 0.0, ts = 0.0;
-    for (int i = 0; i < 256; i++) { to += red[0][i]; ts += red[1][i]; }
-    *loss_out = n > 0 ? opacity_reg * (float)(to / (double)n) + scale_reg * (float)(ts / (double)(n * sd)) : 0.0f;
+    *loss_out = n > 0 ? opacity_reg * (float)(t[0] / (double)n) + scale_reg * (float)(t[1] / (double)(n * sd)) : 0.0f;
 }
 
 unsigned blocks_for(long long work, int per_block) { return (unsigned)((work + per_block - 1) / per_block); }

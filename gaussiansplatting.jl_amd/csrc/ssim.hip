@@ -20,6 +20,7 @@
 //       makes of the reference's source ("contraction order unspecified, LLVM may fuse FMAs");
 //       parity at the stated fp32 tolerance instead of bit for bit; −46 % VALU instructions per pixel.
 #include "gsr_kernels.h"
+#include "block_reduce.h"
 
 #ifndef SSIM_EXACT
 #define SSIM_EXACT 1
@@ -109,12 +110,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 // a·b + c·d.  The contracted build fuses a·b into the add and rounds c·d, which is what the compiler has made of this
@@ -250,7 +245,7 @@ __global__ __launch_bounds__(64 * NPL * SPB, MIN_WAVES) void ssim_fwd_kernel(Src
     if (LOSS) {
         // one partial pair per wave; thousands of waves hammering two words with atomics
         // serialise at ~12 ns each (MI355X_MICROARCH.md "fanin")
-        const float a = wave_sum(l1), b = wave_sum(sv);
+        const float a = gsr::wave_sum(l1), b = gsr::wave_sum(sv);
         if (lane == 0) {
             const size_t pair = (size_t)blockIdx.x * NW + wv;
             partial[2 * pair] = a;
@@ -265,18 +260,15 @@ __global__ __launch_bounds__(64 * NPL * SPB, MIN_WAVES) void ssim_fwd_kernel(Src
 template <int NT>
 __device__ __forceinline__ void loss_finish_body(const float* __restrict__ partial, int n_pairs, float lambda,
                                                  float inv_count, float* __restrict__ loss_out) {
-    __shared__ float red[2][NT / 64];
+    __shared__ float red[NT / 64];
     float a = 0.0f, b = 0.0f;
     for (int i = threadIdx.x; i < n_pairs; i += NT) {
         const float2 p = reinterpret_cast<const float2*>(partial)[i];
         a += p.x; b += p.y;
     }
-    a = wave_sum(a); b = wave_sum(b);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
-    __syncthreads();
+    a = gsr::block_sum<float, NT / 64>(a, red);
+    b = gsr::block_sum<float, NT / 64>(b, red);
     if (threadIdx.x == 0) {
-        a = 0.0f; b = 0.0f;
-        for (int w = 0; w < NT / 64; w++) { a += red[0][w]; b += red[1][w]; }
         const float l1 = a * inv_count;
         const float s = 1.0f - b * inv_count;
         loss_out[0] = (1.0f - lambda) * l1 + lambda * s;

@@ -6,7 +6,7 @@
 // expression tree as the oracle's.
 #include "gsr_kernels.h"
 #include "adam_math.h"
-#include "wave_reduce.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -228,26 +228,7 @@ __global__ __launch_bounds__(256) void findall_count_kernel(long long n, const u
 
 __global__ __launch_bounds__(1024) void findall_scan_kernel(int nb, uint32_t* __restrict__ block_count /* in: counts, out: exclusive offsets */,
                                                             uint32_t* __restrict__ total) {
-    __shared__ uint32_t wave_sums[16];
-    __shared__ uint32_t carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += 1024) {
-        const int i = b0 + tid;
-        const uint32_t v = i < nb ? block_count[i] : 0u;
-        const uint32_t x = gsr::wave_inclusive_scan(v, lane);
-        if (lane == 63) wave_sums[wave] = x;
-        __syncthreads();
-        uint32_t woff = 0;
-        for (int w = 0; w < wave; w++) woff += wave_sums[w];
-        const uint32_t excl = carry_s + woff + x - v;
-        if (i < nb) block_count[i] = excl;
-        __syncthreads();
-        if (tid == 1023) carry_s = excl + v;
-        __syncthreads();
-    }
-    if (tid == 0) *total = carry_s;
+    gsr::block_scan_carry(nb, block_count, total);
 }
 
 __global__ __launch_bounds__(256) void findall_emit_kernel(long long n, const uint8_t* __restrict__ mask,

@@ -15,10 +15,6 @@ import torch
 from . import _lib as L
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def findall(mask: torch.Tensor) -> torch.Tensor:
     """`findall(mask)`: ascending 0-based indices of the true entries (device int32 vector).
     One host read-back (the count sizes the result), as the reference's logical indexing has."""
@@ -33,7 +29,7 @@ def findall(mask: torch.Tensor) -> torch.Tensor:
     idx = torch.empty(max(n, 1), device=mask.device, dtype=torch.int32)
     cnt = torch.zeros(1, device=mask.device, dtype=torch.int32)
     scratch = torch.empty(lib.gsr_mask_findall_scratch_bytes(n), device=mask.device, dtype=torch.uint8)
-    L.check(lib.gsr_mask_findall(mask.data_ptr(), n, idx.data_ptr(), cnt.data_ptr(), scratch.data_ptr(), _stream()))
+    L.check(lib.gsr_mask_findall(mask.data_ptr(), n, idx.data_ptr(), cnt.data_ptr(), scratch.data_ptr(), L.stream()))
     return idx[: int(cnt.item())]
 
 
@@ -57,7 +53,7 @@ def select(arrays: Sequence[torch.Tensor], idx: torch.Tensor):
             y = torch.empty((count,) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype)
             groups[i] = L.GatherGroup(x.data_ptr(), y.data_ptr(), rw)
             out.append(y)
-        L.check(lib.gsr_gather_rows(groups, len(chunk), idx.data_ptr(), count, _stream()))
+        L.check(lib.gsr_gather_rows(groups, len(chunk), idx.data_ptr(), count, L.stream()))
     return out
 
 
@@ -141,7 +137,9 @@ class DefaultStrategy:
 
 
 def _ptr(t):
-    return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+    """L.ptr under the rule of the densification entry points: an EMPTY tensor is NULL too (an empty selection, a model of
+    no rows)."""
+    return L.ptr(t, empty_is_null=True)
 
 
 def _mask(kind, gs, n_grad=0, grad=None, max_radii=None, thr=0.0, gamma=0.0, min_opacity=0.0, max_screen_size=0):
@@ -149,7 +147,7 @@ def _mask(kind, gs, n_grad=0, grad=None, max_radii=None, thr=0.0, gamma=0.0, min
     mask = torch.empty(n, dtype=torch.uint8, device=gs.points.device)
     L.check(L.load().gsr_densify_mask(kind, n, n_grad, _ptr(grad), _ptr(gs.scales), int(gs.scales.shape[1]), _ptr(gs.opacities),
                                       _ptr(max_radii), float(thr), float(gamma), float(min_opacity), int(max_screen_size),
-                                      _ptr(mask), _stream()))
+                                      _ptr(mask), L.stream()))
     return mask
 
 
@@ -176,7 +174,7 @@ def _compose(gs: GaussianModel, optimizers, keep_idx, n_keep, sel_idx, n_sel, re
         new_ids = torch.empty(rows, device=gs.ids.device, dtype=torch.int32)
         groups.append(L.ComposeGroup(gs.ids.data_ptr(), new_ids.data_ptr(), 1, 0))
     arr = (L.ComposeGroup * len(groups))(*groups)
-    L.check(L.load().gsr_compose_rows(arr, len(groups), _ptr(keep_idx), n_keep, _ptr(sel_idx), n_sel, reps, _stream()))
+    L.check(L.load().gsr_compose_rows(arr, len(groups), _ptr(keep_idx), n_keep, _ptr(sel_idx), n_sel, reps, L.stream()))
     for k, y, mu, nu in outs:
         setattr(gs, k, y)
         optimizers[k].mu, optimizers[k].nu = mu, nu
@@ -215,7 +213,7 @@ def densify_split(strategy, gs, optimizers, grad, grad_threshold, extent, dense_
     nk = keep.numel()
     if m2 > 0:  # densification.jl:94
         L.check(L.load().gsr_split_transform(m2, int(gs.scales.shape[1]), gs.points[nk:].data_ptr(), gs.rotations[nk:].data_ptr(),
-                                             gs.scales[nk:].data_ptr(), int(seed) & 0xFFFFFFFF, _stream()))
+                                             gs.scales[nk:].data_ptr(), int(seed) & 0xFFFFFFFF, L.stream()))
     _reset_stats(strategy, len(gs), gs.points.device)
     assert len(gs) == n - sel.numel() + m2
     return mask
@@ -233,7 +231,7 @@ def densify_and_prune(strategy: DefaultStrategy, gs: GaussianModel, optimizers, 
     """densify_and_prune! (densification.jl:1-27).  Returns the three masks (clone, split, valid) for inspection."""
     n = len(gs)
     grad = torch.empty(n, dtype=torch.float32, device=gs.points.device)
-    L.check(L.load().gsr_densify_grad_mean(n, _ptr(strategy.accum_grad_means_2d), _ptr(strategy.denom), _ptr(grad), _stream()))
+    L.check(L.load().gsr_densify_grad_mean(n, _ptr(strategy.accum_grad_means_2d), _ptr(strategy.denom), _ptr(grad), L.stream()))
     m_clone = densify_clone(strategy, gs, optimizers, grad, strategy.densify_grad_threshold, extent, strategy.dense_percent)
     m_split = densify_split(strategy, gs, optimizers, grad, strategy.densify_grad_threshold, extent, strategy.dense_percent, seed)
     valid = _mask(L.DENSIFY_PRUNE, gs, max_radii=strategy.max_radii, gamma=np.float32(0.1) * np.float32(pruning_extent),
@@ -267,7 +265,7 @@ def reorder_spatially(strategy: DefaultStrategy, gs: GaussianModel, optimizers) 
     lo_h = (C.c_float * 3)(*box[:3])
     hi_h = (C.c_float * 3)(*box[3:])
     codes = torch.empty(n, dtype=torch.int64, device=gs.points.device)   # 63-bit codes: order as signed = as unsigned
-    L.check(L.load().gsr_morton_codes(n, _ptr(gs.points), lo_h, hi_h, _ptr(codes), _stream()))
+    L.check(L.load().gsr_morton_codes(n, _ptr(gs.points), lo_h, hi_h, _ptr(codes), L.stream()))
     perm = torch.argsort(codes, stable=True).to(torch.int32)
     _compose(gs, optimizers, perm, n, None, 0, 1)
     strategy.max_radii, strategy.accum_grad_means_2d, strategy.denom = select(
@@ -277,7 +275,7 @@ def reorder_spatially(strategy: DefaultStrategy, gs: GaussianModel, optimizers) 
 
 def reset_opacity(gs: GaussianModel):
     """reset_opacity! (gaussians.jl:115-126)"""
-    L.check(L.load().gsr_reset_opacity(gs.opacities.numel(), _ptr(gs.opacities), _stream()))
+    L.check(L.load().gsr_reset_opacity(gs.opacities.numel(), _ptr(gs.opacities), L.stream()))
 
 
 def post_train_step(strategy: DefaultStrategy, gs: GaussianModel, optimizers, rast, step: int, extent: float, seed=None):

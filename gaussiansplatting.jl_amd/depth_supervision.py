@@ -230,11 +230,6 @@ def _torch():
     return torch
 
 
-def _stream():
-    torch = _torch()
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _check_frame(image, name="image"):
     torch = _torch()
     if not (image.is_cuda and image.dtype == torch.float32 and image.is_contiguous() and image.dim() == 3
@@ -283,7 +278,7 @@ def depth_target(anchor: DepthAnchor, prior, qstep: float):
     an = anchor.struct()
     with torch.cuda.device(prior.device):
         L.check(L.load().gsr_depth_target(W, H, prior.data_ptr(), C.byref(an), float(qstep), target.data_ptr(), half.data_ptr(),
-                                          flags.data_ptr(), _stream()))
+                                          flags.data_ptr(), L.stream()))
     return target, half, flags
 
 
@@ -309,7 +304,7 @@ def depth_loss(image, prior, anchor: DepthAnchor, qstep: float, weight: float, l
         L.check(L.load().gsr_depth_loss_forward(
             W, H, Cn, image.data_ptr(), prior.data_ptr(), C.byref(an), float(qstep), float(lambda_grad), float(weight),
             loss.data_ptr(), st.data_ptr(), *(None if m is None else m.data_ptr() for m in (tm, hm, fm)), buf.data_ptr(),
-            buf.numel() * buf.element_size(), _stream()))
+            buf.numel() * buf.element_size(), L.stream()))
     out = (loss,) + ((st,) if stats else ()) + (((tm, hm, fm),) if maps else ())
     return out[0] if len(out) == 1 else out
 
@@ -334,7 +329,7 @@ def depth_loss_backward_(image, prior, anchor: DepthAnchor, qstep: float, vpixel
     with torch.cuda.device(image.device):
         L.check(L.load().gsr_depth_loss_backward(
             W, H, Cn, image.data_ptr(), prior.data_ptr(), C.byref(an), float(qstep), float(lambda_grad), float(weight),
-            vpixels.data_ptr(), buf.data_ptr(), buf.numel() * buf.element_size(), _stream()))
+            vpixels.data_ptr(), buf.data_ptr(), buf.numel() * buf.element_size(), L.stream()))
     return vpixels
 
 

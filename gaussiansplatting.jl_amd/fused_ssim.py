@@ -5,8 +5,6 @@
 Tensors are (B,CH,H,W) contiguous ≙ the reference's (W,H,CH,B)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib as L
@@ -39,10 +37,6 @@ class exact_arithmetic:
         return False
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _chk(t, name):
     if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4):
         raise ValueError(f"{name} must be a contiguous float32 (B,CH,H,W) HIP tensor")
@@ -57,10 +51,10 @@ def _fused_ssim(img, ref, C1=C1_DEFAULT, C2=C2_DEFAULT, train=True):
     B, CH, H, W = img.shape
     m = torch.empty_like(img)
     d = [torch.empty_like(img) if train else None for _ in range(3)]
-    p = [None if t is None else C.c_void_p(t.data_ptr()) for t in d]
+    p = [L.ptr(t) for t in d]
     with torch.cuda.device(img.device):
         L.check(L.load().gsr_ssim_forward(W, H, CH, B, img.data_ptr(), ref.data_ptr(), C1, C2, 1 if train else 0,
-                                          m.data_ptr(), p[0], p[1], p[2], _stream()))
+                                          m.data_ptr(), p[0], p[1], p[2], L.stream()))
     return m, d[0], d[1], d[2]
 
 
@@ -72,7 +66,7 @@ def fused_ssim_bwd(img, ref, dL_dmap, dm_dmu1, dm_dsigma1_sq, dm_dsigma12):
         L.check(L.load().gsr_ssim_backward(W, H, CH, B, img.data_ptr(), ref.data_ptr(),
                                            _chk(dL_dmap.contiguous(), "dL_dmap").data_ptr(), dm_dmu1.data_ptr(),
                                            dm_dsigma1_sq.data_ptr(), dm_dsigma12.data_ptr(), out.data_ptr(),
-                                           _stream()))
+                                           L.stream()))
     return out
 
 
@@ -109,5 +103,5 @@ def l1_ssim_loss(rast, image, target, lambda_dssim: float = 0.2):
     vpix = torch.empty_like(image)
     with torch.cuda.device(image.device):
         L.check(L.load().gsr_loss_l1_ssim(rast._h, image.data_ptr(), target.contiguous().data_ptr(),
-                                          float(lambda_dssim), loss.data_ptr(), vpix.data_ptr(), _stream()))
+                                          float(lambda_dssim), loss.data_ptr(), vpix.data_ptr(), L.stream()))
     return loss, vpix

@@ -23,10 +23,6 @@ NORMAL_CONSISTENCY_WEIGHT = 0.05   # normal_consistency_weight (utils.jl)
 NORMAL_FLATTEN_WEIGHT = 0.005      # this package's default of normal_flatten_weight
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _check_frame(image: torch.Tensor, name: str = "image"):
     if not (image.is_cuda and image.dtype == torch.float32 and image.is_contiguous() and image.dim() == 3
             and image.shape[2] == 8):
@@ -87,7 +83,7 @@ def depth_normal_loss(image: torch.Tensor, camera: Camera, weight: float = NORMA
     with torch.cuda.device(image.device):
         L.check(lib.gsr_normal_loss_forward(W, H, 8, image.data_ptr(), C.byref(cs), float(weight), loss.data_ptr(),
                                             st.data_ptr(), None if wmap is None else wmap.data_ptr(), buf.data_ptr(),
-                                            buf.numel() * buf.element_size(), _stream()))
+                                            buf.numel() * buf.element_size(), L.stream()))
     out = (loss,) + ((wmap,) if weights else ()) + ((st,) if stats else ())
     return out[0] if len(out) == 1 else out
 
@@ -115,7 +111,7 @@ def depth_normal_loss_backward_(image: torch.Tensor, camera: Camera, vpixels: to
         buf = _check_scratch(scratch, nb, image.device)
     with torch.cuda.device(image.device):
         L.check(lib.gsr_normal_loss_backward(W, H, 8, image.data_ptr(), C.byref(cs), float(weight), vpixels.data_ptr(),
-                                             buf.data_ptr(), buf.numel() * buf.element_size(), _stream()))
+                                             buf.data_ptr(), buf.numel() * buf.element_size(), L.stream()))
     return vpixels
 
 
@@ -145,7 +141,7 @@ def flatten_loss(scales: torch.Tensor, weight: float = NORMAL_FLATTEN_WEIGHT, vs
     with torch.cuda.device(scales.device):
         L.check(lib.gsr_flatten_loss(n, sd, scales.data_ptr() if n else None, float(weight), loss.data_ptr(),
                                      None if vscales is None or n == 0 else vscales.data_ptr(), buf.data_ptr(),
-                                     buf.numel() * buf.element_size(), _stream()))
+                                     buf.numel() * buf.element_size(), L.stream()))
     return loss
 
 

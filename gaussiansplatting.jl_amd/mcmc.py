@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .densification import PARAMS, GaussianModel, _compose, _ptr, _stream, findall
+from .densification import PARAMS, GaussianModel, _compose, _ptr, findall
 
 f32 = np.float32
 
@@ -108,7 +108,7 @@ def weights(gs: GaussianModel, min_opacity: float = 0.0, log_max_scale: float = 
     q = torch.empty(n, dtype=torch.int32, device=dev)
     dead = torch.empty(n, dtype=torch.uint8, device=dev) if with_dead else None
     L.check(L.load().gsr_mcmc_weights(n, _sd(gs), _ptr(gs.opacities), _ptr(gs.scales), float(min_opacity), float(log_max_scale),
-                                      _ptr(q), _ptr(dead), _stream()))
+                                      _ptr(q), _ptr(dead), L.stream()))
     return q, dead
 
 
@@ -128,7 +128,7 @@ def multinomial_sample(q: torch.Tensor, m: int, seed: int, strategy: MCMCStrateg
     words = max(nb // 8, 1)
     scratch = strategy.sample_scratch(words, dev) if strategy is not None else torch.empty(words, dtype=torch.int64, device=dev)
     L.check(lib.gsr_mcmc_sample(n, _ptr(q), int(m), int(seed) & 0xFFFFFFFF, _ptr(sampled), _ptr(counts), total.data_ptr(),
-                                scratch.data_ptr(), scratch.numel() * 8, _stream()))
+                                scratch.data_ptr(), scratch.numel() * 8, L.stream()))
     return sampled, counts, total
 
 
@@ -140,7 +140,7 @@ def relocation_params(strategy: MCMCStrategy, o: torch.Tensor, ratio: torch.Tens
         raise ValueError("o (float32) and ratio (int32) must be contiguous HIP device tensors of one length (no CPU path)")
     new_o, coeff = torch.empty_like(o), torch.empty_like(o)
     L.check(L.load().gsr_mcmc_relocation_params(o.numel(), _ptr(o), _ptr(ratio), _ptr(strategy.binoms_on(o.device)), strategy.n_max,
-                                                strategy.min_opacity, _ptr(new_o), _ptr(coeff), _stream()))
+                                                strategy.min_opacity, _ptr(new_o), _ptr(coeff), L.stream()))
     return new_o, coeff
 
 
@@ -148,7 +148,7 @@ def split_sampled(strategy: MCMCStrategy, gs: GaussianModel, counts: torch.Tenso
     """split_sampled! (mcmc.jl:232-260): Eq. 9 in place on every row with counts > 0, as if it were split into 1 + counts
     identical copies."""
     L.check(L.load().gsr_mcmc_split_sampled(len(gs), _sd(gs), _ptr(counts), _ptr(strategy.binoms_on(gs.points.device)), strategy.n_max,
-                                            strategy.min_opacity, _ptr(gs.opacities), _ptr(gs.scales), _stream()))
+                                            strategy.min_opacity, _ptr(gs.opacities), _ptr(gs.scales), L.stream()))
 
 
 def _relocate_rows(gs: GaussianModel, optimizers, dead_idx: torch.Tensor, sampled: torch.Tensor):
@@ -164,7 +164,7 @@ def _relocate_rows(gs: GaussianModel, optimizers, dead_idx: torch.Tensor, sample
     if gs.ids is not None:   # mcmc.jl:162
         groups.append(L.ComposeGroup(None, gs.ids.data_ptr(), 1, 0))
     arr = (L.ComposeGroup * len(groups))(*groups)
-    L.check(L.load().gsr_mcmc_relocate_rows(arr, len(groups), len(gs), _ptr(dead_idx), _ptr(sampled), dead_idx.numel(), _stream()))
+    L.check(L.load().gsr_mcmc_relocate_rows(arr, len(groups), len(gs), _ptr(dead_idx), _ptr(sampled), dead_idx.numel(), L.stream()))
 
 
 def relocate_gaussians(strategy: MCMCStrategy, gs: GaussianModel, optimizers, extent: float, seed=None) -> int:
@@ -221,7 +221,7 @@ def inject_noise(strategy: MCMCStrategy, gs: GaussianModel, points_lr: float, ex
     max_kick = f32(0.5) * f32(strategy.max_scale) * f32(extent)
     lr = f32(points_lr) * f32(strategy.noise_lr)
     L.check(L.load().gsr_mcmc_inject_noise(n, _sd(gs), _ptr(gs.points), _ptr(gs.opacities), _ptr(gs.scales), _ptr(gs.rotations),
-                                           float(lr), float(max_kick), int(seed) & 0xFFFFFFFF, _stream()))
+                                           float(lr), float(max_kick), int(seed) & 0xFFFFFFFF, L.stream()))
 
 
 def regularization_loss(strategy: MCMCStrategy, opacities: torch.Tensor, scales: torch.Tensor, vopacities: torch.Tensor = None,
@@ -247,7 +247,7 @@ def regularization_loss(strategy: MCMCStrategy, opacities: torch.Tensor, scales:
     loss = torch.empty((), dtype=torch.float32, device=opacities.device)
     L.check(lib.gsr_mcmc_regularization(n, int(scales.shape[1]), _ptr(opacities), _ptr(scales), strategy.opacity_reg,
                                         strategy.scale_reg, loss.data_ptr(), _ptr(vopacities), _ptr(vscales), scratch.data_ptr(),
-                                        scratch.numel(), _stream()))
+                                        scratch.numel(), L.stream()))
     return loss
 
 

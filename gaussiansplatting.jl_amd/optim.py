@@ -16,10 +16,6 @@ import torch
 from . import _lib as L
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class Adam:
     def __init__(self, theta: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
         if not theta.is_cuda or theta.dtype != torch.float32:
@@ -70,7 +66,7 @@ def step_all(opts: Sequence[Adam], thetas: Sequence[torch.Tensor], grads: Sequen
         groups[i] = o._group(t, g, o.current_step + (1 if t.numel() else 0))
         if t.numel():
             bump.append(o)
-    L.check(L.load().gsr_adam_step(groups, len(opts), b1, b2, eps, _stream()))
+    L.check(L.load().gsr_adam_step(groups, len(opts), b1, b2, eps, L.stream()))
     for o in bump:
         o.current_step += 1
 
@@ -109,7 +105,7 @@ def trainer_tail_step(opts, raw, grads, shs, opacities_act, scales_act):
     tg = L.TailGrads(grads["vmeans"].data_ptr(), grads["vshs"].data_ptr(), grads["vopacities"].data_ptr(),
                      grads["vscales"].data_ptr(), grads["vrot"].data_ptr())
     L.check(L.load().gsr_trainer_tail_step(n, k_rest, sd, C.byref(tg), th, mu, nu, lr, st, o0.beta1, o0.beta2, o0.eps,
-                                           shs.data_ptr(), opacities_act.data_ptr(), scales_act.data_ptr(), _stream()))
+                                           shs.data_ptr(), opacities_act.data_ptr(), scales_act.data_ptr(), L.stream()))
     for o in bump:  # committed only after validation and a successful launch
         o.current_step += 1
 
@@ -172,7 +168,7 @@ def sh_views_tail_step(opts, raw, small_grads, vcolors_all, camera_centers, sh_d
     tg = L.TailGrads(small_grads["vmeans"].data_ptr(), None, small_grads["vopacities"].data_ptr(),
                      small_grads["vscales"].data_ptr(), small_grads["vrot"].data_ptr())
     L.check(L.load().gsr_sh_grad_from_views_tail(n, K, int(sh_degree), V, camera_centers.data_ptr(), vcolors_all.data_ptr(),
-                                                 C.byref(tg), C.byref(st), _stream()))
+                                                 C.byref(tg), C.byref(st), L.stream()))
     for o in bump:  # committed only after validation and a successful launch
         o.current_step += 1
 
@@ -197,6 +193,6 @@ def nonfinite_gradient_report(names, grads, n: int):
     if dev is None:
         return {}
     out = torch.empty((2, k), dtype=torch.int32, device=dev)
-    L.check(L.load().gsr_count_nonfinite(arr, rw, k, n, out[0].data_ptr(), out[1].data_ptr(), _stream()))
+    L.check(L.load().gsr_count_nonfinite(arr, rw, k, n, out[0].data_ptr(), out[1].data_ptr(), L.stream()))
     host = out.cpu().numpy().astype("uint32")
     return {names[i]: (int(host[0, i]), int(host[1, i])) for i in range(k) if host[0, i] > 0}

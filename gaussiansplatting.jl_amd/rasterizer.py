@@ -30,14 +30,6 @@ def n_color_features(mode: str) -> int:
     return L.MODES[mode]
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _chk(t: torch.Tensor, name: str, shape=None):
     if not t.is_cuda:
         raise ValueError(f"{name} must be a HIP device tensor (no CPU path)")
@@ -190,7 +182,7 @@ class GaussianRasterizer:
                 raise ValueError("statistics must be contiguous HIP tensors of N elements (int32 / float32 / float32)")
         with torch.cuda.device(self.device):
             L.check(self._lib.gsr_update_stats(self._h, max_radii.data_ptr(), accum_grad_means_2d.data_ptr(),
-                                               denom.data_ptr(), _stream()))
+                                               denom.data_ptr(), L.stream()))
 
     # ---- per-stage kernel timing (HIP events on the launch stream) ----
     def profile(self, on: bool = True, stages=None):
@@ -234,7 +226,7 @@ class GaussianRasterizer:
         # and a second HIP runtime must not be opened next to torch's)
         out = torch.empty(shape, dtype=dtype, device=self.device)
         with torch.cuda.device(self.device):
-            L.check(self._lib.gsr_copy_buffer(self._h, which, out.data_ptr(), n * itemsize, _stream()))
+            L.check(self._lib.gsr_copy_buffer(self._h, which, out.data_ptr(), n * itemsize, L.stream()))
         return out
 
     @property
@@ -340,7 +332,7 @@ class GaussianRasterizer:
                     None if uncertainties is None else uncertainties.data_ptr(),
                     self.gstate._radii.data_ptr() if inp.n else None, L.FORWARD_ONLY if forward_only else 0, 0)
         with torch.cuda.device(self.device):
-            L.check(self._lib.gsr_forward(self._h, C.byref(inp), C.byref(cs), _ptr(img), C.byref(aux), _stream(),
+            L.check(self._lib.gsr_forward(self._h, C.byref(inp), C.byref(cs), L.ptr(img), C.byref(aux), L.stream(),
                                           C.byref(self.stats)))
         self._n = inp.n
         return img
@@ -394,7 +386,7 @@ class GaussianRasterizer:
                     self.gstate._grad_means_2d.data_ptr() if n else None, int(forward_generation),
                     L.GRADS_COLOR_COTANGENT if color_cotangent else 0, 0)
         with torch.cuda.device(self.device):
-            L.check(self._lib.gsr_backward(self._h, C.byref(inp), C.byref(cs), _ptr(vpixels), C.byref(g), _stream()))
+            L.check(self._lib.gsr_backward(self._h, C.byref(inp), C.byref(cs), L.ptr(vpixels), C.byref(g), L.stream()))
         return vmeans, vshs, vopac, vscales, vrot, vR, vt
 
 
@@ -411,8 +403,8 @@ class GaussianRasterizer:
         tail_state.forward_generation = int(forward_generation)
         tail_state.flags = L.GRADS_COLOR_COTANGENT if color_cotangent else 0   # (see backward_raw)
         with torch.cuda.device(self.device):
-            L.check(self._lib.gsr_backward_trainer_tail(self._h, C.byref(inp), C.byref(cs), _ptr(vpixels),
-                                                        C.byref(tail_state), _stream()))
+            L.check(self._lib.gsr_backward_trainer_tail(self._h, C.byref(inp), C.byref(cs), L.ptr(vpixels),
+                                                        C.byref(tail_state), L.stream()))
 
 
 def sh_grad_from_views(means_3d, vcolors_all, camera_centers, n_coeffs: int, sh_degree: int, out=None):
@@ -425,8 +417,8 @@ def sh_grad_from_views(means_3d, vcolors_all, camera_centers, n_coeffs: int, sh_
         out = torch.empty((n, n_coeffs, 3), device=means_3d.device, dtype=torch.float32)
     else:
         _chk(out, "out", (n, n_coeffs, 3))
-    L.check(L.load().gsr_sh_grad_from_views(n, int(n_coeffs), int(sh_degree), V, _ptr(camera_centers), _ptr(means_3d),
-                                            _ptr(vcolors_all), _ptr(out), _stream()))
+    L.check(L.load().gsr_sh_grad_from_views(n, int(n_coeffs), int(sh_degree), V, L.ptr(camera_centers), L.ptr(means_3d),
+                                            L.ptr(vcolors_all), L.ptr(out), L.stream()))
     return out
 
 
@@ -444,8 +436,8 @@ def prologue_forward(sh_color, sh_remainder, opacities, scales):
     shs = torch.empty((n, 1 + k_rest, 3), device=sh_color.device, dtype=torch.float32)
     oa = torch.empty((n, 1), device=sh_color.device, dtype=torch.float32)
     sa = torch.empty((n, 3), device=sh_color.device, dtype=torch.float32)
-    L.check(L.load().gsr_prologue_forward(n, k_rest, sd, _ptr(sh_color), _ptr(sh_remainder) if k_rest else None,
-                                          _ptr(opacities), _ptr(scales), _ptr(shs), _ptr(oa), _ptr(sa), _stream()))
+    L.check(L.load().gsr_prologue_forward(n, k_rest, sd, L.ptr(sh_color), L.ptr(sh_remainder) if k_rest else None,
+                                          L.ptr(opacities), L.ptr(scales), L.ptr(shs), L.ptr(oa), L.ptr(sa), L.stream()))
     return shs, oa, sa
 
 
@@ -460,9 +452,9 @@ def prologue_backward(opacities_act, scales_act, vshs, vopacities_act, vscales_a
     for t, nm in ((opacities_act, "opacities_act"), (scales_act, "scales_act"), (vshs, "vshs"),
                   (vopacities_act, "vopacities_act"), (vscales_act, "vscales_act")):
         _chk(t, nm)
-    L.check(L.load().gsr_prologue_backward(n, K - 1, scale_dims, _ptr(opacities_act), _ptr(scales_act), _ptr(vshs),
-                                           _ptr(vopacities_act), _ptr(vscales_act), _ptr(vdc),
-                                           _ptr(vrest) if K > 1 else None, _ptr(vo), _ptr(vs), _stream()))
+    L.check(L.load().gsr_prologue_backward(n, K - 1, scale_dims, L.ptr(opacities_act), L.ptr(scales_act), L.ptr(vshs),
+                                           L.ptr(vopacities_act), L.ptr(vscales_act), L.ptr(vdc),
+                                           L.ptr(vrest) if K > 1 else None, L.ptr(vo), L.ptr(vs), L.stream()))
     return vdc, vrest, vo, vs
 
 

@@ -4,6 +4,12 @@ import numpy as np
 import torch
 
 
+def stream():
+    """The package's own stream argument (pkg._lib.stream): the current torch stream as a hipStream_t."""
+    import gsr_pkg
+    return gsr_pkg.load()._lib.stream()
+
+
 def dev(a, dtype=torch.float32):
     return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda().contiguous()
 

@@ -53,7 +53,7 @@ import torch
 
 import geometry_torch as gt
 from guarded import placements
-from test_gpu_poisoned_buffers import _stream
+from hip_helpers import stream as _stream
 
 pytestmark = pytest.mark.gpu
 

@@ -545,7 +545,8 @@ def test_noise_stays_finite_and_handles_empty_models(pkg):
 # ---------------------------------------------------------------------------------------------------------------------
 # 7. regulariser
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n,sd", [(2 * 2048 // 3 + 701, 3), (1500, 1), (5, 3)])
+# (200_003, 3): 3n / 2048 = 293 partials, more than the 256 threads of the final pass, so its strided loop adds a second term
+@pytest.mark.parametrize("n,sd", [(2 * 2048 // 3 + 701, 3), (1500, 1), (5, 3), (200_003, 3)])
 def test_regularization_loss_and_gradients(pkg, n, sd):
     M, R = pkg.mcmc, pkg.rasterizer
     st_o, st_d = mr.Strategy(opacity_reg=0.01, scale_reg=0.02), M.MCMCStrategy(opacity_reg=0.01, scale_reg=0.02)

@@ -38,6 +38,7 @@ import pytest
 import torch
 
 from hip_helpers import compare_backward, compare_forward, dev, frac_bad, rel_l2
+from hip_helpers import stream as _stream
 
 pytestmark = pytest.mark.gpu
 
@@ -139,10 +140,6 @@ def assert_same(clean, other, fill):
                 same_bits(x, y, f"{k}[{i}] [{fill}]")
         else:
             assert v == other[k], (k, fill)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class Scene(types.SimpleNamespace):

@@ -8,7 +8,6 @@ test_default_ssim_arithmetic_vs_oracle_at_fp32_tolerance: 1e-5 on the map, 2e-5 
 pullback; test_loss_head_vs_oracle) and of tests/test_gpu_poisoned_buffers.py (poisoned outputs and scratch equal the clean
 run bit for bit)."""
 import contextlib
-import ctypes as C
 import os
 
 import numpy as np
@@ -16,6 +15,7 @@ import pytest
 import torch
 
 from hip_helpers import dev, frac_bad, rel_l2
+from hip_helpers import stream as _stream
 
 pytestmark = pytest.mark.gpu
 
@@ -108,10 +108,6 @@ def same_bits(a, b, what):
     if not torch.equal(a, b):
         d = (a != b).reshape(-1).nonzero()
         raise AssertionError(f"{what}: {d.numel()} of {a.numel()} words differ from the clean run (first at {int(d[0])})")
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 @pytest.mark.parametrize("exact", [False, True])
