@@ -143,15 +143,46 @@ def read_adam(opt, ckpt: Checkpoint, prefix: str, numel=None) -> None:
     opt.current_step = ckpt.read_scalar(f"{prefix}.current_step")
 
 
+# ---- SkyDome (sky_dome.jl:322-333); `sky` has `gaussians` (a ply.GaussianModel), `optimizer` (one moment pair), `radius` ----
+def write_sky(tensors, meta, prefix: str, sky) -> None:
+    write_gaussians(tensors, meta, f"{prefix}.gaussians", sky.gaussians)
+    write_adam(tensors, meta, f"{prefix}.optimizer", sky.optimizer, shape=tuple(_host(sky.gaussians.features_dc).shape))
+    meta[f"{prefix}.radius"] = repr(float(np.float32(sky.radius)))
+
+
+def read_sky(sky, ckpt: Checkpoint, prefix: str) -> None:
+    """In place, as `read_state!(sky, ckpt, prefix)`: the model's arrays and the colour optimizer; the dome keeps the radius
+    (and the rasterizer) it was built with.  The file's dome must have the trainer's size."""
+    g = read_gaussians(ckpt, f"{prefix}.gaussians")
+    cur = sky.gaussians
+    n = int(_host(cur.points).shape[0])
+    if g.n != n:
+        raise ValueError(f"{prefix}.gaussians: {g.n} Gaussians in the file, the trainer's dome has {n}")
+    for name in ("points", "features_dc", "features_rest", "scales", "rotations", "opacities"):
+        dst, src = getattr(cur, name), np.ascontiguousarray(getattr(g, name), dtype=np.float32)
+        if tuple(dst.shape) != src.shape:
+            raise ValueError(f"{prefix}.gaussians.{name}: file shape {src.shape[::-1]} does not match the dome's {tuple(dst.shape)[::-1]}")
+        if hasattr(dst, "copy_"):
+            import torch
+            dst.copy_(torch.from_numpy(src))
+        else:
+            np.copyto(dst, src)
+    read_adam(sky.optimizer, ckpt, f"{prefix}.optimizer", numel=int(g.features_dc.size))
+    if hasattr(sky, "_refresh_activations"):
+        sky._refresh_activations()
+
+
 def save_state(filename: str, gaussians, optimizers: Dict[str, object], step: int, strategy=None,
-               extra_meta: Optional[Dict[str, str]] = None, bilateral_grid=None) -> None:
+               extra_meta: Optional[Dict[str, str]] = None, bilateral_grid=None, sky=None) -> None:
     """The Gaussian + optimizer part of `save_state` (training.jl:418-445).  `strategy` (a densification.DefaultStrategy):
     its split-noise position is added as two metadata scalars (`strategy.split_seed_base`, `strategy.split_rounds`; an
     mcmc.MCMCStrategy: `strategy.seed_base`, `strategy.sample_rounds`, `strategy.noise_steps` — its `state_dict()`) —
     keys the reference's reader never asks for, so the file stays a valid reference checkpoint; the reference itself draws
     split noise from the backend's RNG and has nothing to save there (densification.jl:128).
     `extra_meta`: more string scalars of the same kind — e.g. {"gsr.ssim_precision": "fast"}: the arithmetic of the loss head the
-    run trained with (the library default is the contracted build, not bit-identical to the exact twin)."""
+    run trained with (the library default is the contracted build, not bit-identical to the exact twin).
+    `sky` (a sky_dome.SkyDome): the reference's `sky.*` group (sky_dome.jl:322-327) — `sky.gaussians.*`, the colour
+    optimizer `sky.optimizer.{mu.1,nu.1,n_moments,current_step}` and the scalar `sky.radius`."""
     tensors, meta = {}, {}
     write_gaussians(tensors, meta, "gaussians", gaussians)
     for name in OPTIMIZER_NAMES:
@@ -172,16 +203,20 @@ def save_state(filename: str, gaussians, optimizers: Dict[str, object], step: in
         grids = _host(bilateral_grid.grids)
         tensors["bilateral.grids"] = grids
         write_adam(tensors, meta, "bilateral.opt", bilateral_grid.optimizer, shape=grids.shape)
+    if sky is not None:
+        write_sky(tensors, meta, "sky", sky)
     for k, v in (extra_meta or {}).items():
         meta[str(k)] = str(v)
     save_checkpoint(filename, tensors, meta)
 
 
-def load_state(filename: str, optimizers: Dict[str, object], strategy=None, bilateral_grid=None):
+def load_state(filename: str, optimizers: Dict[str, object], strategy=None, bilateral_grid=None, sky=None):
     """Counterpart (training.jl:447-470): returns (GaussianModel, step); optimizers are filled in place, and so is
     `strategy`'s split-noise position when the file carries one.  `bilateral_grid` (a bilateral_grid.BilateralGrid): its
     grids and optimizer are restored in place when the file has them (training.jl:452-459, `haskey` semantics: a file
-    without them leaves the grids as they are)."""
+    without them leaves the grids as they are).  `sky` (a sky_dome.SkyDome): restored in place when the file has
+    `sky.gaussians.points` (training.jl:463-465, the same semantics: a file without the group leaves the dome as built, and
+    without `sky` the group is ignored)."""
     ckpt = load_checkpoint(filename)
     g = read_gaussians(ckpt, "gaussians")
     for name in OPTIMIZER_NAMES:
@@ -210,4 +245,6 @@ def load_state(filename: str, optimizers: Dict[str, object], strategy=None, bila
                              f"trainer's grids (Julia shape {tuple(reversed(tuple(cur.shape)))})")
         cur.copy_(torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32)))
         read_adam(bilateral_grid.optimizer, ckpt, "bilateral.opt", numel=int(host.size))
+    if sky is not None and "sky.gaussians.points" in ckpt:
+        read_sky(sky, ckpt, "sky")
     return g, ckpt.read_scalar("step")

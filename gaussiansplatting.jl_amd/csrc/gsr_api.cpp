@@ -1732,6 +1732,47 @@ int gsr_depth_loss_backward(int32_t W, int32_t H, int32_t C, const float* image,
     return GSR_OK;
 }
 
+// ---- sky dome: composite, sky-mask loss and their pullback (sky.hip; src/sky_dome.jl) ----
+namespace {
+int check_sky_args(int32_t W, int32_t H, int32_t C, const void* image, const void* sky_rgb) {
+    if (W < 1 || H < 1 || (int64_t)W * H > 0x7FFFFFFF / 8) return fail(GSR_E_INVALID_ARG, "image size %d x %d", W, H);
+    if (C != 5 && C != 8)
+        return fail(GSR_E_INVALID_ARG, "C = %d: the sky composite reads the alpha row of a :rgbd (5) or :rgbdn (8) frame", C);
+    if (!image || !sky_rgb) return fail(GSR_E_INVALID_ARG, "null array");
+    return GSR_OK;
+}
+}  // namespace
+
+size_t gsr_sky_scratch_bytes(int32_t W, int32_t H) {
+    if (W < 1 || H < 1) return 0;
+    return gsr_sky_scratch_size(W, H);
+}
+
+int gsr_sky_composite_forward(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb, const float* sky_weight,
+                              float loss_weight, float* out, float* loss_out, void* scratch, void* stream) {
+    int rc;
+    if ((rc = check_sky_args(W, H, C, image, sky_rgb))) return rc;
+    if (!out) return fail(GSR_E_INVALID_ARG, "null array");
+    if (sky_weight && (!loss_out || !scratch)) return fail(GSR_E_INVALID_ARG, "a sky mask needs loss_out and scratch");
+    if (sky_weight && (uintptr_t)scratch % 8) return fail(GSR_E_INVALID_ARG, "scratch must be 8-byte aligned");
+    gsr_launch_sky_composite_fwd((hipStream_t)stream, W, H, C, image, sky_rgb, sky_weight, loss_weight, out, loss_out, scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_sky_composite_backward(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb, const float* sky_weight,
+                               float loss_weight, float* vpixels, float* vsky, const void* scratch, void* stream) {
+    int rc;
+    if ((rc = check_sky_args(W, H, C, image, sky_rgb))) return rc;
+    if (!vpixels || !vsky) return fail(GSR_E_INVALID_ARG, "null array");
+    if (image == vpixels) return fail(GSR_E_INVALID_ARG, "vpixels must not be the image");
+    if (sky_weight && !scratch) return fail(GSR_E_INVALID_ARG, "a sky mask needs the scratch its forward filled");
+    if (sky_weight && (uintptr_t)scratch % 8) return fail(GSR_E_INVALID_ARG, "scratch must be 8-byte aligned");
+    gsr_launch_sky_composite_bwd((hipStream_t)stream, W, H, C, image, sky_rgb, sky_weight, loss_weight, vpixels, vsky, scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
 int gsr_densify_grad_mean(int64_t n, const float* accum, const float* denom, float* grad_out, void* stream) {
     if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
     if (n == 0) return GSR_OK;

@@ -297,3 +297,10 @@ void gsr_launch_depth_loss_fwd(hipStream_t s, int W, int H, int C, const float* 
                                float* half_band_out, uint8_t* flags_out, void* scratch);
 void gsr_launch_depth_loss_bwd(hipStream_t s, int W, int H, int C, const float* image, float lambda_grad, float weight,
                                float* vpixels, const void* scratch);
+
+// ---- sky.hip (compiled with -ffp-contract=off): sky-dome composite, sky-mask loss and their pullback ----
+size_t gsr_sky_scratch_size(int W, int H);
+void gsr_launch_sky_composite_fwd(hipStream_t s, int W, int H, int C, const float* image, const float* sky_rgb,
+                                  const float* sky_weight, float loss_weight, float* out, float* loss_out, void* scratch);
+void gsr_launch_sky_composite_bwd(hipStream_t s, int W, int H, int C, const float* image, const float* sky_rgb,
+                                  const float* sky_weight, float loss_weight, float* vpixels, float* vsky, const void* scratch);

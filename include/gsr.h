@@ -720,6 +720,42 @@ GSR_API int gsr_depth_loss_backward(int32_t W, int32_t H, int32_t C, const float
                                     const gsr_depth_anchor* anchor, float qstep, float lambda_grad, float weight, float* vpixels,
                                     const void* scratch, size_t scratch_bytes, void* stream);
 
+/* Sky dome, the per-pixel part (src/sky_dome.jl; switched on by `use_sky_dome` / `use_sky_loss`, used by `step!`,
+ * training.jl:593-598,634-639,673-676,721-725, and by `validate`, :512-516).  The dome itself — a frozen shell of Gaussians
+ * with trainable colours — is rendered by a second, independent :rgb handle (gsr_create with far_plane = 4·radius;
+ * sky_dome.jl:144,186-195); these entry points do the work the step adds per pixel.  New functions, no struct change:
+ * GSR_ABI_VERSION stays.  `image` is the scene's frame (C,W,H), C = 5 (:rgbd) or 8 (:rgbdn), rendered over a ZERO background
+ * (training.jl:596): channels 0..2 rgb, 4 alpha — the raw channel, never clamped (sky_dome.jl:306-309).  C = 3 is
+ * GSR_E_INVALID_ARG: :rgb has no alpha row (sky_dome.jl:221, training.jl:349).  `sky_rgb` is the dome's frame (3,W,H),
+ * `sky_weight` the (W,H) sky mask in [0, 1] or NULL.  All array pointers device; no float atomics: every result is run-to-run
+ * bit-identical, and every argument is checked before the device is touched.
+ *
+ * gsr_sky_scratch_bytes       : bytes of `scratch` for a W x H frame (16 + 16 per 1024 pixels); 8-byte aligned.
+ * gsr_sky_composite_forward   : `composite_sky` (sky_dome.jl:246-250): out[0..2] = image[0..2] + (1 - alpha) · sky_rgb (a product,
+ *                               then a sum, per channel).  `out` (C,W,H) may be `image` itself — the in-place `composite_sky!`
+ *                               (:217-228); otherwise channels >= 3 are copied, so `out` is a whole frame.  With `sky_weight`
+ *                               the same pass also gives `sky_opacity_loss` (:315-320): *loss_out = loss_weight · Σ w·alpha² /
+ *                               max(Σw, 1), sums in double in a fixed order, and leaves 1 / max(Σw, 1) in scratch[0] for the
+ *                               backward; a mask needs `loss_out` and `scratch`.  Without a mask neither is touched (both may
+ *                               be NULL).  A mask of zeros gives exactly 0.
+ * gsr_sky_composite_backward  : given `vpixels` (C,W,H) whose channels 0..2 hold the cotangent g of the composite (the loss
+ *                               head's output; channels >= 3 hold whatever other terms added already): vsky (3,W,H) =
+ *                               (1 - alpha) · g, and ADDS -(g · sky_rgb) [+ loss_weight · 2·w·alpha / max(Σw, 1) with a mask] onto
+ *                               channel 4 of vpixels as ONE fp32 add; g · sky = (g0·s0 + g1·s1) + g2·s2, the mask term is
+ *                               ((2·w)·alpha) · (loss_weight · scratch[0]), and the sum added is (-(g · sky)) + the mask term.
+ *                               Channels 0..3 and >= 5 are not written (∂composite/∂image = 1).  `scratch` is the one the
+ *                               forward filled for the same image and mask (NULL without a mask).  `image` is the SCENE frame,
+ *                               not the composite, unless the composite was made in place (alpha is the same in both).
+ *                               vpixels must not be the image.  A vpixels this was added onto must NOT go to gsr_backward
+ *                               with GSR_GRADS_COLOR_COTANGENT. */
+GSR_API size_t gsr_sky_scratch_bytes(int32_t W, int32_t H);
+GSR_API int gsr_sky_composite_forward(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb,
+                                      const float* sky_weight, float loss_weight, float* out, float* loss_out, void* scratch,
+                                      void* stream);
+GSR_API int gsr_sky_composite_backward(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb,
+                                       const float* sky_weight, float loss_weight, float* vpixels, float* vsky,
+                                       const void* scratch, void* stream);
+
 /* The MCMC densification strategy of the reference on the device (src/mcmc.jl, `strategy = :mcmc`, src/strategy.jl:16): the
  * number of Gaussians only grows (up to max_cap), dead Gaussians are relocated onto alive ones sampled ∝ opacity with the
  * Eq. 9 opacity / scale correction, position noise keeps the chain exploring and an L1 on opacity and scale produces the
