@@ -67,11 +67,12 @@ def sh_basis(d, degree):
 
 
 def render_dense(means, shs, opac, scales, rots, cam, sh_degree, background, mode, values_sorted, ranges, radii,
-                 R_w2c=None, t_w2c=None):
+                 R_w2c=None, t_w2c=None, taps=None):
     """Full differentiable float64 model.  Discrete structure (which Gaussian is in
     which tile, in which order; who is culled) is taken from `values_sorted`,
     `ranges`, `radii`; the per-pixel skip/stop decisions are re-derived in float64.
-    Returns image (H,W,C)."""
+    Returns image (H,W,C).  `taps`: a dict that receives the intermediate `m2` (N,2: the
+    projected centres in pixels), so that the caller can `retain_grad()` it."""
     W, H = cam.width, cam.height
     R = torch.as_tensor(cam.R, dtype=DT) if R_w2c is None else R_w2c
     t = torch.as_tensor(cam.t, dtype=DT) if t_w2c is None else t_w2c
@@ -79,6 +80,8 @@ def render_dense(means, shs, opac, scales, rots, cam, sh_degree, background, mod
     Sig = quat_scale_to_cov(rots, scales)
     Sc = R @ Sig @ R.T
     S2, m2 = perspective_projection(pc, Sc, cam.focal, (W, H), cam.principal)
+    if taps is not None:
+        taps["m2"] = m2
     S2 = S2 + cam.blur_eps * torch.eye(2, dtype=DT)
     conic = torch.linalg.inv(S2)
     center = torch.as_tensor(cam.camera_center, dtype=DT)

@@ -24,8 +24,8 @@ import numpy as np
 import pytest
 import torch
 
-import f64_model as fm
 import fuzz_scenes
+from gradient_rows import f64_gradients
 from hip_helpers import HipRun, blend_boundary_pixels
 
 pytestmark = pytest.mark.gpu
@@ -47,15 +47,12 @@ def three_way(pkg, orc, fs, exact_tile_cull=False, grad_precision=None):
                  grad_precision=grad_precision)
     run.forward()
     out = [o.cpu().numpy() for o in run.backward(vp)[:5]]
-    tt = lambda a: torch.tensor(np.asarray(a, np.float64), dtype=DT, requires_grad=True)  # noqa: E731
-    leaves = [tt(fs.means), tt(fs.shs), tt(fs.opac), tt(fs.scales), tt(fs.rots)]
-    img = fm.render_dense(*leaves, fs.cam, fs.deg, np.asarray(fs.bg, np.float32), fs.mode, st.values_sorted, st.ranges, st.radii)
-    (img * torch.tensor(vp, dtype=DT)).sum().backward()
+    f64 = f64_gradients((fs.means, fs.shs, fs.opac, fs.scales, fs.rots), fs.cam, fs.deg, fs.mode, fs.bg, st, vp)
     n = fs.means.shape[0]
     ref = (g.vmeans, g.vshs, g.vopacities, g.vscales, g.vrots)
     res = {}
-    for nm, o, r, leaf in zip(NAMES, out, ref, leaves):
-        res[nm] = tuple(np.asarray(x, np.float64).reshape(n, -1) for x in (r, o, leaf.grad.numpy()))
+    for nm, o, r in zip(NAMES, out, ref):
+        res[nm] = tuple(np.asarray(x, np.float64).reshape(n, -1) for x in (r, o, f64[nm]))
     return res, st
 
 
