@@ -1773,6 +1773,50 @@ int gsr_sky_composite_backward(int32_t W, int32_t H, int32_t C, const float* ima
     return GSR_OK;
 }
 
+// ---- evaluation head: 8-bit SSIM / MSE / PSNR / L1 and the RGB8 export (eval.hip; training.jl:487-532) ----
+namespace {
+int check_eval_frame(int32_t W, int32_t H, int32_t C, const void* image, const void* sky_rgb) {
+    if (W < 1 || H < 1) return fail(GSR_E_INVALID_ARG, "image size %d x %d", W, H);
+    if (C < 3) return fail(GSR_E_INVALID_ARG, "C = %d: a frame has at least the 3 colour channels", C);
+    if (sky_rgb && C < 5) return fail(GSR_E_INVALID_ARG, "C = %d: a sky frame needs the alpha row of a :rgbd / :rgbdn frame (C >= 5)", C);
+    // 32-bit element offsets inside the frame, 32-bit byte offsets inside a row
+    if ((uint64_t)W * (uint64_t)H * (uint64_t)C > 0xFFFFFFFFull || (uint64_t)W * (uint64_t)C * 4 > 0xFFFFFFFFull)
+        return fail(GSR_E_INVALID_ARG, "frame too large: %d x %d x %d is 2^32 elements or more", C, W, H);
+    if (!image) return fail(GSR_E_INVALID_ARG, "null image");
+    return GSR_OK;
+}
+}  // namespace
+
+size_t gsr_eval_scratch_bytes(int32_t W, int32_t H) {
+    if (W < 1 || H < 1) return 0;
+    return gsr_eval_scratch_size(W, H);
+}
+
+int gsr_eval_metrics(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb, const float* target_f32,
+                     const uint8_t* target_u8, int32_t quantize, float* ssim_map, float* out, void* scratch, void* stream) {
+    int rc;
+    if ((rc = check_eval_frame(W, H, C, image, sky_rgb))) return rc;
+    if (!out || !scratch) return fail(GSR_E_INVALID_ARG, "null out or scratch");
+    if ((target_f32 != nullptr) == (target_u8 != nullptr))
+        return fail(GSR_E_INVALID_ARG, "exactly one of target_f32 and target_u8: %s given", target_f32 ? "both" : "neither");
+    if (ssim_map == image) return fail(GSR_E_INVALID_ARG, "ssim_map must not be the image");
+    if ((uintptr_t)scratch % 8) return fail(GSR_E_INVALID_ARG, "scratch must be 8-byte aligned");
+    gsr_launch_eval_metrics((hipStream_t)stream, W, H, C, image, sky_rgb, target_f32, target_u8, quantize != 0, ssim_map, out,
+                            scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_frame_rgb8(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb, int32_t flip_rows,
+                   uint8_t* rgb8_out, void* stream) {
+    int rc;
+    if ((rc = check_eval_frame(W, H, C, image, sky_rgb))) return rc;
+    if (!rgb8_out) return fail(GSR_E_INVALID_ARG, "null rgb8_out");
+    gsr_launch_frame_rgb8((hipStream_t)stream, W, H, C, image, sky_rgb, flip_rows != 0, rgb8_out);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
 int gsr_densify_grad_mean(int64_t n, const float* accum, const float* denom, float* grad_out, void* stream) {
     if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
     if (n == 0) return GSR_OK;

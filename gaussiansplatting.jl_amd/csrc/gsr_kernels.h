@@ -304,3 +304,11 @@ void gsr_launch_sky_composite_fwd(hipStream_t s, int W, int H, int C, const floa
                                   const float* sky_weight, float loss_weight, float* out, float* loss_out, void* scratch);
 void gsr_launch_sky_composite_bwd(hipStream_t s, int W, int H, int C, const float* image, const float* sky_rgb,
                                   const float* sky_weight, float loss_weight, float* vpixels, float* vsky, const void* scratch);
+
+// ---- eval.hip (compiled with -ffp-contract=off): 8-bit SSIM / MSE / PSNR / L1 of a frame, and its RGB8 export ----
+size_t gsr_eval_scratch_size(int W, int H);
+void gsr_launch_eval_metrics(hipStream_t s, int W, int H, int C, const float* image, const float* sky_rgb,
+                             const float* target_f32, const unsigned char* target_u8, int quantize, float* ssim_map, float* out,
+                             void* scratch);
+void gsr_launch_frame_rgb8(hipStream_t s, int W, int H, int C, const float* image, const float* sky_rgb, int flip_rows,
+                           unsigned char* rgb8_out);

@@ -756,6 +756,45 @@ GSR_API int gsr_sky_composite_backward(int32_t W, int32_t H, int32_t C, const fl
                                        const float* sky_weight, float loss_weight, float* vpixels, float* vsky,
                                        const void* scratch, void* stream);
 
+/* The evaluation head: what `validate(trainer; quantize)` (src/training.jl:487-532) computes per test view, and the 8-bit
+ * picture `gl_texture` / `to_image` (src/rasterizer.jl:155-182, scripts/render-views.jl) make of a frame.  New functions, no
+ * struct change: GSR_ABI_VERSION stays.  `image` is the rasterizer's frame (C,W,H), channel fastest, C >= 3: channels 0..2 are
+ * scored; `sky_rgb` (3,W,H) or NULL: when given, C >= 5 and the scored colour is image[c] + (1 - image[4]) · sky_rgb[c], a
+ * product, then a sum (sky_dome.jl:246-250, training.jl:514-517) — the arithmetic of gsr_sky_composite_forward, so scoring
+ * with `sky_rgb` equals scoring that function's output, bit for bit.  One arithmetic: every fp32 operation as written, IEEE
+ * divisions, no contraction (gsr_ssim_precision does not apply).  All array pointers device; every argument is checked
+ * before the device is touched; no float atomics: results are run-to-run bit-identical.
+ *
+ * gsr_eval_scratch_bytes : bytes of `scratch` for a W x H frame (72 per 54 x 32 strip of it); 8-byte aligned; 0 for W, H < 1.
+ * gsr_eval_metrics       : exactly one of `target_f32` — (W,H,3) planar, as gsr_loss_l1_ssim takes it — and `target_u8` —
+ *                          (3,W,H) bytes, channel fastest, as the dataset stores images (dataset.jl:253-260), converted in
+ *                          the loads as (float)u · (1.0f/255.0f) (`Float32.(image) .* (1f0/255f0)`) — is non-NULL; neither
+ *                          needs more alignment than its element size.  quantize != 0 applies `quantize8` (utils.jl:118)
+ *                          after the composite: q(x) = floorf(fminf(fmaxf(x, 0), 1) · 255.0f + 0.5f) · (1.0f/255.0f), each
+ *                          operation its own fp32 operation in that order; ±Inf clamp like any value, NaN is unspecified.
+ *                          `ssim_map` (W,H,3) planar or NULL: the SSIM map of the scored colours, the train = false map of
+ *                          fused_ssim.jl:34-238 (C1 = 0.01², C2 = 0.03², zero padding; symmetric pairs d = 1..5, centre tap
+ *                          last), bit-identical to the CPU oracle; it must not be `image`.  `out`: 4 floats {mean SSIM, MSE
+ *                          (utils.jl:107), PSNR, mean |x - y|} over the 3·W·H scored values.  Per value the map, d = x - y
+ *                          and |d| are fp32, d² is (double)d · (double)d; the sums are double in a fixed order (csrc/eval.hip)
+ *                          and each mean is (float)(Σ / n), rounded once.  PSNR = (float)(-10 · log10(Σd² / n)) in double;
+ *                          the reference evaluates 20f0 · log10(1f0 / sqrt(mse)) on the host in Float32 (utils.jl:109):
+ *                          the two agree to fp32 rounding, and mse = 0 gives +Inf in both.
+ *                          GSR_E_INVALID_ARG: W or H < 1, C < 3, `sky_rgb` with C < 5, a frame of 2^32 elements or more (or
+ *                          a row of 2^32 bytes or more), NULL image / out / scratch, both targets or neither, ssim_map ==
+ *                          image, a scratch that is not 8-byte aligned.
+ * gsr_frame_rgb8         : the 8-bit picture of the same colours: rgb8_out (3,W,H) bytes, channel fastest — the dataset's
+ *                          own layout, so an exported frame can be fed back as `target_u8` — each (uint8) floorf(fminf(fmaxf(
+ *                          x, 0), 1) · 255.0f + 0.5f), the integer inside q (one device function serves both entry
+ *                          points).  flip_rows != 0 reverses the row order (`gl_texture`'s reverse!(…; dims=3)).  No alignment
+ *                          is asked of rgb8_out.  Rejects what gsr_eval_metrics rejects of W, H, C, image and sky_rgb. */
+GSR_API size_t gsr_eval_scratch_bytes(int32_t W, int32_t H);
+GSR_API int gsr_eval_metrics(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb,
+                             const float* target_f32, const uint8_t* target_u8, int32_t quantize, float* ssim_map,
+                             float* out, void* scratch, void* stream);
+GSR_API int gsr_frame_rgb8(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb, int32_t flip_rows,
+                           uint8_t* rgb8_out, void* stream);
+
 /* The MCMC densification strategy of the reference on the device (src/mcmc.jl, `strategy = :mcmc`, src/strategy.jl:16): the
  * number of Gaussians only grows (up to max_cap), dead Gaussians are relocated onto alive ones sampled ∝ opacity with the
  * Eq. 9 opacity / scale correction, position noise keeps the chain exploring and an L1 on opacity and scale produces the

@@ -709,4 +709,37 @@ function mcmc_post_train_step!(strategy, gs, optimizers, seeds; step::Int, exten
     return refining
 end
 
+# ---- the evaluation head (training.jl:487-532 `validate`; include/gsr.h: gsr_eval_*, gsr_frame_rgb8) ----
+
+eval_scratch_bytes(w::Integer, h::Integer) = Int(ccall((:gsr_eval_scratch_bytes, LIB), Csize_t, (Int32, Int32), w, h))
+
+"""
+    eval_metrics!(out, image, target; sky_rgb = nothing, quantize = false, ssim_map = nothing, scratch = nothing)
+
+`out` (4 Float32 on the device) <- (mean SSIM, MSE, PSNR, mean |x - y|) of the rgb channels of `image` (C, W, H) against
+`target`: Float32 (W, H, 3) or UInt8 (3, W, H), as the dataset stores it.  `sky_rgb` (3, W, H) composites the dome behind the
+frame first (`composite_sky`), `quantize` rounds to the 8-bit grid (`quantize8`), `ssim_map` (W, H, 3) receives the map.
+What `validate` accumulates per view (training.jl:514-526), with nothing read back.
+"""
+function eval_metrics!(out, image, target; sky_rgb = nothing, quantize::Bool = false, ssim_map = nothing, scratch = nothing)
+    c, w, h = size(image)
+    scratch === nothing && (scratch = AMDGPU.zeros(UInt8, eval_scratch_bytes(w, h)))
+    t32 = eltype(target) === UInt8 ? nothing : target
+    t8 = eltype(target) === UInt8 ? target : nothing
+    check(ccall((:gsr_eval_metrics, LIB), Cint,
+        (Int32, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{UInt8}, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}, Ptr{Cvoid}),
+        w, h, c, dptr(image), dptr(sky_rgb), dptr(t32), dptr(UInt8, t8), quantize ? 1 : 0, dptr(ssim_map), dptr(out),
+        dptr(Cvoid, scratch), hipstream()))
+    return out
+end
+
+# `gl_texture` / `to_image` (rasterizer.jl:155-182) up to the bytes: rgb8 (3, W, H) UInt8 of the frame's colours
+function frame_rgb8!(rgb8, image; sky_rgb = nothing, flip_rows::Bool = false)
+    c, w, h = size(image)
+    check(ccall((:gsr_frame_rgb8, LIB), Cint,
+        (Int32, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Int32, Ptr{UInt8}, Ptr{Cvoid}),
+        w, h, c, dptr(image), dptr(sky_rgb), flip_rows ? 1 : 0, dptr(UInt8, rgb8), hipstream()))
+    return rgb8
+end
+
 end # module
