@@ -12,12 +12,9 @@
 //   x = quant_level(x) * (1/255)                   with quantize; quant_level(x) = floorf(fminf(fmaxf(x, 0), 1) * 255 + 0.5)
 // and the target y = target_f32 (W,H,3 planar), or (float)target_u8 * (1/255) from the (3,W,H) byte image.
 //
-// Strips, as in ssim.hip: a wave owns 54 output columns (lane = column, 5 halo lanes on each side) of ONE channel and walks
-// down a strip of STRIP_H = 32 rows (+ 5 above and below); a workgroup is the three channel waves of one strip (they read the
-// same lines of the channel-interleaved frame), strips in raster order over blockIdx.x.  Per input row the horizontal 11x1
-// goes through the wave's LDS row, its results enter a ring of 11 rows in registers, and the vertical 1x11 of output row r is
-// taken over the ring when row r + 5 has arrived.  Accumulation order of ssim.hip's exact build (the reference's): symmetric
-// pairs d = 1..5 with weight GAUSS[5 - d], centre tap last, horizontally and vertically; zero padding outside the frame.
+// The strip walk of ssim_strip.h, shared with ssim.hip and in its exact build's arithmetic (SSIM_EXACT at its default of 1):
+// a wave walks ONE channel of a strip of STRIP_H = 32 rows; a workgroup is the three channel waves of one strip (they read
+// the same lines of the channel-interleaved frame), strips in raster order over blockIdx.x.
 //
 // The sums, all in double, in this order:
 //   lane   : per owned pixel, rows ascending:  s_ssim += (double)map;  with d = x - y (fp32):  s_sq += (double)d * (double)d;
@@ -31,53 +28,16 @@
 // reads was written by the scoring launch.
 #include "gsr_kernels.h"
 #include "block_reduce.h"
+#include "ssim_strip.h"
 
 namespace {
 
-constexpr int HALO = 5;
-constexpr int STRIP_W = 64 - 2 * HALO;  // 54 output columns per wave
-constexpr int STRIP_H = 32;             // output rows per wave: fixed, so that the scratch size depends on W and H alone
-constexpr int AHEAD = 3;                // rows requested from memory before the row being filtered
-constexpr int RING = 2 * HALO + 1;
-constexpr int ROW_LDS = 64 + 2 * HALO;
-constexpr int NSUM = 3;                 // Σssim, Σd², Σ|d|
-
-__constant__ float GAUSS[11] = {0.001028380123898387f, 0.0075987582094967365f, 0.036000773310661316f,
-                                0.10936068743467331f,  0.21300552785396576f,   0.26601171493530273f,
-                                0.21300552785396576f,  0.10936068743467331f,   0.036000773310661316f,
-                                0.0075987582094967365f, 0.001028380123898387f};
-
-typedef float v2f __attribute__((ext_vector_type(2)));
+constexpr int STRIP_H = 32;  // output rows per wave: fixed, so that the scratch size depends on W and H alone
+constexpr int NSUM = 3;      // Σssim, Σd², Σ|d|
 
 // The integer level of `quantize8` (utils.jl:118) as a float: THE quantiser of both entry points.  Each operation is its own
 // fp32 operation (the product is rounded before the sum: not rintf, not a float -> integer conversion of x · 255).
 __device__ __forceinline__ float quant_level(float x) { return floorf(fminf(fmaxf(x, 0.0f), 1.0f) * 255.0f + 0.5f); }
-
-// element at byte offset `lane_off` of the row that starts `row` elements into `plane` (offsets inside a frame are 32-bit:
-// the entry points refuse frames of 2^32 elements or more)
-template <class T>
-__device__ __forceinline__ T& at(T* plane, unsigned row, unsigned lane_off) {
-    return *(T*)((char*)(plane + row) + lane_off);
-}
-template <class T>
-__device__ __forceinline__ const T& at(const T* plane, unsigned row, unsigned lane_off) {
-    return *(const T*)((const char*)(plane + row) + lane_off);
-}
-
-__device__ __forceinline__ void wave_sync() {  // a wave's own LDS writes before its other lanes' reads: holds the compiler only
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <class T>
-__device__ __forceinline__ T ring_vertical(const T (&h)[RING], int j) {
-    T a = 0;
-#pragma unroll
-    for (int d = 1; d <= HALO; d++) a += (h[(j + HALO + 1 + RING - d) % RING] + h[(j + HALO + 1 + d) % RING]) * GAUSS[HALO - d];
-    a += h[(j + HALO + 1) % RING] * GAUSS[HALO];
-    return a;
-}
 
 // what one lane loads of one row: untouched until the row is filtered
 template <bool SKY, bool U8>
@@ -97,12 +57,9 @@ __global__ __launch_bounds__(192) void eval_score_kernel(int W, int H, int C, co
     const int x0 = ((int)blockIdx.x % nsx) * STRIP_W, y0 = ((int)blockIdx.x / nsx) * STRIP_H;
     const int rows = min(STRIP_H, H - y0);
     v2f* buf = rowbuf[ch];
-    if (lane < HALO) { buf[lane] = v2f{0.0f, 0.0f}; buf[64 + HALO + lane] = v2f{0.0f, 0.0f}; }
-    const int gx = x0 - HALO + lane, cx = lane + HALO;
-    const bool col_in = gx >= 0 && gx < W;
-    const bool own = lane >= HALO && lane < 64 - HALO && gx < W;
-    const int nrows = rows + 2 * HALO;  // input rows: rr = 0 is frame row y0 - 5
-    const int gxc = min(max(gx, 0), W - 1);
+    if (lane < HALO) clear_halo(lane, buf);
+    const Column col{x0, lane, W};
+    const int nrows = rows + 2 * HALO, gxc = col.gxc();  // input rows: rr = 0 is frame row y0 - 5
     const unsigned io = 4u * (unsigned)(C * gxc), so = 12u * (unsigned)gxc, po = 4u * (unsigned)gxc, uo = 3u * (unsigned)gxc;
     const float* ip = image + ch;
     const float* sp = SKY ? sky + ch : nullptr;
@@ -147,24 +104,9 @@ __global__ __launch_bounds__(192) void eval_score_kernel(int W, int H, int C, co
                 }
                 if (quantize) x = quant_level(x) * (1.0f / 255.0f);
                 const float y = U8 ? (float)r.tb * (1.0f / 255.0f) : r.t;
-                const v2f XY = col_in && gy >= 0 && gy < H ? v2f{x, y} : v2f{0.0f, 0.0f};
-                buf[cx] = XY;
-                wave_sync();
-                v2f m = 0, q = 0;
-                float c = 0;
-#pragma unroll
-                for (int d = 1; d <= HALO; d++) {
-                    const float w = GAUSS[HALO - d];
-                    const v2f L = buf[cx - d], R = buf[cx + d];
-                    m += (L + R) * w;
-                    q += (L * L + R * R) * w;
-                    c += (L.x * L.y + R.x * R.y) * w;
-                }
-                wave_sync();
-                const float wc = GAUSS[HALO];
-                m += XY * wc; q += XY * XY * wc; c += XY.x * XY.y * wc;
-                hm[j] = m; hq[j] = q; hc[j] = c;
-                if (own && rr >= HALO && rr < nrows - HALO) {
+                const v2f XY = col.col_in && gy >= 0 && gy < H ? v2f{x, y} : v2f{0.0f, 0.0f};
+                horizontal_stats(buf, col.cx, XY, hm[j], hq[j], hc[j]);
+                if (col.own && rr >= HALO && rr < nrows - HALO) {
                     const float df = XY.x - XY.y;
                     s_sq += (double)df * (double)df;
                     s_abs += (double)fabsf(df);
@@ -172,14 +114,10 @@ __global__ __launch_bounds__(192) void eval_score_kernel(int W, int H, int C, co
                 if (rr >= 2 * HALO) {  // output row rr - 10 of the strip is complete
                     const v2f om = ring_vertical(hm, j), oq = ring_vertical(hq, j);
                     const float oc = ring_vertical(hc, j);
-                    if (own) {
+                    if (col.own) {
                         const int py = y0 + rr - 2 * HALO;
-                        const float mu1 = om.x, mu2 = om.y;
-                        const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2;
-                        const float sigma1_sq = oq.x - mu1_sq, sigma2_sq = oq.y - mu2_sq, sigma12 = oc - mu1 * mu2;
-                        const float A = mu1_sq + mu2_sq + C1, Bv = sigma1_sq + sigma2_sq + C2;
-                        const float Cv = 2.0f * mu1 * mu2 + C1, Dv = 2.0f * sigma12 + C2;
-                        const float val = (Cv * Dv) / (A * Bv);
+                        const SsimTerms t{om.x, om.y, oq.x, oq.y, oc, C1, C2};
+                        const float val = (t.Cv * t.Dv) / (t.A * t.Bv);
                         if (mp) at(mp, (unsigned)W * (unsigned)py, po) = val;
                         s_ssim += (double)val;
                     }

@@ -2,15 +2,11 @@
 // Reference behaviour: src/fused_ssim.jl:34-371 (kernels), :373-424 (host wrappers),
 // src/training.jl:656,684-694 (L = (1-λ)·L1 + λ·(1 - mean SSIM)); SURVEY.md A.12.
 //
-// Strips, not tiles: one wave owns 54 output columns (lane = column, 5 halo lanes on each side) and walks down a strip of
-// rows.  Per input row the horizontal 11x1 goes through a per-wave LDS row (one 8-byte write, 10 8-byte reads per lane, no
-// workgroup barrier: the waves of a workgroup are independent); its results enter a ring of the last 11 rows held in
-// registers, and the vertical 1x11 of output row r is evaluated over the ring when row r + 5 has arrived.  The statistics
-// travel as float2 pairs ((x, y), (x², y²), (d0, d1)): packed fp32 instructions, two per issue slot.  Rows are requested
-// from memory AHEAD rows before they are filtered.  Accumulation order follows the reference (symmetric pairs d = 1..5 with
-// weight GAUSS[5-d], centre tap last).  One channel plane per wave: grid.z enumerates (channel, batch) planes for the generic
-// entry points, the loss head puts the three channel waves of a strip into one workgroup (they read the same lines of the
-// channel-interleaved image).  The strip height is chosen per launch (ssim_strip_h).  DESIGN.md §4, §4.2.
+// The kernels walk strips (ssim_strip.h: a wave owns 54 output columns and walks down a strip of rows through a per-wave LDS
+// row and a ring of 11 rows in registers; the evaluation head, eval.hip, walks the same way).  One channel plane per wave:
+// grid.z enumerates (channel, batch) planes for the generic entry points, the loss head puts the three channel waves of a
+// strip into one workgroup (they read the same lines of the channel-interleaved image).  The strip height is chosen per
+// launch (ssim_strip_h).  DESIGN.md §4, §4.2.
 //
 // This file is compiled TWICE into the library (csrc/Makefile):
 //   SSIM_EXACT = 1, -ffp-contract=off: every fp32 operation as written, IEEE divisions — the maps are
@@ -21,10 +17,8 @@
 //       parity at the stated fp32 tolerance instead of bit for bit; −46 % VALU instructions per pixel.
 #include "gsr_kernels.h"
 #include "block_reduce.h"
+#include "ssim_strip.h"
 
-#ifndef SSIM_EXACT
-#define SSIM_EXACT 1
-#endif
 #if SSIM_EXACT
 #define SSIM_NAME(x) x##_exact
 #else
@@ -33,25 +27,11 @@
 
 namespace {
 
-constexpr int HALO = 5;
-// The strip shape; the series that chose these values is in DESIGN.md §4.2 and profiles/ssim_strips/knobs.txt
-constexpr int STRIP_W = 64 - 2 * HALO;  // 54 output columns per wave
-constexpr int AHEAD = 3;                // rows requested from memory before the row being filtered
-constexpr int MIN_WAVES = 4;            // waves per SIMD the register allocation has to leave room for
-constexpr int RING = 2 * HALO + 1;      // 11 rows of horizontal results live in registers
-constexpr int LOSS_STRIPS = 1;          // loss head: strips per workgroup (x 3 channel waves); planar entry points: 4 waves
-constexpr int ROW_LDS = 64 + 2 * HALO;  // a wave's row buffer, padded so that the halo lanes read inside it
-
-__constant__ float GAUSS[11] = {0.001028380123898387f, 0.0075987582094967365f, 0.036000773310661316f,
-                                0.10936068743467331f,  0.21300552785396576f,   0.26601171493530273f,
-                                0.21300552785396576f,  0.10936068743467331f,   0.036000773310661316f,
-                                0.0075987582094967365f, 0.001028380123898387f};
-
-typedef float v2f __attribute__((ext_vector_type(2)));  // two statistics per lane: the packed fp32 instructions of gfx950
+constexpr int MIN_WAVES = 4;    // waves per SIMD the register allocation has to leave room for
+constexpr int LOSS_STRIPS = 1;  // loss head: strips per workgroup (x 3 channel waves); planar entry points: 4 waves
 
 // A source hands out a plane (64-bit, once per wave), a row's offset inside it (wave-uniform: scalar arithmetic) and a lane's
-// byte offset inside the row, so that a load is `scalar base + 32-bit lane offset` with no 64-bit lane arithmetic.  Offsets
-// inside a plane are 32-bit: the entry points refuse images of 2^32 elements or more.
+// byte offset inside the row, for at().
 // (W,H,CH,B) planar arrays, x fastest (fused_ssim.jl:27-31)
 struct PlanarSrc {
     const float* img;
@@ -74,16 +54,6 @@ struct RasterSrc {
     __device__ __forceinline__ unsigned xlane(int gx) const { return 4u * (unsigned)(C * gx); }
 };
 
-// element at byte offset `lane_off` of the row that starts `row` elements into `plane`
-template <class T>
-__device__ __forceinline__ T& at(T* plane, unsigned row, unsigned lane_off) {
-    return *(T*)((char*)(plane + row) + lane_off);
-}
-template <class T>
-__device__ __forceinline__ const T& at(const T* plane, unsigned row, unsigned lane_off) {
-    return *(const T*)((const char*)(plane + row) + lane_off);
-}
-
 // A wave's strip.  Workgroups are dealt round-robin to the 8 XCDs (one L2 each).  Neighbouring strips share 10 of 64
 // columns and 10 input rows, so XCD x gets the x-th contiguous eighth of the strip groups (raster order) instead of every
 // 8th group.  Grid: (8 * ceil(groups / 8), 1, planes) with groups = ceil(strips / SPB); a workgroup is NPL * SPB independent
@@ -104,42 +74,7 @@ __device__ __forceinline__ bool strip_of_wave(int W, int H, int strip_h, int wv,
     return true;
 }
 
-// Orders a wave's own LDS writes before its other lanes' reads (and the reads before the next row's writes).  The LDS
-// serves one wave's instructions in order, so this only has to hold the compiler: no instruction, no workgroup barrier.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// a·b + c·d.  The contracted build fuses a·b into the add and rounds c·d, which is what the compiler has made of this
-// expression in the default build since it exists; left to itself it picks the other product when the operands come out
-// of float2 pairs, and the default build's results would move in the last bit (a training run then takes another path).
-__device__ __forceinline__ float sum_of_products(float a, float b, float c, float d) {
-#if SSIM_EXACT
-    return a * b + c * d;
-#else
-    return __builtin_fmaf(a, b, c * d);
-#endif
-}
-
-// 1x11 over the ring of horizontal results, input row in slot j just arrived: output row = slot j - 5, symmetric pairs
-// d = 1..5, centre tap last (the reference's order, fused_ssim.jl:160-190: what keeps the exact build bit-identical to the
-// oracle; scattering each new row into eleven pending outputs is another order).  j is static after the unroll.
-template <class T>
-__device__ __forceinline__ T ring_vertical(const T (&h)[RING], int j) {
-    T a = 0;
-#pragma unroll
-    for (int d = 1; d <= HALO; d++) a += (h[(j + HALO + 1 + RING - d) % RING] + h[(j + HALO + 1 + d) % RING]) * GAUSS[HALO - d];
-    a += h[(j + HALO + 1) % RING] * GAUSS[HALO];
-    return a;
-}
-
 // fused_ssim.jl:34-238.  LOSS: additionally reduce Σ|x-y| and Σssim into one partial pair per wave.
-// Lane = column (gx = x0 - 5 + lane), the wave walks down its strip's rows + 5 above and below.  Per input row: horizontal
-// 11x1 through the wave's LDS row (one 8-byte write, ten 8-byte reads per lane), result into slot `row % 11` of a register ring; when row
-// r + 5 has arrived, output row r is the 1x11 over the ring.  The row loop is unrolled 11 times so that every ring index
-// is static (a `break` in it defeats the unroll and sends the ring to scratch: guard the body instead).
 template <class Src, bool LOSS, int NPL, int SPB>
 __global__ __launch_bounds__(64 * NPL * SPB, MIN_WAVES) void ssim_fwd_kernel(Src src, int W, int H, int strip_h, float C1, float C2, int train,
                                                                  float* __restrict__ ssim_map, float* __restrict__ d0,
@@ -155,20 +90,14 @@ __global__ __launch_bounds__(64 * NPL * SPB, MIN_WAVES) void ssim_fwd_kernel(Src
     }
     const int plane = blockIdx.z * NPL + wv % NPL;
     v2f* buf = rowbuf[wv];
-    if (lane < HALO) { buf[lane] = v2f{0.0f, 0.0f}; buf[64 + HALO + lane] = v2f{0.0f, 0.0f}; }
-    const int gx = st.x0 - HALO + lane, cx = lane + HALO;
-    const bool col_in = gx >= 0 && gx < W;
-    const bool own = lane >= HALO && lane < 64 - HALO && gx < W;  // this lane's column is an output of this strip
-    const int nrows = st.rows + 2 * HALO;                         // input rows: rr = 0 is image row y0 - 5
-    const int gxc = min(max(gx, 0), W - 1);
-    const unsigned xo = src.xlane(gxc), yo = 4u * (unsigned)gxc;
+    if (lane < HALO) clear_halo(lane, buf);
+    const Column col{st.x0, lane, W};
+    const int nrows = st.rows + 2 * HALO;  // input rows: rr = 0 is image row y0 - 5
+    const unsigned xo = src.xlane(col.gxc()), yo = 4u * (unsigned)col.gxc();
     const float* xp = src.xplane(plane);
     const float* yp = src.yplane(plane);
     const size_t po = (size_t)W * H * plane;  // this wave's plane of the planar outputs
-    // Straight-line loads from a clamped address, the value untouched until its row is filtered (rows and columns
-    // outside the image become zeros then): a load under a branch, or a select right behind it, makes
-    // the wave wait for the row it has just requested, and the rows in flight are gone.
-    auto fetch = [&](int rr) {
+    auto fetch = [&](int rr) {  // straight-line, from a clamped address, untouched until the row is filtered (ssim_strip.h)
         const int gyc = min(max(st.y0 - HALO + rr, 0), H - 1);
         return v2f{at(xp, src.xrow(gyc), xo), at(yp, (unsigned)W * (unsigned)gyc, yo)};
     };
@@ -184,37 +113,19 @@ __global__ __launch_bounds__(64 * NPL * SPB, MIN_WAVES) void ssim_fwd_kernel(Src
             const int rr = base + j;
             if (rr < nrows) {
                 const int gy = st.y0 - HALO + rr;
-                const v2f XY = col_in && gy >= 0 && gy < H ? nxt[0] : v2f{0.0f, 0.0f};  // outside the image: zeros
+                const v2f XY = col.col_in && gy >= 0 && gy < H ? nxt[0] : v2f{0.0f, 0.0f};  // outside the image: zeros
 #pragma unroll
                 for (int i = 0; i + 1 < AHEAD; i++) nxt[i] = nxt[i + 1];
                 nxt[AHEAD - 1] = fetch(rr + AHEAD);
-                buf[cx] = XY;
-                wave_sync();
-                v2f m = 0, q = 0;
-                float c = 0;
-#pragma unroll
-                for (int d = 1; d <= HALO; d++) {
-                    const float w = GAUSS[HALO - d];
-                    const v2f L = buf[cx - d], R = buf[cx + d];
-                    m += (L + R) * w;
-                    q += (L * L + R * R) * w;
-                    c += sum_of_products(L.x, L.y, R.x, R.y) * w;
-                }
-                wave_sync();
-                const float wc = GAUSS[HALO];
-                m += XY * wc; q += XY * XY * wc; c += XY.x * XY.y * wc;
-                hm[j] = m; hq[j] = q; hc[j] = c;
-                if (LOSS && own && rr >= HALO && rr < nrows - HALO) l1 += fabsf(XY.x - XY.y);
+                horizontal_stats(buf, col.cx, XY, hm[j], hq[j], hc[j]);
+                if (LOSS && col.own && rr >= HALO && rr < nrows - HALO) l1 += fabsf(XY.x - XY.y);
                 if (rr >= 2 * HALO) {  // output row rr - 10 of the strip is complete
                     const v2f om = ring_vertical(hm, j), oq = ring_vertical(hq, j);
-                    const float o[5] = {om.x, oq.x, om.y, oq.y, ring_vertical(hc, j)};
-                    if (own) {
+                    const float o[5] = {om.x, om.y, oq.x, oq.y, ring_vertical(hc, j)};  // scalars before the branch
+                    if (col.own) {
                         const int py = st.y0 + rr - 2 * HALO;
-                        const float mu1 = o[0], mu2 = o[2];
-                        const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2;
-                        const float sigma1_sq = o[1] - mu1_sq, sigma2_sq = o[3] - mu2_sq, sigma12 = o[4] - mu1 * mu2;
-                        const float A = mu1_sq + mu2_sq + C1, Bv = sigma1_sq + sigma2_sq + C2;
-                        const float Cv = 2.0f * mu1 * mu2 + C1, Dv = 2.0f * sigma12 + C2;
+                        const SsimTerms t{o[0], o[1], o[2], o[3], o[4], C1, C2};
+                        const float mu1 = t.mu1, mu2 = t.mu2, A = t.A, Bv = t.Bv, Cv = t.Cv, Dv = t.Dv;
                         const unsigned orow = (unsigned)W * (unsigned)py;
 #if SSIM_EXACT
                         const float val = (Cv * Dv) / (A * Bv);
@@ -299,16 +210,10 @@ __global__ __launch_bounds__(64 * NPL * SPB, MIN_WAVES) void ssim_bwd_kernel(Src
     const size_t P = (size_t)W * H;
     v2f* b01 = rowbuf01[wv];
     float* b2 = rowbuf2[wv];
-    if (lane < HALO) {
-        b01[lane] = v2f{0.0f, 0.0f}; b2[lane] = 0.0f;
-        b01[64 + HALO + lane] = v2f{0.0f, 0.0f}; b2[64 + HALO + lane] = 0.0f;
-    }
-    const int gx = st.x0 - HALO + lane, cx = lane + HALO;
-    const bool col_in = gx >= 0 && gx < W;
-    const bool own = lane >= HALO && lane < 64 - HALO && gx < W;
-    const int nrows = st.rows + 2 * HALO;
-    const int gxc = min(max(gx, 0), W - 1);
-    const unsigned xo = src.xlane(gxc), yo = 4u * (unsigned)gxc;
+    if (lane < HALO) clear_halo(lane, b01, b2);
+    const Column col{st.x0, lane, W};
+    const int cx = col.cx, nrows = st.rows + 2 * HALO;
+    const unsigned xo = src.xlane(col.gxc()), yo = 4u * (unsigned)col.gxc();
     const float* xp = src.xplane(plane);
     const float* yp = src.yplane(plane);
     const size_t po = P * plane;  // this wave's plane of the planar maps
@@ -336,7 +241,7 @@ __global__ __launch_bounds__(64 * NPL * SPB, MIN_WAVES) void ssim_bwd_kernel(Src
             const int rr = base + j;
             if (rr < nrows) {
                 const int gy = st.y0 - HALO + rr;
-                const bool in = col_in && gy >= 0 && gy < H;  // outside the image: zeros
+                const bool in = col.col_in && gy >= 0 && gy < H;  // outside the image: zeros
                 Row r = nr[0];
                 r.chain = in ? r.chain : 0.0f;
                 r.a01 = (in ? r.a01 : v2f{0.0f, 0.0f}) * r.chain;
@@ -360,14 +265,14 @@ __global__ __launch_bounds__(64 * NPL * SPB, MIN_WAVES) void ssim_bwd_kernel(Src
                 if (rr >= 2 * HALO) {
                     const v2f v01 = ring_vertical(h01, j);
                     const float s[3] = {v01.x, v01.y, ring_vertical(h2, j)};
-                    if (own) {
+                    if (col.own) {
                         const int py = st.y0 + rr - 2 * HALO;
                         const float p1 = r.p1, p2 = r.p2;
                         float g = s[0] + 2.0f * p1 * s[1] + p2 * s[2];
                         if (LOSS) {
                             const float df = p1 - p2;
                             g = g + l1_scale * (df > 0.0f ? 1.0f : (df < 0.0f ? -1.0f : 0.0f));
-                            float* o = &at(out + ch, (unsigned)(outC * W) * (unsigned)py, 4u * (unsigned)(outC * gxc));
+                            float* o = &at(out + ch, (unsigned)(outC * W) * (unsigned)py, 4u * (unsigned)(outC * col.gxc()));
                             o[0] = g;
                             // the loss head only sees features[1:3]: the other channels of vpixels (C > 3) get their zeros
                             // here, from the last colour channel's wave (a launch of its own for them was 17 us in :rgbd mode)

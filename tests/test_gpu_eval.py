@@ -188,10 +188,12 @@ def test_quantiser_on_the_tie_set_as_a_frame(EV):
     assert _within_one_ulp(out[3].item(), float(np.mean(q.astype(np.float64))))
 
 
-@pytest.mark.parametrize("W,H", [(55, 23), (130, 35), (64, 48)])
+@pytest.mark.parametrize("W,H", [(55, 23), (130, 35), (64, 48), (1, 1), (54, 32), (55, 33), (109, 65)])
 def test_cross_check_with_the_loss_head(EV, pkg, W, H):
     """At gsr_ssim_precision(1), no sky, no quantiser: the map is gsr_ssim_forward's exact map bit for bit, and out[0] and
-    out[3] reproduce gsr_loss_l1_ssim's loss (1 - λ) · L1 + λ · (1 - mean SSIM) to its stated 1e-6 absolute."""
+    out[3] reproduce gsr_loss_l1_ssim's loss (1 - λ) · L1 + λ · (1 - mean SSIM) to its stated 1e-6 absolute.  Both kernels walk
+    the strips of csrc/ssim_strip.h and cut them differently (eval.hip: 32 rows; ssim.hip: 8..64 per launch): 54 / 55 columns
+    are one / two strip columns, 32 / 33 and 65 rows one / two and three of eval.hip's strip rows."""
     FS = pkg.fused_ssim
     r = np.random.default_rng(W + H)
     frame = r.uniform(0.0, 1.0, (H, W, 3)).astype(f32)
