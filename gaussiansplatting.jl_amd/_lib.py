@@ -180,7 +180,7 @@ def bind_policy(lib):
     return lib
 
 
-EXPORTS = ["gsr_create", "gsr_destroy", "gsr_release_scene_buffers", "gsr_memory_usage", "gsr_debug_check_guards", "gsr_reserve", "gsr_bins_capacity_after", "gsr_forward",
+EXPORTS = ["gsr_create", "gsr_destroy", "gsr_release_scene_buffers", "gsr_memory_usage", "gsr_debug_check_guards", "gsr_reserve", "gsr_drop_forward", "gsr_bins_capacity_after", "gsr_forward",
            "gsr_backward", "gsr_host_wait_policy", "gsr_buffer", "gsr_copy_buffer", "gsr_ssim_forward", "gsr_ssim_backward", "gsr_loss_l1_ssim",
            "gsr_ssim_precision", "gsr_get_ssim_precision", "gsr_preprocess_form", "gsr_get_preprocess_form",
            "gsr_allreduce_grads", "gsr_last_error_string", "gsr_version", "gsr_abi_version", "gsr_check_abi", "gsr_profile_enable",
@@ -244,6 +244,7 @@ def load():
     lib.gsr_memory_usage.restype = C.c_int64
     lib.gsr_debug_check_guards.argtypes = [vp]  # GSR_DEBUG_GUARD=1 (gsr.h): GSR_E_STATE names a handle buffer written past its end
     lib.gsr_reserve.argtypes = [vp, C.c_int64, C.c_int64]
+    lib.gsr_drop_forward.argtypes = [vp]  # ends the live forward as a reallocating gsr_reserve does (gsr.h)
     bind_policy(lib)
     lib.gsr_forward.argtypes = [vp, C.POINTER(Inputs), C.POINTER(CameraS), vp, C.POINTER(Aux), vp, C.POINTER(Stats)]
     lib.gsr_backward.argtypes = [vp, C.POINTER(Inputs), C.POINTER(CameraS), vp, C.POINTER(Grads), vp]

@@ -323,6 +323,7 @@ struct gsr_handle {
     bool fwd_valid = false, bwd_valid = false;
     bool fwd_only = false;         // the last forward was GSR_FORWARD_ONLY: no stream / ids / row storage behind it
     bool inputs_consumed = false;  // gsr_backward_trainer_tail updated the forward's inputs in place
+    bool dropped_by_reserve = false;  // the forward is not live because gsr_reserve / gsr_drop_forward ended it (for the messages)
     uint64_t generation = 0;             // ordinal of the last gsr_forward (gsr_stats.generation)
     int32_t* radii_cur = nullptr;        // gstate.radii of the last forward: caller's (gsr_aux.radii) or h->radii
     float2* vmean2d_cur = nullptr;       // gstate.∇means_2d of the last backward: caller's (gsr_grads.vmeans2d) or h->vmean2d
@@ -714,6 +715,19 @@ int gsr_destroy(gsr_handle* h) {
     return GSR_OK;
 }
 
+// The handle after its last forward stopped being live (its buffers were released or reallocated, or the caller's state arrays
+// were): no backward, no statistics, and the per-forward buffers of gsr_buffer report 0 bytes — nothing below reads what the
+// forward left.  The policy state, the bins and the loss head's buffers are not part of it.
+static void end_live_forward(gsr_handle* h) {
+    h->fwd_valid = false;
+    h->bwd_valid = false;
+    h->radii_cur = nullptr;
+    h->vmean2d_cur = nullptr;
+    h->last_n = 0;
+    h->last_D = 0;
+    h->last_slots = 0;
+}
+
 int gsr_release_scene_buffers(gsr_handle* h) {
     if (!h) return fail(GSR_E_INVALID_ARG, "null handle");
     DevBuf* scene[] = {&h->geo, &h->gnormal, &h->radii, &h->bsum, &h->bpre, &h->bvis, &h->bins, &h->values_sorted, &h->s0, &h->s1,
@@ -724,12 +738,15 @@ int gsr_release_scene_buffers(gsr_handle* h) {
         int rc = b->release();
         if (rc) return rc;
     }
-    h->fwd_valid = false;
-    h->bwd_valid = false;
-    h->radii_cur = nullptr;
-    h->vmean2d_cur = nullptr;
-    h->last_n = 0;
-    h->last_D = 0;
+    end_live_forward(h);
+    h->dropped_by_reserve = false;
+    return GSR_OK;
+}
+
+int gsr_drop_forward(gsr_handle* h) {
+    if (!h) return fail(GSR_E_INVALID_ARG, "null handle");
+    h->dropped_by_reserve = h->dropped_by_reserve || h->fwd_valid;
+    end_live_forward(h);
     return GSR_OK;
 }
 
@@ -744,7 +761,18 @@ int gsr_reserve(gsr_handle* h, int64_t n_gaussians, int64_t n_instances) {
         uint32_t before = 0;
         uint32_t sum() const { uint32_t g = 0; for (int i = 0; i < h->n_all; i++) g += h->all[i]->regrowths; return g; }
         explicit Uncount(gsr_handle* h_) : h(h_) { before = sum(); }
-        ~Uncount() { h->reserved_regrowths += sum() - before; }
+        // ... and a buffer that existed was freed (on the error paths too): whatever the last forward left in it is gone, and
+        // so may be what radii_cur / vmean2d_cur point at.  The forward is no longer live: the backward entry points,
+        // gsr_update_stats and gsr_copy_buffer fail with GSR_E_STATE until the next gsr_forward instead of reading fresh
+        // allocations.  A call that reallocated nothing (sizes within capacity, first allocations) leaves the forward as it is.
+        ~Uncount() {
+            const uint32_t grown = sum() - before;
+            h->reserved_regrowths += grown;
+            if (grown > 0) {
+                h->dropped_by_reserve = h->dropped_by_reserve || h->fwd_valid;
+                end_live_forward(h);
+            }
+        }
     } uncount(h);
     if (n_gaussians > 0) {
         const size_t nn = (size_t)n_gaussians, nb = (nn + 255) / 256 + 1;
@@ -815,6 +843,7 @@ static int fwd_begin(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam,
     h->fwd_valid = false;
     h->bwd_valid = false;
     h->inputs_consumed = false;
+    h->dropped_by_reserve = false;
     h->fwd_only = v.fwd_only;
 
     const size_t nn = v.n > 0 ? (size_t)v.n : 1;
@@ -1122,6 +1151,9 @@ static int launch_composite_bwd(gsr_handle* h, hipStream_t s, int C, const GsrCa
 
 // What both backward entry points ask of the handle's last forward (`entry`: the entry point's name, for the messages).
 static int check_backward_state(const gsr_handle* h, const gsr_inputs* in, const char* entry) {
+    if (!h->fwd_valid && h->dropped_by_reserve)
+        return fail(GSR_E_STATE, "%s: a gsr_reserve that reallocated scratch (or gsr_drop_forward) dropped the handle's last "
+                    "forward; run gsr_forward again", entry);
     if (!h->fwd_valid || h->last_n != in->n)
         return fail(GSR_E_STATE, "%s without a matching gsr_forward on this handle", entry);
     if (h->fwd_only)
@@ -1288,6 +1320,9 @@ int gsr_loss_l1_ssim(gsr_handle* h, const float* image, const float* target, flo
 
 int gsr_update_stats(gsr_handle* h, int32_t* max_radii, float* accum_grad_means2d, float* denom, void* stream) {
     if (!h || !max_radii || !accum_grad_means2d || !denom) return fail(GSR_E_INVALID_ARG, "null argument");
+    if (!h->fwd_valid && h->dropped_by_reserve)
+        return fail(GSR_E_STATE, "gsr_update_stats: a gsr_reserve that reallocated scratch (or gsr_drop_forward) dropped the "
+                    "handle's last forward/backward pair");
     if (!h->fwd_valid || !h->bwd_valid) return fail(GSR_E_STATE, "gsr_update_stats needs a completed forward/backward pair");
     gsr_launch_update_stats((hipStream_t)stream, h->last_n, h->radii_cur, h->vmean2d_cur,
                             h->cfg.width, h->cfg.height, max_radii, accum_grad_means2d, denom);

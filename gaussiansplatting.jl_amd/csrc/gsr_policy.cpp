@@ -41,6 +41,22 @@ uint32_t bins_capacity_after(uint64_t instances, uint64_t longest, uint64_t tile
     return (uint32_t)std::min<uint64_t>(want, 1u << 20);
 }
 
+// Capacity for the NEXT view of a handle whose bins hold `current` keys per tile (0: no bins in use — no view yet, or the compact
+// mode): THE rule, for gsr_policy_end_view and for the planner gsr_bins_capacity_after alike.  Grow-only while bins are in use;
+// and where they have to GROW, by at least a quarter of what is there (within the budget's cap and the ceiling of 2^20 keys).  A
+// multi-view batch brings a slightly longer list every few views (round 6, 16 views at reduced size: 2112 -> 2176 -> 2368 keys
+// within one densification round — three reallocations of the bins for 3 % each); geometric growth bounds their number by the
+// logarithm of the growth.  0: no bins for the next view (compact mode), whatever is in place.
+uint32_t bins_capacity_next(uint64_t instances, uint64_t longest, uint64_t tiles, uint64_t budget_bytes, uint32_t current) {
+    uint32_t want = bins_capacity_after(instances, longest, tiles, budget_bytes);
+    if (current > 0u && want > current) {
+        const uint64_t cap = (budget_of(budget_bytes, instances) / (8ull * (tiles + 1))) & ~63ull;
+        const uint64_t grown = ((uint64_t)current + current / 4 + 63) & ~63ull;
+        want = (uint32_t)std::max<uint64_t>(want, std::min<uint64_t>(std::min<uint64_t>(grown, cap), 1u << 20));
+    }
+    return want == 0u ? 0u : std::max(want, current);
+}
+
 inline uint64_t tiles_of(const gsr_policy_config* c) { return (uint64_t)c->grid_x * (uint64_t)c->grid_y; }
 
 int form_for(const gsr_policy_config* cfg, int request, int n, uint32_t bin_cap_view, bool skewed) {
@@ -89,8 +105,7 @@ uint32_t gsr_bins_capacity_after(int64_t n_rendered, int32_t max_tile_instances,
                                  uint64_t bins_budget_bytes, uint32_t current_capacity) {
     if (n_rendered < 0 || max_tile_instances < 0 || width <= 0 || height <= 0) return 0u;
     const uint64_t tiles = (uint64_t)((width + kTile - 1) / kTile) * (uint64_t)((height + kTile - 1) / kTile);
-    const uint32_t want = bins_capacity_after((uint64_t)n_rendered, (uint64_t)max_tile_instances, tiles, bins_budget_bytes);
-    return want == 0u ? 0u : std::max(want, current_capacity);
+    return bins_capacity_next((uint64_t)n_rendered, (uint64_t)max_tile_instances, tiles, bins_budget_bytes, current_capacity);
 }
 
 void gsr_policy_agg_plan(int32_t grid_x, int32_t grid_y, uint32_t max_pos, int32_t* n_bands, int32_t* band_rows,
@@ -196,16 +211,9 @@ void gsr_policy_end_view(const gsr_policy_config* cfg, gsr_policy_state* st, con
     const bool hybrid = overflow && plan->bin_cap_view >= kHybridMinCap;
     const bool compact = !use_bins || (overflow && !hybrid);
     out->binning = compact ? GSR_BINNING_COMPACT : (hybrid ? GSR_BINNING_OVERFLOW : GSR_BINNING_BINS);
-    // capacity for the NEXT view: grow-only while bins are in use
-    uint32_t want = bins_capacity_after(D, max_tile_instances, T, cfg->bins_budget_bytes);
-    if (use_bins && want > st->bin_cap) {
-        // the bins GROW: by at least a quarter of what is there (within the budget).  A multi-view batch brings a slightly longer
-        // list every few views (round 6, 16 views at reduced size: 2112 -> 2176 -> 2368 keys within one densification round —
-        // three reallocations of the bins for 3 % each); geometric growth bounds their number by the logarithm of the growth.
-        const uint64_t cap = (budget_of(cfg->bins_budget_bytes, D) / (8ull * (T + 1))) & ~63ull;
-        const uint64_t grown = ((uint64_t)st->bin_cap + st->bin_cap / 4 + 63) & ~63ull;
-        want = (uint32_t)std::max<uint64_t>(want, std::min<uint64_t>(std::min<uint64_t>(grown, cap), 1u << 20));
-    }
+    // capacity for the NEXT view: grow-only while bins are in use, geometric where they grow (bins_capacity_next — what the
+    // planner gsr_bins_capacity_after answers from the same numbers)
+    const uint32_t want = bins_capacity_next(D, max_tile_instances, T, cfg->bins_budget_bytes, use_bins ? st->bin_cap : 0u);
     if (want == 0u) {
         st->bin_cap = 0; st->compact_sticky = 1;
     } else if (want > st->bin_cap || !use_bins) {

@@ -59,11 +59,18 @@ class GeometryState:
     def __len__(self):  # Base.length(::GeometryState), states.jl
         return self._cap
 
-    def reserve(self, n: int):
+    def reserve(self, n: int) -> bool:
+        """True when the arrays were replaced: addresses taken from the old ones are dead."""
         if self._cap < n:
             self._radii = torch.zeros(n, dtype=torch.int32, device=self.device)
             self._grad_means_2d = torch.zeros((n, 2), dtype=torch.float32, device=self.device)
             self._cap = n
+            return True
+        return False
+
+    def drop(self):
+        """The forward that filled the arrays is no longer live: `radii` / `grad_means_2d` read as empty (capacity stays)."""
+        self._n = 0
 
     def ensure(self, n: int):
         if self._cap < n:  # rasterizer.jl:275-278: reallocate when the model grew (here: by at least a quarter)
@@ -164,10 +171,27 @@ class GaussianRasterizer:
     def reserve(self, n_gaussians: int, n_instances: int = 0):
         """gsr_reserve: pre-size the grow-only scratch (and `gstate`) for views of up to that many Gaussians / tile instances, so
         that the forwards that follow allocate nothing (a reallocation inside a forward synchronises the device).  What a trainer
-        calls right after a densification round, with headroom — `densification.post_train_step` does."""
-        with torch.cuda.device(self.device):
-            L.check(self._lib.gsr_reserve(self._h, int(n_gaussians), int(n_instances)))
-        self.gstate.reserve(int(n_gaussians))
+        calls right after a densification round, with headroom — `densification.post_train_step` does.
+
+        A reserve that has to REPLACE something — the library reallocates a buffer that existed, or `gstate` its arrays, whose
+        addresses the handle holds since the last forward (gsr_aux.radii) — ends the live forward: `gstate.radii` /
+        `.grad_means_2d` are empty as after `release_scene_buffers`, and `backward_raw`, `backward_trainer_tail`, `update_stats`
+        raise GsrError(GSR_E_STATE) until the next forward.  So reserve after `update_stats`, as `post_train_step` does.  A
+        reserve that replaces nothing changes nothing."""
+        try:
+            with torch.cuda.device(self.device):
+                L.check(self._lib.gsr_reserve(self._h, int(n_gaussians), int(n_instances)))
+                if self.gstate.reserve(int(n_gaussians)):
+                    L.check(self._lib.gsr_drop_forward(self._h))
+        finally:
+            if not self._forward_live():
+                self.gstate.drop()
+
+    def _forward_live(self) -> bool:
+        """Does the handle still hold the last forward's state?  (GSR_BUF_RADII is null without one, or for a forward of no Gaussian)"""
+        p, sz = C.c_void_p(), C.c_size_t()
+        L.check(self._lib.gsr_buffer(self._h, L.BUF_RADII, C.byref(p), C.byref(sz)))
+        return bool(p.value)
 
     def memory_usage(self) -> int:
         """memory_usage(rast) — rasterizer.jl:127-134"""

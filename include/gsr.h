@@ -283,13 +283,27 @@ GSR_API int gsr_debug_check_guards(gsr_handle* h);
  * + hipMalloc pair, i.e. a device synchronisation in the middle of a training step.  Where a trainer calls it: right after a
  * densification round changed the model (the reference empties its allocation cache at the same place, strategy.jl:92), with
  * headroom for the next rounds; the Python mirror's post_train_step does (1.5 x).  The key bins are not covered: their capacity is
- * a policy of its own (gsr_policy.h).  Never shrinks; 0 / smaller values are no-ops. */
+ * a policy of its own (gsr_policy.h).  Never shrinks; 0 / smaller values are no-ops.
+ * A call that has to REALLOCATE a buffer that already existed frees what the handle's last forward left in it, so it ENDS that
+ * forward: until the next gsr_forward, gsr_backward / gsr_backward_trainer_tail / gsr_update_stats fail with GSR_E_STATE (before
+ * any launch), gsr_buffer reports a null pointer and 0 bytes for the per-forward buffers (GSR_BUF_RADII, _GRAD_MEANS2D,
+ * _VALUES_SORTED, _GEOM, _NORMALS, _GRAD_ROWS, _INSTANCE_AUX) and gsr_copy_buffer of any of their bytes fails with GSR_E_STATE.
+ * So reserve after gsr_update_stats, not between a forward and what reads it.  A call that reallocates nothing — sizes within
+ * capacity, (0, 0), the first allocation of a buffer that did not exist, a repeat of an earlier call — leaves the forward live,
+ * bit for bit.  The view history, the key bins and the loss head's scratch are not touched either way. */
 GSR_API int gsr_reserve(gsr_handle* h, int64_t n_gaussians, int64_t n_instances);
+/* A new function, no struct change: GSR_ABI_VERSION stays.  Ends the handle's live forward exactly as a reallocating gsr_reserve
+ * does (see there), freeing nothing.  For a binding that owns the arrays it hands to gsr_aux.radii / gsr_grads.vmeans2d and is
+ * about to replace them: the handle keeps those addresses until the next gsr_forward and must not be asked to read them again. */
+GSR_API int gsr_drop_forward(gsr_handle* h);
 /* Memory planning; no GPU needed.  The capacity — keys per tile — of the fixed-capacity key bins gsr_forward chooses for the view
  * AFTER one that rendered n_rendered instances with a longest tile list of max_tile_instances on a width x height image, under
- * bins_budget_bytes (0 = the default budget, see gsr_config) and with bins of current_capacity keys in place (0 = none yet; the
- * capacity only grows).  0 = no bins: compact mode.  The bins take (tiles + 1) x capacity x 8 bytes; a view whose longest list
- * exceeds the capacity scatters those lists a second time (+ 8 bytes per instance: gsr_stats.compact_binning == 2).
+ * bins_budget_bytes (0 = the default budget, see gsr_config) and with bins of current_capacity keys in place (0 = none: no view
+ * yet, or the handle is in compact mode).  It is the policy's own function (gsr_policy_end_view calls the same helper): the
+ * capacity only grows, and where bins in place have to grow they grow by at least a quarter of current_capacity, within the
+ * budget's cap and the ceiling of 2^20 keys — so the result can exceed the longest list + 25 %.  0 = no bins: compact mode.  The
+ * bins take (tiles + 1) x capacity x 8 bytes; a view whose longest list exceeds the capacity scatters those lists a second time
+ * (+ 8 bytes per instance: gsr_stats.compact_binning == 2).
  * (No reference counterpart: the reference's BinningState is O(instances), states.jl:66-85.) */
 GSR_API uint32_t gsr_bins_capacity_after(int64_t n_rendered, int32_t max_tile_instances, int32_t width, int32_t height,
                                          uint64_t bins_budget_bytes, uint32_t current_capacity);

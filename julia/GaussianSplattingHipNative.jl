@@ -292,10 +292,21 @@ function ChainRulesCore.rrule(::typeof(rasterize), means_3d::RM, shs::R3, opacit
 end
 
 # gsr_reserve: pre-size the native scratch for up to n_gaussians / n_instances (call it after a densification round, with headroom:
-# a reallocation inside a forward synchronises the device in the middle of a training step)
+# a reallocation inside a forward synchronises the device in the middle of a training step).  `rast.gstate` — whose radii /
+# ∇means_2d arrays the native forward / backward write through gsr_aux.radii / gsr_grads.vmeans2d — is pre-sized with it.
+# A reserve that REPLACES anything ends the live forward (include/gsr.h: gsr_reserve): the library does when it reallocates a
+# buffer that existed; when only `rast.gstate` is replaced here, the handle still holds the old radii array's address from the
+# last forward, so it is told (gsr_drop_forward) BEFORE that array is freed.  Until the next `rasterize`, ∇rasterize /
+# backward_trainer_tail! / update_stats! then fail with GSR_E_STATE instead of reading freed memory: reserve after update_stats!.
 function reserve!(rast::GaussianRasterizer, n_gaussians::Integer, n_instances::Integer = 0)
     st = native(rast)
-    st === nothing || check(ccall((:gsr_reserve, LIB), Cint, (Ptr{Cvoid}, Int64, Int64), st.handle, n_gaussians, n_instances))
+    st === nothing && return rast
+    check(ccall((:gsr_reserve, LIB), Cint, (Ptr{Cvoid}, Int64, Int64), st.handle, n_gaussians, n_instances))
+    if length(rast.gstate) < n_gaussians
+        check(ccall((:gsr_drop_forward, LIB), Cint, (Ptr{Cvoid},), st.handle))
+        KA.unsafe_free!(rast.gstate)
+        rast.gstate = GPUArrays.@uncached GeometryState(KA.get_backend(rast), Int(n_gaussians); n_features=n_color_features(rast.mode))
+    end
     return rast
 end
 

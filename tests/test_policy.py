@@ -50,8 +50,13 @@ def test_library_and_standalone_builds_agree(P, pkg):
     """libgsr_hip.so exports the same policy functions (they ARE what gsr_forward calls): same answers as the g++-only build."""
     lib, L = P
     full = L.load()
-    for args in ((3_888_089, 569, 1920, 1080, 0, 0), (4_032_599, 32_451, 1920, 1080, 0, 0), (1_000_000, 5000, 1920, 1080, 8161 * 8 * 512, 0)):
-        assert lib.gsr_bins_capacity_after(*args) == full.gsr_bins_capacity_after(*args)
+    for args in ((3_888_089, 569, 1920, 1080, 0, 0), (4_032_599, 32_451, 1920, 1080, 0, 0), (1_000_000, 5000, 1920, 1080, 8161 * 8 * 512, 0),
+                 # bins in place (current_capacity > 0): kept, grown by a quarter, grown to the list, capped by a budget, dropped
+                 (3_900_000, 1500, 1920, 1080, 0, 2048), (3_900_000, 1690, 1920, 1080, 0, 2048), (3_900_000, 4000, 1920, 1080, 0, 2048),
+                 (3_900_000, 1690, 1920, 1080, 8161 * 8 * 2304, 2048), (1_000_000, 5000, 1920, 1080, 8161 * 8 * 512, 512)):
+        assert lib.gsr_bins_capacity_after(*args) == full.gsr_bins_capacity_after(*args), args
+    assert [full.gsr_bins_capacity_after(3_900_000, m, 1920, 1080, b, 2048) for m, b in
+            ((1500, 0), (1690, 0), (4000, 0), (1690, 8161 * 8 * 2304))] == [2048, 2560, 5056, 2304]
     for gx, gy, pos in ((120, 68, 768), (160, 90, 1024), (240, 135, 1024), (240, 135, 70_000), (8192, 2, 64)):
         got = []
         for l_ in (lib, full):
@@ -269,3 +274,80 @@ def test_training_history_replay(P):
         assert regrow_in_round <= 1, f"bins regrown twice after the first view of the round that began at step {last_round_start}"
         assert (st.bins_regrowths, st.compact_fallbacks, st.tuner_rearms) == (v["bins_regrowths"], v["compact_fallbacks"], v["tuner_rearms"]), v
     assert st.tuner_rearms == 0
+
+
+# ---- the planner gsr_bins_capacity_after IS the policy: replayed view by view -------------------------------------------------
+def replay_planner(P, width, height, budget, views):
+    """`views`: (n, D, longest, tiers) per view, through gsr_policy_begin_view / gsr_policy_end_view on a fresh handle.  After
+    EVERY view the planner, asked with the capacity that was in place for it (gsr_view_plan.bin_cap_view: 0 in compact mode),
+    must name the capacity the policy chose for the next one.  Returns per view (capacity in place, capacity chosen, bins
+    regrown); the first disagreement is reported with its 1-based view number."""
+    lib, L = P
+    cfg, st = new_handle(P, width, height, budget)
+    out = []
+    for i, (n, D, longest, tiers) in enumerate(views, 1):
+        plan, oc = view(P, cfg, st, n, D, longest, tiers)
+        planned = lib.gsr_bins_capacity_after(D, longest, width, height, budget, plan.bin_cap_view)
+        assert planned == oc.bin_cap_next, (f"view {i}: {plan.bin_cap_view} keys in place, longest list {longest}: the policy goes to "
+                                            f"{oc.bin_cap_next}, the planner says {planned}")
+        out.append((int(plan.bin_cap_view), int(oc.bin_cap_next), int(oc.bins_regrown)))
+    return out, st
+
+
+R64 = lambda v: (v + v // 4 + 63) & ~63  # noqa: E731   (longest list + 25 %, in whole cache lines of keys)
+HISTORY_A = [(1_000_000, 3_900_000, m, (0, 0, 0)) for m in (1600, 1690, 1740, 1900, 1700, 2300)]
+
+
+def test_planner_replay_six_views_1080p(P):
+    """(a) 1 M Gaussians, 3.9 M instances at 1080p under the default budget; the longest list moves 1600, 1690, 1740, 1900, 1700,
+    2300.  View 2 finds 2048 keys in place and needs 2112: the bins grow by a quarter, to 2560 (the planner used to answer 2112);
+    view 6 finds 2560 and needs 2880: 3200."""
+    hist, st = replay_planner(P, 1920, 1080, 0, HISTORY_A)
+    assert [h[0] for h in hist] == [1088, 2048, 2560, 2560, 2560, 2560]
+    assert [h[1] for h in hist] == [2048, 2560, 2560, 2560, 2560, 3200]
+    assert R64(1690) == 2112 and R64(2300) == 2880 and st.bins_regrowths == 3
+
+
+def test_planner_replay_slow_growth_batch(P):
+    """(b) 16 views whose longest list creeps up by 1, 2, 3, 1, ... % per view (a multi-view batch within one densification
+    round): the geometric growth keeps the reallocations to the logarithm of the growth, and the planner follows each of them."""
+    longest, views = 1600, []
+    for i in range(16):
+        views.append((1_000_000, 3_900_000, longest, (0, 0, 0)))
+        longest += longest * (1 + i % 3) // 100
+    assert views[-1][2] > 1.3 * views[0][2]
+    hist, st = replay_planner(P, 1920, 1080, 0, views)
+    grew = [(have, nxt, v[2]) for (have, nxt, re), v in zip(hist, views) if re and have >= 2048]
+    assert grew and all(nxt == R64(have) > R64(m) for have, nxt, m in grew), grew   # the quarter, not the list, set the capacity
+    assert st.bins_regrowths <= 3 and st.compact_fallbacks == 0
+
+
+def test_planner_replay_recorded_training_history(P):
+    """(c) the history a training run recorded on the GPU (test_training_history_replay's file, through the same `view` helper)."""
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "train_history.json")))
+    views = [(v["n"], v["n_rendered"], v["max_tile"], tuple(v["tiers"])) for v in rec["views"]]
+    hist, st = replay_planner(P, rec["width"], rec["height"], rec.get("bins_budget_bytes", 0), views)
+    assert [h[0] for h in hist] == [v["bin_capacity"] for v in rec["views"]]
+    assert st.bins_regrowths == rec["views"][-1]["bins_regrowths"] > 0
+
+
+def test_planner_replay_growth_capped_by_the_budget(P):
+    """(d) a configured budget of 2304 keys per tile: 2048 keys + a quarter would be 2560, the budget's cap is what the bins get;
+    lists whose + 25 % no longer fit leave them there (the overflow path takes those lists)."""
+    T = 120 * 68
+    budget = (T + 1) * 8 * 2304
+    views = [(1_000_000, 3_900_000, m, (0, 0, 0)) for m in (1600, 1690, 1740, 1900, 2300, 1700)]
+    hist, st = replay_planner(P, 1920, 1080, budget, views)
+    assert [h[1] for h in hist] == [2048, 2304, 2304, 2304, 2304, 2304] and st.bins_regrowths == 2
+
+
+def test_planner_replay_sticky_compact_mode(P):
+    """(e) a budget of 512 keys per tile against a list of 5000: compact mode, sticky — the capacity in place is 0 and the planner
+    says 0; the hot tile goes away and bins come back (no quarter on top of bins that are not there), then grow to the cap."""
+    T = 120 * 68
+    budget = (T + 1) * 8 * 512
+    views = [(1_000_000, 1_000_000, m, (0, 0, 0)) for m in (5000, 5000, 5000, 300, 300, 350, 350)]
+    hist, st = replay_planner(P, 1920, 1080, budget, views)
+    assert [h[0] for h in hist] == [512, 0, 0, 0, 384, 384, 512]
+    assert [h[1] for h in hist] == [0, 0, 0, 384, 384, 512, 512]
+    assert st.compact_views == 3 and st.compact_fallbacks == 1 and st.compact_sticky == 0
