@@ -2046,6 +2046,30 @@ int gsr_morton_codes(int64_t n, const float* points, const float* box_lo, const 
     return GSR_OK;
 }
 
+// ---- a model from a point cloud: exact 3-NN initial scales (knn.hip; dataset.jl:236-249 `compute_scales`) ----
+size_t gsr_knn_scratch_bytes(int64_t n) {
+    if (n <= 0 || n > 0x7FFFFFFFll) return 0;
+    return gsr_knn_scratch_size(n);
+}
+
+int gsr_knn_scales(int64_t n, const float* points, const int32_t* order, float point_size, int32_t scale_dims, float* scales_out,
+                   float* dist2_out, void* scratch, size_t scratch_bytes, void* stream) {
+    if (n < 0) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: negative n");
+    if (n == 0) return GSR_OK;
+    if (n <= 3)  // the reference's knn(kdtree, xyz, 3 + 1) throws there
+        return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: n = %lld: three neighbours need at least 4 points", (long long)n);
+    if (n > 0x7FFFFFFFll) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: n = %lld: rows are indexed with 31 bits", (long long)n);
+    if (scale_dims != 1 && scale_dims != 3) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: scale_dims = %d: 1 (isotropic) or 3", scale_dims);
+    if (!(point_size > 0.0f)) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: point_size = %g must be positive", (double)point_size);
+    if (!points || !scales_out || !scratch) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: null points, scales_out or scratch");
+    const size_t need = gsr_knn_scratch_bytes(n);
+    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: scratch_bytes = %zu, the search needs %zu", scratch_bytes, need);
+    if ((uintptr_t)scratch % 16) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: scratch must be 16-byte aligned");
+    gsr_launch_knn_scales((hipStream_t)stream, n, points, order, point_size, scale_dims, scales_out, dist2_out, scratch);
+    HIPCHK(hipGetLastError());
+    return GSR_OK;
+}
+
 int gsr_count_nonfinite(const float* const* arrays, const int32_t* row_words, int32_t n_groups, int64_t n_rows, uint32_t* counts,
                         uint32_t* first_bad, void* stream) {
     if (n_groups < 0 || n_groups > GSR_ADAM_MAX_GROUPS || (n_groups > 0 && (!arrays || !row_words)))

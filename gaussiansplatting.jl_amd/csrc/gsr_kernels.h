@@ -312,3 +312,8 @@ void gsr_launch_eval_metrics(hipStream_t s, int W, int H, int C, const float* im
                              void* scratch);
 void gsr_launch_frame_rgb8(hipStream_t s, int W, int H, int C, const float* image, const float* sky_rgb, int flip_rows,
                            unsigned char* rgb8_out);
+
+// ---- knn.hip (compiled with -ffp-contract=off): exact 3-NN of a point cloud and the initial scales from it ----
+size_t gsr_knn_scratch_size(long long n);
+void gsr_launch_knn_scales(hipStream_t s, long long n, const float* points, const int32_t* order, float point_size,
+                           int scale_dims, float* scales_out, float* dist2_out, void* scratch);

@@ -592,6 +592,29 @@ GSR_API int gsr_reset_opacity(int64_t n, float* opacities, void* stream);
 GSR_API int gsr_morton_codes(int64_t n, const float* points, const float* box_lo, const float* box_hi, uint64_t* codes,
                              void* stream);
 
+/* The first step of a training run: the initial scales of a model built from a point cloud (src/dataset.jl:236-249
+ * `compute_scales`; what simple-knn is to the original 3DGS code).  Per point i the three smallest
+ *   d2(i,j) = (dx*dx + dy*dy) + dz*dz   (fp32, uncontracted; dx = x_i - x_j, …)   over all rows j != i
+ * — j is excluded by index, a duplicate at distance 0 is a neighbour —, ascending, found by an EXACT search (the multiset
+ * equals a brute-force search's for every input and every `order`), and from them, as the reference does on the tree's
+ * distances:   q_k = sqrtf(d2_k)·sqrtf(d2_k);  md = ((q_0 + q_1) + q_2) / 3;  s = logf(sqrtf(fmaxf(1e-7f, md) · point_size)).
+ *   points     : device, (n,3) rows.
+ *   order      : device, n row numbers, or NULL = 0, 1, …: the order in which the search groups the points (64 consecutive
+ *                entries share a box).  A permutation along a space-filling curve (gsr_morton_codes + a sort) makes the
+ *                search fast; any permutation gives the same bits.  Entries are clamped into [0, n): a vector that is no
+ *                permutation gives wrong numbers, never an access outside the arrays.
+ *   scales_out : device, (n,scale_dims): s in all three columns, or ((s + s) + s) / 3 in the one (the isotropic model's
+ *                `mean(scales; dims=1)`, gaussians.jl:53).
+ *   dist2_out  : device, (n,3): the three d2, ascending; NULL: not wanted.
+ *   scratch    : device, gsr_knn_scratch_bytes(n) bytes (16 per point + 24 per 64 points), 16-byte aligned.
+ * n == 0: GSR_OK, nothing is launched.  GSR_E_INVALID_ARG, before anything touches the device: 1 <= n <= 3 (the reference's
+ * knn(…, 4) throws there) or n >= 2^31, scale_dims not 1 or 3, !(point_size > 0), a null points / scales_out / scratch,
+ * scratch_bytes < gsr_knn_scratch_bytes(n), a misaligned scratch.  A point with a non-finite coordinate is never anybody's
+ * neighbour; its own row is unspecified.  gsr_knn_scratch_bytes is 0 for n <= 0 (and n >= 2^31). */
+GSR_API size_t gsr_knn_scratch_bytes(int64_t n);
+GSR_API int gsr_knn_scales(int64_t n, const float* points, const int32_t* order, float point_size, int32_t scale_dims,
+                           float* scales_out, float* dist2_out, void* scratch, size_t scratch_bytes, void* stream);
+
 /* The non-finite gradient guard of `step!` under GSP_DEBUG (src/training.jl:772-777: `isfinite(sum(∇ᵢ))` per parameter)
  * and the per-parameter counts of `nonfinite_gradient_report` (:534-552), in one pass over up to GSR_ADAM_MAX_GROUPS
  * gradient arrays of n_rows Gaussians each (rows of row_words floats; row_words = 0 skips an empty array):

@@ -334,6 +334,22 @@ function morton_codes!(codes, points, lo::NTuple{3,Float32}, hi::NTuple{3,Float3
     return codes
 end
 
+# compute_scales (dataset.jl:236-249) on the device: the exact three nearest neighbours of every point of `points`
+# (3 x N Float32 device array) and the reference's scale from them, written to `scales` (3 x N, or 1 x N for an isotropic
+# model).  `order`: a device Int32 vector of N 0-based row numbers that groups the search (sortperm of morton_codes! .- 1),
+# or nothing; the result does not depend on it.  `dist2` (3 x N), when given, receives the squared distances, ascending.
+knn_scratch_bytes(n::Integer) = Int(ccall((:gsr_knn_scratch_bytes, LIB), Csize_t, (Int64,), n))
+function knn_scales!(scales, points; order = nothing, point_size::Float32 = 1f0, dist2 = nothing, scratch = nothing)
+    n = size(points, 2)
+    nb = knn_scratch_bytes(n)
+    scratch === nothing && (scratch = AMDGPU.zeros(UInt8, nb))
+    check(ccall((:gsr_knn_scales, LIB), Cint,
+        (Int64, Ptr{Float32}, Ptr{Int32}, Float32, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        n, dptr(points), dptr(Int32, order), point_size, size(scales, 1), dptr(scales), dptr(dist2), dptr(Cvoid, scratch), nb,
+        hipstream()))
+    return scales
+end
+
 # ---- optional fused tails (not needed for the drop-in; callers opt in) ----
 
 # update_stats!(strategy, radii, ∇means_2d, resolution) (strategy.jl:107-136) on the library's kernel
