@@ -12,8 +12,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
-from . import fused_ssim
 from .optim import Adam
 
 GRID_SIZE = (16, 16, 8)  # bilateral_grid_size (utils.jl:60): (x, y, guidance)
@@ -46,25 +46,11 @@ def bilateral_grid_scheduler(lr: float, steps: int, warmup_steps: int = 1000, wa
     return _scheduler
 
 
-def _check_image(image: torch.Tensor, name: str = "image"):
-    if not (image.is_cuda and image.dtype == torch.float32 and image.is_contiguous() and image.dim() == 3
-            and image.shape[2] in (3, 5, 8)):
-        raise ValueError(f"{name} must be a contiguous float32 (H, W, C) HIP tensor with C in (3, 5, 8)")
-    return image
+_check_image = A.frame_check((3, 5, 8), "{} must be a contiguous float32 (H, W, C) HIP tensor with C in (3, 5, 8)")
 
 
 def _check_grid(grid: torch.Tensor):
-    if not (grid.is_cuda and grid.dtype == torch.float32 and grid.is_contiguous() and grid.dim() == 4 and grid.shape[0] == 12):
-        raise ValueError("grid must be a contiguous float32 (12, gz, gy, gx) HIP tensor")
-    return grid
-
-
-def _scratch(cache: dict, key: str, nbytes: int, device) -> torch.Tensor:
-    buf = cache.get(key)
-    if buf is None or buf.numel() < nbytes or buf.device != device:
-        buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
-        cache[key] = buf
-    return buf
+    return A.check(grid, "grid must be a contiguous float32 (12, gz, gy, gx) HIP tensor", shape=(12, None, None, None))
 
 
 _SCRATCH: dict = {}  # grow-only scratch of the functional entry points, per device
@@ -74,9 +60,7 @@ def slice_forward(image: torch.Tensor, grid: torch.Tensor, out: torch.Tensor = N
     """`bilateral_slice(image, grid)` (bilateral_grid.jl:75-85): rgb corrected, channels >= 3 copied."""
     H, W, Cc = _check_image(image).shape
     gz, gy, gx = _check_grid(grid).shape[1:]
-    out = torch.empty_like(image) if out is None else _check_image(out, "out")
-    if out.shape != image.shape or out.device != image.device:
-        raise ValueError("out must have the image's shape and device")
+    out = torch.empty_like(image) if out is None else A.check_same(_check_image(out, "out"), "out", image)
     with torch.cuda.device(image.device):
         L.check(L.load().gsr_bilateral_slice_forward(W, H, Cc, image.data_ptr(), grid.data_ptr(), gx, gy, gz, out.data_ptr(),
                                                      L.stream()))
@@ -89,18 +73,12 @@ def slice_backward(image: torch.Tensor, grid: torch.Tensor, vout: torch.Tensor, 
     overwritten.  Run-to-run bit-identical."""
     H, W, Cc = _check_image(image).shape
     gz, gy, gx = _check_grid(grid).shape[1:]
-    _check_image(vout, "vout")
-    if vout.shape != image.shape or vout.device != image.device:
-        raise ValueError("vout must have the image's shape and device")
-    vimage = torch.empty_like(image) if vimage is None else _check_image(vimage, "vimage")
-    vgrid = torch.empty_like(grid) if vgrid is None else _check_grid(vgrid)
-    if vimage.shape != image.shape or vimage.device != image.device:
-        raise ValueError("vimage must have the image's shape and device")
-    if vgrid.shape != grid.shape or vgrid.device != grid.device:
-        raise ValueError("vgrid must have the grid's shape and device")
+    A.check_same(_check_image(vout, "vout"), "vout", image)
+    vimage = torch.empty_like(image) if vimage is None else A.check_same(_check_image(vimage, "vimage"), "vimage", image)
+    vgrid = torch.empty_like(grid) if vgrid is None else A.check_same(_check_grid(vgrid), "vgrid", grid, "grid")
     lib = L.load()
     nb = int(lib.gsr_bilateral_scratch_bytes(W, H, gx, gy, gz))
-    buf = _scratch(_SCRATCH if scratch is None else scratch, "slice", nb, image.device)
+    buf = A.grow_scratch(_SCRATCH if scratch is None else scratch, "slice", nb, image.device)
     with torch.cuda.device(image.device):
         L.check(lib.gsr_bilateral_slice_backward(W, H, Cc, image.data_ptr(), grid.data_ptr(), gx, gy, gz, vout.data_ptr(),
                                                  vimage.data_ptr(), vgrid.data_ptr(), buf.data_ptr(), buf.numel(), L.stream()))
@@ -109,13 +87,12 @@ def slice_backward(image: torch.Tensor, grid: torch.Tensor, vout: torch.Tensor, 
 
 def tv(grids: torch.Tensor, weight: float = 1.0, grad: bool = False, scratch: dict = None):
     """weight · tv_loss(grids) (bilateral_grid.jl:102-119) as a 0-d tensor, and weight · ∇tv_loss when `grad`."""
-    if not (grids.is_cuda and grids.dtype == torch.float32 and grids.is_contiguous() and grids.dim() == 5 and grids.shape[1] == 12):
-        raise ValueError("grids must be a contiguous float32 (n, 12, gz, gy, gx) HIP tensor")
+    A.check(grids, "grids must be a contiguous float32 (n, 12, gz, gy, gx) HIP tensor", shape=(None, 12, None, None, None))
     n, _, gz, gy, gx = grids.shape
     loss = torch.empty((), dtype=torch.float32, device=grids.device)
     g = torch.empty_like(grids) if grad else None
     lib = L.load()
-    buf = _scratch(_SCRATCH if scratch is None else scratch, "tv", int(lib.gsr_bilateral_tv_scratch_bytes(n)), grids.device)
+    buf = A.grow_scratch(_SCRATCH if scratch is None else scratch, "tv", int(lib.gsr_bilateral_tv_scratch_bytes(n)), grids.device)
     with torch.cuda.device(grids.device):
         L.check(lib.gsr_bilateral_tv(n, gx, gy, gz, grids.data_ptr(), float(weight), loss.data_ptr(),
                                      None if g is None else g.data_ptr(), buf.data_ptr(), buf.numel(), L.stream()))
@@ -211,7 +188,7 @@ class BilateralGrid:
         o = self.optimizer
         o.lr = float(self.scheduler(int(trainer_step)))
         lib = L.load()
-        buf = _scratch(self._scratch, "tv", int(lib.gsr_bilateral_tv_scratch_bytes(n)), self.grids.device)
+        buf = A.grow_scratch(self._scratch, "tv", int(lib.gsr_bilateral_tv_scratch_bytes(n)), self.grids.device)
         with torch.cuda.device(self.grids.device):
             L.check(lib.gsr_bilateral_adam_tail(n, gx, gy, gz, self.grids.data_ptr(), o.mu.data_ptr(), o.nu.data_ptr(),
                                                 self.vgrid.data_ptr(), int(view), float(tv_weight), o.lr, o.current_step + 1,
@@ -224,11 +201,9 @@ class BilateralGrid:
 
 def l1_ssim_bilateral_loss(rast, image: torch.Tensor, target: torch.Tensor, bgrid: BilateralGrid, view: int,
                            lambda_dssim: float = 0.2):
-    """training.jl:676-694 with the appearance correction: slice the render with the view's grid, the fused L1 / D-SSIM
-    loss head on the corrected image, and the slice's pullback IN PLACE on the loss head's cotangent.  Returns
-    (photometric loss, vpixels): vpixels is the cotangent w.r.t. the RAW render — channels >= 3 still the loss head's
-    zeros, so it is valid with `color_cotangent=True` — and the view's ∇grid stays in `bgrid` for `bgrid.step`."""
-    corrected = bgrid.slice(_check_image(image), view)
-    loss, vpix = fused_ssim.l1_ssim_loss(rast, corrected, target, lambda_dssim)
-    bgrid.slice_backward_(image, view, vpix)
-    return loss, vpix
+    """training.jl:676-694 with the appearance correction alone: `training_loss(..., bgrid=, view=)`.  Returns (photometric
+    loss, vpixels): vpixels is the cotangent w.r.t. the RAW render (`StepLoss.color_cotangent` stays true), and the view's
+    ∇grid stays in `bgrid` for `bgrid.step`."""
+    from .training_loss import training_loss
+    step = training_loss(rast, _check_image(image), target, lambda_dssim=lambda_dssim, bgrid=bgrid, view=view)
+    return step.photometric, step.vpixels

@@ -19,6 +19,7 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
+from . import _args as A
 from . import _lib as L
 
 DEPTH_LOSS_WEIGHT = 2.0            # depth_loss_weight (utils.jl)
@@ -225,53 +226,25 @@ def depth_weight(step, weight=DEPTH_LOSS_WEIGHT, final_scale=DEPTH_LOSS_FINAL_SC
 
 # ---- the loss (device) ----
 
-def _torch():
-    import torch
-    return torch
-
-
-def _check_frame(image, name="image"):
-    torch = _torch()
-    if not (image.is_cuda and image.dtype == torch.float32 and image.is_contiguous() and image.dim() == 3
-            and image.shape[2] in (5, 8)):
-        raise ValueError(f"{name} must be a contiguous float32 (H, W, 5) or (H, W, 8) HIP tensor (a :rgbd / :rgbdn frame)")
-    return image
+check_frame = A.frame_check((5, 8), "{} must be a contiguous float32 (H, W, 5) or (H, W, 8) HIP tensor (a :rgbd / :rgbdn frame)")
 
 
 def _check_prior(prior, H=None, W=None, device=None):
-    torch = _torch()
-    if not (prior.is_cuda and prior.dtype == torch.float32 and prior.is_contiguous() and prior.dim() == 2):
-        raise ValueError("prior must be a contiguous float32 (H, W) HIP tensor")
-    if H is not None and (tuple(prior.shape) != (H, W) or prior.device != device):
-        raise ValueError("prior must have the image's height, width and device")
-    return prior
-
-
-_SCRATCH: dict = {}  # grow-only scratch of the functional entry points, per device and image size
+    A.check(prior, "prior must be a contiguous float32 (H, W) HIP tensor", shape=(None, None))
+    return prior if H is None else A.check(prior, "prior must have the image's height, width and device", shape=(H, W), device=device)
 
 
 def depth_loss_scratch_bytes(W: int, H: int) -> int:
     return int(L.load().gsr_depth_loss_scratch_bytes(int(W), int(H)))
 
 
-def _scratch_for(scratch, W, H, device, create=True):
-    torch = _torch()
-    nb = depth_loss_scratch_bytes(W, H)
-    if scratch is None:
-        buf = _SCRATCH.get((W, H, device))
-        if buf is None and create:
-            buf = _SCRATCH[(W, H, device)] = torch.empty(nb, dtype=torch.uint8, device=device)
-        return buf
-    if not (isinstance(scratch, torch.Tensor) and scratch.is_cuda and scratch.is_contiguous() and scratch.device == device
-            and scratch.numel() * scratch.element_size() >= nb and scratch.data_ptr() % 16 == 0):
-        raise ValueError(f"scratch must be a contiguous, 16-byte aligned HIP tensor of at least {nb} bytes on the image's device")
-    return scratch
+_SCRATCH = A.FrameScratch(depth_loss_scratch_bytes, align=16)  # what depth_loss leaves for depth_loss_backward_
 
 
 def depth_target(anchor: DepthAnchor, prior, qstep: float):
     """`depth_target` (depth_supervision.jl:425-438) on the device -> (target (H, W) float32, half_band (H, W) float32,
     flags (H, W) uint8: bit 0 valid, bit 1 far_extrap)."""
-    torch = _torch()
+    torch = A._torch()
     H, W = _check_prior(prior).shape
     target, half = torch.empty_like(prior), torch.empty_like(prior)
     flags = torch.empty((H, W), dtype=torch.uint8, device=prior.device)
@@ -289,10 +262,10 @@ def depth_loss(image, prior, anchor: DepthAnchor, qstep: float, weight: float, l
     `maps=True` the (target, half_band, flags) the kernel built.  `scratch` (optional, caller-owned, >=
     depth_loss_scratch_bytes): what `depth_loss_backward_` of the same image reads; by default a buffer kept per device
     and image size."""
-    torch = _torch()
-    H, W, Cn = _check_frame(image).shape
+    torch = A._torch()
+    H, W, Cn = check_frame(image).shape
     _check_prior(prior, H, W, image.device)
-    buf = _scratch_for(scratch, W, H, image.device)
+    buf = _SCRATCH.get(scratch, W, H, image.device)
     loss = torch.empty((), dtype=torch.float32, device=image.device)
     st = torch.empty(4, dtype=torch.float32, device=image.device)
     tm = hm = fm = None
@@ -314,15 +287,11 @@ def depth_loss_backward_(image, prior, anchor: DepthAnchor, qstep: float, vpixel
     """ADDS weight · ∂ssi_depth_loss/∂(D, α) onto channels 3 and 4 of `vpixels` (H, W, C), in place; no other channel is
     touched.  Needs `depth_loss` of the same image, prior, anchor and qstep (and the same `scratch`) run before it.
     Run-to-run bit-identical.  A `vpixels` this was added onto must go to `backward_raw` with `color_cotangent=False`."""
-    torch = _torch()
-    H, W, Cn = _check_frame(image).shape
-    _check_frame(vpixels, "vpixels")
-    if vpixels.shape != image.shape or vpixels.device != image.device:
-        raise ValueError("vpixels must have the image's shape and device")
-    if vpixels.data_ptr() == image.data_ptr():
-        raise ValueError("vpixels must not be the image")
+    torch = A._torch()
+    H, W, Cn = check_frame(image).shape
+    A.check_vpixels(check_frame, vpixels, image)
     _check_prior(prior, H, W, image.device)
-    buf = _scratch_for(scratch, W, H, image.device, create=False)
+    buf = _SCRATCH.get(scratch, W, H, image.device, create=False)
     if buf is None:
         raise ValueError("run depth_loss of this image first: the backward reads what it left on the device")
     an = anchor.struct()
@@ -336,59 +305,27 @@ def depth_loss_backward_(image, prior, anchor: DepthAnchor, qstep: float, vpixel
 def ssi_depth_loss(image, prior, anchor: DepthAnchor, qstep: float, weight: float = 1.0,
                    lambda_grad: float = DEPTH_LOSS_GRADIENT_WEIGHT):
     """weight · ssi_depth_loss, differentiable w.r.t. the (H, W, C) frame (channels 3 and 4; the others get zeros)."""
-    torch = _torch()
-
-    class _SsiDepthLoss(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, image):
-            image = image.detach().contiguous()
-            ctx.scratch = torch.empty(depth_loss_scratch_bytes(image.shape[1], image.shape[0]), dtype=torch.uint8,
-                                      device=image.device)
-            ctx.save_for_backward(image)
-            return depth_loss(image, prior, anchor, qstep, weight, lambda_grad, scratch=ctx.scratch)
-
-        @staticmethod
-        def backward(ctx, delta):
-            (image,) = ctx.saved_tensors
-            v = torch.zeros_like(image)
-            depth_loss_backward_(image, prior, anchor, qstep, v, weight, lambda_grad, scratch=ctx.scratch)
-            return v * delta
-
-    return _SsiDepthLoss.apply(image)
+    return A.cotangent_term(
+        image, lambda im, scratch: depth_loss(im, prior, anchor, qstep, weight, lambda_grad, scratch=scratch),
+        lambda im, v, scratch: depth_loss_backward_(im, prior, anchor, qstep, v, weight, lambda_grad, scratch=scratch),
+        depth_loss_scratch_bytes)
 
 
 def l1_ssim_depth_loss(rast, image, target, prior, anchor: Optional[DepthAnchor], qstep: float, step: int,
                        lambda_dssim: float = 0.2, weight: float = DEPTH_LOSS_WEIGHT, final_scale: float = DEPTH_LOSS_FINAL_SCALE,
                        steps: int = 30000, lambda_grad: float = DEPTH_LOSS_GRADIENT_WEIGHT, camera=None,
                        normal_weight: float = None, bgrid=None, view: int = None, terms: dict = None):
-    """The loss of `step!` with `use_depth_loss` (training.jl:604-620,709-718): the fused L1 / D-SSIM loss head (through
-    the view's bilateral grid when `bgrid` and `view` are given), then depth_weight(step) · ssi_depth_loss ADDED onto
-    channels 3 and 4 of the head's cotangent.  For a :rgbdn frame, `camera` and `normal_weight` add the depth-normal
-    consistency term onto the same cotangent (its value goes into `terms["normal"]` when a dict is passed).  Returns
-    (photometric, depth_term, vpixels).
-
-    This `vpixels` carries depth / alpha cotangents: it must go to `backward_raw` with `color_cotangent=False`.  With
-    `anchor=None` (a camera that lost the vote) and no normal term, the plain head runs: depth_term is None and `vpixels`
-    is the head's own cotangent, for which `color_cotangent=True` stays valid."""
-    from . import fused_ssim
-    _check_frame(image)
-    if bgrid is not None:
-        from . import bilateral_grid
-        loss, vpix = bilateral_grid.l1_ssim_bilateral_loss(rast, image, target, bgrid, view, lambda_dssim)
-    else:
-        loss, vpix = fused_ssim.l1_ssim_loss(rast, image, target, lambda_dssim)
-    depth_term = None
-    if anchor is not None:
-        w = depth_weight(step, weight, final_scale, steps)
-        depth_term = depth_loss(image, prior, anchor, qstep, w, lambda_grad)
-        depth_loss_backward_(image, prior, anchor, qstep, vpix, w, lambda_grad)
-    if normal_weight is None:
-        return loss, depth_term, vpix
-    from . import geometry_regularization as G
-    if camera is None:
-        raise ValueError("the depth-normal term needs the camera")
-    normal_term = G.depth_normal_loss(image, camera, normal_weight)
-    G.depth_normal_loss_backward_(image, camera, vpix, normal_weight)
-    if terms is not None:
-        terms["normal"] = normal_term
-    return loss, depth_term, vpix
+    """The loss of `step!` with `use_depth_loss` (training.jl:604-620,709-718), one term only: `training_loss` with the
+    depth term at depth_weight(step) and, for a :rgbdn frame given `camera` and `normal_weight`, the depth-normal term (its
+    value goes into `terms["normal"]` when a dict is passed).  Returns (photometric, depth_term, vpixels); `anchor=None` (a
+    camera that lost the vote) means no depth term: depth_term is None.  Whether `vpixels` may still go to `backward_raw`
+    with `color_cotangent=True` is `StepLoss.color_cotangent` of the same call of `training_loss`."""
+    from . import training_loss as T
+    check_frame(image)
+    w = depth_weight(step, weight, final_scale, steps)
+    out = T.training_loss(rast, image, target, lambda_dssim=lambda_dssim, bgrid=bgrid, view=view,
+                          depth=None if anchor is None else T.DepthTerm(prior, anchor, qstep, w, lambda_grad),
+                          normal=None if normal_weight is None else T.NormalTerm(camera, normal_weight))
+    if terms is not None and out.normal_term is not None:
+        terms["normal"] = out.normal_term
+    return out.photometric, out.depth_term, out.vpixels

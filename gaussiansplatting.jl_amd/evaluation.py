@@ -11,57 +11,29 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _args as A
 from . import _lib as L
 
 METRICS = ("eval_ssim", "eval_mse", "eval_psnr", "eval_l1")
 
 
-def _torch():
-    import torch
-    return torch
-
-
-def _check_frame(image, sky_rgb):
-    torch = _torch()
-    if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dtype == torch.float32 and image.is_contiguous()
-            and image.dim() == 3 and image.shape[2] >= 3):
-        raise ValueError("image must be a contiguous float32 (H, W, C >= 3) HIP tensor")
-    H, W, Cn = image.shape
+def _check_scored(image, sky_rgb):
+    message = "image must be a contiguous float32 (H, W, C >= 3) HIP tensor"
+    H, W, Cn = A.check(image, message, shape=(None, None, None)).shape
+    if Cn < 3:
+        raise ValueError(message)
     if sky_rgb is not None:
         if Cn < 5:
             raise ValueError("a sky frame needs the alpha row of a :rgbd / :rgbdn frame (C >= 5): :rgb has none")
-        _check_like(sky_rgb, "sky_rgb", (H, W, 3), image.device)
+        A.check_like(sky_rgb, "sky_rgb", (H, W, 3), image.device)
     return H, W, Cn
-
-
-def _check_like(t, name, shape, device, dtype=None):
-    torch = _torch()
-    dtype = torch.float32 if dtype is None else dtype
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)
-            and t.device == device):
-        raise ValueError(f"{name} must be a contiguous {str(dtype).split('.')[-1]} HIP tensor of shape {tuple(shape)} on the image's device")
-    return t
 
 
 def eval_scratch_bytes(W: int, H: int) -> int:
     return int(L.load().gsr_eval_scratch_bytes(int(W), int(H)))
 
 
-_SCRATCH: dict = {}  # grow-only scratch of eval_metrics, per device and image size
-
-
-def _scratch_for(scratch, W, H, device):
-    torch = _torch()
-    nb = eval_scratch_bytes(W, H)
-    if scratch is None:
-        buf = _SCRATCH.get((W, H, device))
-        if buf is None:
-            buf = _SCRATCH[(W, H, device)] = torch.empty(nb, dtype=torch.uint8, device=device)
-        return buf
-    if not (isinstance(scratch, torch.Tensor) and scratch.is_cuda and scratch.is_contiguous() and scratch.device == device
-            and scratch.numel() * scratch.element_size() >= nb and scratch.data_ptr() % 8 == 0):
-        raise ValueError(f"scratch must be a contiguous, 8-byte aligned HIP tensor of at least {nb} bytes on the image's device")
-    return scratch
+_SCRATCH = A.FrameScratch(eval_scratch_bytes, align=8)  # eval_metrics' per-workgroup partials
 
 
 def eval_metrics(image, target, sky_rgb=None, quantize: bool = False, ssim_map=None, out=None, scratch=None):
@@ -70,24 +42,24 @@ def eval_metrics(image, target, sky_rgb=None, quantize: bool = False, ssim_map=N
     `quantize` (training.jl:514-526).  `target`: float32 (3, H, W), or uint8 (H, W, 3) as the dataset stores images —
     converted as u · (1/255) in the kernel's loads.  `ssim_map` (3, H, W), when given, receives the SSIM map of the scored
     colours.  Nothing is read back: `.cpu()` the result, or let `validate` do it once for all views."""
-    torch = _torch()
-    H, W, Cn = _check_frame(image, sky_rgb)
+    torch = A._torch()
+    H, W, Cn = _check_scored(image, sky_rgb)
     if not isinstance(target, torch.Tensor):
         raise ValueError("target must be a HIP tensor")
     if target.dtype == torch.uint8:
-        _check_like(target, "target", (H, W, 3), image.device, torch.uint8)
+        A.check_like(target, "target", (H, W, 3), image.device, torch.uint8)
         t32, t8 = None, target
     elif target.dtype == torch.float32:
-        _check_like(target, "target", (3, H, W), image.device)
+        A.check_like(target, "target", (3, H, W), image.device)
         t32, t8 = target, None
     else:
         raise ValueError("target must be float32 (3, H, W) or uint8 (H, W, 3)")
     if ssim_map is not None:
-        _check_like(ssim_map, "ssim_map", (3, H, W), image.device)
+        A.check_like(ssim_map, "ssim_map", (3, H, W), image.device)
         if ssim_map.data_ptr() == image.data_ptr():
             raise ValueError("ssim_map must not be the image")
-    out = torch.empty(4, dtype=torch.float32, device=image.device) if out is None else _check_like(out, "out", (4,), image.device)
-    buf = _scratch_for(scratch, W, H, image.device)
+    out = torch.empty(4, dtype=torch.float32, device=image.device) if out is None else A.check_like(out, "out", (4,), image.device)
+    buf = _SCRATCH.get(scratch, W, H, image.device)
     with torch.cuda.device(image.device):
         L.check(L.load().gsr_eval_metrics(W, H, Cn, image.data_ptr(), L.ptr(sky_rgb), L.ptr(t32), L.ptr(t8), 1 if quantize else 0,
                                           L.ptr(ssim_map), out.data_ptr(), buf.data_ptr(), L.stream()))
@@ -99,10 +71,10 @@ def frame_rgb8(image, sky_rgb=None, flip_rows: bool = False, out=None):
     `sky_rgb` when given, each floor(clamp(x, 0, 1) · 255 + 0.5) — the level `eval_metrics(quantize=True)` scores, bit for
     bit.  flip_rows=True reverses the row order (`gl_texture`, rasterizer.jl:155-182).  The layout is the dataset's: an
     exported frame can be passed back as a uint8 `target`."""
-    torch = _torch()
-    H, W, Cn = _check_frame(image, sky_rgb)
+    torch = A._torch()
+    H, W, Cn = _check_scored(image, sky_rgb)
     out = torch.empty((H, W, 3), dtype=torch.uint8, device=image.device) if out is None else \
-        _check_like(out, "out", (H, W, 3), image.device, torch.uint8)
+        A.check_like(out, "out", (H, W, 3), image.device, torch.uint8)
     with torch.cuda.device(image.device):
         L.check(L.load().gsr_frame_rgb8(W, H, Cn, image.data_ptr(), L.ptr(sky_rgb), 1 if flip_rows else 0, out.data_ptr(), L.stream()))
     return out
@@ -135,7 +107,7 @@ def validate(rast, points, acts, rotations, cameras, targets, sh_degree, backgro
     when `sky` (a SkyDome) is given — pass the zero background a dome trains over —, and `eval_metrics` into row v of one
     (V, 4) device tensor; ONE read-back at the end.  quantize=True scores the 8-bit picture (the published numbers:
     GaussianSplatting.jl:329); False is the in-training readout (:182)."""
-    torch = _torch()
+    torch = A._torch()
     cameras, targets = list(cameras), list(targets)
     if len(cameras) != len(targets):
         raise ValueError(f"{len(cameras)} cameras, {len(targets)} targets")

@@ -13,6 +13,7 @@ import numpy as np
 
 import torch
 
+from . import _args as A
 from . import _lib as L
 from .densification import GaussianModel
 from .sky_dome import SH0, inverse_sigmoid
@@ -23,9 +24,7 @@ f32 = np.float32
 def _check_points(points, name="points"):
     if not (isinstance(points, torch.Tensor) and points.is_cuda):
         raise ValueError(f"{name} must be a HIP device tensor (no CPU path)")
-    if not (points.dtype == torch.float32 and points.is_contiguous() and points.dim() == 2 and points.shape[1] == 3):
-        raise ValueError(f"{name} must be a contiguous float32 (N, 3) HIP tensor")
-    return int(points.shape[0])
+    return int(A.check(points, f"{name} must be a contiguous float32 (N, 3) HIP tensor", shape=(None, 3)).shape[0])
 
 
 def morton_permutation(points: torch.Tensor, box) -> torch.Tensor | None:

@@ -17,6 +17,7 @@ import math
 
 import numpy as np
 
+from . import _args as A
 from . import _lib as L
 
 f32 = np.float32
@@ -82,11 +83,6 @@ def sky_hard(mask):
 
 # ---- the dome ----
 
-def _torch():
-    import torch
-    return torch
-
-
 class SkyDome:
     """SkyDome(kab, camera, opt_params; center, radius, up, color) — sky_dome.jl:43-48,120-146.  `gaussians` (a
     ply.GaussianModel of device tensors, max_sh_degree 0): frozen points `center + radius · dirs`, log-scales
@@ -97,7 +93,7 @@ class SkyDome:
 
     def __init__(self, camera, n: int = SKY_DOME_POINTS, shape: str = "hemisphere", center=(0.0, 0.0, 0.0), radius: float = 100.0,
                  up=(0.0, 0.0, 1.0), color=(0.5, 0.5, 0.5), lr: float = SKY_DOME_LR, device="cuda"):
-        torch = _torch()
+        torch = A._torch()
         from . import optim, ply
         from .rasterizer import GaussianRasterizer
         if n <= 0:
@@ -169,41 +165,15 @@ def sky_backward(sky: SkyDome, camera, vsky, features_dc=None, rast=None):
 
 # ---- composite and sky-mask loss (device) ----
 
-def _check_frame(image, name="image"):
-    torch = _torch()
-    if not (image.is_cuda and image.dtype == torch.float32 and image.is_contiguous() and image.dim() == 3
-            and image.shape[2] in (5, 8)):
-        raise ValueError(f"{name} must be a contiguous float32 (H, W, 5) or (H, W, 8) HIP tensor (a :rgbd / :rgbdn frame: "
-                         ":rgb has no alpha row)")
-    return image
-
-
-def _check_like(t, name, shape, device):
-    torch = _torch()
-    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == device):
-        raise ValueError(f"{name} must be a contiguous float32 HIP tensor of shape {tuple(shape)} on the image's device")
-    return t
+check_frame = A.frame_check((5, 8), "{} must be a contiguous float32 (H, W, 5) or (H, W, 8) HIP tensor (a :rgbd / :rgbdn frame: "
+                            ":rgb has no alpha row)")
 
 
 def sky_scratch_bytes(W: int, H: int) -> int:
     return int(L.load().gsr_sky_scratch_bytes(int(W), int(H)))
 
 
-_SCRATCH: dict = {}  # grow-only scratch of the functional entry points, per device and image size
-
-
-def _scratch_for(scratch, W, H, device, create=True):
-    torch = _torch()
-    nb = sky_scratch_bytes(W, H)
-    if scratch is None:
-        buf = _SCRATCH.get((W, H, device))
-        if buf is None and create:
-            buf = _SCRATCH[(W, H, device)] = torch.empty(nb, dtype=torch.uint8, device=device)
-        return buf
-    if not (isinstance(scratch, torch.Tensor) and scratch.is_cuda and scratch.is_contiguous() and scratch.device == device
-            and scratch.numel() * scratch.element_size() >= nb and scratch.data_ptr() % 8 == 0):
-        raise ValueError(f"scratch must be a contiguous, 8-byte aligned HIP tensor of at least {nb} bytes on the image's device")
-    return scratch
+_SCRATCH = A.FrameScratch(sky_scratch_bytes, align=8)  # what composite_sky with a mask leaves for its backward
 
 
 def composite_sky(image, sky_rgb, out=None, sky_weight=None, sky_loss_weight: float = 1.0, scratch=None):
@@ -211,14 +181,14 @@ def composite_sky(image, sky_rgb, out=None, sky_weight=None, sky_loss_weight: fl
     whole frame (channels >= 3 copied); `out=image` composites in place.  With `sky_weight` (H, W) the same pass evaluates
     the sky-mask loss: returns (out, sky_loss_weight · sky_opacity_loss) and leaves in `scratch` (default: a buffer kept
     per device and image size) what `sky_composite_backward_` reads."""
-    torch = _torch()
-    H, W, Cn = _check_frame(image).shape
-    _check_like(sky_rgb, "sky_rgb", (H, W, 3), image.device)
-    out = torch.empty_like(image) if out is None else _check_like(out, "out", image.shape, image.device)
+    torch = A._torch()
+    H, W, Cn = check_frame(image).shape
+    A.check_like(sky_rgb, "sky_rgb", (H, W, 3), image.device)
+    out = torch.empty_like(image) if out is None else A.check_like(out, "out", image.shape, image.device)
     loss = buf = None
     if sky_weight is not None:
-        _check_like(sky_weight, "sky_weight", (H, W), image.device)
-        buf = _scratch_for(scratch, W, H, image.device)
+        A.check_like(sky_weight, "sky_weight", (H, W), image.device)
+        buf = _SCRATCH.get(scratch, W, H, image.device)
         loss = torch.empty((), dtype=torch.float32, device=image.device)
     with torch.cuda.device(image.device):
         L.check(L.load().gsr_sky_composite_forward(W, H, Cn, image.data_ptr(), sky_rgb.data_ptr(), L.ptr(sky_weight),
@@ -241,17 +211,17 @@ def sky_composite_backward_(image, sky_rgb, vpixels, sky_weight=None, sky_loss_w
     ADDS -(g · sky) + sky_loss_weight · 2·w·α / max(Σw, 1) onto channel 4 of `vpixels`, in place, as one fp32 add; no other
     channel is written.  With a mask it needs `composite_sky` of the same image and mask (and the same `scratch`) run
     before it.  A `vpixels` this was added onto must go to `backward_raw` with `color_cotangent=False`."""
-    torch = _torch()
-    H, W, Cn = _check_frame(image).shape
-    _check_like(sky_rgb, "sky_rgb", (H, W, 3), image.device)
-    _check_like(vpixels, "vpixels", image.shape, image.device)
+    torch = A._torch()
+    H, W, Cn = check_frame(image).shape
+    A.check_like(sky_rgb, "sky_rgb", (H, W, 3), image.device)
+    A.check_like(vpixels, "vpixels", image.shape, image.device)
     if vpixels.data_ptr() == image.data_ptr():
         raise ValueError("vpixels must not be the image")
-    vsky = torch.empty_like(sky_rgb) if vsky is None else _check_like(vsky, "vsky", (H, W, 3), image.device)
+    vsky = torch.empty_like(sky_rgb) if vsky is None else A.check_like(vsky, "vsky", (H, W, 3), image.device)
     buf = None
     if sky_weight is not None:
-        _check_like(sky_weight, "sky_weight", (H, W), image.device)
-        buf = _scratch_for(scratch, W, H, image.device, create=False)
+        A.check_like(sky_weight, "sky_weight", (H, W), image.device)
+        buf = _SCRATCH.get(scratch, W, H, image.device, create=False)
         if buf is None:
             raise ValueError("run composite_sky of this image and mask first: the backward reads what it left on the device")
     with torch.cuda.device(image.device):
@@ -266,73 +236,39 @@ def sky_opacity_loss(image, sky_weight, weight: float = 1.0):
     channel, so that a saturated pixel keeps its gradient 2w / Σw —, differentiable w.r.t. the (H, W, C) frame (channel 4;
     the others get zeros).  The stand-alone form: it runs the fused passes against a zero sky frame; a training step uses
     `l1_ssim_sky_loss`, where the loss rides on the composite's passes."""
-    torch = _torch()
-
-    class _SkyOpacityLoss(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, image):
-            image = image.detach().contiguous()
-            H, W, _ = _check_frame(image).shape
-            ctx.scratch = torch.empty(sky_scratch_bytes(W, H), dtype=torch.uint8, device=image.device)
-            ctx.zero_sky = torch.zeros((H, W, 3), dtype=torch.float32, device=image.device)
-            ctx.save_for_backward(image)
-            return composite_sky(image, ctx.zero_sky, None, sky_weight, weight, scratch=ctx.scratch)[1]
-
-        @staticmethod
-        def backward(ctx, delta):
-            (image,) = ctx.saved_tensors
-            v = torch.zeros_like(image)
-            sky_composite_backward_(image, ctx.zero_sky, v, sky_weight, weight, scratch=ctx.scratch)
-            return v * delta
-
-    return _SkyOpacityLoss.apply(image)
+    zero_sky = A._torch().zeros(tuple(image.shape[:2]) + (3,), dtype=A._torch().float32, device=image.device)
+    return A.cotangent_term(image, lambda im, scratch: composite_sky(im, zero_sky, None, sky_weight, weight, scratch=scratch)[1],
+                            lambda im, v, scratch: sky_composite_backward_(im, zero_sky, v, sky_weight, weight, scratch=scratch),
+                            sky_scratch_bytes)
 
 
 def l1_ssim_sky_loss(rast, image, target, sky: SkyDome, camera, sky_weight=None, sky_loss_weight: float = 1.0, step: int = None,
                      sky_loss_from_iter: int = SKY_LOSS_FROM_ITER, lambda_dssim: float = 0.2, bgrid=None, view: int = None,
                      depth: dict = None, normal: float = None, terms: dict = None):
-    """The loss of `step!` with `use_sky_dome` (training.jl:634-639,673-676,721-725): renders the dome, composites it behind
-    `image`, runs the fused L1 / D-SSIM loss head on the composite (through the view's bilateral grid when `bgrid` and
-    `view` are given), and pulls the head's cotangent back through the composite: onto the sky frame, and onto the scene's
-    alpha channel.  With `sky_weight` (H, W) — ignored while `step` < `sky_loss_from_iter`; `step=None` means "active" —
-    sky_loss_weight · sky_opacity_loss rides on the same two passes.  Then, exactly as `l1_ssim_depth_loss` adds them:
-    `depth` = dict(prior=, anchor=, qstep=, step=[, weight=, final_scale=, steps=, lambda_grad=]) adds the anchored depth term
-    (its value goes into `terms["depth"]`), and for a :rgbdn frame `normal` (a weight) adds the depth-normal consistency term
-    (`terms["normal"]`).  Returns (photometric, sky_term or None, vpixels, vsky).
+    """The loss of `step!` with `use_sky_dome` (training.jl:634-639,673-676,721-725): `training_loss` with the dome behind
+    `image` and the schedules resolved here.  `sky_weight` (H, W) is ignored while `step` < `sky_loss_from_iter` (`step=None`
+    means "active"): sky_term is then None.  `depth` = dict(prior=, anchor=, qstep=, step=[, weight=, final_scale=, steps=,
+    lambda_grad=]) adds the anchored depth term at depth_weight(step) (`terms["depth"]`; ignored when its anchor is None), and
+    for a :rgbdn frame `normal` (a weight) the depth-normal term (`terms["normal"]`).  Returns (photometric, sky_term or None,
+    vpixels, vsky).
 
-    `image` must be the scene rendered over a ZERO background (training.jl:596), and `vpixels` carries an alpha cotangent:
-    it must go to the scene's `backward_raw` with `color_cotangent=False`.  `vsky` goes to `sky_backward(sky, camera, vsky)`."""
-    from . import fused_ssim
-    _check_frame(image)
+    `image` must be the scene rendered over a ZERO background (training.jl:596); `vpixels` carries an alpha cotangent
+    (`StepLoss.color_cotangent` is false); `vsky` goes to `sky_backward(sky, camera, vsky)`."""
+    from . import depth_supervision as DS, training_loss as T
+    check_frame(image)
     active = sky_weight is not None and (step is None or step >= sky_loss_from_iter)
-    mask = sky_weight if active else None
-    sky_rgb = render_sky(sky, camera)
-    comp = composite_sky(image, sky_rgb, None, mask, sky_loss_weight)
-    sky_term = None
-    if active:
-        comp, sky_term = comp
-    if bgrid is not None:
-        from . import bilateral_grid
-        loss, vpix = bilateral_grid.l1_ssim_bilateral_loss(rast, comp, target, bgrid, view, lambda_dssim)
-    else:
-        loss, vpix = fused_ssim.l1_ssim_loss(rast, comp, target, lambda_dssim)
-    vsky = sky_composite_backward_(image, sky_rgb, vpix, mask, sky_loss_weight)
     if depth is not None and depth.get("anchor") is not None:
-        from . import depth_supervision as DS
         w = DS.depth_weight(depth["step"], depth.get("weight", DS.DEPTH_LOSS_WEIGHT),
                             depth.get("final_scale", DS.DEPTH_LOSS_FINAL_SCALE), depth.get("steps", 30000))
-        lg = depth.get("lambda_grad", DS.DEPTH_LOSS_GRADIENT_WEIGHT)
-        depth_term = DS.depth_loss(image, depth["prior"], depth["anchor"], depth["qstep"], w, lg)
-        DS.depth_loss_backward_(image, depth["prior"], depth["anchor"], depth["qstep"], vpix, w, lg)
-        if terms is not None:
-            terms["depth"] = depth_term
-    if normal is not None:
-        from . import geometry_regularization as G
-        normal_term = G.depth_normal_loss(image, camera, normal)
-        G.depth_normal_loss_backward_(image, camera, vpix, normal)
-        if terms is not None:
-            terms["normal"] = normal_term
-    return loss, sky_term, vpix, vsky
+        depth = T.DepthTerm(depth["prior"], depth["anchor"], depth["qstep"], w, depth.get("lambda_grad", DS.DEPTH_LOSS_GRADIENT_WEIGHT))
+    else:
+        depth = None
+    out = T.training_loss(rast, image, target, lambda_dssim=lambda_dssim, bgrid=bgrid, view=view, depth=depth,
+                          sky=T.SkyTerm(sky, camera, sky_weight if active else None, sky_loss_weight),
+                          normal=None if normal is None else T.NormalTerm(camera, normal))
+    if terms is not None:
+        terms.update({k: v for k, v in (("depth", out.depth_term), ("normal", out.normal_term)) if v is not None})
+    return out.photometric, out.sky_term, out.vpixels, out.vsky
 
 
 # ---- export ----
