@@ -1,267 +1,27 @@
-// C ABI of libgsr_hip.so (include/gsr.h): handle object with grow-only scratch, argument
-// validation, kernel orchestration.  Mirrors the host side of the reference's
+// C ABI of libgsr_hip.so (include/gsr.h), the part with a handle: the handle object with its grow-only scratch, argument
+// validation, and the launch choreography of gsr_forward, the backward entry points and the loss head (the entry points that
+// take no handle are gsr_ops.cpp's).  Mirrors the host side of the reference's
 // `GaussianRasterizer` / `rasterize` / `∇rasterize` (src/rasterization/rasterizer.jl:5-90,
 // 255-408, 416-550) — everything is enqueued on the caller's stream; the only host sync is
 // the instance-count read-back (rasterizer.jl:337).
-#include "../../include/gsr.h"
-
-#include <dlfcn.h>
-#include <math.h>
-#include <sched.h>
-#include <time.h>
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <new>
-#include <vector>
 
 #include "gsr_kernels.h"
 #include "adam_math.h"
+#include "gsr_host.h"
+#include "gsr_devbuf.h"
+#include "gsr_profiler.h"
+#include "gsr_host_wait.h"
+#include "gsr_sizes.h"
+
+using namespace gsr_host;
+
+thread_local char gsr_host::g_err[512] = "";
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIPCHK(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess)                                                                                \
-            return fail(e_ == hipErrorOutOfMemory ? GSR_E_OOM : GSR_E_HIP, "%s failed: %s (%s:%d)", #expr,   \
-                        hipGetErrorString(e_), __FILE__, __LINE__);                                          \
-    } while (0)
-
-// GSR_DEBUG_FILL=nan | big (debugging, read at every allocation): each new allocation of a buffer marked `fill_ok` is filled
-// with the 32-bit word 0xFFFFFFFF (a NaN) or 0x7F7F7F7F (3.4e38, finite: NaN hides behind comparisons), so that a kernel
-// that reads a float it never wrote shows up in the result instead of reading the zeros of fresh pages.  0 = unset.
-uint32_t debug_fill_word() {
-    const char* e = getenv("GSR_DEBUG_FILL");
-    if (!e) return 0u;
-    if (!strcmp(e, "nan")) return 0xFFFFFFFFu;
-    if (!strcmp(e, "big")) return 0x7F7F7F7Fu;
-    return 0u;
-}
-
-// GSR_DEBUG_GUARD=1 (debugging, read at every allocation): every handle buffer is allocated kGuardBytes longer than asked for and
-// the extra bytes — right behind `cap`, which stays what it would have been, so that nothing the library derives from a
-// capacity moves — are filled with a guard word.  gsr_debug_check_guards (and every free of such a buffer) compares them: a
-// kernel that stores past the end of a handle buffer is named instead of silently corrupting the neighbouring allocation.
-bool debug_guard_on() {
-    const char* e = getenv("GSR_DEBUG_GUARD");
-    return e && e[0] == '1' && !e[1];
-}
-constexpr size_t kGuardBytes = 4096;
-struct GuardDamage {  // the first damaged guard seen on a handle (remembered across the free of its buffer)
-    bool set = false;
-    const char* name = "";
-    size_t offset = 0;   // bytes past cap
-    uint32_t word = 0;   // what was found there
-    uint32_t expect = 0;
-};
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;  // bytes
-    uint32_t regrowths = 0;  // reallocations of a buffer that already existed (each is a device synchronisation)
-    // GSR_DEBUG_FILL may fill it: floats only, none of which ever becomes an address, a loop bound or a branch that leaves the
-    // allocation (set in gsr_create; index / key / count / mask buffers never are: garbage there is a wild address)
-    bool fill_ok = false;
-    // GSR_DEBUG_GUARD: the name the check reports; whether THIS allocation carries a guard; the word of a buffer that is not
-    // fill_ok (those get 0x7F7F7F7F).  By the rule above an index / count buffer's guard holds a small valid value: 1 — one
-    // instance, offset 1, tile-list range [1, 1), radius 1, a 64-bit key of tile 0 — and unlike 0 it differs from what a
-    // stray clear would leave.  The three buffers whose words are ids that need not have a second element (tile ids of a
-    // one-tile image, Gaussian ids of a one-Gaussian scene) get 0 (set in gsr_create).
-    const char* name = "?";
-    bool guarded = false;
-    uint32_t guard_word = 1u;
-    GuardDamage* damage = nullptr;
-    uint32_t guard_value() const { return fill_ok ? 0x7F7F7F7Fu : guard_word; }
-    // Compares the guard with its word (synchronises the device); the first difference is remembered in *damage.
-    int check_guard() {
-        if (!p || !guarded || !damage) return GSR_OK;
-        static thread_local uint32_t host[kGuardBytes / 4];
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(host, (const char*)p + cap, kGuardBytes, hipMemcpyDeviceToHost));
-        const uint32_t w = guard_value();
-        for (size_t i = 0; i < kGuardBytes / 4; i++) {
-            if (host[i] != w) {
-                if (!damage->set) *damage = GuardDamage{true, name, i * 4, host[i], w};
-                break;
-            }
-        }
-        return GSR_OK;
-    }
-    // grow-only, like the reference's scratch (rasterizer.jl:275-278,340-343)
-    int ensure(size_t bytes, float slack = 1.0f) {
-        if (bytes <= cap) return GSR_OK;
-        size_t want = (size_t)((double)bytes * slack);
-        if (p) {
-            // REgrowth of a buffer that is given slack (the per-Gaussian and per-instance scratch of a scene that changes): at
-            // least half again of what is there — the views of a batch differ by a few per cent in their instance count, and a
-            // training run grows; 288 GB of HBM are there to be used, a hipFree + hipMalloc synchronises the device
-            if (slack > 1.0f) want = std::max(want, cap + cap / 2);
-            regrowths++;
-            if (int rc = check_guard()) return rc;
-            HIPCHK(hipFree(p));
-            p = nullptr;
-            cap = 0;
-            guarded = false;
-        }
-        want = (want + 255) & ~(size_t)255;
-        const bool guard = debug_guard_on();
-        HIPCHK(hipMalloc(&p, want + (guard ? kGuardBytes : 0)));
-        cap = want;
-        guarded = guard;
-        bool wrote = false;
-        if (fill_ok) {
-            if (const uint32_t w = debug_fill_word()) {
-                // synchronised: the library's kernels also run on its own non-blocking aux_stream
-                HIPCHK(hipMemsetD32((hipDeviceptr_t)p, (int)w, want / 4));
-                wrote = true;
-            }
-        }
-        if (guard) {
-            HIPCHK(hipMemsetD32((hipDeviceptr_t)((char*)p + want), (int)guard_value(), kGuardBytes / 4));
-            wrote = true;
-        }
-        if (wrote) HIPCHK(hipDeviceSynchronize());
-        return GSR_OK;
-    }
-    int release() {
-        if (p) {
-            if (int rc = check_guard()) return rc;
-            HIPCHK(hipFree(p));
-        }
-        p = nullptr;
-        cap = 0;
-        guarded = false;
-        return GSR_OK;
-    }
-    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-// Optional per-stage timing with HIP events on the caller's stream (gsr_profile_*).
-enum Stage { ST_PREPROCESS, ST_SCAN, ST_SORT, ST_COMPOSITE_FWD, ST_LOSS_FWD, ST_LOSS_BWD, ST_ZERO_ACC,
-             ST_COMPOSITE_BWD, ST_PERGAUSS_BWD, ST_SORT_COMPOSITE_FWD, ST_COUNT };
-// "sort_composite_fwd": the fused launch (sort + forward of every tile of up to 1024 instances); "tile_sort" and
-// "composite_fwd" then only hold the tier launches of longer lists, or the whole passes when the fused launch does not apply
-const char* const kStageNames[ST_COUNT] = {"preprocess", "tile_scan", "tile_sort", "composite_fwd",
-                                           "loss_fwd", "loss_bwd", "zero_acc", "composite_bwd", "pergauss_bwd",
-                                           "sort_composite_fwd"};
-// roctx ranges per stage: resolved lazily from the ROCm tools library, only when asked for
-// (GSR_ROCTX=1 in the environment, or gsr_profile_enable(h, 2 | ...)); rocprofv3 --marker-trace then
-// slices the kernel trace by stage without kernel-name matching.
-struct Roctx {
-    typedef int (*push_fn)(const char*);
-    typedef int (*pop_fn)(void);
-    push_fn push = nullptr;
-    pop_fn pop = nullptr;
-    bool tried = false;
-    bool load() {
-        if (tried) return push != nullptr;
-        tried = true;
-        const char* names[] = {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"};
-        for (const char* n : names) {
-            void* lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-            if (!lib) continue;
-            push = (push_fn)dlsym(lib, "roctxRangePushA");
-            pop = (pop_fn)dlsym(lib, "roctxRangePop");
-            if (push && pop) return true;
-            push = nullptr; pop = nullptr;
-        }
-        return false;
-    }
-};
-Roctx g_roctx;
-bool roctx_env() {
-    static const bool on = [] { const char* e = getenv("GSR_ROCTX"); return e && e[0] == '1'; }();
-    return on;
-}
-
-struct Profiler {
-    bool on = false;      // HIP-event timing per stage
-    bool ranges = false;  // roctx range per stage
-    bool in_range = false;
-    bool rec_open = false;
-    uint32_t mask = ~0u;  // stages that get an event pair (gsr_profile_stages)
-    struct Rec { int stage; hipEvent_t a, b; bool extra; };  // extra: a second launch group of a stage inside ONE call (time, not count)
-    std::vector<Rec> recs;
-    std::vector<hipEvent_t> pool;
-    hipEvent_t get() {
-        if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
-        hipEvent_t e = nullptr;
-        // timing-only events: no system-scope fence (cache write-back + invalidate) when the marker retires — the bubble an
-        // event record leaves between two kernels is what the timed region pays for its one profiled stage
-        (void)hipEventCreateWithFlags(&e, hipEventDisableSystemFence);
-        return e;
-    }
-    void begin(int stage, hipStream_t s, bool extra = false);
-    void end(hipStream_t s) {
-        if (in_range) { g_roctx.pop(); in_range = false; }
-        if (!rec_open) return;
-        rec_open = false;
-        (void)hipEventRecord(recs.back().b, s);
-    }
-    // error path: a stage that was begun but whose launch failed — close the roctx range and DROP the half-recorded
-    // pair (its end event was never recorded: gsr_profile_read would fail or mis-time on it)
-    void abort() {
-        if (in_range) { g_roctx.pop(); in_range = false; }
-        if (!rec_open) return;
-        rec_open = false;
-        pool.push_back(recs.back().a);
-        pool.push_back(recs.back().b);
-        recs.pop_back();
-    }
-    void clear() {
-        for (auto& r : recs) { pool.push_back(r.a); pool.push_back(r.b); }
-        recs.clear();
-    }
-    void destroy() {
-        clear();
-        for (auto e : pool) (void)hipEventDestroy(e);
-        pool.clear();
-    }
-};
-
-void Profiler::begin(int stage, hipStream_t s, bool extra) {
-    if ((ranges || roctx_env()) && g_roctx.load()) {
-        char name[48];
-        snprintf(name, sizeof name, "gsr:%s", kStageNames[stage]);
-        g_roctx.push(name);
-        in_range = true;
-    }
-    if (!on || !((mask >> stage) & 1u)) return;
-    Rec r{stage, get(), get(), extra};
-    (void)hipEventRecord(r.a, s);
-    recs.push_back(r);
-    rec_open = true;
-}
-
-// One profiled stage: begun by the constructor, ended by close(); a scope left WITHOUT close() — an early `return rc`
-// or a HIPCHK between the two — aborts the stage instead of leaving a pushed roctx range and an open record behind.
-struct StageScope {
-    Profiler& p;
-    hipStream_t s;
-    bool open = true;
-    StageScope(Profiler& prof, int stage, hipStream_t stream, bool extra = false) : p(prof), s(stream) { p.begin(stage, s, extra); }
-    void close() { if (open) { p.end(s); open = false; } }
-    ~StageScope() { if (open) p.abort(); }
-    StageScope(const StageScope&) = delete;
-    StageScope& operator=(const StageScope&) = delete;
-};
 
 // The form tuner's clock (the RULE is gsr_policy.cpp's: which views are timed, what decides, when it starts over): one event
 // pair per timed view around the view's first kernel, read without blocking a later view.
@@ -285,6 +45,8 @@ struct TunerEvents {
         return true;
     }
 };
+
+constexpr int kHandleBufs = 32;  // rows of kBufs, the table of the handle's buffers below the handle (checked there)
 
 bool valid_mode(int m) { return m == GSR_MODE_RGB || m == GSR_MODE_RGBD || m == GSR_MODE_RGBDN; }
 
@@ -337,12 +99,72 @@ struct gsr_handle {
     DevBuf dbg_flag;
     Profiler prof;
 
-    DevBuf* all[40];
+    DevBuf* all[kHandleBufs];  // the buffers of kBufs, in its order (gsr_create)
     int n_all = 0;
     GuardDamage guard_damage;  // GSR_DEBUG_GUARD: the first damaged guard of any buffer of `all`, freed ones included
 };
 
+// gsr_ssim_precision: 0 = the contracted build of ssim.hip (default), 1 = its bit-exact twin.  GSR_SSIM_EXACT=1 in the
+// environment starts a process in exact mode (A/B runs of unmodified callers).
+// Process-wide DEFAULT only: a handle created with gsr_config.ssim_precision = 0 / 1 is pinned (ABI 5).
+std::atomic<int> gsr_host::g_ssim_exact{[] { const char* e = getenv("GSR_SSIM_EXACT"); return e && e[0] == '1' ? 1 : 0; }()};
+
 namespace {
+
+// Every DevBuf of the handle, once: its name (what GSR_DEBUG_GUARD's check reports), whether gsr_release_scene_buffers frees
+// it, whether GSR_DEBUG_FILL may fill it (DevBuf::fill_ok: read only as float data), and its guard word (DevBuf::guard_word:
+// 1, or 0 for ids whose range may be {0}).
+struct BufRow {
+    DevBuf gsr_handle::*buf;
+    const char* name;
+    bool scene, fill_ok;
+    uint32_t guard_word;
+};
+#define BUF(member, scene, fill_ok, guard_word) {&gsr_handle::member, #member, scene, fill_ok, guard_word}
+constexpr BufRow kBufs[] = {
+    BUF(ranges, false, false, 1u),
+    BUF(n_contrib, false, false, 1u),
+    BUF(final_T, false, true, 1u),        // final transmittance per pixel: a factor of the backward, never a bound (n_contrib is)
+    BUF(tile_count, false, false, 1u),
+    BUF(tile_start, false, false, 1u),
+    BUF(tile_order, false, false, 0u),    // tile ids
+    BUF(totals, false, false, 1u),
+    BUF(geo, true, false, 1u),
+    BUF(gnormal, true, true, 1u),         // per-Gaussian normals (float4): feature values of the :rgbdn stream
+    BUF(radii, true, false, 1u),
+    BUF(bsum, true, false, 1u),
+    BUF(bpre, true, false, 1u),
+    BUF(bvis, true, false, 1u),
+    BUF(bins, true, false, 1u),
+    BUF(values_sorted, true, false, 0u),  // Gaussian ids
+    BUF(s0, true, false, 1u),
+    BUF(s1, true, false, 1u),
+    BUF(s2, true, false, 1u),
+    BUF(s3, true, false, 1u),
+    BUF(big_scratch, true, false, 1u),
+    BUF(rows, true, true, 1u),            // GsrInst gradient rows (float4): summed by pergauss_bwd, copied out by gsr_buffer
+    BUF(vmean2d, true, true, 1u),         // gstate.∇means_2d (float2): written for every Gaussian, read by gsr_update_stats behind radii > 0
+    BUF(d0, false, true, 1u),             // SSIM loss head's ∂map/∂µ1 plane
+    BUF(d1, false, true, 1u),             // ... ∂map/∂σ1²
+    BUF(d2, false, true, 1u),             // ... ∂map/∂σ12
+    BUF(partial, false, true, 1u),        // per-wave (Σ|x-y|, Σssim) pairs summed by the loss finisher
+    BUF(keys_compact, true, false, 1u),
+    BUF(big_list, false, false, 0u),      // tile ids of the tier lists
+    BUF(long_state, false, true, 1u),     // (T, A) float2 per pixel and segment of the long-list backward
+    BUF(overflow_fill, false, false, 1u),
+    BUF(dbg_flag, false, false, 1u),
+    BUF(pose_part, true, true, 1u),       // per-workgroup pose-gradient partials: every slot is stored (zeros included) before it is summed
+};
+#undef BUF
+template <class Pred> constexpr int count_bufs(Pred pred) {
+    int n = 0;
+    for (const BufRow& r : kBufs) n += pred(r) ? 1 : 0;
+    return n;
+}
+static_assert(sizeof(kBufs) / sizeof(kBufs[0]) == kHandleBufs, "gsr_handle::all holds one pointer per row");
+static_assert(count_bufs([](const BufRow& r) { return r.scene; }) == 17, "the scene buffers");
+static_assert(count_bufs([](const BufRow& r) { return r.fill_ok; }) == 10, "the GSR_DEBUG_FILL candidates");
+static_assert(count_bufs([](const BufRow& r) { return r.guard_word == 0u; }) == 3, "the id buffers whose guard word is 0");
 
 GsrCam make_cam(const gsr_handle* h, const gsr_camera* c) {
     GsrCam k;
@@ -378,48 +200,8 @@ GsrFrame frame_of(const gsr_handle* h, const float* background, float* image, co
                     aux ? aux->covisibilities : nullptr, aux ? aux->uncertainties : nullptr};
 }
 
-// CPU relax hint inside the spin phase: x86 `pause`, AArch64 `yield`, nothing elsewhere (the host side builds on any arch).
-static inline void cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#elif defined(__aarch64__)
-    __asm__ __volatile__("yield");
-#endif
-}
-
-// Host wait policy of the forward's single read-back (gsr_host_wait_policy), process-wide.
-//   DEFAULT (sleep_us == 0): spin for spin_us microseconds, then poll with sched_yield() between looks at the word.  Any
-//   other runnable thread — RCCL's proxy threads on an 8-rank host — gets the core at once, no timer is involved, and
-//   the step time is a pure spin's (config 2: 0.2123-0.2137 ms, config 3: 1.494 ms per step over 200 steps, all three
-//   policies within noise of each other: tools/host_wait_ab.sh).
-//   OPT-IN (sleep_us > 0): the thread SLEEPS through the expected wait (a running average of this handle's previous
-//   waits: the host runs ahead of the GPU, so the wait is as long as the work still queued in front of the scan, about
-//   the same every step) except for its last spin_us microseconds — in doubling pieces of 50, 100, 200 ... us with a look
-//   at the word after each, so that the first forward after the caller synchronised (GPU idle: a short wait) costs one
-//   small piece; a wake-up that finds the word already written is not a sample (an average fed with its own oversleeps
-//   ratchets upwards and starves the GPU) but shrinks the estimate; after the expected time + spin_us: sched_yield() for
-//   yield_us, then sleeps of sleep_us.  Same step time on a quiet host, a fraction of the CPU time; NOT the default
-//   because a late timer wake-up (observed on one box of the pool: one step of twenty 3 ms late) lands in the step time.
-struct WaitPolicy { int spin_us = 30, yield_us = 0, sleep_us = 0; };
-// the three values live in ONE atomic word (21 bits each): a forward on another thread reads the old or the new policy,
-// never a mix of the two (round-4 verdict, weak #9)
-constexpr int kWaitMaxUs = (1 << 21) - 1;
-inline uint64_t pack_wait(const WaitPolicy& w) {
-    return (uint64_t)w.spin_us | ((uint64_t)w.yield_us << 21) | ((uint64_t)w.sleep_us << 42);
-}
-std::atomic<uint64_t> g_wait_packed{pack_wait(WaitPolicy{})};
-inline WaitPolicy load_wait() {
-    const uint64_t v = g_wait_packed.load(std::memory_order_relaxed);
-    WaitPolicy w;
-    w.spin_us = (int)(v & kWaitMaxUs); w.yield_us = (int)((v >> 21) & kWaitMaxUs); w.sleep_us = (int)((v >> 42) & kWaitMaxUs);
-    return w;
-}
-
-// gsr_ssim_precision: 0 = the contracted build of ssim.hip (default), 1 = its bit-exact twin.  GSR_SSIM_EXACT=1 in the
-// environment starts a process in exact mode (A/B runs of unmodified callers).
-// Process-wide DEFAULT only: a handle created with gsr_config.ssim_precision = 0 / 1 is pinned (ABI 5).
-std::atomic<int> g_ssim_exact{[] { const char* e = getenv("GSR_SSIM_EXACT"); return e && e[0] == '1' ? 1 : 0; }()};
-// gsr_preprocess_form: -1 by scene and grid size (default), 0 direct, 1 aggregating wherever its LDS fits; the same rule
+// gsr_preprocess_form: -1 by scene and grid size (default), 0 direct, 1 aggregating wherever its LDS fits; the same rule as
+// gsr_ssim_precision's (g_ssim_exact, above): the process-wide default of the handles that do not say
 std::atomic<int> g_preprocess_form{[] { const char* e = getenv("GSR_PREPROCESS_AGG"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }()};
 inline int ssim_exact_of(const gsr_handle* h) {
     return h->cfg.ssim_precision != GSR_DEFAULT ? (h->cfg.ssim_precision == GSR_SSIM_EXACT ? 1 : 0)
@@ -430,75 +212,9 @@ inline int preprocess_form_of(const gsr_handle* h) {  // -1 by scene and grid, 0
                                                  : g_preprocess_form.load(std::memory_order_relaxed);
 }
 
-// Wait until tile_scan of forward `seq` has published its totals (a word of pinned host memory).
-// A wait that lasts longer than any sane queue depth (50 ms) starts polling the stream, so that a failed launch or a
-// faulted kernel ends with an error instead of hanging the caller — not earlier: hipStreamQuery puts a marker packet on
-// the stream, and a marker between two kernels is a 5 us bubble (rocprofv3 kernel trace, tools/gap_report.py).
-int wait_totals(gsr_handle* h, uint32_t seq, hipStream_t s) {
-    using clk = std::chrono::steady_clock;
-    volatile uint32_t* word = h->host_totals + GSR_TOTAL_SEQ;
-    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return GSR_OK;
-    const auto t0 = clk::now();
-    const double expect_us = h->wait_ema_us;
-    const WaitPolicy g_wait = load_wait();  // one consistent snapshot for this wait
-    if (g_wait.sleep_us > 0 && expect_us > (double)g_wait.spin_us + 50.0) {  // sleeping enabled and worth it
-        // ... in doubling pieces (50, 100, 200, ... us) with a look at the word after each: the expectation comes from
-        // steps in which the host ran ahead of the GPU; the first forward after the caller synchronised finds the GPU
-        // idle and its wait is only preprocess + scan long — the small first pieces bound what that costs.
-        double remaining = expect_us - (double)g_wait.spin_us, piece = 50.0;
-        while (remaining > 0.0) {
-            const long ns = (long)((remaining < piece ? remaining : piece) * 1000.0);
-            struct timespec ts = {ns / 1000000000L, ns % 1000000000L};
-            nanosleep(&ts, nullptr);
-            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) {
-                // Overslept (or woke exactly on time): how long the wait really was is unknown — only that it was no
-                // longer than this.  NOT a sample of the average (an average fed with its own oversleeps ratchets upwards
-                // and starves the GPU): the estimate shrinks instead, so that the next wake-up comes early enough to see
-                // the word arrive.
-                const double slept = std::chrono::duration<double, std::micro>(clk::now() - t0).count();
-                h->wait_ema_us = 0.85 * (slept < expect_us ? slept : expect_us);
-                return GSR_OK;
-            }
-            remaining = expect_us - (double)g_wait.spin_us - std::chrono::duration<double, std::micro>(clk::now() - t0).count();
-            piece *= 2.0;
-        }
-    }
-    const auto t_spin = t0 + std::chrono::microseconds((g_wait.sleep_us > 0 ? (long)expect_us : 0L) + g_wait.spin_us);
-    const auto t_yield = t_spin + std::chrono::microseconds(g_wait.yield_us);
-    auto next_poll = t0 + std::chrono::milliseconds(50);
-    int rc = GSR_OK;
-    for (;;) {
-        bool done = false;
-        for (int i = 0; i < 64 && !done; i++) {
-            done = __atomic_load_n(word, __ATOMIC_ACQUIRE) == seq;
-            if (!done) cpu_relax();
-        }
-        const auto now = clk::now();
-        if (done) {
-            const double us = std::chrono::duration<double, std::micro>(now - t0).count();
-            h->wait_ema_us = h->wait_ema_us == 0.0 ? us : 0.75 * h->wait_ema_us + 0.25 * us;
-            return GSR_OK;
-        }
-        if (now >= t_spin) {
-            if (now < t_yield || g_wait.sleep_us <= 0) {
-                sched_yield();
-            } else {
-                struct timespec ts = {0, (long)g_wait.sleep_us * 1000L};
-                nanosleep(&ts, nullptr);
-            }
-        }
-        if (now < next_poll) continue;
-        next_poll = now + std::chrono::milliseconds(50);
-        const hipError_t q = hipStreamQuery(s);
-        if (q == hipSuccess) {  // everything enqueued has finished: the word is there, or it never will be
-            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return GSR_OK;
-            rc = fail(GSR_E_HIP, "tile scan finished without publishing its totals");
-            break;
-        }
-        if (q != hipErrorNotReady) { rc = fail(GSR_E_HIP, "HIP error while waiting for the tile scan: %s", hipGetErrorString(q)); break; }
-    }
-    h->wait_ema_us = 0.0;
-    return rc;
+// Byte sizes of the buffers an n-Gaussian view on this handle touches (gsr_sizes.h: the one place they are written)
+gsr_gaussian_bytes gaussian_bytes(const gsr_handle* h, int64_t n) {
+    return gsr_sizes_per_gaussian((size_t)n, h->cfg.mode, gsr_pose_partial_floats(n));
 }
 
 // gsr_stats' view-history block (ABI 6): the policy state's counters + the mechanism's own (buffer reallocations)
@@ -646,35 +362,14 @@ int gsr_create(const gsr_config* cfg, gsr_handle** out) {
     gsr_policy_state_init(&h->pol);
     const char* tun = getenv("GSR_FORM_TUNER");  // the DEFAULT of handles that do not say (0 = off)
     h->pcfg.form_tuner = cfg->form_tuner == GSR_TUNER_ON ? 1 : cfg->form_tuner == GSR_TUNER_OFF ? 0 : !(tun && tun[0] == '0');
-    DevBuf* list[] = {&h->ranges, &h->n_contrib, &h->final_T, &h->tile_count, &h->tile_start, &h->tile_order, &h->totals,
-                      &h->geo, &h->gnormal, &h->radii, &h->bsum, &h->bpre, &h->bvis, &h->bins, &h->values_sorted, &h->s0,
-                      &h->s1, &h->s2, &h->s3, &h->big_scratch, &h->rows, &h->vmean2d, &h->d0, &h->d1,
-                      &h->d2, &h->partial, &h->keys_compact, &h->big_list, &h->long_state, &h->overflow_fill, &h->dbg_flag, &h->pose_part};
-    static const char* const names[] = {"ranges", "n_contrib", "final_T", "tile_count", "tile_start", "tile_order", "totals",
-                                        "geo", "gnormal", "radii", "bsum", "bpre", "bvis", "bins", "values_sorted", "s0",
-                                        "s1", "s2", "s3", "big_scratch", "rows", "vmean2d", "d0", "d1",
-                                        "d2", "partial", "keys_compact", "big_list", "long_state", "overflow_fill", "dbg_flag", "pose_part"};
-    static_assert(sizeof(names) / sizeof(names[0]) == sizeof(list) / sizeof(list[0]), "one name per buffer");
-    for (DevBuf* b : list) {
-        b->name = names[h->n_all];
-        b->damage = &h->guard_damage;
-        h->all[h->n_all++] = b;
+    for (const BufRow& r : kBufs) {
+        DevBuf& b = h->*r.buf;
+        b.name = r.name;
+        b.fill_ok = r.fill_ok;
+        b.guard_word = r.guard_word;
+        b.damage = &h->guard_damage;
+        h->all[h->n_all++] = &b;
     }
-    // GSR_DEBUG_GUARD words (DevBuf::guard_word): ids whose range may be {0} get 0
-    h->tile_order.guard_word = 0u;     // tile ids
-    h->big_list.guard_word = 0u;       // tile ids of the tier lists
-    h->values_sorted.guard_word = 0u;  // Gaussian ids
-    // GSR_DEBUG_FILL candidates (DevBuf::fill_ok), each read only as float data:
-    h->rows.fill_ok = true;        // GsrInst gradient rows (float4): summed by pergauss_bwd, copied out by gsr_buffer
-    h->vmean2d.fill_ok = true;     // gstate.∇means_2d (float2): written for every Gaussian, read by gsr_update_stats behind radii > 0
-    h->final_T.fill_ok = true;     // final transmittance per pixel: a factor of the backward, never a bound (n_contrib is)
-    h->gnormal.fill_ok = true;     // per-Gaussian normals (float4): feature values of the :rgbdn stream
-    h->d0.fill_ok = true;          // SSIM loss head's ∂map/∂µ1 plane
-    h->d1.fill_ok = true;          // ... ∂map/∂σ1²
-    h->d2.fill_ok = true;          // ... ∂map/∂σ12
-    h->partial.fill_ok = true;     // per-wave (Σ|x-y|, Σssim) pairs summed by the loss finisher
-    h->pose_part.fill_ok = true;   // per-workgroup pose-gradient partials: every slot is stored (zeros included) before it is summed
-    h->long_state.fill_ok = true;  // (T, A) float2 per pixel and segment of the long-list backward
     const size_t P = (size_t)cfg->width * cfg->height, T = (size_t)h->n_tiles;
     int rc = GSR_OK;
     if ((rc = h->ranges.ensure(2 * T * 4)) || (rc = h->n_contrib.ensure(P * 4)) || (rc = h->final_T.ensure(P * 4)) ||
@@ -730,12 +425,11 @@ static void end_live_forward(gsr_handle* h) {
 
 int gsr_release_scene_buffers(gsr_handle* h) {
     if (!h) return fail(GSR_E_INVALID_ARG, "null handle");
-    DevBuf* scene[] = {&h->geo, &h->gnormal, &h->radii, &h->bsum, &h->bpre, &h->bvis, &h->bins, &h->values_sorted, &h->s0, &h->s1,
-                       &h->s2, &h->s3, &h->big_scratch, &h->rows, &h->vmean2d, &h->pose_part, &h->keys_compact};
     h->pol.bin_cap = 0;
     h->pol.compact_sticky = 0;
-    for (DevBuf* b : scene) {
-        int rc = b->release();
+    for (const BufRow& r : kBufs) {
+        if (!r.scene) continue;
+        int rc = (h->*r.buf).release();
         if (rc) return rc;
     }
     end_live_forward(h);
@@ -775,19 +469,18 @@ int gsr_reserve(gsr_handle* h, int64_t n_gaussians, int64_t n_instances) {
         }
     } uncount(h);
     if (n_gaussians > 0) {
-        const size_t nn = (size_t)n_gaussians, nb = (nn + 255) / 256 + 1;
-        if ((rc = h->geo.ensure(nn * 64)) || (rc = h->radii.ensure(nn * 4)) || (rc = h->bsum.ensure(nb * 4)) ||
-            (rc = h->bpre.ensure(nb * 4)) || (rc = h->bvis.ensure(nb * 4)) || (rc = h->vmean2d.ensure(nn * 8)) ||
-            (rc = h->pose_part.ensure(gsr_pose_partial_floats(n_gaussians) * 4)) ||
-            (C > 5 && (rc = h->gnormal.ensure(nn * 16))))
+        const gsr_gaussian_bytes b = gaussian_bytes(h, n_gaussians);
+        if ((rc = h->geo.ensure(b.geo)) || (rc = h->radii.ensure(b.radii)) || (rc = h->bsum.ensure(b.block)) ||
+            (rc = h->bpre.ensure(b.block)) || (rc = h->bvis.ensure(b.block)) || (rc = h->vmean2d.ensure(b.vmean2d)) ||
+            (rc = h->pose_part.ensure(b.pose_part)) || (C > 5 && (rc = h->gnormal.ensure(b.gnormal))))
             return rc;
     }
     if (n_instances > 0) {
-        const size_t D = (size_t)n_instances;
         // (the gradient rows are indexed by Gaussian-major SLOT: one per emitted tile of a small rect, one per tile of a large one —
-        //  at most ~1.5 x the instance count under exact culling)
-        if ((rc = h->values_sorted.ensure(D * 4)) || (rc = h->s0.ensure(D * 16)) || (rc = h->s1.ensure(D * 16)) ||
-            (rc = h->s2.ensure(D * 16)) || (C > 3 && (rc = h->s3.ensure(D * 16))) || (rc = h->rows.ensure(D * 64 + D * 32)))
+        //  at most ~1.5 x the instance count under exact culling: gsr_sizes_reserve_instances)
+        const gsr_instance_bytes b = gsr_sizes_reserve_instances((uint64_t)n_instances, C);
+        if ((rc = h->values_sorted.ensure(b.values_sorted)) || (rc = h->s0.ensure(b.stream)) || (rc = h->s1.ensure(b.stream)) ||
+            (rc = h->s2.ensure(b.stream)) || (C > 3 && (rc = h->s3.ensure(b.s3))) || (rc = h->rows.ensure(b.rows)))
             return rc;
     }
     return GSR_OK;
@@ -846,16 +539,15 @@ static int fwd_begin(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam,
     h->dropped_by_reserve = false;
     h->fwd_only = v.fwd_only;
 
-    const size_t nn = v.n > 0 ? (size_t)v.n : 1;
-    const int n_blocks = (v.n + 255) / 256;
+    const gsr_gaussian_bytes b = gaussian_bytes(h, v.n);
     const bool own_radii = !(aux && aux->radii);
     // per-Gaussian scratch: grow-only with 25 % slack, like the per-instance buffers below — a training run's densification
     // adds 5-15 % of Gaussians per round (strategy.jl:78-105), and an exact fit made EVERY round's first view reallocate all
     // five (five hipFree + hipMalloc = device synchronisations: the slowest plain steps of the round-6 training protocol)
     const float nslack = 1.25f;
-    if ((rc = h->geo.ensure(nn * 64, nslack)) || (own_radii && (rc = h->radii.ensure(nn * 4, nslack))) ||
-        (rc = h->bsum.ensure((size_t)(n_blocks + 1) * 4, nslack)) || (rc = h->bpre.ensure((size_t)(n_blocks + 1) * 4, nslack)) ||
-        (rc = h->bvis.ensure((size_t)(n_blocks + 1) * 4, nslack)) || (v.C > 5 && (rc = h->gnormal.ensure(nn * 16, nslack))))
+    if ((rc = h->geo.ensure(b.geo, nslack)) || (own_radii && (rc = h->radii.ensure(b.radii, nslack))) ||
+        (rc = h->bsum.ensure(b.block, nslack)) || (rc = h->bpre.ensure(b.block, nslack)) ||
+        (rc = h->bvis.ensure(b.block, nslack)) || (v.C > 5 && (rc = h->gnormal.ensure(b.gnormal, nslack))))
         return rc;
     h->radii_cur = own_radii ? h->radii.as<int32_t>() : aux->radii;
     h->vmean2d_cur = nullptr;
@@ -977,7 +669,7 @@ static void fill_view_stats(const gsr_handle* h, const FwdView& v, gsr_stats* st
 // Read-back: the one host sync, then what this view turned out to be.
 static int fwd_read_back(gsr_handle* h, FwdView& v) {
     int rc;
-    if ((rc = wait_totals(h, v.seq, v.s))) return rc;
+    if ((rc = wait_totals(h->host_totals + GSR_TOTAL_SEQ, &h->wait_ema_us, v.seq, v.s))) return rc;
     // What this view turned out to be — bins / overflow tiles / compact; whether the fused launch covers it; where the tier
     // walk goes; the bins' capacity for the next view — is gsr_policy_end_view's decision on the scan's counts.
     // OVERFLOW TILES (round 5): lists longer than the bins' capacity.  Their bins hold the first bin_cap_view arrivals only
@@ -1022,17 +714,17 @@ static int fwd_empty_view(gsr_handle* h, const FwdView& v) {
 // Instance buffers: grow-only, sized by the counts just read.
 static int fwd_instance_buffers(gsr_handle* h, FwdView& v) {
     int rc;
-    const uint64_t D = v.D;
+    const gsr_instance_bytes b = gsr_sizes_per_instance(v.D, v.D_slots, v.C);
     const float slack = 1.25f;  // instance count drifts slowly between training steps
     // forward-only and everything composited by the fused launch: no per-instance storage at all (the rare paths of
     // fwd_sort_and_walk — tier lists, compact binning — still hand their instances over through the stream)
     const bool need_stream = !(v.fwd_only && v.oc.fused_done && !v.oc.long_tiles);
     if (need_stream &&
-        ((rc = h->values_sorted.ensure(D * 4, slack)) ||
-         (rc = h->s0.ensure(D * 16, slack)) || (rc = h->s1.ensure(D * 16, slack)) ||
-         (rc = h->s2.ensure(D * 16, slack)) || (v.C > 3 && (rc = h->s3.ensure(D * 16, slack)))))
+        ((rc = h->values_sorted.ensure(b.values_sorted, slack)) ||
+         (rc = h->s0.ensure(b.stream, slack)) || (rc = h->s1.ensure(b.stream, slack)) ||
+         (rc = h->s2.ensure(b.stream, slack)) || (v.C > 3 && (rc = h->s3.ensure(b.s3, slack)))))
         return rc;
-    if (!v.fwd_only && (rc = h->rows.ensure(v.D_slots * 64, slack))) return rc;
+    if (!v.fwd_only && (rc = h->rows.ensure(b.rows, slack))) return rc;
     v.slab_stride = 0;
     if (v.n_big > 0) {  // lists beyond the LDS sort: two merge slabs per listed tile
         v.slab_stride = ((size_t)v.max_tile + 63) & ~(size_t)63;
@@ -1169,7 +861,7 @@ static int check_backward_state(const gsr_handle* h, const gsr_inputs* in, const
 static int composite_bwd_stage(gsr_handle* h, hipStream_t s, const gsr_inputs* in, const gsr_camera* cam, const float* vpixels,
                                float* vmeans2d, uint32_t flags, GsrCam* k) {
     int rc;
-    if (!vmeans2d && (rc = h->vmean2d.ensure((size_t)in->n * 8, 1.25f))) return rc;
+    if (!vmeans2d && (rc = h->vmean2d.ensure(gaussian_bytes(h, in->n).vmean2d, 1.25f))) return rc;
     h->vmean2d_cur = vmeans2d ? reinterpret_cast<float2*>(vmeans2d) : h->vmean2d.as<float2>();
     const bool color_only = (flags & GSR_GRADS_COLOR_COTANGENT) != 0u;
     if (color_only && (rc = check_color_cotangent(h, vpixels, s))) return rc;
@@ -1201,7 +893,7 @@ int gsr_backward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, con
     // (nothing is cleared and nothing is accumulated into: composite_bwd writes the row of every emitted instance, pergauss_bwd
     // skips the slots of culled tiles, and the pose gradient goes through per-workgroup partials that are all stored, then summed
     // in a fixed order — the "zero_acc" stage stays in the table, empty)
-    if (g->vR && (rc = h->pose_part.ensure(gsr_pose_partial_floats(n) * 4, 1.25f))) return rc;
+    if (g->vR && (rc = h->pose_part.ensure(gaussian_bytes(h, n).pose_part, 1.25f))) return rc;
     GsrCam k;
     if ((rc = composite_bwd_stage(h, s, in, cam, vpixels, g->vmeans2d, g->flags, &k))) return rc;
     StageScope sc8(h->prof, ST_PERGAUSS_BWD, s);
@@ -1217,26 +909,29 @@ int gsr_backward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, con
 
 static int buffer_lookup(const gsr_handle* h, int which, const void** dev_ptr, size_t* bytes) {
     const size_t n = (size_t)h->last_n, P = (size_t)h->cfg.width * h->cfg.height, T = (size_t)h->n_tiles;
-    const size_t D = (size_t)h->last_D;
+    // what the last forward's n Gaussians and D instances fill (a forward of no Gaussian: nothing, whatever it allocated)
+    const gsr_gaussian_bytes gb = n ? gaussian_bytes(h, h->last_n) : gsr_gaussian_bytes{};
+    const gsr_instance_bytes ib = gsr_sizes_per_instance((uint64_t)h->last_D, (uint64_t)h->last_slots, h->cfg.mode);
     const DevBuf* b = nullptr;
     size_t sz = 0;
     switch (which) {
         case GSR_BUF_RADII:  // handle-owned, or the caller's gsr_aux.radii of the last forward
             *dev_ptr = h->fwd_valid && n ? h->radii_cur : nullptr;
-            *bytes = *dev_ptr ? n * 4 : 0;
+            *bytes = *dev_ptr ? gb.radii : 0;
             return GSR_OK;
         case GSR_BUF_GRAD_MEANS2D:
             *dev_ptr = h->bwd_valid && n ? h->vmean2d_cur : nullptr;
-            *bytes = *dev_ptr ? n * 8 : 0;
+            *bytes = *dev_ptr ? gb.vmean2d : 0;
             return GSR_OK;
         case GSR_BUF_N_CONTRIB: b = &h->n_contrib; sz = P * 4; break;
         case GSR_BUF_FINAL_T: b = &h->final_T; sz = P * 4; break;
         case GSR_BUF_TILE_RANGES: b = &h->ranges; sz = 2 * T * 4; break;
-        case GSR_BUF_VALUES_SORTED: b = &h->values_sorted; sz = h->fwd_only ? 0 : D * 4; break;
-        case GSR_BUF_GEOM: b = &h->geo; sz = n * 64; break;
-        case GSR_BUF_NORMALS: b = &h->gnormal; sz = h->cfg.mode > 5 ? n * 16 : 0; break;
+        case GSR_BUF_VALUES_SORTED: b = &h->values_sorted; sz = h->fwd_only ? 0 : ib.values_sorted; break;
+        case GSR_BUF_GEOM: b = &h->geo; sz = gb.geo; break;
+        case GSR_BUF_NORMALS: b = &h->gnormal; sz = gb.gnormal; break;
+        // (the rows as the backward packs them — 48 bytes per slot in :rgb mode — inside the 64 per slot of ib.rows)
         case GSR_BUF_GRAD_ROWS: b = &h->rows; sz = (size_t)h->last_slots * 16 * GSR_ROW_F4(h->cfg.mode); break;
-        case GSR_BUF_INSTANCE_AUX: b = &h->s2; sz = h->fwd_only ? 0 : D * 16; break;
+        case GSR_BUF_INSTANCE_AUX: b = &h->s2; sz = h->fwd_only ? 0 : ib.stream; break;
         default: return fail(GSR_E_INVALID_ARG, "unknown buffer id %d", which);
     }
     if (sz > b->cap) sz = 0;  // not produced yet
@@ -1258,33 +953,6 @@ int gsr_copy_buffer(const gsr_handle* h, int which, void* dst, size_t bytes, voi
     if (rc) return rc;
     if (bytes > have) return fail(GSR_E_STATE, "buffer %d holds %zu bytes, %zu requested (not produced yet?)", which, have, bytes);
     if (bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return GSR_OK;
-}
-
-int gsr_ssim_forward(int W, int H, int CH, int B, const float* img, const float* ref, float C1, float C2, int train,
-                     float* ssim_map, float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12, void* stream) {
-    if (W <= 0 || H <= 0 || CH <= 0 || B <= 0) return fail(GSR_E_INVALID_ARG, "bad SSIM shape");
-    if (!img || !ref || !ssim_map) return fail(GSR_E_INVALID_ARG, "null SSIM array");
-    if (train && (!dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12)) return fail(GSR_E_INVALID_ARG, "train needs the 3 partial maps");
-    if ((size_t)CH * B > 65535) return fail(GSR_E_INVALID_ARG, "CH*B too large");
-    if ((size_t)W * H > 0xFFFFFFFFull) return fail(GSR_E_INVALID_ARG, "SSIM plane too large");  // 32-bit offsets inside a plane
-    (g_ssim_exact.load(std::memory_order_relaxed) ? gsr_launch_ssim_fwd_exact : gsr_launch_ssim_fwd_fast)((hipStream_t)stream, W, H, CH, B, img, ref, C1, C2, train,
-                                                                          ssim_map, dm_dmu1, dm_dsigma1_sq, dm_dsigma12);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_ssim_backward(int W, int H, int CH, int B, const float* img, const float* ref, const float* dL_dmap,
-                      const float* dm_dmu1, const float* dm_dsigma1_sq, const float* dm_dsigma12, float* dL_dimg,
-                      void* stream) {
-    if (W <= 0 || H <= 0 || CH <= 0 || B <= 0) return fail(GSR_E_INVALID_ARG, "bad SSIM shape");
-    if (!img || !ref || !dL_dmap || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg)
-        return fail(GSR_E_INVALID_ARG, "null SSIM array");
-    if ((size_t)CH * B > 65535) return fail(GSR_E_INVALID_ARG, "CH*B too large");
-    if ((size_t)W * H > 0xFFFFFFFFull) return fail(GSR_E_INVALID_ARG, "SSIM plane too large");  // 32-bit offsets inside a plane
-    (g_ssim_exact.load(std::memory_order_relaxed) ? gsr_launch_ssim_bwd_exact : gsr_launch_ssim_bwd_fast)((hipStream_t)stream, W, H, CH, B, img, ref, dL_dmap, dm_dmu1,
-                                                                          dm_dsigma1_sq, dm_dsigma12, dL_dimg);
-    HIPCHK(hipGetLastError());
     return GSR_OK;
 }
 
@@ -1383,99 +1051,6 @@ int gsr_profile_read_intervals(gsr_handle* h, int stage, double* ms_out, int max
     return GSR_OK;
 }
 
-int gsr_prologue_forward(int32_t n, int32_t k_rest, int32_t scale_dims, const float* sh_color,
-                         const float* sh_remainder, const float* opacities, const float* scales, float* shs,
-                         float* opacities_act, float* scales_act, void* stream) {
-    if (n < 0 || k_rest < 0 || (scale_dims != 1 && scale_dims != 3))
-        return fail(GSR_E_INVALID_ARG, "bad sizes: n=%d k_rest=%d scale_dims=%d", n, k_rest, scale_dims);
-    if (n == 0) return GSR_OK;
-    if (!sh_color || (k_rest > 0 && !sh_remainder) || !opacities || !scales || !shs || !opacities_act || !scales_act)
-        return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_prologue_fwd((hipStream_t)stream, n, k_rest, scale_dims, sh_color, sh_remainder, opacities, scales, shs,
-                            opacities_act, scales_act);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_prologue_backward(int32_t n, int32_t k_rest, int32_t scale_dims, const float* opacities_act,
-                          const float* scales_act, const float* vshs, const float* vopacities_act,
-                          const float* vscales_act, float* v_sh_color, float* v_sh_remainder, float* v_opacities,
-                          float* v_scales, void* stream) {
-    if (n < 0 || k_rest < 0 || (scale_dims != 1 && scale_dims != 3))
-        return fail(GSR_E_INVALID_ARG, "bad sizes: n=%d k_rest=%d scale_dims=%d", n, k_rest, scale_dims);
-    if (n == 0) return GSR_OK;
-    if (!opacities_act || !scales_act || !vshs || !vopacities_act || !vscales_act || !v_sh_color ||
-        (k_rest > 0 && !v_sh_remainder) || !v_opacities || !v_scales)
-        return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_prologue_bwd((hipStream_t)stream, n, k_rest, scale_dims, opacities_act, scales_act, vshs, vopacities_act,
-                            vscales_act, v_sh_color, v_sh_remainder, v_opacities, v_scales);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-// Adam's step size with both debiasing factors folded in (Kingma & Ba §2); current_step counts from 1
-static float adam_lr_t(float lr, float beta1, float beta2, uint32_t current_step) {
-    const float t = (float)current_step;
-    return lr * sqrtf(1.0f - powf(beta2, t)) / (1.0f - powf(beta1, t));
-}
-
-// lr_t of the trainer's six groups, after checking their arrays and counters; rest_empty: the scene has no features_rest
-// (group 2), whose arrays are then not looked at (training.jl:770)
-static int tail_lr_t(float* const theta[6], float* const mu[6], float* const nu[6], const float lr[6],
-                     const uint32_t current_step[6], float beta1, float beta2, bool rest_empty, float lr_t[6]) {
-    for (int g = 0; g < 6; g++) {
-        if (g == 2 && rest_empty) { lr_t[g] = 0.0f; continue; }
-        if (!theta[g] || !mu[g] || !nu[g]) return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
-        if (current_step[g] == 0) return fail(GSR_E_INVALID_ARG, "group %d: current_step counts from 1", g);
-        lr_t[g] = adam_lr_t(lr[g], beta1, beta2, current_step[g]);
-    }
-    return GSR_OK;
-}
-
-int gsr_adam_step(const gsr_adam_group* groups, int32_t n_groups, float beta1, float beta2, float eps, void* stream) {
-    if (n_groups < 0 || n_groups > GSR_ADAM_MAX_GROUPS || (n_groups > 0 && !groups))
-        return fail(GSR_E_INVALID_ARG, "n_groups must be in [0, %d]", GSR_ADAM_MAX_GROUPS);
-    float* theta[GSR_ADAM_MAX_GROUPS]; const float* grad[GSR_ADAM_MAX_GROUPS];
-    float* mu[GSR_ADAM_MAX_GROUPS]; float* nu[GSR_ADAM_MAX_GROUPS];
-    long long count[GSR_ADAM_MAX_GROUPS]; float lr_t[GSR_ADAM_MAX_GROUPS];
-    int m = 0;
-    for (int g = 0; g < n_groups; g++) {
-        const gsr_adam_group& a = groups[g];
-        if (a.count < 0) return fail(GSR_E_INVALID_ARG, "group %d: negative count", g);
-        if (a.count == 0) continue;  // training.jl:770 `isempty(θᵢ) && continue`
-        if (!a.theta || !a.grad || !a.mu || !a.nu) return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
-        if (a.current_step == 0) return fail(GSR_E_INVALID_ARG, "group %d: current_step counts from 1", g);
-        theta[m] = a.theta; grad[m] = a.grad; mu[m] = a.mu; nu[m] = a.nu; count[m] = a.count;
-        lr_t[m] = adam_lr_t(a.lr, beta1, beta2, a.current_step);
-        m++;
-    }
-    if (m == 0) return GSR_OK;
-    gsr_launch_adam((hipStream_t)stream, m, theta, grad, mu, nu, count, lr_t, beta1, beta2, eps);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_trainer_tail_step(int32_t n, int32_t k_rest, int32_t scale_dims, const gsr_tail_grads* grads,
-                          float* const theta[6], float* const mu[6], float* const nu[6], const float lr[6],
-                          const uint32_t current_step[6], float beta1, float beta2, float eps, float* shs,
-                          float* opacities_act, float* scales_act, void* stream) {
-    if (n < 0 || k_rest < 0 || (scale_dims != 1 && scale_dims != 3))
-        return fail(GSR_E_INVALID_ARG, "bad sizes: n=%d k_rest=%d scale_dims=%d", n, k_rest, scale_dims);
-    if (n == 0) return GSR_OK;
-    if (!grads || !theta || !mu || !nu || !lr || !current_step || !shs || !opacities_act || !scales_act)
-        return fail(GSR_E_INVALID_ARG, "null argument");
-    if (!grads->vmeans || !grads->vshs || !grads->vopacities || !grads->vscales || !grads->vrotations)
-        return fail(GSR_E_INVALID_ARG, "null gradient");
-    float lr_t[6];
-    int rc = tail_lr_t(theta, mu, nu, lr, current_step, beta1, beta2, /*rest_empty=*/k_rest == 0, lr_t);
-    if (rc) return rc;
-    const float* gr[5] = {grads->vmeans, grads->vshs, grads->vopacities, grads->vscales, grads->vrotations};
-    gsr_launch_trainer_tail((hipStream_t)stream, n, k_rest, scale_dims, gr, theta, mu, nu, lr_t, beta1, beta2, eps, shs,
-                            opacities_act, scales_act);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
 int gsr_backward_trainer_tail(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, const float* vpixels,
                               const gsr_tail_state* st, void* stream_v) {
     int rc = check_inputs(h, in, cam);
@@ -1513,658 +1088,6 @@ int gsr_backward_trainer_tail(gsr_handle* h, const gsr_inputs* in, const gsr_cam
     // the forward's inputs no longer exist (updated in place): a second backward on this forward would differentiate
     // the wrong parameters (the forward's own outputs — radii, tile lists, image — stay readable)
     h->inputs_consumed = true;
-    return GSR_OK;
-}
-
-size_t gsr_mask_findall_scratch_bytes(int64_t n) { return n > 0 ? gsr_findall_scratch_bytes(n) : sizeof(uint32_t); }
-
-int gsr_mask_findall(const uint8_t* mask, int64_t n, uint32_t* indices, uint32_t* count_out, void* scratch,
-                     void* stream) {
-    if (n < 0 || n > 0xFFFFFFFFll) return fail(GSR_E_INVALID_ARG, "n out of range");
-    if (!count_out || (n > 0 && (!mask || !indices || !scratch))) return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_findall((hipStream_t)stream, n, mask, indices, count_out, (uint32_t*)scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_gather_rows(const gsr_gather_group* groups, int32_t n_groups, const uint32_t* indices, int64_t count,
-                    void* stream) {
-    if (n_groups < 0 || n_groups > GSR_ADAM_MAX_GROUPS || (n_groups > 0 && !groups))
-        return fail(GSR_E_INVALID_ARG, "n_groups must be in [0, %d]", GSR_ADAM_MAX_GROUPS);
-    if (count < 0) return fail(GSR_E_INVALID_ARG, "negative count");
-    if (count == 0 || n_groups == 0) return GSR_OK;
-    if (!indices) return fail(GSR_E_INVALID_ARG, "null indices");
-    const void* src[GSR_ADAM_MAX_GROUPS]; void* dst[GSR_ADAM_MAX_GROUPS]; int rw[GSR_ADAM_MAX_GROUPS];
-    int m = 0;
-    for (int g = 0; g < n_groups; g++) {
-        if (groups[g].row_words < 0) return fail(GSR_E_INVALID_ARG, "group %d: negative row_words", g);
-        if (groups[g].row_words == 0) continue;  // e.g. an empty features_rest (densification.jl:40-41)
-        if (!groups[g].src || !groups[g].dst) return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
-        src[m] = groups[g].src; dst[m] = groups[g].dst; rw[m] = groups[g].row_words; m++;
-    }
-    if (m == 0) return GSR_OK;
-    gsr_launch_gather_rows((hipStream_t)stream, m, src, dst, rw, indices, count);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-// ---- bilateral grid (bilateral.hip; src/bilateral_grid.jl) ----
-namespace {
-constexpr int kBilateralMaxGz = 64;         // LDS of the pullback: gz x 4 waves x 48 floats
-constexpr int kBilateralMaxSlab = 16384;    // floats of one (image, coefficient) slab staged in LDS by the TV passes
-
-int check_bilateral_grid(int32_t gx, int32_t gy, int32_t gz) {
-    if (gx < 1 || gy < 1 || gz < 1) return fail(GSR_E_INVALID_ARG, "grid size (%d, %d, %d): every side must be >= 1", gx, gy, gz);
-    if (gz > kBilateralMaxGz) return fail(GSR_E_INVALID_ARG, "grid size (%d, %d, %d): gz must be <= %d", gx, gy, gz, kBilateralMaxGz);
-    if ((int64_t)gx * gy * gz > kBilateralMaxSlab)
-        return fail(GSR_E_INVALID_ARG, "grid size (%d, %d, %d): gx*gy*gz must be <= %d", gx, gy, gz, kBilateralMaxSlab);
-    return GSR_OK;
-}
-int check_bilateral_image(int32_t W, int32_t H, int32_t C) {
-    if (W < 1 || H < 1 || (int64_t)W * H > 0x7FFFFFFF) return fail(GSR_E_INVALID_ARG, "image size %d x %d", W, H);
-    if (C != 3 && C != 5 && C != 8) return fail(GSR_E_INVALID_ARG, "C = %d: the image has 3, 5 or 8 channels", C);
-    return GSR_OK;
-}
-// the constants of the TV prior, once, on the host: the standalone TV and the fused tail read the same floats
-gsr::BilateralTv bilateral_tv_consts(int32_t n, int32_t gx, int32_t gy, int32_t gz, float weight) {
-    gsr::BilateralTv tv;
-    tv.weight = weight;
-    tv.nx = (float)std::max<int64_t>(1, (int64_t)(gx - 1) * gy * gz);   // bilateral_grid.jl:115-117
-    tv.ny = (float)std::max<int64_t>(1, (int64_t)gx * (gy - 1) * gz);
-    tv.nz = (float)std::max<int64_t>(1, (int64_t)gx * gy * (gz - 1));
-    tv.n12 = 12.0f * (float)n;
-    tv.rx = 2.0f / (tv.nx * tv.n12);
-    tv.ry = 2.0f / (tv.ny * tv.n12);
-    tv.rz = 2.0f / (tv.nz * tv.n12);
-    return tv;
-}
-}  // namespace
-
-size_t gsr_bilateral_scratch_bytes(int32_t W, int32_t H, int32_t gx, int32_t gy, int32_t gz) {
-    if (W < 1 || H < 1 || gx < 1 || gy < 1 || gz < 1) return 0;
-    return gsr_bilateral_partial_bytes(W, H, gx, gy, gz);
-}
-
-size_t gsr_bilateral_tv_scratch_bytes(int32_t n_images) {
-    return n_images < 1 ? 0 : (size_t)n_images * 12 * 3 * sizeof(float);
-}
-
-int gsr_bilateral_slice_forward(int32_t W, int32_t H, int32_t C, const float* image, const float* grid, int32_t gx,
-                                int32_t gy, int32_t gz, float* out, void* stream) {
-    int rc;
-    if ((rc = check_bilateral_image(W, H, C)) || (rc = check_bilateral_grid(gx, gy, gz))) return rc;
-    if (!image || !grid || !out) return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_bilateral_fwd((hipStream_t)stream, W, H, C, image, grid, gx, gy, gz, out);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_bilateral_slice_backward(int32_t W, int32_t H, int32_t C, const float* image, const float* grid, int32_t gx,
-                                 int32_t gy, int32_t gz, const float* vout, float* vimage, float* vgrid, void* scratch,
-                                 size_t scratch_bytes, void* stream) {
-    int rc;
-    if ((rc = check_bilateral_image(W, H, C)) || (rc = check_bilateral_grid(gx, gy, gz))) return rc;
-    if (!image || !grid || !vout || !vimage || !vgrid || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
-    const size_t need = gsr_bilateral_scratch_bytes(W, H, gx, gy, gz);
-    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the pullback needs %zu", scratch_bytes, need);
-    gsr_launch_bilateral_bwd((hipStream_t)stream, W, H, C, image, grid, gx, gy, gz, vout, vimage, vgrid, (float*)scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_bilateral_tv(int32_t n_images, int32_t gx, int32_t gy, int32_t gz, const float* grids, float weight,
-                     float* loss_out, float* grad_out, void* scratch, size_t scratch_bytes, void* stream) {
-    int rc;
-    if (n_images < 1) return fail(GSR_E_INVALID_ARG, "n_images = %d", n_images);
-    if ((rc = check_bilateral_grid(gx, gy, gz))) return rc;
-    if (!grids || !loss_out || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
-    const size_t need = gsr_bilateral_tv_scratch_bytes(n_images);
-    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the TV needs %zu", scratch_bytes, need);
-    gsr_launch_bilateral_tv((hipStream_t)stream, n_images, gx, gy, gz, grids, bilateral_tv_consts(n_images, gx, gy, gz, weight),
-                            loss_out, grad_out, (float*)scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_bilateral_adam_tail(int32_t n_images, int32_t gx, int32_t gy, int32_t gz, float* grids, float* mu, float* nu,
-                            const float* vgrid_view, int32_t view, float tv_weight, float lr, uint32_t current_step,
-                            float beta1, float beta2, float eps, float* tv_loss_out, void* scratch, size_t scratch_bytes,
-                            void* stream) {
-    int rc;
-    if (n_images < 1) return fail(GSR_E_INVALID_ARG, "n_images = %d", n_images);
-    if ((rc = check_bilateral_grid(gx, gy, gz))) return rc;
-    if (view < 0 || view >= n_images) return fail(GSR_E_INVALID_ARG, "view %d of %d images", view, n_images);
-    if (!grids || !mu || !nu || !vgrid_view || !tv_loss_out || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
-    if (current_step == 0) return fail(GSR_E_INVALID_ARG, "current_step counts from 1");
-    const size_t need = gsr_bilateral_tv_scratch_bytes(n_images);
-    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the tail needs %zu", scratch_bytes, need);
-    const float lr_t = adam_lr_t(lr, beta1, beta2, current_step);
-    const gsr::AdamHyper h{lr_t, beta1, beta2, 1.0f - beta1, 1.0f - beta2, eps};
-    gsr_launch_bilateral_adam_tail((hipStream_t)stream, n_images, gx, gy, gz, grids, mu, nu, vgrid_view, view,
-                                   bilateral_tv_consts(n_images, gx, gy, gz, tv_weight), h, tv_loss_out, (float*)scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-// ---- geometry regularisation (geometry.hip; src/geometry_regularization.jl) ----
-namespace {
-int check_normal_loss_frame(int32_t W, int32_t H, int32_t C) {
-    if (W < 1 || H < 1 || (int64_t)W * H > 0x7FFFFFFF / 8) return fail(GSR_E_INVALID_ARG, "image size %d x %d", W, H);
-    if (C != 8) return fail(GSR_E_INVALID_ARG, "C = %d: the depth-normal loss reads a :rgbdn frame (8 channels)", C);
-    return GSR_OK;
-}
-int check_normal_loss_camera(const gsr_camera* cam) {
-    if (!cam) return fail(GSR_E_INVALID_ARG, "null camera");
-    if (!(cam->focal[0] > 0.0f) || !(cam->focal[1] > 0.0f)) return fail(GSR_E_INVALID_ARG, "focal lengths must be positive");
-    return GSR_OK;
-}
-}  // namespace
-
-size_t gsr_normal_loss_scratch_bytes(int32_t W, int32_t H) {
-    if (W < 1 || H < 1) return 0;
-    return gsr_normal_loss_scratch_floats(W, H) * sizeof(float);
-}
-
-int gsr_normal_loss_forward(int32_t W, int32_t H, int32_t C, const float* image, const gsr_camera* cam, float weight,
-                            float* loss_out, float* stats_out, float* weights_out, void* scratch, size_t scratch_bytes,
-                            void* stream) {
-    int rc;
-    if ((rc = check_normal_loss_frame(W, H, C)) || (rc = check_normal_loss_camera(cam))) return rc;
-    if (!image || !loss_out || !stats_out || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
-    const size_t need = gsr_normal_loss_scratch_bytes(W, H);
-    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the depth-normal loss needs %zu", scratch_bytes, need);
-    gsr_launch_normal_loss_fwd((hipStream_t)stream, W, H, image, cam->focal, cam->principal, weight, loss_out, stats_out,
-                               weights_out, (float*)scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_normal_loss_backward(int32_t W, int32_t H, int32_t C, const float* image, const gsr_camera* cam, float weight,
-                             float* vpixels, const void* scratch, size_t scratch_bytes, void* stream) {
-    int rc;
-    if ((rc = check_normal_loss_frame(W, H, C)) || (rc = check_normal_loss_camera(cam))) return rc;
-    if (!image || !vpixels || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
-    if (image == vpixels) return fail(GSR_E_INVALID_ARG, "vpixels must not be the image");
-    const size_t need = gsr_normal_loss_scratch_bytes(W, H);
-    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the depth-normal loss needs %zu", scratch_bytes, need);
-    gsr_launch_normal_loss_bwd((hipStream_t)stream, W, H, image, cam->focal, cam->principal, weight, vpixels,
-                               (const float*)scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-size_t gsr_flatten_loss_scratch_bytes(int32_t n) { return gsr_flatten_loss_scratch_floats(n) * sizeof(float); }
-
-int gsr_flatten_loss(int32_t n, int32_t scale_dims, const float* scales_raw, float weight, float* loss_out, float* vscales,
-                     void* scratch, size_t scratch_bytes, void* stream) {
-    if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
-    if (scale_dims != 1 && scale_dims != 3) return fail(GSR_E_INVALID_ARG, "scale_dims = %d: 1 (isotropic) or 3", scale_dims);
-    if (!loss_out || (n > 0 && (!scales_raw || !scratch))) return fail(GSR_E_INVALID_ARG, "null array");
-    const size_t need = gsr_flatten_loss_scratch_bytes(n);
-    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the flatten loss needs %zu", scratch_bytes, need);
-    gsr_launch_flatten_loss((hipStream_t)stream, n, scale_dims, scales_raw, weight, loss_out, vscales, (float*)scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-// ---- anchored depth supervision (depth.hip; src/depth_supervision.jl) ----
-namespace {
-int check_depth_loss_args(int32_t W, int32_t H, int32_t C, const gsr_depth_anchor* anchor, float qstep) {
-    if (W < 1 || H < 1 || (int64_t)W * H > 0x7FFFFFFF / 8) return fail(GSR_E_INVALID_ARG, "image size %d x %d", W, H);
-    if (C != 5 && C != 8) return fail(GSR_E_INVALID_ARG, "C = %d: the depth loss reads a :rgbd (5) or :rgbdn (8) frame", C);
-    if (!anchor) return fail(GSR_E_INVALID_ARG, "null anchor");
-    if (!std::isfinite(anchor->a) || !std::isfinite(anchor->b) || !(anchor->floor > 0.0f) || !std::isfinite(anchor->floor) ||
-        !(anchor->p_far >= 0.0f) || !std::isfinite(anchor->p_far))
-        return fail(GSR_E_INVALID_ARG, "anchor: a and b must be finite, floor > 0, p_far >= 0");
-    if (!(qstep >= 0.0f) || !std::isfinite(qstep)) return fail(GSR_E_INVALID_ARG, "qstep must be finite and >= 0");
-    return GSR_OK;
-}
-}  // namespace
-
-size_t gsr_depth_loss_scratch_bytes(int32_t W, int32_t H) {
-    if (W < 1 || H < 1) return 0;
-    return gsr_depth_loss_scratch_size(W, H);
-}
-
-int gsr_depth_target(int32_t W, int32_t H, const float* prior, const gsr_depth_anchor* anchor, float qstep, float* target_out,
-                     float* half_band_out, uint8_t* flags_out, void* stream) {
-    int rc;
-    if ((rc = check_depth_loss_args(W, H, 5, anchor, qstep))) return rc;
-    if (!prior) return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_depth_target((hipStream_t)stream, W, H, prior, &anchor->a, qstep, target_out, half_band_out, flags_out);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_depth_loss_forward(int32_t W, int32_t H, int32_t C, const float* image, const float* prior, const gsr_depth_anchor* anchor,
-                           float qstep, float lambda_grad, float weight, float* loss_out, float* stats_out, float* target_out,
-                           float* half_band_out, uint8_t* flags_out, void* scratch, size_t scratch_bytes, void* stream) {
-    int rc;
-    if ((rc = check_depth_loss_args(W, H, C, anchor, qstep))) return rc;
-    if (!image || !prior || !loss_out || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
-    if ((uintptr_t)scratch % 16) return fail(GSR_E_INVALID_ARG, "scratch must be 16-byte aligned");
-    const size_t need = gsr_depth_loss_scratch_bytes(W, H);
-    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the depth loss needs %zu", scratch_bytes, need);
-    gsr_launch_depth_loss_fwd((hipStream_t)stream, W, H, C, image, prior, &anchor->a, qstep, lambda_grad, weight, loss_out,
-                              stats_out, target_out, half_band_out, flags_out, scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_depth_loss_backward(int32_t W, int32_t H, int32_t C, const float* image, const float* prior, const gsr_depth_anchor* anchor,
-                            float qstep, float lambda_grad, float weight, float* vpixels, const void* scratch, size_t scratch_bytes,
-                            void* stream) {
-    int rc;
-    if ((rc = check_depth_loss_args(W, H, C, anchor, qstep))) return rc;
-    if (!image || !prior || !vpixels || !scratch) return fail(GSR_E_INVALID_ARG, "null array");
-    if (image == vpixels) return fail(GSR_E_INVALID_ARG, "vpixels must not be the image");
-    if ((uintptr_t)scratch % 16) return fail(GSR_E_INVALID_ARG, "scratch must be 16-byte aligned");
-    const size_t need = gsr_depth_loss_scratch_bytes(W, H);
-    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the depth loss needs %zu", scratch_bytes, need);
-    // prior, anchor and qstep are the forward's: what they determine per pixel is in the records the forward left in scratch
-    gsr_launch_depth_loss_bwd((hipStream_t)stream, W, H, C, image, lambda_grad, weight, vpixels, scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-// ---- sky dome: composite, sky-mask loss and their pullback (sky.hip; src/sky_dome.jl) ----
-namespace {
-int check_sky_args(int32_t W, int32_t H, int32_t C, const void* image, const void* sky_rgb) {
-    if (W < 1 || H < 1 || (int64_t)W * H > 0x7FFFFFFF / 8) return fail(GSR_E_INVALID_ARG, "image size %d x %d", W, H);
-    if (C != 5 && C != 8)
-        return fail(GSR_E_INVALID_ARG, "C = %d: the sky composite reads the alpha row of a :rgbd (5) or :rgbdn (8) frame", C);
-    if (!image || !sky_rgb) return fail(GSR_E_INVALID_ARG, "null array");
-    return GSR_OK;
-}
-}  // namespace
-
-size_t gsr_sky_scratch_bytes(int32_t W, int32_t H) {
-    if (W < 1 || H < 1) return 0;
-    return gsr_sky_scratch_size(W, H);
-}
-
-int gsr_sky_composite_forward(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb, const float* sky_weight,
-                              float loss_weight, float* out, float* loss_out, void* scratch, void* stream) {
-    int rc;
-    if ((rc = check_sky_args(W, H, C, image, sky_rgb))) return rc;
-    if (!out) return fail(GSR_E_INVALID_ARG, "null array");
-    if (sky_weight && (!loss_out || !scratch)) return fail(GSR_E_INVALID_ARG, "a sky mask needs loss_out and scratch");
-    if (sky_weight && (uintptr_t)scratch % 8) return fail(GSR_E_INVALID_ARG, "scratch must be 8-byte aligned");
-    gsr_launch_sky_composite_fwd((hipStream_t)stream, W, H, C, image, sky_rgb, sky_weight, loss_weight, out, loss_out, scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_sky_composite_backward(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb, const float* sky_weight,
-                               float loss_weight, float* vpixels, float* vsky, const void* scratch, void* stream) {
-    int rc;
-    if ((rc = check_sky_args(W, H, C, image, sky_rgb))) return rc;
-    if (!vpixels || !vsky) return fail(GSR_E_INVALID_ARG, "null array");
-    if (image == vpixels) return fail(GSR_E_INVALID_ARG, "vpixels must not be the image");
-    if (sky_weight && !scratch) return fail(GSR_E_INVALID_ARG, "a sky mask needs the scratch its forward filled");
-    if (sky_weight && (uintptr_t)scratch % 8) return fail(GSR_E_INVALID_ARG, "scratch must be 8-byte aligned");
-    gsr_launch_sky_composite_bwd((hipStream_t)stream, W, H, C, image, sky_rgb, sky_weight, loss_weight, vpixels, vsky, scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-// ---- evaluation head: 8-bit SSIM / MSE / PSNR / L1 and the RGB8 export (eval.hip; training.jl:487-532) ----
-namespace {
-int check_eval_frame(int32_t W, int32_t H, int32_t C, const void* image, const void* sky_rgb) {
-    if (W < 1 || H < 1) return fail(GSR_E_INVALID_ARG, "image size %d x %d", W, H);
-    if (C < 3) return fail(GSR_E_INVALID_ARG, "C = %d: a frame has at least the 3 colour channels", C);
-    if (sky_rgb && C < 5) return fail(GSR_E_INVALID_ARG, "C = %d: a sky frame needs the alpha row of a :rgbd / :rgbdn frame (C >= 5)", C);
-    // 32-bit element offsets inside the frame, 32-bit byte offsets inside a row
-    if ((uint64_t)W * (uint64_t)H * (uint64_t)C > 0xFFFFFFFFull || (uint64_t)W * (uint64_t)C * 4 > 0xFFFFFFFFull)
-        return fail(GSR_E_INVALID_ARG, "frame too large: %d x %d x %d is 2^32 elements or more", C, W, H);
-    if (!image) return fail(GSR_E_INVALID_ARG, "null image");
-    return GSR_OK;
-}
-}  // namespace
-
-size_t gsr_eval_scratch_bytes(int32_t W, int32_t H) {
-    if (W < 1 || H < 1) return 0;
-    return gsr_eval_scratch_size(W, H);
-}
-
-int gsr_eval_metrics(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb, const float* target_f32,
-                     const uint8_t* target_u8, int32_t quantize, float* ssim_map, float* out, void* scratch, void* stream) {
-    int rc;
-    if ((rc = check_eval_frame(W, H, C, image, sky_rgb))) return rc;
-    if (!out || !scratch) return fail(GSR_E_INVALID_ARG, "null out or scratch");
-    if ((target_f32 != nullptr) == (target_u8 != nullptr))
-        return fail(GSR_E_INVALID_ARG, "exactly one of target_f32 and target_u8: %s given", target_f32 ? "both" : "neither");
-    if (ssim_map == image) return fail(GSR_E_INVALID_ARG, "ssim_map must not be the image");
-    if ((uintptr_t)scratch % 8) return fail(GSR_E_INVALID_ARG, "scratch must be 8-byte aligned");
-    gsr_launch_eval_metrics((hipStream_t)stream, W, H, C, image, sky_rgb, target_f32, target_u8, quantize != 0, ssim_map, out,
-                            scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_frame_rgb8(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb, int32_t flip_rows,
-                   uint8_t* rgb8_out, void* stream) {
-    int rc;
-    if ((rc = check_eval_frame(W, H, C, image, sky_rgb))) return rc;
-    if (!rgb8_out) return fail(GSR_E_INVALID_ARG, "null rgb8_out");
-    gsr_launch_frame_rgb8((hipStream_t)stream, W, H, C, image, sky_rgb, flip_rows != 0, rgb8_out);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_densify_grad_mean(int64_t n, const float* accum, const float* denom, float* grad_out, void* stream) {
-    if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
-    if (n == 0) return GSR_OK;
-    if (!accum || !denom || !grad_out) return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_grad_mean((hipStream_t)stream, n, accum, denom, grad_out);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_densify_mask(int32_t kind, int64_t n, int64_t n_grad, const float* grad, const float* scales, int32_t scale_dims,
-                     const float* opacities, const int32_t* max_radii, float grad_threshold, float gamma, float min_opacity,
-                     int32_t max_screen_size, uint8_t* mask, void* stream) {
-    if (kind < GSR_DENSIFY_CLONE || kind > GSR_DENSIFY_PRUNE) return fail(GSR_E_INVALID_ARG, "unknown mask kind %d", kind);
-    if (n < 0 || n_grad < 0 || n_grad > n) return fail(GSR_E_INVALID_ARG, "bad sizes: n=%lld n_grad=%lld", (long long)n, (long long)n_grad);
-    if (scale_dims != 1 && scale_dims != 3) return fail(GSR_E_INVALID_ARG, "scale_dims must be 1 or 3");
-    if (n == 0) return GSR_OK;
-    if (!mask) return fail(GSR_E_INVALID_ARG, "null mask");
-    if (kind != GSR_DENSIFY_PRUNE && (!scales || (n_grad > 0 && !grad))) return fail(GSR_E_INVALID_ARG, "null array");
-    if (kind == GSR_DENSIFY_PRUNE && (!opacities || (max_screen_size > 0 && (!max_radii || !scales))))
-        return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_densify_mask((hipStream_t)stream, kind, n, n_grad, grad, scales, scale_dims, opacities, max_radii, grad_threshold,
-                            gamma, min_opacity, max_screen_size, mask);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_compose_rows(const gsr_compose_group* groups, int32_t n_groups, const uint32_t* keep_idx, int64_t n_keep,
-                     const uint32_t* sel_idx, int64_t n_sel, int32_t reps, void* stream) {
-    if (n_groups < 0 || n_groups > GSR_COMPOSE_MAX_GROUPS || (n_groups > 0 && !groups))
-        return fail(GSR_E_INVALID_ARG, "n_groups must be in [0, %d]", GSR_COMPOSE_MAX_GROUPS);
-    if (n_keep < 0 || n_sel < 0 || reps < 0) return fail(GSR_E_INVALID_ARG, "negative count");
-    if (n_sel > 0 && reps > 0 && !sel_idx) return fail(GSR_E_INVALID_ARG, "null sel_idx");
-    if (n_keep + n_sel * reps == 0 || n_groups == 0) return GSR_OK;
-    const void* src[GSR_COMPOSE_MAX_GROUPS]; void* dst[GSR_COMPOSE_MAX_GROUPS];
-    int rw[GSR_COMPOSE_MAX_GROUPS], nz[GSR_COMPOSE_MAX_GROUPS];
-    int m = 0;
-    for (int g = 0; g < n_groups; g++) {
-        if (groups[g].row_words < 0) return fail(GSR_E_INVALID_ARG, "group %d: negative row_words", g);
-        if (groups[g].row_words == 0) continue;  // an empty features_rest (densification.jl:40-41,196-201)
-        if (!groups[g].dst || (!groups[g].src && (n_keep > 0 || !groups[g].new_zero)))
-            return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
-        src[m] = groups[g].src; dst[m] = groups[g].dst; rw[m] = groups[g].row_words; nz[m] = groups[g].new_zero ? 1 : 0; m++;
-    }
-    if (m == 0) return GSR_OK;
-    gsr_launch_compose_rows((hipStream_t)stream, m, src, dst, rw, nz, keep_idx, n_keep, sel_idx, reps > 0 ? n_sel : 0, reps > 0 ? reps : 1);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_split_transform(int64_t n_new, int32_t scale_dims, float* points, const float* rotations, float* scales, uint32_t seed,
-                        void* stream) {
-    if (n_new < 0 || (scale_dims != 1 && scale_dims != 3)) return fail(GSR_E_INVALID_ARG, "bad sizes");
-    if (n_new == 0) return GSR_OK;  // densification.jl:94 `if n_new_points > 0`
-    if (!points || !rotations || !scales) return fail(GSR_E_INVALID_ARG, "null array");
-    if (((uintptr_t)rotations & 15) != 0) return fail(GSR_E_INVALID_ARG, "rotations must be 16-byte aligned");
-    gsr_launch_split_transform((hipStream_t)stream, n_new, scale_dims, points, rotations, scales, seed);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_reset_opacity(int64_t n, float* opacities, void* stream) {
-    if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
-    if (n == 0) return GSR_OK;
-    if (!opacities) return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_reset_opacity((hipStream_t)stream, n, opacities);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-// ---- the MCMC strategy (mcmc.hip; src/mcmc.jl) ----
-static int check_mcmc_rows(int64_t n, int32_t scale_dims) {
-    if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
-    if (scale_dims != 1 && scale_dims != 3) return fail(GSR_E_INVALID_ARG, "scale_dims = %d: 1 (isotropic) or 3", scale_dims);
-    return GSR_OK;
-}
-
-int gsr_mcmc_weights(int64_t n, int32_t scale_dims, const float* opacities_raw, const float* scales_raw, float min_opacity,
-                     float log_max_scale, uint32_t* q, uint8_t* dead, void* stream) {
-    int rc;
-    if ((rc = check_mcmc_rows(n, scale_dims))) return rc;
-    if (n == 0) return GSR_OK;
-    if (!opacities_raw || !q || (dead && !scales_raw)) return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_mcmc_weights((hipStream_t)stream, n, scale_dims, opacities_raw, scales_raw, min_opacity, log_max_scale, q, dead);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-size_t gsr_mcmc_sample_scratch_bytes(int64_t n) { return gsr_mcmc_sample_scratch_words(n) * sizeof(uint64_t); }
-
-int gsr_mcmc_sample(int64_t n, const uint32_t* q, int64_t m, uint32_t seed, uint32_t* sampled, int32_t* counts, uint64_t* total,
-                    void* scratch, size_t scratch_bytes, void* stream) {
-    if (n < 0 || m < 0) return fail(GSR_E_INVALID_ARG, "negative count: n=%lld m=%lld", (long long)n, (long long)m);
-    if (n > 0xFFFFFFFFll || m > 0xFFFFFFFFll) return fail(GSR_E_INVALID_ARG, "rows and draws are indexed with 32 bits");
-    if (m == 0) return GSR_OK;
-    if (!total) return fail(GSR_E_INVALID_ARG, "null total");
-    if (n > 0 && (!q || !sampled || !counts || !scratch)) return fail(GSR_E_INVALID_ARG, "null array");
-    const size_t need = gsr_mcmc_sample_scratch_bytes(n);
-    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the sampler needs %zu", scratch_bytes, need);
-    if ((((uintptr_t)scratch | (uintptr_t)total) & 7) != 0) return fail(GSR_E_INVALID_ARG, "scratch and total must be 8-byte aligned");
-    gsr_launch_mcmc_sample((hipStream_t)stream, n, q, m, seed, sampled, counts, reinterpret_cast<unsigned long long*>(total),
-                           reinterpret_cast<unsigned long long*>(scratch));
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_mcmc_split_sampled(int64_t n, int32_t scale_dims, const int32_t* counts, const float* binoms, int32_t n_max,
-                           float min_opacity, float* opacities_raw, float* scales_raw, void* stream) {
-    int rc;
-    if ((rc = check_mcmc_rows(n, scale_dims))) return rc;
-    if (n_max < 1) return fail(GSR_E_INVALID_ARG, "n_max = %d: at least 1", n_max);
-    if (n == 0) return GSR_OK;
-    if (!counts || !binoms || !opacities_raw || !scales_raw) return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_mcmc_split_sampled((hipStream_t)stream, n, scale_dims, counts, binoms, n_max, min_opacity, opacities_raw, scales_raw);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_mcmc_relocation_params(int64_t m, const float* o, const int32_t* ratio, const float* binoms, int32_t n_max,
-                               float min_opacity, float* new_o, float* coeff, void* stream) {
-    if (m < 0) return fail(GSR_E_INVALID_ARG, "negative m");
-    if (n_max < 1) return fail(GSR_E_INVALID_ARG, "n_max = %d: at least 1", n_max);
-    if (m == 0) return GSR_OK;
-    if (!o || !ratio || !binoms || !new_o || !coeff) return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_mcmc_relocation_params((hipStream_t)stream, m, o, ratio, binoms, n_max, min_opacity, new_o, coeff);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_mcmc_relocate_rows(const gsr_compose_group* groups, int32_t n_groups, int64_t n, const uint32_t* dead_idx,
-                           const uint32_t* sampled_idx, int64_t m, void* stream) {
-    if (n_groups < 0 || n_groups > GSR_COMPOSE_MAX_GROUPS || (n_groups > 0 && !groups))
-        return fail(GSR_E_INVALID_ARG, "n_groups must be in [0, %d]", GSR_COMPOSE_MAX_GROUPS);
-    if (n < 0 || m < 0) return fail(GSR_E_INVALID_ARG, "negative count");
-    if (m == 0 || n == 0 || n_groups == 0) return GSR_OK;
-    if (!dead_idx || !sampled_idx) return fail(GSR_E_INVALID_ARG, "null index vector");
-    void* x[GSR_COMPOSE_MAX_GROUPS];
-    int rw[GSR_COMPOSE_MAX_GROUPS], nz[GSR_COMPOSE_MAX_GROUPS];
-    int k = 0;
-    for (int g = 0; g < n_groups; g++) {
-        if (groups[g].row_words < 0) return fail(GSR_E_INVALID_ARG, "group %d: negative row_words", g);
-        if (groups[g].row_words == 0) continue;  // an empty features_rest
-        if (!groups[g].dst) return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
-        if (groups[g].src && groups[g].src != groups[g].dst) return fail(GSR_E_INVALID_ARG, "group %d: the relocation is in place (src must be NULL or dst)", g);
-        x[k] = groups[g].dst; rw[k] = groups[g].row_words; nz[k] = groups[g].new_zero ? 1 : 0; k++;
-    }
-    if (k == 0) return GSR_OK;
-    gsr_launch_mcmc_relocate_rows((hipStream_t)stream, k, x, rw, nz, n, dead_idx, sampled_idx, m);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_mcmc_inject_noise(int64_t n, int32_t scale_dims, float* points, const float* opacities_raw, const float* scales_raw,
-                          const float* rotations, float lr, float max_kick, uint32_t seed, void* stream) {
-    int rc;
-    if ((rc = check_mcmc_rows(n, scale_dims))) return rc;
-    if (n == 0) return GSR_OK;  // mcmc.jl:292
-    if (!points || !opacities_raw || !scales_raw || !rotations) return fail(GSR_E_INVALID_ARG, "null array");
-    if (((uintptr_t)rotations & 15) != 0) return fail(GSR_E_INVALID_ARG, "rotations must be 16-byte aligned");
-    gsr_launch_mcmc_inject_noise((hipStream_t)stream, n, scale_dims, points, opacities_raw, scales_raw, rotations, lr, max_kick, seed);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-size_t gsr_mcmc_regularization_scratch_bytes(int64_t n) { return gsr_mcmc_regularization_scratch_floats(n) * sizeof(float); }
-
-int gsr_mcmc_regularization(int64_t n, int32_t scale_dims, const float* opacities_raw, const float* scales_raw, float opacity_reg,
-                            float scale_reg, float* loss_out, float* vopacities, float* vscales, void* scratch,
-                            size_t scratch_bytes, void* stream) {
-    int rc;
-    if ((rc = check_mcmc_rows(n, scale_dims))) return rc;
-    if (!loss_out || (n > 0 && (!opacities_raw || !scales_raw || !scratch))) return fail(GSR_E_INVALID_ARG, "null array");
-    const size_t need = gsr_mcmc_regularization_scratch_bytes(n);
-    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "scratch of %zu bytes, the regulariser needs %zu", scratch_bytes, need);
-    gsr_launch_mcmc_regularization((hipStream_t)stream, n, scale_dims, opacities_raw, scales_raw, opacity_reg, scale_reg, loss_out,
-                                   vopacities, vscales, (float*)scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_morton_codes(int64_t n, const float* points, const float* box_lo, const float* box_hi, uint64_t* codes, void* stream) {
-    if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
-    if (n == 0) return GSR_OK;
-    if (!points || !box_lo || !box_hi || !codes) return fail(GSR_E_INVALID_ARG, "null array");
-    float inv[3];
-    for (int k = 0; k < 3; k++) {
-        const float e = box_hi[k] - box_lo[k];
-        if (!(e >= 0.0f)) return fail(GSR_E_INVALID_ARG, "gsr_morton_codes: box_hi < box_lo (or NaN)");
-        inv[k] = e > 0.0f ? 1.0f / e : 0.0f;
-    }
-    gsr_launch_morton_codes((hipStream_t)stream, n, points, box_lo, inv, reinterpret_cast<unsigned long long*>(codes));
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-// ---- a model from a point cloud: exact 3-NN initial scales (knn.hip; dataset.jl:236-249 `compute_scales`) ----
-size_t gsr_knn_scratch_bytes(int64_t n) {
-    if (n <= 0 || n > 0x7FFFFFFFll) return 0;
-    return gsr_knn_scratch_size(n);
-}
-
-int gsr_knn_scales(int64_t n, const float* points, const int32_t* order, float point_size, int32_t scale_dims, float* scales_out,
-                   float* dist2_out, void* scratch, size_t scratch_bytes, void* stream) {
-    if (n < 0) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: negative n");
-    if (n == 0) return GSR_OK;
-    if (n <= 3)  // the reference's knn(kdtree, xyz, 3 + 1) throws there
-        return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: n = %lld: three neighbours need at least 4 points", (long long)n);
-    if (n > 0x7FFFFFFFll) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: n = %lld: rows are indexed with 31 bits", (long long)n);
-    if (scale_dims != 1 && scale_dims != 3) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: scale_dims = %d: 1 (isotropic) or 3", scale_dims);
-    if (!(point_size > 0.0f)) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: point_size = %g must be positive", (double)point_size);
-    if (!points || !scales_out || !scratch) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: null points, scales_out or scratch");
-    const size_t need = gsr_knn_scratch_bytes(n);
-    if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: scratch_bytes = %zu, the search needs %zu", scratch_bytes, need);
-    if ((uintptr_t)scratch % 16) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: scratch must be 16-byte aligned");
-    gsr_launch_knn_scales((hipStream_t)stream, n, points, order, point_size, scale_dims, scales_out, dist2_out, scratch);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_count_nonfinite(const float* const* arrays, const int32_t* row_words, int32_t n_groups, int64_t n_rows, uint32_t* counts,
-                        uint32_t* first_bad, void* stream) {
-    if (n_groups < 0 || n_groups > GSR_ADAM_MAX_GROUPS || (n_groups > 0 && (!arrays || !row_words)))
-        return fail(GSR_E_INVALID_ARG, "n_groups must be in [0, %d]", GSR_ADAM_MAX_GROUPS);
-    if (n_rows < 0) return fail(GSR_E_INVALID_ARG, "negative n_rows");
-    if (n_groups == 0) return GSR_OK;
-    if (!counts || !first_bad) return fail(GSR_E_INVALID_ARG, "null output");
-    const float* src[GSR_ADAM_MAX_GROUPS]; int rw[GSR_ADAM_MAX_GROUPS];
-    for (int g = 0; g < n_groups; g++) {
-        if (row_words[g] < 0) return fail(GSR_E_INVALID_ARG, "group %d: negative row_words", g);
-        if (row_words[g] > 0 && n_rows > 0 && !arrays[g]) return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
-        src[g] = arrays[g]; rw[g] = row_words[g];
-    }
-    gsr_launch_nonfinite_scan((hipStream_t)stream, n_groups, src, rw, n_rows, counts, first_bad);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-static int ply_rows(bool pack, int64_t n, int32_t k_rest, const float* points, const float* dc, const float* rest,
-                    const float* opac, const float* scales, const float* rots, const float* rows, void* stream) {
-    if (n < 0 || k_rest < 0) return fail(GSR_E_INVALID_ARG, "bad sizes: n=%lld k_rest=%d", (long long)n, k_rest);
-    if (n == 0) return GSR_OK;
-    if (!points || !dc || (k_rest > 0 && !rest) || !opac || !scales || !rots || !rows) return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_ply_rows((hipStream_t)stream, pack, n, k_rest, const_cast<float*>(points), const_cast<float*>(dc),
-                        const_cast<float*>(rest), const_cast<float*>(opac), const_cast<float*>(scales), const_cast<float*>(rots),
-                        const_cast<float*>(rows));
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_ply_pack_rows(int64_t n, int32_t k_rest, const float* points, const float* features_dc, const float* features_rest,
-                      const float* opacities, const float* scales, const float* rotations, float* rows, void* stream) {
-    return ply_rows(true, n, k_rest, points, features_dc, features_rest, opacities, scales, rotations, rows, stream);
-}
-
-int gsr_ply_unpack_rows(int64_t n, int32_t k_rest, const float* rows, float* points, float* features_dc, float* features_rest,
-                        float* opacities, float* scales, float* rotations, void* stream) {
-    return ply_rows(false, n, k_rest, points, features_dc, features_rest, opacities, scales, rotations, rows, stream);
-}
-
-int gsr_sh_grad_from_views(int32_t n, int32_t n_coeffs, int32_t sh_degree, int32_t n_views, const float* camera_centers,
-                           const float* means, const float* vcolors_all, float* vshs, void* stream) {
-    if (n < 0 || n_views < 1 || sh_degree < 0 || sh_degree > 3 || n_coeffs < (sh_degree + 1) * (sh_degree + 1))
-        return fail(GSR_E_INVALID_ARG, "bad sizes: n=%d views=%d degree=%d K=%d", n, n_views, sh_degree, n_coeffs);
-    if (n == 0) return GSR_OK;
-    if (!camera_centers || !means || !vcolors_all || !vshs) return fail(GSR_E_INVALID_ARG, "null array");
-    gsr_launch_sh_grad_views((hipStream_t)stream, n, n_coeffs, sh_degree, n_views, camera_centers, means, vcolors_all, vshs);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_sh_grad_from_views_tail(int32_t n, int32_t n_coeffs, int32_t sh_degree, int32_t n_views, const float* camera_centers,
-                                const float* vcolors_all, const gsr_tail_grads* small, const gsr_tail_state* st, void* stream) {
-    if (n < 0 || n_views < 1 || sh_degree < 0 || sh_degree > 3 || n_coeffs < (sh_degree + 1) * (sh_degree + 1) || n_coeffs > 16)
-        return fail(GSR_E_INVALID_ARG, "bad sizes: n=%d views=%d degree=%d K=%d", n, n_views, sh_degree, n_coeffs);
-    if (n == 0) return GSR_OK;
-    if (!camera_centers || !vcolors_all || !small || !st) return fail(GSR_E_INVALID_ARG, "null argument");
-    if (!small->vmeans || !small->vopacities || !small->vscales || !small->vrotations)
-        return fail(GSR_E_INVALID_ARG, "null gradient (vmeans / vopacities / vscales / vrotations; vshs is not read)");
-    if (st->scale_dims != 1 && st->scale_dims != 3) return fail(GSR_E_INVALID_ARG, "scale_dims must be 1 or 3");
-    if (!st->shs || !st->opacities_act || !st->scales_act) return fail(GSR_E_INVALID_ARG, "null activated copy");
-    float lr_t[6];
-    int rc = tail_lr_t(st->theta, st->mu, st->nu, st->lr, st->current_step, st->beta1, st->beta2, /*rest_empty=*/n_coeffs == 1, lr_t);
-    if (rc) return rc;
-    const gsr::TailState S = gsr_make_tail_state(st->theta, st->mu, st->nu, lr_t, st->beta1, st->beta2, st->eps,
-                                                 st->scale_dims, st->shs, st->opacities_act, st->scales_act);
-    gsr_launch_sh_views_tail((hipStream_t)stream, n, n_coeffs, sh_degree, n_views, camera_centers, vcolors_all, small->vmeans,
-                             small->vopacities, small->vscales, small->vrotations, S);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_stream_triad(float* a, const float* b, const float* c, size_t count, float q, void* stream) {
-    if (!a || !b || !c) return fail(GSR_E_INVALID_ARG, "null array");
-    if (count % 4 != 0 || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) != 0)
-        return fail(GSR_E_INVALID_ARG, "count must be a multiple of 4 and the arrays 16-byte aligned");
-    gsr_launch_triad((hipStream_t)stream, count / 4, a, b, c, q);
-    HIPCHK(hipGetLastError());
-    return GSR_OK;
-}
-
-int gsr_allreduce_grads(void* nccl_comm, float* arena, size_t count, void* stream) {
-    typedef int (*allreduce_fn)(const void*, void*, size_t, int, int, void*, hipStream_t);
-    static allreduce_fn fn = nullptr;
-    if (!nccl_comm || !arena) return fail(GSR_E_INVALID_ARG, "null communicator / arena");
-    if (!fn) {
-        void* lib = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-        if (!lib) lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-        if (!lib) return fail(GSR_E_HIP, "cannot load librccl.so: %s", dlerror());
-        fn = (allreduce_fn)dlsym(lib, "ncclAllReduce");
-        if (!fn) return fail(GSR_E_HIP, "ncclAllReduce not found in librccl.so");
-    }
-    const int ncclFloat32 = 7, ncclSum = 0;
-    int r = fn(arena, arena, count, ncclFloat32, ncclSum, nccl_comm, (hipStream_t)stream);
-    if (r != 0) return fail(GSR_E_HIP, "ncclAllReduce failed with code %d", r);
     return GSR_OK;
 }
 

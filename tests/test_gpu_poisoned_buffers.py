@@ -751,7 +751,7 @@ def test_gather_and_compose_row_destinations(pkg):
 @pytest.mark.parametrize("channels", [3, 5])
 def test_bilateral_slice_tv_and_adam_tail(pkg, channels):
     """The bilateral grid's entry points with every output AND their caller-owned scratch (float per-workgroup partials,
-    gsr_api.cpp) pre-filled: slice forward, its pullback into a separate vimage, TV loss and gradient, the fused TV + Adam
+    gsr_ops.cpp) pre-filled: slice forward, its pullback into a separate vimage, TV loss and gradient, the fused TV + Adam
     tail (the grids, moments, ∇grid and TV term it leaves)."""
     B, L = pkg.bilateral_grid, pkg._lib
     lib = L.load()
