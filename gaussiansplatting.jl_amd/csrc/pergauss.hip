@@ -202,6 +202,15 @@ __device__ __forceinline__ void gaussian_normal(const M33& Rw, const M33& Rg, co
     for (int r = 0; r < 3; r++) n[r] = sign * nc[r];
 }
 
+// The view direction of the SH stages (spherical_harmonics.jl:41-48): d0 = p - center, dir = d0 / |d0|.  The one definition
+// for preprocess, the per-Gaussian backward (which also pulls back through the normalisation: it keeps d0) and the two
+// multi-view SH kernels.
+__device__ __forceinline__ void view_dir(const float p[3], const float* center, float d0[3], float dir[3]) {
+    d0[0] = p[0] - center[0]; d0[1] = p[1] - center[1]; d0[2] = p[2] - center[2];
+    const float inv = 1.0f / sqrtf(d0[0] * d0[0] + d0[1] * d0[1] + d0[2] * d0[2]);
+    dir[0] = d0[0] * inv; dir[1] = d0[1] * inv; dir[2] = d0[2] * inv;
+}
+
 // ---------------------------------------------------------------------------------
 // The FLATTENED walk of preprocess_kernel's binning (both forms).  In scene order a wave's slowest lane has 13.6 pair
 // requests at config 3 and the average lane 3.9 — a per-lane walk runs at 28 % lane efficiency.  Instead every lane
@@ -285,6 +294,150 @@ __device__ __forceinline__ void item_may_touch(const GsrCam& cam, const FlatItem
     if (f.vb) c1 = (!cam.exact_cull || tile_may_touch(smx, smy, sa, sb, sc, stau, (f.xe + 1) * GSR_TILE, f.y * GSR_TILE)) ? 1u : 0u;
 }
 
+// AGG: per counter word (an aligned tile pair), this workgroup's two counts, then its two bin positions — 2 x 32 bits, or
+// 2 x 16 bits (W32) where a larger grid would not fit otherwise: a workgroup adds at most NT per tile, and a position that
+// does not fit 16 bits is beyond bin_cap (the launcher checks) and is clamped to "not stored"
+template <bool W32> using AggWord = typename std::conditional<W32, uint32_t, unsigned long long>::type;
+template <bool W32>
+__device__ __forceinline__ AggWord<W32> agg_inc(uint32_t c0, uint32_t c1) {
+    return W32 ? (AggWord<W32>)(c0 | (c1 << 16)) : (AggWord<W32>)((unsigned long long)c0 | ((unsigned long long)c1 << 32));
+}
+template <bool W32>
+__device__ __forceinline__ uint32_t agg_lo(AggWord<W32> v) { return W32 ? (uint32_t)v & 0xFFFFu : (uint32_t)v; }
+template <bool W32>
+__device__ __forceinline__ uint32_t agg_hi(AggWord<W32> v) {
+    return W32 ? (uint32_t)v >> 16 : (uint32_t)((unsigned long long)v >> 32);
+}
+// an item's two instances as the emitted mask has them (SCATTER's restricted pass, only_above != 0: a tile whose list fits
+// its bin takes no position here)
+template <bool SCATTER>
+__device__ __forceinline__ void replay(const FlatItem& f, const uint32_t* emit, uint32_t only_above,
+                                       const uint32_t* __restrict__ tile_start, uint32_t& c0, uint32_t& c1) {
+    const uint32_t em = emit[f.src];
+    c0 = f.va ? (em >> f.kka) & 1u : 0u; c1 = f.vb ? (em >> f.kkb) & 1u : 0u;
+    if (SCATTER && only_above) {
+        if (c0) c0 = tile_start[f.t + 1u] - tile_start[f.t] > only_above ? 1u : 0u;
+        if (c1) c1 = tile_start[f.t + 2u] - tile_start[f.t + 1u] > only_above ? 1u : 0u;
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// The stages of preprocess_kernel (below) that are functions, each of the kernel's own per-lane state as separate arguments
+// (as one struct the state moves the spill of the BANDED instantiations: profiles/pergauss_stages/codegen_compare.txt).
+// ---------------------------------------------------------------------------------
+constexpr int FLAT_MAX = 16;  // pair requests per lane up to which a rect takes the flattened walks
+
+// SCATTER — the second pass of the compact mode: everything the walks need is in the record preprocess wrote.
+//   in: the record of a Gaussian with radius > 0.  out: its state as project left it (no rgb / clamp bits: this pass neither
+//   has nor needs them); `emitted` = the record's mask.
+__device__ __forceinline__ void splat_from_record(const GsrGeoRec& rec, bool& visible, float m2[2], float conic[3], float& opac_v,
+                                                  float& mc_z, int rmin[2], int rmax[2], uint32_t& area, float& tau, uint32_t& emitted) {
+    visible = true;
+    m2[0] = rec.q0.x; m2[1] = rec.q0.y; conic[0] = rec.q0.z; conic[1] = rec.q0.w; conic[2] = rec.q1.x;
+    opac_v = rec.q1.y; mc_z = rec.q2.z;
+    const uint32_t lo = __float_as_uint(rec.q3.x), hi = __float_as_uint(rec.q3.y);
+    rmin[0] = (int)(lo & 0xFFFFu); rmin[1] = (int)(lo >> 16); rmax[0] = (int)(hi & 0xFFFFu); rmax[1] = (int)(hi >> 16);
+    area = (uint32_t)((rmax[0] - rmin[0]) * (rmax[1] - rmin[1]));
+    tau = footprint_tau(opac_v);
+    emitted = __float_as_uint(rec.q3.w);
+}
+
+// The DIRECT form of the flattened walk: an item = one pair request = (at most) one returning global atomic; two rounds of
+// items in flight per lane.
+//   in: the rect, the footprint floats, the depth, this lane's walk class (fcnt, fppr); own / emit: this wave's owner table and
+//   mask row in LDS.  out: tile_count and bins; `emitted` of the lanes that took the walk (fcnt > 0).  No template flag but NT.
+template <int NT>
+__device__ __forceinline__ void emit_direct(const GsrCam& cam, int fcnt, int fppr, const float m2[2], const float conic[3], float tau,
+                                            float mc_z, const int rmin[2], const int rmax[2], uint8_t* own, uint32_t* emit,
+                                            uint32_t* __restrict__ tile_count, uint64_t* __restrict__ bins, uint32_t bin_cap,
+                                            uint32_t& emitted) {
+    const int ln = threadIdx.x & 63;
+    unsigned long long* tc64 = reinterpret_cast<unsigned long long*>(tile_count);
+    emit[ln] = 0u;
+    uint32_t ftotal;
+    const uint32_t fpre = announce_items(own, fcnt, ln, ftotal);
+    const uint32_t rlo = (uint32_t)rmin[0] | ((uint32_t)rmin[1] << 16);
+    const uint32_t rhi = (uint32_t)rmax[0] | (pair_div_mul(fppr) << 16);
+    constexpr int INFL = 2;
+    for (uint32_t base = 0; base < ftotal; base += 64u * INFL) {
+        uint32_t tt[INFL], cc[INFL], zz[INFL], ss[INFL];
+        unsigned long long old[INFL];
+#pragma unroll
+        for (int u = 0; u < INFL; u++) {
+            const FlatItem f = flat_item<false>(own, base + 64u * (uint32_t)u + (uint32_t)ln, ftotal, fpre, rlo, rhi, cam.grid_x);
+            zz[u] = __shfl(__float_as_uint(mc_z), f.src);
+            ss[u] = (uint32_t)f.src;
+            tt[u] = f.t;
+            uint32_t c0, c1;
+            item_may_touch(cam, f, m2, conic, tau, c0, c1);
+            cc[u] = c0 | (c1 << 1);
+            if (cc[u]) {
+                atomicOr(&emit[f.src], (c0 << f.kka) | (c1 << f.kkb));
+                old[u] = atomicAdd(tc64 + (tt[u] >> 1), (unsigned long long)c0 | ((unsigned long long)c1 << 32));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < INFL; u++)
+            if (cc[u]) {
+                const uint64_t skey = ((uint64_t)zz[u] << 32) | (uint32_t)(blockIdx.x * NT + (threadIdx.x & ~63) + ss[u]);
+                const uint32_t p0 = (uint32_t)old[u], p1 = (uint32_t)(old[u] >> 32);
+                if ((cc[u] & 1u) && p0 < bin_cap) bins[(size_t)tt[u] * bin_cap + p0] = skey;
+                if ((cc[u] & 2u) && p1 < bin_cap) bins[(size_t)(tt[u] + 1) * bin_cap + p1] = skey;
+            }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (fcnt > 0) emitted = emit[ln];
+}
+
+// Large footprints: one thread walking hundreds of tiles serialises the wave (the reference's
+// duplicate_with_keys! has exactly this loop, utils.jl:96-119).  Rects of more than EMIT_COOP
+// tiles are emitted by the whole wave, one tile per lane and round — same tests on the same
+// (broadcast) floats, so the lists are identical.
+//   in: the rect (rmin, rmax, area), the footprint floats (m2, conic, tau), the depth; coop_small: a rect of at most EMIT_COOP
+//   tiles with more than FLAT_MAX pair requests joins.  out: tile_count and bins (SCATTER: the fill counters and the compact
+//   keys at tile_start, restricted by only_above); !SCATTER: `emitted` of a joined rect of at most DENSE_RECT tiles.
+//   Depends on NT (the key) and SCATTER.
+template <int NT, bool SCATTER>
+__device__ __forceinline__ void emit_cooperative(const GsrCam& cam, bool visible, uint32_t area, bool coop_small, const float m2[2],
+                                                 const float conic[3], float tau, const int rmin[2], const int rmax[2], float mc_z,
+                                                 uint32_t only_above, uint32_t bin_cap, const uint32_t* __restrict__ tile_start,
+                                                 uint32_t* __restrict__ tile_count, uint64_t* __restrict__ bins, uint32_t& emitted) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long big = __builtin_amdgcn_ballot_w64(visible && (area > EMIT_COOP || coop_small));
+    while (big) {
+        const int src = __builtin_ctzll(big);
+        big &= big - 1;
+        const float bmx = __shfl(m2[0], src), bmy = __shfl(m2[1], src);
+        const float ba = __shfl(conic[0], src), bb = __shfl(conic[1], src), bc = __shfl(conic[2], src);
+        const float btau = __shfl(tau, src);
+        const int bx0 = __shfl(rmin[0], src), by0 = __shfl(rmin[1], src);
+        const int bx1 = __shfl(rmax[0], src), by1 = __shfl(rmax[1], src);
+        const uint32_t bz = __shfl(__float_as_uint(mc_z), src);
+        const uint64_t bkey = ((uint64_t)bz << 32) | (uint32_t)(blockIdx.x * NT + (threadIdx.x & ~63) + src);
+        const int w = bx1 - bx0, total = w * (by1 - by0);
+        uint32_t first32 = 0u;  // which of the rect's first 32 tiles got an instance (its emitted mask when it is a small one)
+        for (int e = lane; e < total; e += 64) {
+            const int ry = e / w, rx = e - ry * w;
+            const int x = bx0 + rx, y = by0 + ry;
+            const bool pass = !cam.exact_cull || tile_may_touch(bmx, bmy, ba, bb, bc, btau, x * GSR_TILE, y * GSR_TILE);
+            if (e < 64) first32 = (uint32_t)__builtin_amdgcn_ballot_w64(pass);  // (lane 0 is in the first trip)
+            if (pass) {
+                const uint32_t t = (uint32_t)(y * cam.grid_x + x);
+                if (SCATTER) {
+                    const uint32_t ts = tile_start[t];
+                    if (!only_above || tile_start[t + 1u] - ts > only_above) bins[ts + atomicAdd(tile_count + t, 1u)] = bkey;
+                } else {
+                    const uint32_t pos = atomicAdd(tile_count + t, 1u);
+                    if (pos < bin_cap) bins[(size_t)t * bin_cap + pos] = bkey;
+                }
+            }
+        }
+        first32 = __shfl(first32, 0);
+        if (!SCATTER && lane == src && (uint32_t)total <= DENSE_RECT) emitted = first32;
+    }
+}
+
 // ---------------------------------------------------------------------------------
 // preprocess: project! (projection.jl:69-129) + spherical_harmonics!
 // (spherical_harmonics.jl:12-17,41-74) + count_tiles_per_gaussian! (utils.jl:131-141),
@@ -329,17 +482,9 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
     static_assert(!BANDED || AGG_NT != 0, "bands are the aggregating form's");
     constexpr bool AGG = AGG_NT != 0;
     constexpr int NT = AGG ? AGG_NT : 256;
-    // AGG: per counter word (an aligned tile pair), this workgroup's two counts, then its two bin positions — 2 x 32 bits, or
-    // 2 x 16 bits (W32) where a larger grid would not fit otherwise: a workgroup adds at most NT per tile, and a position that
-    // does not fit 16 bits is beyond bin_cap (the launcher checks) and is clamped to "not stored"
-    using AggWord = typename std::conditional<W32, uint32_t, unsigned long long>::type;
+    using Word = AggWord<W32>;
     extern __shared__ unsigned long long agg_raw[];
-    AggWord* agg = reinterpret_cast<AggWord*>(agg_raw);
-    auto agg_inc = [](uint32_t c0, uint32_t c1) -> AggWord {
-        return W32 ? (AggWord)(c0 | (c1 << 16)) : (AggWord)((unsigned long long)c0 | ((unsigned long long)c1 << 32));
-    };
-    auto agg_lo = [](AggWord v) -> uint32_t { return W32 ? (uint32_t)v & 0xFFFFu : (uint32_t)v; };
-    auto agg_hi = [](AggWord v) -> uint32_t { return W32 ? (uint32_t)v >> 16 : (uint32_t)((unsigned long long)v >> 32); };
+    Word* agg = reinterpret_cast<Word*>(agg_raw);
     const int i = blockIdx.x * NT + threadIdx.x;
     // SCATTER: `bin_cap` carries only_above — 0: every tile; else only the tiles whose list is longer (the lists that overflowed
     // the fixed-capacity bins: the others' keys sit complete in their bins, round 5)
@@ -352,9 +497,8 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
     // SH colour of Gaussian i at world position p (spherical_harmonics.jl:12-17,41-74)
     auto sh_colour = [&](const float p[3]) {
         const float* sh = shs + (size_t)3 * K * i;
-        float d[3] = {p[0] - cam.center[0], p[1] - cam.center[1], p[2] - cam.center[2]};
-        float inv = 1.0f / sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        d[0] *= inv; d[1] *= inv; d[2] *= inv;
+        float d0[3], d[3];
+        view_dir(p, cam.center, d0, d);
         float b[16];
         sh_basis<DEG>(d, b);
         constexpr int NB = (DEG + 1) * (DEG + 1);
@@ -369,17 +513,8 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
         }
     };
     if (SCATTER) {
-        // second pass of the compact mode: everything the walks need is in the record preprocess wrote
         if (i < n && geom.radii[i] > 0) {
-            const GsrGeoRec rec = geom.rec[i];
-            visible = true;
-            m2[0] = rec.q0.x; m2[1] = rec.q0.y; conic[0] = rec.q0.z; conic[1] = rec.q0.w; conic[2] = rec.q1.x;
-            opac_v = rec.q1.y; mc_z = rec.q2.z;
-            const uint32_t lo = __float_as_uint(rec.q3.x), hi = __float_as_uint(rec.q3.y);
-            rmin[0] = (int)(lo & 0xFFFFu); rmin[1] = (int)(lo >> 16); rmax[0] = (int)(hi & 0xFFFFu); rmax[1] = (int)(hi >> 16);
-            area = (uint32_t)((rmax[0] - rmin[0]) * (rmax[1] - rmin[1]));
-            tau = footprint_tau(opac_v);
-            emitted = __float_as_uint(rec.q3.w);
+            splat_from_record(geom.rec[i], visible, m2, conic, opac_v, mc_z, rmin, rmax, area, tau, emitted);
         }
     } else if (i < n) {
         M33 R; float t[3];
@@ -470,7 +605,6 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
     // denser view).
     // Rects of at most EMIT_COOP tiles take the flattened walks (flat_item above); Gaussians of more than FLAT_MAX requests
     // (1 %) join the wave-cooperative path below, which then also leaves their emitted mask.
-    constexpr int FLAT_MAX = 16;
     __shared__ uint8_t own_tab[NT / 64][64 * FLAT_MAX];
     __shared__ uint32_t emit_tab[NT / 64][64];
     const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -485,43 +619,7 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
     }
     unsigned long long* tc64 = reinterpret_cast<unsigned long long*>(tile_count);
     if (!AGG) {
-        // the direct form: an item = one pair request = (at most) one returning global atomic; two rounds of items in flight
-        // per lane
-        emit_tab[wv][ln] = 0u;
-        uint32_t ftotal;
-        const uint32_t fpre = announce_items(own_tab[wv], fcnt, ln, ftotal);
-        const uint32_t rlo = (uint32_t)rmin[0] | ((uint32_t)rmin[1] << 16);
-        const uint32_t rhi = (uint32_t)rmax[0] | (pair_div_mul(fppr) << 16);
-        constexpr int INFL = 2;
-        for (uint32_t base = 0; base < ftotal; base += 64u * INFL) {
-            uint32_t tt[INFL], cc[INFL], zz[INFL], ss[INFL];
-            unsigned long long old[INFL];
-#pragma unroll
-            for (int u = 0; u < INFL; u++) {
-                const FlatItem f = flat_item<false>(own_tab[wv], base + 64u * (uint32_t)u + (uint32_t)ln, ftotal, fpre, rlo, rhi, cam.grid_x);
-                zz[u] = __shfl(__float_as_uint(mc_z), f.src);
-                ss[u] = (uint32_t)f.src;
-                tt[u] = f.t;
-                uint32_t c0, c1;
-                item_may_touch(cam, f, m2, conic, tau, c0, c1);
-                cc[u] = c0 | (c1 << 1);
-                if (cc[u]) {
-                    atomicOr(&emit_tab[wv][f.src], (c0 << f.kka) | (c1 << f.kkb));
-                    old[u] = atomicAdd(tc64 + (tt[u] >> 1), (unsigned long long)c0 | ((unsigned long long)c1 << 32));
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < INFL; u++)
-                if (cc[u]) {
-                    const uint64_t skey = ((uint64_t)zz[u] << 32) | (uint32_t)(blockIdx.x * NT + (threadIdx.x & ~63) + ss[u]);
-                    const uint32_t p0 = (uint32_t)old[u], p1 = (uint32_t)(old[u] >> 32);
-                    if ((cc[u] & 1u) && p0 < bin_cap) bins[(size_t)tt[u] * bin_cap + p0] = skey;
-                    if ((cc[u] & 2u) && p1 < bin_cap) bins[(size_t)(tt[u] + 1) * bin_cap + p1] = skey;
-                }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (fcnt > 0) emitted = emit_tab[wv][ln];
+        emit_direct<NT>(cam, fcnt, fppr, m2, conic, tau, mc_z, rmin, rmax, own_tab[wv], emit_tab[wv], tile_count, bins, bin_cap, emitted);
     } else {
         // AGGREGATING form, in horizontal BANDS of the tile grid (round 5: n_bands == 1 is round 4's kernel).  The counter words of
         // a 4K grid do not fit the LDS three times per CU; the words of HALF the grid do — so the workgroup runs its two walks
@@ -530,24 +628,16 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
         // FULL rect).  What the LDS buys on a large grid is not fewer global atomics (a 512-Gaussian workgroup hits mostly distinct
         // words there) but (a) their address order and (b) no same-address serialisation: a hot tile's instances meet in LDS first
         // (dense scenes: 1 % of a 4K grid at 50 x density took the direct form 1.9 ms).
+        // (This stage, the projection above, sh_colour and the slot scan below stay in the kernel's body: as functions they cost
+        //  scalar loads, VGPRs, spill or time in some instantiation — profiles/pergauss_stages/codegen_compare.txt.)
         const bool flat_lane = fcnt > 0;  // this lane's rect takes the flattened walks
         emit_tab[wv][ln] = SCATTER ? emitted : 0u;  // SCATTER replays the record's mask; else the first walk's tests fill it
-        // an item's two instances as the emitted mask has them (SCATTER's restricted pass: a tile whose list fits its bin takes
-        // no position here)
-        auto replay = [&](const FlatItem& f, uint32_t& c0, uint32_t& c1) {
-            const uint32_t em = emit_tab[wv][f.src];
-            c0 = f.va ? (em >> f.kka) & 1u : 0u; c1 = f.vb ? (em >> f.kkb) & 1u : 0u;
-            if (SCATTER && only_above) {
-                if (c0) c0 = tile_start[f.t + 1u] - tile_start[f.t] > only_above ? 1u : 0u;
-                if (c1) c1 = tile_start[f.t + 2u] - tile_start[f.t + 1u] > only_above ? 1u : 0u;
-            }
-        };
         for (int band = 0; band < (BANDED ? n_bands : 1); band++) {
             const int yb0 = BANDED ? band * band_rows : 0, yb1 = BANDED ? min(cam.grid_y, yb0 + band_rows) : cam.grid_y;
             const int wbase = BANDED ? (yb0 * cam.grid_x) >> 1 : 0;
             const int wcount = BANDED ? ((yb1 * cam.grid_x - 1) >> 1) - wbase + 1 : n_words;
             if (BANDED && band > 0) __syncthreads();  // the previous band's second walk has taken its positions
-            for (int w = threadIdx.x; w < wcount; w += NT) agg[w] = (AggWord)0;
+            for (int w = threadIdx.x; w < wcount; w += NT) agg[w] = (Word)0;
             // this lane's rect clipped to the band
             const int yc0 = BANDED ? max(rmin[1], yb0) : rmin[1], yc1 = BANDED ? min(rmax[1], yb1) : rmax[1];
             int bcnt = BANDED ? 0 : fcnt, bppr = BANDED ? 0 : fppr;
@@ -566,11 +656,11 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
             for (uint32_t base = 0; base < ftotal; base += 64u) {
                 const FlatItem f = flat_item<BANDED>(own_tab[wv], base + (uint32_t)ln, ftotal, fpre, rlo, rhi, cam.grid_x);
                 uint32_t c0, c1;
-                if (SCATTER) replay(f, c0, c1);
+                if (SCATTER) replay<SCATTER>(f, emit_tab[wv], only_above, tile_start, c0, c1);
                 else item_may_touch(cam, f, m2, conic, tau, c0, c1);
                 if (c0 | c1) {
                     if (!SCATTER) atomicOr(&emit_tab[wv][f.src], (c0 << f.kka) | (c1 << f.kkb));
-                    atomicAdd(&agg[(f.t >> 1) - (uint32_t)wbase], agg_inc(c0, c1));
+                    atomicAdd(&agg[(f.t >> 1) - (uint32_t)wbase], agg_inc<W32>(c0, c1));
                 }
             }
             __syncthreads();
@@ -580,9 +670,10 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
                 uint32_t any = 0u;
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
-                    const AggWord c = w0 + k * NT < wcount ? agg[w0 + k * NT] : (AggWord)0;
+                    const Word c = w0 + k * NT < wcount ? agg[w0 + k * NT] : (Word)0;
                     if (c) {
-                        old[k] = atomicAdd(tc64 + wbase + w0 + k * NT, (unsigned long long)agg_lo(c) | ((unsigned long long)agg_hi(c) << 32));
+                        old[k] = atomicAdd(tc64 + wbase + w0 + k * NT,
+                                           (unsigned long long)agg_lo<W32>(c) | ((unsigned long long)agg_hi<W32>(c) << 32));
                         any |= 1u << k;
                     }
                 }
@@ -591,9 +682,9 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
                     if (any & (1u << k)) {
                         if (W32) {
                             const uint32_t lim = 0xFFFFu - (uint32_t)NT;  // (beyond every stored position: "not stored", and no carry into the other half)
-                            agg[w0 + k * NT] = (AggWord)(min((uint32_t)old[k], lim) | (min((uint32_t)(old[k] >> 32), lim) << 16));
+                            agg[w0 + k * NT] = (Word)(min((uint32_t)old[k], lim) | (min((uint32_t)(old[k] >> 32), lim) << 16));
                         } else {
-                            agg[w0 + k * NT] = (AggWord)old[k];
+                            agg[w0 + k * NT] = (Word)old[k];
                         }
                     }
             }
@@ -604,11 +695,11 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
                     const FlatItem f = flat_item<BANDED>(own_tab[wv], base + (uint32_t)ln, ftotal, fpre, rlo, rhi, cam.grid_x);
                     const uint32_t zb = __shfl(__float_as_uint(mc_z), f.src);
                     uint32_t c0, c1;
-                    replay(f, c0, c1);
+                    replay<SCATTER>(f, emit_tab[wv], only_above, tile_start, c0, c1);
                     if (c0 | c1) {
-                        const AggWord old = atomicAdd(&agg[(f.t >> 1) - (uint32_t)wbase], agg_inc(c0, c1));
+                        const Word old = atomicAdd(&agg[(f.t >> 1) - (uint32_t)wbase], agg_inc<W32>(c0, c1));
                         const uint64_t skey = ((uint64_t)zb << 32) | (uint32_t)(blockIdx.x * NT + (threadIdx.x & ~63) + f.src);
-                        const uint32_t p0 = agg_lo(old), p1 = agg_hi(old);
+                        const uint32_t p0 = agg_lo<W32>(old), p1 = agg_hi<W32>(old);
                         if (SCATTER) {
                             if (c0) bins[tile_start[f.t] + p0] = skey;
                             if (c1) bins[tile_start[f.t + 1u] + p1] = skey;
@@ -624,45 +715,8 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
         __builtin_amdgcn_wave_barrier();
         if (!SCATTER && flat_lane) emitted = emit_tab[wv][ln];
     }
-    // Large footprints: one thread walking hundreds of tiles serialises the wave (the reference's
-    // duplicate_with_keys! has exactly this loop, utils.jl:96-119).  Rects of more than EMIT_COOP
-    // tiles are emitted by the whole wave, one tile per lane and round — same tests on the same
-    // (broadcast) floats, so the lists are identical.
-    {
-        const int lane = threadIdx.x & 63;
-        unsigned long long big = __builtin_amdgcn_ballot_w64(visible && (area > EMIT_COOP || coop_small));
-        while (big) {
-            const int src = __builtin_ctzll(big);
-            big &= big - 1;
-            const float bmx = __shfl(m2[0], src), bmy = __shfl(m2[1], src);
-            const float ba = __shfl(conic[0], src), bb = __shfl(conic[1], src), bc = __shfl(conic[2], src);
-            const float btau = __shfl(tau, src);
-            const int bx0 = __shfl(rmin[0], src), by0 = __shfl(rmin[1], src);
-            const int bx1 = __shfl(rmax[0], src), by1 = __shfl(rmax[1], src);
-            const uint32_t bz = __shfl(__float_as_uint(mc_z), src);
-            const uint64_t bkey = ((uint64_t)bz << 32) | (uint32_t)(blockIdx.x * NT + (threadIdx.x & ~63) + src);
-            const int w = bx1 - bx0, total = w * (by1 - by0);
-            uint32_t first32 = 0u;  // which of the rect's first 32 tiles got an instance (its emitted mask when it is a small one)
-            for (int e = lane; e < total; e += 64) {
-                const int ry = e / w, rx = e - ry * w;
-                const int x = bx0 + rx, y = by0 + ry;
-                const bool pass = !cam.exact_cull || tile_may_touch(bmx, bmy, ba, bb, bc, btau, x * GSR_TILE, y * GSR_TILE);
-                if (e < 64) first32 = (uint32_t)__builtin_amdgcn_ballot_w64(pass);  // (lane 0 is in the first trip)
-                if (pass) {
-                    const uint32_t t = (uint32_t)(y * cam.grid_x + x);
-                    if (SCATTER) {
-                        const uint32_t ts = tile_start[t];
-                        if (!only_above || tile_start[t + 1u] - ts > only_above) bins[ts + atomicAdd(tile_count + t, 1u)] = bkey;
-                    } else {
-                        const uint32_t pos = atomicAdd(tile_count + t, 1u);
-                        if (pos < bin_cap) bins[(size_t)t * bin_cap + pos] = bkey;
-                    }
-                }
-            }
-            first32 = __shfl(first32, 0);
-            if (!SCATTER && lane == src && (uint32_t)total <= DENSE_RECT) emitted = first32;
-        }
-    }
+    emit_cooperative<NT, SCATTER>(cam, visible, area, coop_small, m2, conic, tau, rmin, rmax, mc_z, only_above, bin_cap, tile_start,
+                                  tile_count, bins, emitted);
     // Exclusive scan of the tile-rect areas inside the block: with bpre[block] (tile_scan) it
     // gives every Gaussian the offset of its instance slots (gradient rows) — the reference's
     // cumsum!(tiles_touched) (rasterizer.jl:333-335), restated hierarchically.
@@ -864,61 +918,54 @@ __device__ __forceinline__ void scales_rots_bwd_f64(const GsrCam& cam, const M33
     unnorm_quat2rot_bwd<double>(vRq, qn, inv_norm, vq_out);
 }
 
+// One gradient row (GSR_ROW_F4(channels) float4, written by composite_bwd) onto the 13 sums of pergauss_bwd_kernel (acc
+// layout: at sum_gradient_rows); f3 is read for channels > 5 only.  The four-in-flight form of the row sum adds through it.
+__device__ __forceinline__ void add_row(float acc[16], const float4& f0, const float4& f1, const float4& f2, const float4& f3,
+                                        int channels) {
+    acc[0] += f0.x; acc[1] += f0.y; acc[2] += f0.z; acc[3] += f0.w;
+    acc[4] += f1.x; acc[5] += f1.y; acc[6] += f1.z; acc[7] += f1.w;
+    acc[8] += f2.x; acc[9] += f2.y;
+    if (channels > 5) { acc[10] += f2.z; acc[11] += f2.w; acc[12] += f3.x; }
+}
+// coefficient of band k >= 1, channel c, of an SH row that starts at band 1 (∇SH of pergauss_bwd_kernel)
+__device__ __forceinline__ float sh_coeff(const float* sh, int k, int c) { return sh[3 * (k - 1) + c]; }
+
+// pos_world_to_cam (projection.jl:75)
+__device__ __forceinline__ void to_camera(const M33& R, const float t[3], const float p[3], float mc[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) mc[r] = (R.m[r][0] * p[0] + R.m[r][1] * p[1] + R.m[r][2] * p[2]) + t[r];
+}
+
+// The forward chain both per-Gaussian kernels start from (projection.jl:76-95): the Gaussian's rotation Rg with the
+// normalised quaternion qn and 1 / |q|, M = Rg diag(s), Sigma = M M', its camera-space image Sc = R Sigma R', and the
+// perspective terms at the camera-space mean mc.  project_bwd recomputes it through this function; preprocess_kernel keeps
+// the same expression trees written out inside its (inline) projection.  A caller reads the members it needs, the others
+// are dead code there.
+struct ForwardChain {
+    M33 Rg, M, Sigma, Sc;
+    float qn[4], inv_norm;
+    Persp pr;
+};
+__device__ __forceinline__ ForwardChain forward_chain(const M33& R, const float mc[3], const float4 q4, const float s[3],
+                                                      const GsrCam& cam) {
+    ForwardChain c;
+    c.Rg = quat2rot(q4, c.qn, c.inv_norm);
+    c.Sigma = cov3d(c.Rg, s, c.M);
+    c.Sc = mul33(mul33(R, c.Sigma), tr33(R));
+    c.pr = persp_common(mc, cam);
+    return c;
+}
+
 // ---------------------------------------------------------------------------------
-// fused ∇project! (projection.jl:170-256) + ∇spherical_harmonics!
-// (spherical_harmonics.jl:32-37,76-181).  Every output element is written exactly
-// once (zeros for culled Gaussians and for SH bands above the active degree), so the
-// 59·N-float gradient arena needs no memset.
-//
-// FUSED: the single-GPU trainer step.  The 59 gradient floats of a Gaussian never reach HBM: the
-// trainer tail (pullback of the sigmoid / exp prologue + the six NU.Adam updates + the activated
-// copies of the next forward; trainer.hip, training.jl:768-779) is applied in the epilogue.  The
-// per-Gaussian groups are updated by the owning thread; the SH groups (48 of the 59 floats) by the
-// whole workgroup, element-major over the workgroup's contiguous slice of features_dc /
-// features_rest so that θ, μ, ν stream as full cache lines — the per-Gaussian factors of the SH
-// gradient (basis x colour cotangent) wait in LDS.  `means` / `rots` ARE the raw points / rotations,
-// `scales` the activated copy; the SH coefficients are read from features_rest (the hcat copy `shs`
-// is only written).  Same expression trees as the unfused chain (adam_math.h): identical bits.
+// The stages of pergauss_bwd_kernel (below), in the order the kernel runs them.
 // ---------------------------------------------------------------------------------
-// F32CHAIN (gsr_config.grad_precision = GSR_GRAD_FP32_REFERENCE): ∇scales / ∇rotations through the reference's own fp32
-// expression trees instead of the float64 chain — reference-parity runs (ADVICE r5); a template parameter, not a branch, so
-// that the default kernels are round 5's register for register.
-template <int DEG, bool FUSED, bool F32CHAIN = false>
-__global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int channels, const float* __restrict__ means,
-                                                           const float* __restrict__ scales,
-                                                           const float4* __restrict__ rots,
-                                                           const float* __restrict__ shs, GsrCam cam, GsrGeom geom,
-                                                           GsrInst inst, float2* __restrict__ vmean2d_out,
-                                                           float* __restrict__ vmeans,
-                                                           float* __restrict__ vshs, float* __restrict__ vopac,
-                                                           float* __restrict__ vscales, float4* __restrict__ vrots,
-                                                           float* __restrict__ pose_part,
-                                                           float* __restrict__ vcolors, gsr::TailState TS) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    float poseR[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, poset[3] = {0, 0, 0};
-    // ---- sum this Gaussian's per-instance gradient rows (written by composite_bwd) ----
-    // acc: [0..2] v rgb, [3] v opacity, [4..6] v conic, [7] v depth, [8..9] v mean2d, [10..12] v normal
-    // The radius, the geometry record and the Gaussian's own inputs are all requested at once (the record and the
-    // inputs of a culled Gaussian are fetched for nothing: 104 bytes x 14 %); fetched one after the other — radius ->
-    // record -> rows -> inputs -> SH — they would be five dependent round trips at 3 waves per SIMD.
-    GsrGeoRec rec;
-    rec.q0 = rec.q1 = rec.q2 = rec.q3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float p_in[3] = {0, 0, 0}, s_in[3] = {0, 0, 0};
-    float4 q_in = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
-    int radius_in = 0;
-    if (i < n) {
-        radius_in = geom.radii[i];
-        rec = geom.rec[i];
-        // (FUSED: these arrays are updated in place by the epilogue — read through the same non-restrict pointers)
-        const float* mp = FUSED ? TS.points : means;
-        const float* sp = FUSED ? TS.scales_act : scales;
-        const float4* qp = FUSED ? reinterpret_cast<const float4*>(TS.rots) : rots;
-        p_in[0] = mp[3 * i]; p_in[1] = mp[3 * i + 1]; p_in[2] = mp[3 * i + 2];
-        s_in[0] = sp[3 * i]; s_in[1] = sp[3 * i + 1]; s_in[2] = sp[3 * i + 2];
-        q_in = qp[i];
-    }
-    const bool visible = radius_in > 0;
-    float acc[16];
+// Sum this Gaussian's per-instance gradient rows (written by composite_bwd).
+// acc: [0..2] v rgb, [3] v opacity, [4..6] v conic, [7] v depth, [8..9] v mean2d, [10..12] v normal
+//   in: visible, the record (rect, slot offset, emitted mask, footprint floats), geom.bpre, the rows.  out: acc[0..12]
+//   (zeros for a culled Gaussian).  The sums run in ascending slot order (per lane; the wave-cooperative form: lane-strided
+//   partial sums, then wave_reduce_transposed<13>) — fixed orders, bit-reproducible gradients.  No template flag.
+__device__ __forceinline__ void sum_gradient_rows(int i, bool visible, const GsrGeoRec& rec, const GsrGeom& geom, const GsrCam& cam,
+                                                  const GsrInst& inst, int channels, float acc[16]) {
 #pragma unroll
     for (int k = 0; k < 16; k++) acc[k] = 0.0f;
     uint32_t area = 0, goff = 0;
@@ -974,16 +1021,10 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
             const float4 d0 = r3[0], d1 = r3[1], d2 = r3[2];
             float4 a3 = a2, b3 = a2, c3 = a2, d3 = a2;
             if (channels > 5) { a3 = r0[3]; b3 = r1[3]; c3 = r2[3]; d3 = r3[3]; }
-#define GSR_ADD_ROW(F0, F1, F2, F3)                                                                      \
-            acc[0] += F0.x; acc[1] += F0.y; acc[2] += F0.z; acc[3] += F0.w;                              \
-            acc[4] += F1.x; acc[5] += F1.y; acc[6] += F1.z; acc[7] += F1.w;                              \
-            acc[8] += F2.x; acc[9] += F2.y;                                                              \
-            if (channels > 5) { acc[10] += F2.z; acc[11] += F2.w; acc[12] += F3.x; }
-            GSR_ADD_ROW(a0, a1, a2, a3)
-            if (h1) { GSR_ADD_ROW(b0, b1, b2, b3) }  // (a duplicate load stands in for a missing row; it is not added)
-            if (h2) { GSR_ADD_ROW(c0, c1, c2, c3) }
-            if (h3) { GSR_ADD_ROW(d0, d1, d2, d3) }
-#undef GSR_ADD_ROW
+            add_row(acc, a0, a1, a2, a3, channels);
+            if (h1) add_row(acc, b0, b1, b2, b3, channels);  // (a duplicate load stands in for a missing row; it is not added)
+            if (h2) add_row(acc, c0, c1, c2, c3, channels);
+            if (h3) add_row(acc, d0, d1, d2, d3, channels);
         }
     }
     {
@@ -1026,251 +1067,199 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
             __builtin_amdgcn_wave_barrier();
         }
     }
+}
 
-    // FUSED: the gradients of this Gaussian stay here (zeros for a culled one)
-    float f_vmean[3] = {0, 0, 0}, f_vs[3] = {0, 0, 0}, f_vq[4] = {0, 0, 0, 0}, f_vopac = 0.0f;
-    float f_vc[3] = {0, 0, 0}, f_b[16];
-    int f_nb = 0;  // SH bands carrying a gradient: 0 for a culled Gaussian
+// ∇project (projection.jl:170-256) of a visible Gaussian, from the forward chain recomputed on its raw inputs.
+//   in: the pose R, t; p, q4, s; the record's conic (q0.z, q0.w, q1.x); a1 = (v conic a, b, c, v depth), vm2 = v mean2d.
+//   out: the struct below — vmean (the projection's share of ∇means), vSigma (fp32 chain only), and the forward values the
+//   next stages read (mc, Rg: normal channel; M, qn, inv_norm: fp32 chain); with_pose: the thresholded pose terms of this
+//   Gaussian in poseR (∇R, column-major) / poset (projection.jl:243-256), else left as they are.  No template flag.
+struct ProjectBwd {
+    float mc[3];
+    M33 Rg, M;
+    float qn[4], inv_norm;
+    float vmean[3];
+    M33 vSigma;
+};
+__device__ __forceinline__ ProjectBwd project_bwd(const GsrCam& cam, const M33& R, const float t[3], const float p[3],
+                                                  const float4 q4, const float s[3], const GsrGeoRec& rec, const float4 a1,
+                                                  const float2 vm2, int channels, bool with_pose, float poseR[9],
+                                                  float poset[3]) {
+    ProjectBwd o;
+    const float4 g0 = rec.q0, g1 = rec.q1;
+    M22 Ci, vCi;
+    Ci.m[0][0] = g0.z; Ci.m[1][0] = g0.w; Ci.m[0][1] = g0.w; Ci.m[1][1] = g1.x;
+    vCi.m[0][0] = a1.x; vCi.m[1][0] = a1.y; vCi.m[0][1] = a1.y; vCi.m[1][1] = a1.z;
+    M22 nC;
 #pragma unroll
-    for (int k = 0; k < 16; k++) f_b[k] = 0.0f;
-    if (i < n) {
-        if (!visible) {
-            vmean2d_out[i] = make_float2(0.0f, 0.0f);
-            if constexpr (!FUSED) {
+    for (int a = 0; a < 2; a++)
 #pragma unroll
-                for (int c = 0; c < 3; c++) { vmeans[3 * i + c] = 0.0f; vscales[3 * i + c] = 0.0f; }
-                vrots[i] = make_float4(0, 0, 0, 0);
-                vopac[i] = 0.0f;
-                if (vcolors) { vcolors[3 * i] = 0.0f; vcolors[3 * i + 1] = 0.0f; vcolors[3 * i + 2] = 0.0f; }
-                // (else: f_nb = 0 — the cooperative store below writes this Gaussian's zeros)
-            }
-        } else {
-            const float4 a0 = make_float4(acc[0], acc[1], acc[2], acc[3]);
-            const float4 a1 = make_float4(acc[4], acc[5], acc[6], acc[7]);
-            const float2 vm2 = make_float2(acc[8], acc[9]);
-            vmean2d_out[i] = vm2;  // gstate.∇means_2d, read by densification (strategy.jl:85-86)
-            const float4 g0 = rec.q0, g1 = rec.q1, g2 = rec.q2;
-            if constexpr (FUSED) f_vopac = a0.w; else vopac[i] = a0.w;
-            M33 R; float t[3];
-            load_pose(cam, R, t);
-            // ---- ∇project ----
-            M22 Ci, vCi;
-            Ci.m[0][0] = g0.z; Ci.m[1][0] = g0.w; Ci.m[0][1] = g0.w; Ci.m[1][1] = g1.x;
-            vCi.m[0][0] = a1.x; vCi.m[1][0] = a1.y; vCi.m[0][1] = a1.y; vCi.m[1][1] = a1.z;
-            M22 nC;
+        for (int b = 0; b < 2; b++) nC.m[a][b] = -Ci.m[a][b];
+    M22 vS2 = mul22(mul22(nC, vCi), Ci);  // ∇inverse (render.jl:383-385)
+    to_camera(R, t, p, o.mc);
+    const float* mc = o.mc;
+    const ForwardChain fc = forward_chain(R, mc, q4, s, cam);
+    o.Rg = fc.Rg; o.M = fc.M; o.inv_norm = fc.inv_norm;
 #pragma unroll
-            for (int a = 0; a < 2; a++)
+    for (int k = 0; k < 4; k++) o.qn[k] = fc.qn[k];
+    const M33& Sigma = fc.Sigma;
+    const M33& Sc = fc.Sc;
+    const Persp& pr = fc.pr;
+    const float rz = pr.rz, rz2 = rz * rz, rz3 = rz2 * rz;
+    const float* f = cam.focal;
+    // ∇perspective_projection (projection.jl:289-353)
+    float JtV[3][2];
 #pragma unroll
-                for (int b = 0; b < 2; b++) nC.m[a][b] = -Ci.m[a][b];
-            M22 vS2 = mul22(mul22(nC, vCi), Ci);  // ∇inverse (render.jl:383-385)
-            const float p[3] = {p_in[0], p_in[1], p_in[2]};
-            float mc[3];
+    for (int a = 0; a < 3; a++)
 #pragma unroll
-            for (int r = 0; r < 3; r++) mc[r] = (R.m[r][0] * p[0] + R.m[r][1] * p[1] + R.m[r][2] * p[2]) + t[r];
-            const float4 q4 = q_in;
-            float qn[4], inv_norm;
-            M33 Rg = quat2rot(q4, qn, inv_norm);
-            const float s[3] = {s_in[0], s_in[1], s_in[2]};
-            M33 M;
-            M33 Sigma = cov3d(Rg, s, M);
-            M33 Sc = mul33(mul33(R, Sigma), tr33(R));
-            Persp pr = persp_common(mc, cam);
-            const float rz = pr.rz, rz2 = rz * rz, rz3 = rz2 * rz;
-            const float* f = cam.focal;
-            // ∇perspective_projection (projection.jl:289-353)
-            float JtV[3][2];
+        for (int b = 0; b < 2; b++) JtV[a][b] = pr.J[0][a] * vS2.m[0][b] + pr.J[1][a] * vS2.m[1][b];
+    M33 vSc;
 #pragma unroll
-            for (int a = 0; a < 3; a++)
+    for (int a = 0; a < 3; a++)
 #pragma unroll
-                for (int b = 0; b < 2; b++) JtV[a][b] = pr.J[0][a] * vS2.m[0][b] + pr.J[1][a] * vS2.m[1][b];
-            M33 vSc;
+        for (int b = 0; b < 3; b++) vSc.m[a][b] = JtV[a][0] * pr.J[0][b] + JtV[a][1] * pr.J[1][b];
+    float A[2][3], B[2][3], vJ[2][3];
 #pragma unroll
-            for (int a = 0; a < 3; a++)
+    for (int a = 0; a < 2; a++)
 #pragma unroll
-                for (int b = 0; b < 3; b++) vSc.m[a][b] = JtV[a][0] * pr.J[0][b] + JtV[a][1] * pr.J[1][b];
-            float A[2][3], B[2][3], vJ[2][3];
+        for (int b = 0; b < 3; b++) {
+            A[a][b] = vS2.m[a][0] * pr.J[0][b] + vS2.m[a][1] * pr.J[1][b];
+            B[a][b] = vS2.m[0][a] * pr.J[0][b] + vS2.m[1][a] * pr.J[1][b];
+        }
 #pragma unroll
-            for (int a = 0; a < 2; a++)
+    for (int a = 0; a < 2; a++)
 #pragma unroll
-                for (int b = 0; b < 3; b++) {
-                    A[a][b] = vS2.m[a][0] * pr.J[0][b] + vS2.m[a][1] * pr.J[1][b];
-                    B[a][b] = vS2.m[0][a] * pr.J[0][b] + vS2.m[1][a] * pr.J[1][b];
-                }
+        for (int b = 0; b < 3; b++) {
+            float u = A[a][0] * Sc.m[b][0] + A[a][1] * Sc.m[b][1] + A[a][2] * Sc.m[b][2];
+            float v = B[a][0] * Sc.m[0][b] + B[a][1] * Sc.m[1][b] + B[a][2] * Sc.m[2][b];
+            vJ[a][b] = u + v;
+        }
+    float vx = f[0] * rz * vm2.x;
+    float vy = f[1] * rz * vm2.y;
+    float vz = -rz2 * (f[0] * mc[0] * vm2.x + f[1] * mc[1] * vm2.y);
+    float rx = mc[0] * rz, ry = mc[1] * rz;
+    if (-pr.lim_neg[0] <= rx && rx <= pr.lim[0]) vx += -f[0] * rz2 * vJ[0][2];
+    else vz += -f[0] * rz3 * vJ[0][2] * pr.txy[0];
+    if (-pr.lim_neg[1] <= ry && ry <= pr.lim[1]) vy += -f[1] * rz2 * vJ[1][2];
+    else vz += -f[1] * rz3 * vJ[1][2] * pr.txy[1];
+    vz += -f[0] * rz2 * vJ[0][0] - f[1] * rz2 * vJ[1][1] + 2.0f * f[0] * pr.txy[0] * rz3 * vJ[0][2] +
+          2.0f * f[1] * pr.txy[1] * rz3 * vJ[1][2];
+    float vmc[3] = {vx, vy, vz};
+    if (channels > 3) vmc[2] = vmc[2] + a1.w;  // vdepth (projection.jl:218-222)
+    // ∇pos_world_to_cam, ∇covar_world_to_cam
 #pragma unroll
-            for (int a = 0; a < 2; a++)
+    for (int c = 0; c < 3; c++) o.vmean[c] = R.m[0][c] * vmc[0] + R.m[1][c] * vmc[1] + R.m[2][c] * vmc[2];
+    o.vSigma = mul33(mul33(tr33(R), vSc), R);
+    if (with_pose) {
+        M33 vR0;
 #pragma unroll
-                for (int b = 0; b < 3; b++) {
-                    float u = A[a][0] * Sc.m[b][0] + A[a][1] * Sc.m[b][1] + A[a][2] * Sc.m[b][2];
-                    float v = B[a][0] * Sc.m[0][b] + B[a][1] * Sc.m[1][b] + B[a][2] * Sc.m[2][b];
-                    vJ[a][b] = u + v;
-                }
-            float vx = f[0] * rz * vm2.x;
-            float vy = f[1] * rz * vm2.y;
-            float vz = -rz2 * (f[0] * mc[0] * vm2.x + f[1] * mc[1] * vm2.y);
-            float rx = mc[0] * rz, ry = mc[1] * rz;
-            if (-pr.lim_neg[0] <= rx && rx <= pr.lim[0]) vx += -f[0] * rz2 * vJ[0][2];
-            else vz += -f[0] * rz3 * vJ[0][2] * pr.txy[0];
-            if (-pr.lim_neg[1] <= ry && ry <= pr.lim[1]) vy += -f[1] * rz2 * vJ[1][2];
-            else vz += -f[1] * rz3 * vJ[1][2] * pr.txy[1];
-            vz += -f[0] * rz2 * vJ[0][0] - f[1] * rz2 * vJ[1][1] + 2.0f * f[0] * pr.txy[0] * rz3 * vJ[0][2] +
-                  2.0f * f[1] * pr.txy[1] * rz3 * vJ[1][2];
-            float vmc[3] = {vx, vy, vz};
-            if (channels > 3) vmc[2] = vmc[2] + a1.w;  // vdepth (projection.jl:218-222)
-            // ∇pos_world_to_cam, ∇covar_world_to_cam
-            float vmean[3];
+        for (int r = 0; r < 3; r++)
 #pragma unroll
-            for (int c = 0; c < 3; c++) vmean[c] = R.m[0][c] * vmc[0] + R.m[1][c] * vmc[1] + R.m[2][c] * vmc[2];
-            M33 vSigma = mul33(mul33(tr33(R), vSc), R);
-            if (pose_part) {
-                M33 vR0;
+            for (int c = 0; c < 3; c++) vR0.m[r][c] = vmc[r] * p[c];
+        M33 u = mul33(mul33(vSc, R), tr33(Sigma));
+        M33 v = mul33(mul33(tr33(vSc), R), Sigma);
+        M33 vR2 = add33(add33(vR0, u), v);
 #pragma unroll
-                for (int r = 0; r < 3; r++)
+        for (int r = 0; r < 3; r++) {
 #pragma unroll
-                    for (int c = 0; c < 3; c++) vR0.m[r][c] = vmc[r] * p[c];
-                M33 u = mul33(mul33(vSc, R), tr33(Sigma));
-                M33 v = mul33(mul33(tr33(vSc), R), Sigma);
-                M33 vR2 = add33(add33(vR0, u), v);
-#pragma unroll
-                for (int r = 0; r < 3; r++) {
-#pragma unroll
-                    for (int c = 0; c < 3; c++) poseR[c * 3 + r] = fabsf(vR2.m[r][c]) > 1e-7f ? vR2.m[r][c] : 0.0f;
-                    poset[r] = fabsf(vmc[r]) > 1e-7f ? vmc[r] : 0.0f;
-                }
-            }
-            // normal channel (projection.jl:227-235)
-            M33 vRg;
-#pragma unroll
-            for (int a = 0; a < 3; a++)
-#pragma unroll
-                for (int b = 0; b < 3; b++) vRg.m[a][b] = 0.0f;
-            if (channels > 5) {
-                const float4 a2 = make_float4(acc[10], acc[11], acc[12], 0.0f);
-                float nn[3]; int k; float sg;
-                gaussian_normal(R, Rg, s, mc, nn, k, sg);
-#pragma unroll
-                for (int r = 0; r < 3; r++) {
-                    float g = R.m[0][r] * a2.x + R.m[1][r] * a2.y + R.m[2][r] * a2.z;
-                    float v = sg * g;
-                    vRg.m[r][0] = k == 0 ? v : 0.0f;
-                    vRg.m[r][1] = k == 1 ? v : 0.0f;
-                    vRg.m[r][2] = k == 2 ? v : 0.0f;
-                }
-            }
-            // ∇quat_scale_to_cov (render.jl:302-320) + ∇unnorm_quat2rot (render.jl:335-366): in float64 from the raw inputs
-            // (scales_rots_bwd_f64 above — the fp32 chain loses a needle's thin eigen-direction).  F32CHAIN keeps the
-            // reference's fp32 expression trees (gsr_config.grad_precision = GSR_GRAD_FP32_REFERENCE).
-            float vs[3], vq[4];
-            if constexpr (!F32CHAIN) {
-                scales_rots_bwd_f64(cam, R, t, p, q4, s, a1.x, a1.y, a1.z, vRg, vs, vq);
-                (void)vSigma; (void)M; (void)qn; (void)inv_norm;
-            } else {
-                M33 S;
-#pragma unroll
-                for (int a = 0; a < 3; a++)
-#pragma unroll
-                    for (int b = 0; b < 3; b++) S.m[a][b] = 0.0f;
-                S.m[0][0] = s[0]; S.m[1][1] = s[1]; S.m[2][2] = s[2];
-                M33 vM = mul33(add33(vSigma, tr33(vSigma)), M);
-                M33 vRq = add33(mul33(vM, S), vRg);
-#pragma unroll
-                for (int c = 0; c < 3; c++)
-                    vs[c] = Rg.m[0][c] * vM.m[0][c] + Rg.m[1][c] * vM.m[1][c] + Rg.m[2][c] * vM.m[2][c];
-                unnorm_quat2rot_bwd<float>(vRq.m, qn, inv_norm, vq);
-            }
-            if constexpr (FUSED) {
-#pragma unroll
-                for (int k = 0; k < 4; k++) f_vq[k] = vq[k];
-#pragma unroll
-                for (int c = 0; c < 3; c++) f_vs[c] = vs[c];
-            } else {
-                vrots[i] = make_float4(vq[0], vq[1], vq[2], vq[3]);
-#pragma unroll
-                for (int c = 0; c < 3; c++) vscales[3 * i + c] = vs[c];
-            }
+            for (int c = 0; c < 3; c++) poseR[c * 3 + r] = fabsf(vR2.m[r][c]) > 1e-7f ? vR2.m[r][c] : 0.0f;
+            poset[r] = fabsf(vmc[r]) > 1e-7f ? vmc[r] : 0.0f;
+        }
+    }
+    return o;
+}
 
-            // ---- ∇SH ----
-            // coefficients of band k >= 1 (band 0 has no directional gradient)
-            const float* sh = FUSED ? TS.rest + (size_t)3 * (K - 1) * i : shs + (size_t)3 * K * i + 3;
-            const uint32_t clamp_bits = __float_as_uint(g2.y);
-            float vc[3] = {a0.x * (1.0f - (float)(clamp_bits & 1u)), a0.y * (1.0f - (float)((clamp_bits >> 1) & 1u)),
-                           a0.z * (1.0f - (float)((clamp_bits >> 2) & 1u))};
-            float d0[3] = {p[0] - cam.center[0], p[1] - cam.center[1], p[2] - cam.center[2]};
-            float inv = 1.0f / sqrtf(d0[0] * d0[0] + d0[1] * d0[1] + d0[2] * d0[2]);
-            const float dx = d0[0] * inv, dy = d0[1] * inv, dz = d0[2] * inv;
-            const float dir[3] = {dx, dy, dz};
-            float b[16];
-            sh_basis<DEG>(dir, b);
-            constexpr int NB = (DEG + 1) * (DEG + 1);
-            if (!FUSED && vcolors) {
-                // factored form for the multi-view exchange: ∇shs of a view is the outer product
-                // basis(dir) x vc, so 3 floats per Gaussian travel instead of 3K (sh_grad_views_kernel
-                // rebuilds Σ_views on every rank)
-                vcolors[3 * i] = vc[0]; vcolors[3 * i + 1] = vc[1]; vcolors[3 * i + 2] = vc[2];
-            } else {
-                // ∇shs = basis x vc is stored (FUSED: applied) by the whole workgroup below (coalesced float4 rows instead
-                // of 48 dword stores 192 bytes apart per lane)
-                f_nb = NB;
+// The normal channel's pullback (projection.jl:227-235): the cotangent of the Gaussian's rotation matrix from acc[10..12].
+//   out: vRg (zeros unless channels > 5).  No template flag.
+__device__ __forceinline__ void normal_bwd(int channels, const float acc[16], const M33& R, const M33& Rg, const float s[3],
+                                           const float mc[3], M33& vRg) {
 #pragma unroll
-                for (int c = 0; c < 3; c++) f_vc[c] = vc[c];
+    for (int a = 0; a < 3; a++)
 #pragma unroll
-                for (int k = 0; k < NB; k++) f_b[k] = b[k];
-            }
-            float dcx[3] = {0, 0, 0}, dcy[3] = {0, 0, 0}, dcz[3] = {0, 0, 0};
-#define SHC(k_, c_) sh[3 * ((k_) - 1) + (c_)]
-            if (DEG > 0) {
-                const float x = dx, y = dy, z = dz;
+        for (int b = 0; b < 3; b++) vRg.m[a][b] = 0.0f;
+    if (channels > 5) {
+        const float4 a2 = make_float4(acc[10], acc[11], acc[12], 0.0f);
+        float nn[3]; int k; float sg;
+        gaussian_normal(R, Rg, s, mc, nn, k, sg);
 #pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    dcx[c] = -SH1 * SHC(3, c); dcy[c] = -SH1 * SHC(1, c); dcz[c] = SH1 * SHC(2, c);
-                }
-                if (DEG > 1) {
-                    float x2 = x * x, y2 = y * y, z2 = z * z, xy = x * y, xz = x * z, yz = y * z;
+        for (int r = 0; r < 3; r++) {
+            float g = R.m[0][r] * a2.x + R.m[1][r] * a2.y + R.m[2][r] * a2.z;
+            float v = sg * g;
+            vRg.m[r][0] = k == 0 ? v : 0.0f;
+            vRg.m[r][1] = k == 1 ? v : 0.0f;
+            vRg.m[r][2] = k == 2 ? v : 0.0f;
+        }
+    }
+}
+
+// ∇spherical_harmonics! with respect to the direction (spherical_harmonics.jl:76-181).
+//   in: sh = the coefficients of band 1 on (3 floats per band; band 0 has no directional gradient), p, the camera centre,
+//   vc = the colour cotangent with the clamp mask applied.  out: b = the SH basis at the view direction (the coefficient
+//   gradient is the outer product b x vc, stored by store_or_apply_sh), vmsh = the SH stage's share of ∇means.  Depends on DEG.
+template <int DEG>
+__device__ __forceinline__ void sh_bwd(const float* sh, const float p[3], const GsrCam& cam, const float vc[3], float b[16],
+                                       float vmsh[3]) {
+    float d0[3], dir[3];
+    view_dir(p, cam.center, d0, dir);
+    sh_basis<DEG>(dir, b);
+    float dcx[3] = {0, 0, 0}, dcy[3] = {0, 0, 0}, dcz[3] = {0, 0, 0};
+    if (DEG > 0) {
+        const float x = dir[0], y = dir[1], z = dir[2];
 #pragma unroll
-                    for (int c = 0; c < 3; c++) {
-                        dcx[c] = dcx[c] + SH2C1 * y * SHC(4, c) + SH2C3 * 2.0f * -x * SHC(6, c) +
-                                 SH2C4 * z * SHC(7, c) + SH2C5 * 2.0f * x * SHC(8, c);
-                        dcy[c] = dcy[c] + SH2C1 * x * SHC(4, c) + SH2C2 * z * SHC(5, c) +
-                                 SH2C3 * 2.0f * -y * SHC(6, c) + SH2C5 * 2.0f * -y * SHC(8, c);
-                        dcz[c] = dcz[c] + SH2C2 * y * SHC(5, c) + SH2C3 * 4.0f * z * SHC(6, c) + SH2C4 * x * SHC(7, c);
-                    }
-                    if (DEG > 2) {
-#pragma unroll
-                        for (int c = 0; c < 3; c++) {
-                            dcx[c] = dcx[c] + SH3C1 * SHC(9, c) * 3.0f * 2.0f * xy + SH3C2 * SHC(10, c) * yz +
-                                     SH3C3 * SHC(11, c) * -2.0f * xy + SH3C4 * SHC(12, c) * -3.0f * 2.0f * xz +
-                                     SH3C5 * SHC(13, c) * (-3.0f * x2 + 4.0f * z2 - y2) +
-                                     SH3C6 * SHC(14, c) * 2.0f * xz + SH3C7 * SHC(15, c) * 3.0f * (x2 - y2);
-                            dcy[c] = dcy[c] + SH3C1 * SHC(9, c) * 3.0f * (x2 - y2) + SH3C2 * SHC(10, c) * xz +
-                                     SH3C3 * SHC(11, c) * (-3.0f * y2 + 4.0f * z2 - x2) +
-                                     SH3C4 * SHC(12, c) * -3.0f * 2.0f * yz + SH3C5 * SHC(13, c) * -2.0f * xy +
-                                     SH3C6 * SHC(14, c) * -2.0f * yz + SH3C7 * SHC(15, c) * -3.0f * 2.0f * xy;
-                            dcz[c] = dcz[c] + SH3C2 * SHC(10, c) * xy + SH3C3 * SHC(11, c) * 4.0f * 2.0f * yz +
-                                     SH3C4 * SHC(12, c) * 3.0f * (2.0f * z2 - x2 - y2) +
-                                     SH3C5 * SHC(13, c) * 4.0f * 2.0f * xz + SH3C6 * SHC(14, c) * (x2 - y2);
-                        }
-                    }
-                }
-            }
-#undef SHC
-            float vdir[3];
-            vdir[0] = dcx[0] * vc[0] + dcx[1] * vc[1] + dcx[2] * vc[2];
-            vdir[1] = dcy[0] * vc[0] + dcy[1] * vc[1] + dcy[2] * vc[2];
-            vdir[2] = dcz[0] * vc[0] + dcz[1] * vc[1] + dcz[2] * vc[2];
-            // ∇normalize (spherical_harmonics.jl:174-181)
-            float s2 = d0[0] * d0[0] + d0[1] * d0[1] + d0[2] * d0[2];
-            float inv_s = 1.0f / sqrtf(s2 * s2 * s2);
-            float vmsh[3];
-            vmsh[0] = ((s2 - d0[0] * d0[0]) * vdir[0] - d0[1] * d0[0] * vdir[1] - d0[2] * d0[0] * vdir[2]) * inv_s;
-            vmsh[1] = (-d0[0] * d0[1] * vdir[0] + (s2 - d0[1] * d0[1]) * vdir[1] - d0[2] * d0[1] * vdir[2]) * inv_s;
-            vmsh[2] = (-d0[0] * d0[2] * vdir[0] - d0[1] * d0[2] * vdir[1] + (s2 - d0[2] * d0[2]) * vdir[2]) * inv_s;
+        for (int c = 0; c < 3; c++) {
+            dcx[c] = -SH1 * sh_coeff(sh, 3, c); dcy[c] = -SH1 * sh_coeff(sh, 1, c); dcz[c] = SH1 * sh_coeff(sh, 2, c);
+        }
+        if (DEG > 1) {
+            float x2 = x * x, y2 = y * y, z2 = z * z, xy = x * y, xz = x * z, yz = y * z;
 #pragma unroll
             for (int c = 0; c < 3; c++) {
-                if constexpr (FUSED) f_vmean[c] = vmean[c] + vmsh[c]; else vmeans[3 * i + c] = vmean[c] + vmsh[c];
+                dcx[c] = dcx[c] + SH2C1 * y * sh_coeff(sh, 4, c) + SH2C3 * 2.0f * -x * sh_coeff(sh, 6, c) +
+                         SH2C4 * z * sh_coeff(sh, 7, c) + SH2C5 * 2.0f * x * sh_coeff(sh, 8, c);
+                dcy[c] = dcy[c] + SH2C1 * x * sh_coeff(sh, 4, c) + SH2C2 * z * sh_coeff(sh, 5, c) +
+                         SH2C3 * 2.0f * -y * sh_coeff(sh, 6, c) + SH2C5 * 2.0f * -y * sh_coeff(sh, 8, c);
+                dcz[c] = dcz[c] + SH2C2 * y * sh_coeff(sh, 5, c) + SH2C3 * 4.0f * z * sh_coeff(sh, 6, c) +
+                         SH2C4 * x * sh_coeff(sh, 7, c);
+            }
+            if (DEG > 2) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    dcx[c] = dcx[c] + SH3C1 * sh_coeff(sh, 9, c) * 3.0f * 2.0f * xy + SH3C2 * sh_coeff(sh, 10, c) * yz +
+                             SH3C3 * sh_coeff(sh, 11, c) * -2.0f * xy + SH3C4 * sh_coeff(sh, 12, c) * -3.0f * 2.0f * xz +
+                             SH3C5 * sh_coeff(sh, 13, c) * (-3.0f * x2 + 4.0f * z2 - y2) +
+                             SH3C6 * sh_coeff(sh, 14, c) * 2.0f * xz + SH3C7 * sh_coeff(sh, 15, c) * 3.0f * (x2 - y2);
+                    dcy[c] = dcy[c] + SH3C1 * sh_coeff(sh, 9, c) * 3.0f * (x2 - y2) + SH3C2 * sh_coeff(sh, 10, c) * xz +
+                             SH3C3 * sh_coeff(sh, 11, c) * (-3.0f * y2 + 4.0f * z2 - x2) +
+                             SH3C4 * sh_coeff(sh, 12, c) * -3.0f * 2.0f * yz + SH3C5 * sh_coeff(sh, 13, c) * -2.0f * xy +
+                             SH3C6 * sh_coeff(sh, 14, c) * -2.0f * yz + SH3C7 * sh_coeff(sh, 15, c) * -3.0f * 2.0f * xy;
+                    dcz[c] = dcz[c] + SH3C2 * sh_coeff(sh, 10, c) * xy + SH3C3 * sh_coeff(sh, 11, c) * 4.0f * 2.0f * yz +
+                             SH3C4 * sh_coeff(sh, 12, c) * 3.0f * (2.0f * z2 - x2 - y2) +
+                             SH3C5 * sh_coeff(sh, 13, c) * 4.0f * 2.0f * xz + SH3C6 * sh_coeff(sh, 14, c) * (x2 - y2);
+                }
             }
         }
     }
-    // The SH part of the gradient is the outer product basis x colour cotangent: its factors wait in LDS and the whole
-    // workgroup writes (FUSED: updates) the workgroup's contiguous slice element-major, as full cache lines.
+    float vdir[3];
+    vdir[0] = dcx[0] * vc[0] + dcx[1] * vc[1] + dcx[2] * vc[2];
+    vdir[1] = dcy[0] * vc[0] + dcy[1] * vc[1] + dcy[2] * vc[2];
+    vdir[2] = dcz[0] * vc[0] + dcz[1] * vc[1] + dcz[2] * vc[2];
+    // ∇normalize (spherical_harmonics.jl:174-181)
+    float s2 = d0[0] * d0[0] + d0[1] * d0[1] + d0[2] * d0[2];
+    float inv_s = 1.0f / sqrtf(s2 * s2 * s2);
+    vmsh[0] = ((s2 - d0[0] * d0[0]) * vdir[0] - d0[1] * d0[0] * vdir[1] - d0[2] * d0[0] * vdir[2]) * inv_s;
+    vmsh[1] = (-d0[0] * d0[1] * vdir[0] + (s2 - d0[1] * d0[1]) * vdir[1] - d0[2] * d0[1] * vdir[2]) * inv_s;
+    vmsh[2] = (-d0[0] * d0[2] * vdir[0] - d0[1] * d0[2] * vdir[1] + (s2 - d0[2] * d0[2]) * vdir[2]) * inv_s;
+}
+
+// The SH part of the gradient is the outer product basis x colour cotangent: its factors wait in LDS and the whole
+// workgroup writes (FUSED: updates) the workgroup's contiguous slice element-major, as full cache lines.
+//   in: per thread, the factors f_b (basis), f_vc (colour cotangent), f_nb (bands carrying a gradient; 0: culled), and for
+//   FUSED the Gaussian's own gradients f_vmean, f_vopac, f_vs, f_vq.  out: !FUSED: vshs (unless vcolors: the factored
+//   form left the kernel already); FUSED: the trainer tail applied to TS (adam_math.h).  Depends on FUSED.
+template <bool FUSED>
+__device__ __forceinline__ void store_or_apply_sh(int i, int n, int K, float* __restrict__ vshs, const float* vcolors,
+                                                  const gsr::TailState& TS, const float f_b[16], const float f_vc[3],
+                                                  int f_nb, const float f_vmean[3], float f_vopac, const float f_vs[3],
+                                                  const float f_vq[4]) {
     __shared__ float tail_b[256][17];  // SH basis of each Gaussian of the workgroup (odd stride: no bank conflicts)
     __shared__ float tail_vc[256][3];  // its colour cotangent (clamp mask applied)
     __shared__ int tail_nb[256];       // SH bands carrying a gradient (0: culled Gaussian)
@@ -1303,6 +1292,162 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
         sh_group(TS.dc, TS.dc_mu, TS.dc_nu, 3, 0, TS.h_dc);
         if (K > 1) sh_group(TS.rest, TS.rest_mu, TS.rest_nu, 3 * (K - 1), 1, TS.h_rest);
     }
+}
+
+// ---------------------------------------------------------------------------------
+// fused ∇project! (projection.jl:170-256) + ∇spherical_harmonics!
+// (spherical_harmonics.jl:32-37,76-181).  Every output element is written exactly
+// once (zeros for culled Gaussians and for SH bands above the active degree), so the
+// 59·N-float gradient arena needs no memset.
+//
+// FUSED: the single-GPU trainer step.  The 59 gradient floats of a Gaussian never reach HBM: the
+// trainer tail (pullback of the sigmoid / exp prologue + the six NU.Adam updates + the activated
+// copies of the next forward; trainer.hip, training.jl:768-779) is applied in the epilogue.  The
+// per-Gaussian groups are updated by the owning thread; the SH groups (48 of the 59 floats) by the
+// whole workgroup, element-major over the workgroup's contiguous slice of features_dc /
+// features_rest so that θ, μ, ν stream as full cache lines — the per-Gaussian factors of the SH
+// gradient (basis x colour cotangent) wait in LDS.  `means` / `rots` ARE the raw points / rotations,
+// `scales` the activated copy; the SH coefficients are read from features_rest (the hcat copy `shs`
+// is only written).  Same expression trees as the unfused chain (adam_math.h): identical bits.
+// ---------------------------------------------------------------------------------
+// F32CHAIN (gsr_config.grad_precision = GSR_GRAD_FP32_REFERENCE): ∇scales / ∇rotations through the reference's own fp32
+// expression trees instead of the float64 chain — reference-parity runs (ADVICE r5); a template parameter, not a branch, so
+// that the default kernels are round 5's register for register.
+template <int DEG, bool FUSED, bool F32CHAIN = false>
+__global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int channels, const float* __restrict__ means,
+                                                           const float* __restrict__ scales,
+                                                           const float4* __restrict__ rots,
+                                                           const float* __restrict__ shs, GsrCam cam, GsrGeom geom,
+                                                           GsrInst inst, float2* __restrict__ vmean2d_out,
+                                                           float* __restrict__ vmeans,
+                                                           float* __restrict__ vshs, float* __restrict__ vopac,
+                                                           float* __restrict__ vscales, float4* __restrict__ vrots,
+                                                           float* __restrict__ pose_part,
+                                                           float* __restrict__ vcolors, gsr::TailState TS) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    float poseR[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, poset[3] = {0, 0, 0};
+    // The radius, the geometry record and the Gaussian's own inputs are all requested at once (the record and the
+    // inputs of a culled Gaussian are fetched for nothing: 104 bytes x 14 %); fetched one after the other — radius ->
+    // record -> rows -> inputs -> SH — they would be five dependent round trips at 3 waves per SIMD.
+    GsrGeoRec rec;
+    rec.q0 = rec.q1 = rec.q2 = rec.q3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float p_in[3] = {0, 0, 0}, s_in[3] = {0, 0, 0};
+    float4 q_in = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+    int radius_in = 0;
+    if (i < n) {
+        radius_in = geom.radii[i];
+        rec = geom.rec[i];
+        // (FUSED: these arrays are updated in place by the epilogue — read through the same non-restrict pointers)
+        const float* mp = FUSED ? TS.points : means;
+        const float* sp = FUSED ? TS.scales_act : scales;
+        const float4* qp = FUSED ? reinterpret_cast<const float4*>(TS.rots) : rots;
+        p_in[0] = mp[3 * i]; p_in[1] = mp[3 * i + 1]; p_in[2] = mp[3 * i + 2];
+        s_in[0] = sp[3 * i]; s_in[1] = sp[3 * i + 1]; s_in[2] = sp[3 * i + 2];
+        q_in = qp[i];
+    }
+    const bool visible = radius_in > 0;
+    // 1. the summed gradient row
+    float acc[16];
+    sum_gradient_rows(i, visible, rec, geom, cam, inst, channels, acc);
+
+    // FUSED: the gradients of this Gaussian stay here (zeros for a culled one)
+    float f_vmean[3] = {0, 0, 0}, f_vs[3] = {0, 0, 0}, f_vq[4] = {0, 0, 0, 0}, f_vopac = 0.0f;
+    float f_vc[3] = {0, 0, 0}, f_b[16];
+    int f_nb = 0;  // SH bands carrying a gradient: 0 for a culled Gaussian
+#pragma unroll
+    for (int k = 0; k < 16; k++) f_b[k] = 0.0f;
+    if (i < n) {
+        if (!visible) {
+            vmean2d_out[i] = make_float2(0.0f, 0.0f);
+            if constexpr (!FUSED) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) { vmeans[3 * i + c] = 0.0f; vscales[3 * i + c] = 0.0f; }
+                vrots[i] = make_float4(0, 0, 0, 0);
+                vopac[i] = 0.0f;
+                if (vcolors) { vcolors[3 * i] = 0.0f; vcolors[3 * i + 1] = 0.0f; vcolors[3 * i + 2] = 0.0f; }
+                // (else: f_nb = 0 — the cooperative store below writes this Gaussian's zeros)
+            }
+        } else {
+            const float4 a0 = make_float4(acc[0], acc[1], acc[2], acc[3]);
+            const float4 a1 = make_float4(acc[4], acc[5], acc[6], acc[7]);
+            const float2 vm2 = make_float2(acc[8], acc[9]);
+            vmean2d_out[i] = vm2;  // gstate.∇means_2d, read by densification (strategy.jl:85-86)
+            if constexpr (FUSED) f_vopac = a0.w; else vopac[i] = a0.w;
+            M33 R; float t[3];
+            load_pose(cam, R, t);
+            const float p[3] = {p_in[0], p_in[1], p_in[2]};
+            const float4 q4 = q_in;
+            const float s[3] = {s_in[0], s_in[1], s_in[2]};
+            // 2. ∇project
+            const ProjectBwd pb = project_bwd(cam, R, t, p, q4, s, rec, a1, vm2, channels, pose_part != nullptr, poseR, poset);
+            // 3. the normal channel
+            M33 vRg;
+            normal_bwd(channels, acc, R, pb.Rg, s, pb.mc, vRg);
+            // 4. ∇scales / ∇rotations
+            // ∇quat_scale_to_cov (render.jl:302-320) + ∇unnorm_quat2rot (render.jl:335-366): in float64 from the raw inputs
+            // (scales_rots_bwd_f64 above — the fp32 chain loses a needle's thin eigen-direction).  F32CHAIN keeps the
+            // reference's fp32 expression trees (gsr_config.grad_precision = GSR_GRAD_FP32_REFERENCE).
+            float vs[3], vq[4];
+            if constexpr (!F32CHAIN) {
+                scales_rots_bwd_f64(cam, R, t, p, q4, s, a1.x, a1.y, a1.z, vRg, vs, vq);
+            } else {
+                // (inline, and pose partials below: as functions either takes instantiations of this kernel over their register
+                //  ceilings — profiles/pergauss_stages/codegen_compare.txt)
+                M33 S;
+#pragma unroll
+                for (int a = 0; a < 3; a++)
+#pragma unroll
+                    for (int b = 0; b < 3; b++) S.m[a][b] = 0.0f;
+                S.m[0][0] = s[0]; S.m[1][1] = s[1]; S.m[2][2] = s[2];
+                M33 vM = mul33(add33(pb.vSigma, tr33(pb.vSigma)), pb.M);
+                M33 vRq = add33(mul33(vM, S), vRg);
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+                    vs[c] = pb.Rg.m[0][c] * vM.m[0][c] + pb.Rg.m[1][c] * vM.m[1][c] + pb.Rg.m[2][c] * vM.m[2][c];
+                unnorm_quat2rot_bwd<float>(vRq.m, pb.qn, pb.inv_norm, vq);
+            }
+            if constexpr (FUSED) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) f_vq[k] = vq[k];
+#pragma unroll
+                for (int c = 0; c < 3; c++) f_vs[c] = vs[c];
+            } else {
+                vrots[i] = make_float4(vq[0], vq[1], vq[2], vq[3]);
+#pragma unroll
+                for (int c = 0; c < 3; c++) vscales[3 * i + c] = vs[c];
+            }
+
+            // 5. ∇SH
+            // coefficients of band k >= 1 (band 0 has no directional gradient)
+            const float* sh = FUSED ? TS.rest + (size_t)3 * (K - 1) * i : shs + (size_t)3 * K * i + 3;
+            const uint32_t clamp_bits = __float_as_uint(rec.q2.y);
+            float vc[3] = {a0.x * (1.0f - (float)(clamp_bits & 1u)), a0.y * (1.0f - (float)((clamp_bits >> 1) & 1u)),
+                           a0.z * (1.0f - (float)((clamp_bits >> 2) & 1u))};
+            float b[16], vmsh[3];
+            sh_bwd<DEG>(sh, p, cam, vc, b, vmsh);
+            constexpr int NB = (DEG + 1) * (DEG + 1);
+            if (!FUSED && vcolors) {
+                // factored form for the multi-view exchange: ∇shs of a view is the outer product
+                // basis(dir) x vc, so 3 floats per Gaussian travel instead of 3K (sh_grad_views_kernel
+                // rebuilds Σ_views on every rank)
+                vcolors[3 * i] = vc[0]; vcolors[3 * i + 1] = vc[1]; vcolors[3 * i + 2] = vc[2];
+            } else {
+                // ∇shs = basis x vc is stored (FUSED: applied) by the whole workgroup below (coalesced float4 rows instead
+                // of 48 dword stores 192 bytes apart per lane)
+                f_nb = NB;
+#pragma unroll
+                for (int c = 0; c < 3; c++) f_vc[c] = vc[c];
+#pragma unroll
+                for (int k = 0; k < NB; k++) f_b[k] = b[k];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                if constexpr (FUSED) f_vmean[c] = pb.vmean[c] + vmsh[c]; else vmeans[3 * i + c] = pb.vmean[c] + vmsh[c];
+            }
+        }
+    }
+    // 6. the epilogues: ∇shs stored (FUSED: the trainer tail applied) by the whole workgroup, then the pose partials
+    store_or_apply_sh<FUSED>(i, n, K, vshs, vcolors, TS, f_b, f_vc, f_nb, f_vmean, f_vopac, f_vs, f_vq);
     if (pose_part) {  // projection.jl:243-256: thresholded per Gaussian, then summed
         // wave sum -> workgroup sum in LDS -> the workgroup's 12 partials (∇R column-major, ∇t) to ITS slot of pose_part, zeros
         // included (the scratch needs no clearing); pose_final_kernel adds the slots in a fixed order — float atomics onto the 12
@@ -1366,9 +1511,8 @@ __global__ __launch_bounds__(256) void sh_grad_views_kernel(int n, int K, int n_
             const float* vcp = vc_all + ((size_t)v * n + i) * 3;
             const float vc[3] = {vcp[0], vcp[1], vcp[2]};
             if (vc[0] == 0.0f && vc[1] == 0.0f && vc[2] == 0.0f) continue;  // culled in this view (or zero cotangent)
-            float d0[3] = {p[0] - centers[3 * v], p[1] - centers[3 * v + 1], p[2] - centers[3 * v + 2]};
-            float inv = 1.0f / sqrtf(d0[0] * d0[0] + d0[1] * d0[1] + d0[2] * d0[2]);
-            const float dir[3] = {d0[0] * inv, d0[1] * inv, d0[2] * inv};
+            float d0[3], dir[3];
+            view_dir(p, centers + 3 * v, d0, dir);
             float b[16];
             sh_basis<DEG>(dir, b);
 #pragma unroll
@@ -1416,9 +1560,8 @@ __global__ __launch_bounds__(256) void sh_views_tail_kernel(int n, int K, int n_
             const float* vcp = vc_all + ((size_t)v * n + i) * 3;
             const float vc[3] = {vcp[0], vcp[1], vcp[2]};
             if (vc[0] == 0.0f && vc[1] == 0.0f && vc[2] == 0.0f) continue;  // culled in this view (or zero cotangent)
-            float d0[3] = {p[0] - centers[3 * v], p[1] - centers[3 * v + 1], p[2] - centers[3 * v + 2]};
-            float inv = 1.0f / sqrtf(d0[0] * d0[0] + d0[1] * d0[1] + d0[2] * d0[2]);
-            const float dir[3] = {d0[0] * inv, d0[1] * inv, d0[2] * inv};
+            float d0[3], dir[3];
+            view_dir(p, centers + 3 * v, d0, dir);
             float b[16];
             sh_basis<DEG>(dir, b);
 #pragma unroll

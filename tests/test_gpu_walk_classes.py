@@ -11,6 +11,7 @@ forced compact mode (the SCATTER pass) run two views each — the second one wit
   exact cull:      image bit-identical to the reference-list image, every list an order-preserving subsequence of the
                    reference's, gradients meet the oracle criteria;
   every cell and view of a mode is bit-identical to the others in lists, image and gradients.
+The form matrix runs at SH degree 0, 1 and 3 (the SH stage sits inside every binning form); the rects do not depend on it.
 The banded and 2 x 16-bit instantiations need 1440p / 4K grids: test_gpu_preprocess_forms.py holds them to the direct form."""
 import ctypes as C
 
@@ -24,23 +25,24 @@ from test_gpu_preprocess_forms import form
 pytestmark = pytest.mark.gpu
 
 FLAT_MAX, DENSE_RECT, EMIT_COOP = 16, 32, 48   # csrc/pergauss.hip, gsr_kernels.h
-N, DEG, SIGMA_PX, BG = 3000, 1, 9.0, (0.1, 0.3, 0.2)
+N, DEGREES, SIGMA_PX, BG = 3000, (0, 1, 3), 9.0, (0.1, 0.3, 0.2)
 SCENES = {"odd_21x13": (328, 200, 5100), "even_20x12": (320, 192, 5101)}
 CELLS = {"direct": (0, 0), "aggregating": (1, 0), "compact": (1, 1)}   # (gsr_preprocess_form, bins_budget_bytes)
 _cache = {}
 
 
-def _oracle(pkg, orc, name):
-    """Scene, camera, oracle forward state, pixel cotangent and oracle gradients: computed once per scene, never modified."""
-    if name not in _cache:
+def _oracle(pkg, orc, name, deg):
+    """Scene, camera, oracle forward state, pixel cotangent and oracle gradients: computed once per scene and degree, never
+    modified."""
+    if (name, deg) not in _cache:
         W, H, seed = SCENES[name]
-        s = pkg.synthetic.make_scene(N, W, H, DEG, seed, sigma_px=SIGMA_PX)
+        s = pkg.synthetic.make_scene(N, W, H, deg, seed, sigma_px=SIGMA_PX)
         cam = orc.Camera(W, H, s.focal)
-        st = orc.forward(s.means, s.shs, s.opacities, s.scales, s.rotations, cam, DEG, background=BG)
+        st = orc.forward(s.means, s.shs, s.opacities, s.scales, s.rotations, cam, deg, background=BG)
         vp = np.random.default_rng(seed).standard_normal((H, W, 3)).astype(np.float32)
-        g = orc.backward(st, vp, s.means, s.shs, s.opacities, s.scales, s.rotations, cam, DEG, background=BG)
-        _cache[name] = (s, cam, st, vp, g)
-    return _cache[name]
+        g = orc.backward(st, vp, s.means, s.shs, s.opacities, s.scales, s.rotations, cam, deg, background=BG)
+        _cache[name, deg] = (s, cam, st, vp, g)
+    return _cache[name, deg]
 
 
 def _rects(orc, st, grid):
@@ -66,7 +68,7 @@ def _pair_counts(x0, y0, x1, grid_x):
 
 @pytest.mark.parametrize("name", list(SCENES))
 def test_scene_holds_every_walk_class(pkg, orc, name):
-    _, cam, st, _, _ = _oracle(pkg, orc, name)
+    _, cam, st, _, _ = _oracle(pkg, orc, name, 1)   # (the geometry is drawn before the SH coefficients: the same at every degree)
     grid_x = cam.grid[0]
     classes = dict.fromkeys(["fcnt == 16", "fcnt 17..18, area <= 48", "area == 32", "area 33..36", "area == 48", "area 49..56",
                              "pa != pb, height > 1"], 0)
@@ -92,11 +94,11 @@ def test_scene_holds_every_walk_class(pkg, orc, name):
     assert min(classes.values()) >= 10, classes
 
 
-def _run_cell(pkg, cam, s, vp, exact, f, budget, check):
+def _run_cell(pkg, cam, s, deg, vp, exact, f, budget, check):
     """Two views on one handle under form f; check(run, img) is called per view while the handle lives."""
     out = []
     with form(pkg, f):
-        run = HipRun(pkg, s.means, s.shs, s.opacities, s.scales, s.rotations, cam, DEG, BG, "rgb", exact_tile_cull=exact,
+        run = HipRun(pkg, s.means, s.shs, s.opacities, s.scales, s.rotations, cam, deg, BG, "rgb", exact_tile_cull=exact,
                      bins_budget_bytes=budget)
         for _ in range(2):
             img = run.forward().clone()
@@ -118,16 +120,17 @@ def _assert_same_view(a, b):
         assert torch.equal(ga, gb)
 
 
+@pytest.mark.parametrize("deg", DEGREES)
 @pytest.mark.parametrize("name", list(SCENES))
-def test_walk_classes_match_the_oracle_in_every_form(pkg, orc, name):
-    s, cam, st, vp, g = _oracle(pkg, orc, name)
+def test_walk_classes_match_the_oracle_in_every_form(pkg, orc, name, deg):
+    s, cam, st, vp, g = _oracle(pkg, orc, name, deg)
     vis = st.radii > 0
     views = {}
     for exact in (False, True):
         for cell, (f, budget) in CELLS.items():
             # reference lists: n_rendered, ranges, sorted ids, per-Gaussian tile counts exactly the oracle's; image within parity
             check = (lambda run, img: None) if exact else (lambda run, img: compare_forward(st, run, img, s.opacities))
-            views[exact, cell] = _run_cell(pkg, cam, s, vp, exact, f, budget, check)
+            views[exact, cell] = _run_cell(pkg, cam, s, deg, vp, exact, f, budget, check)
             assert views[exact, cell][-1]["compact"] == budget, cell   # fitted bins, or the count -> scan -> SCATTER passes
         first = views[exact, "direct"][0]
         for cell in CELLS:
