@@ -135,11 +135,15 @@ struct RowColConsts {  // loop-invariant per lane
     }
 };
 
-__device__ __forceinline__ float wave_reduce_rowcol_rgb(float P, float U1, float U2, float c0, float c1, float c2,
-                                                        float dx, const LaneBits& L, const RowColConsts& K) {
-    // rows: pairs (P,U1), (c0,c1), (U2,c2) over lane^32, then pair + single over lane^16
-    const float a0 = pair_swap32(P, U1), a1 = pair_swap32(c0, c1), a2 = pair_swap32(U2, c2);
-    const float b0 = pair_swap16(a0, a1), b1 = pair_swap16(a2, a2);
+// The first level alone: pairs (P,U1), (c0,c1), (U2,c2) over lane^32.
+struct RowColHalf { float a0, a1, a2; };
+__device__ __forceinline__ RowColHalf wave_reduce_rowcol_rgb_half(float P, float U1, float U2, float c0, float c1, float c2) {
+    return {pair_swap32(P, U1), pair_swap32(c0, c1), pair_swap32(U2, c2)};
+}
+// ... and the levels behind it.
+__device__ __forceinline__ float wave_reduce_rowcol_rgb_rest(const RowColHalf& h, float dx, const LaneBits& L, const RowColConsts& K) {
+    // pair + single over lane^16
+    const float b0 = pair_swap16(h.a0, h.a1), b1 = pair_swap16(h.a2, h.a2);
     // column weights
     const float o0 = b0;
     const float o1 = b0 * (dx * K.e1) + b1 * K.k2;
@@ -148,6 +152,68 @@ __device__ __forceinline__ float wave_reduce_rowcol_rgb(float P, float U1, float
     const float x0 = pair_level<2>(o0, o1, L), x1 = single_level<2>(o2, L);
     float r = pair_level<3>(x0, x1, L);
     r = r + dpp_xor2(r);
+    r = r + dpp_shr4(r);
+    return r;
+}
+__device__ __forceinline__ float wave_reduce_rowcol_rgb(float P, float U1, float U2, float c0, float c1, float c2,
+                                                        float dx, const LaneBits& L, const RowColConsts& K) {
+    return wave_reduce_rowcol_rgb_rest(wave_reduce_rowcol_rgb_half(P, U1, U2, c0, c1, c2), dx, L, K);
+}
+
+// a * b rounded to fp32 whatever consumes it: the product carries no `contract` flag, so it cannot fuse into a following add
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+// ---- two consecutive :rgb instances, A and B, in ONE network ----
+// The unpaired network above carries one value where two fit (pair_swap16(a2, a2), single_level<2>(o2)) and runs its last two
+// levels on one value.  Two instances fill those places.  Each does its first level by itself, when its sums are complete
+// (wave_reduce_rowcol_rgb_half: A then waits for B in three registers, not six); behind it three swap16 (nine swaps for the
+// pair, not ten), one set of dx weights, and a 16-lane tail over 5 -> 3 -> 2 -> 1 values.  Row r (= lane >> 4) ends up with
+// (b0, b1, b2) and the outputs
+//   r = 0: (P, c0, U2) of A -> {P, dx*P, dx^2*P, c0, U2}      r = 2: (U1, c1, c2) of A -> {U1, dx*U1, -, c1, c2}
+//   r = 1: the same of B                                       r = 3: the same of B
+// EVERY value passes the levels in the order it does above — swap32, swap16, weight, ror8, xor1, xor2, shr4 — and every level adds
+// the same two operands; only which lanes carry which value differs.  The 18 sums are therefore the unpaired network's bit for
+// bit (up to the sign of an exact zero: above, o1 and o2 also add the other value times a zero weight).
+// A lane with bit 2 set holds, by (b1, b3, b0): (0,0,0) o0 = b0, (0,1,0) o1 = dx*b0, (0,0,1) o3 = b1, (0,1,1) o4 = b2, and
+// (1,-,-) o2 = dx^2*b0, which rows 0 and 1 write from their lane (1,0,0).
+struct RowColConstsPair {  // loop-invariant per lane
+    bool b1;   // lane & 2: the xor2 level is a pair level here
+    int slot;  // index into the 9-float accumulator row of instance (odd row ? B : A) this lane's total goes to, or -1
+    __device__ __forceinline__ explicit RowColConstsPair(int lane) : b1(lane & 2) {
+        const int r = lane >> 4;
+        // accumulator row layout (composite.hip): [0..2] rgb, [3] P, [4] dx^2*P, [5] dx*U1, [6] U2, [7] dx*P, [8] U1
+        const int j = (lane & 2) ? 2 : ((lane & 1) ? 3 : 0) + ((lane & 8) ? 1 : 0);  // which of o0..o4
+        const int table[2][5] = {{3, 7, 4, 0, 6}, {8, 5, -1, 1, 2}};
+        int t = -1;
+#pragma unroll
+        for (int hh = 0; hh < 2; hh++)
+#pragma unroll
+            for (int jj = 0; jj < 5; jj++)
+                if (hh == (r >> 1) && jj == j) t = table[hh][jj];
+        const bool writer = (lane & 4) && (!(lane & 2) || !(lane & 9));  // o2 sits on four lanes of a row: (b3, b0) = (0, 0) writes
+        slot = writer ? t : -1;
+    }
+};
+
+// In: the first level and dx of instance A and of instance B.  Out: the wave total that K.slot names, of A on the even lane
+// rows and of B on the odd ones.
+__device__ __forceinline__ float wave_reduce_rowcol_rgb_pair(const RowColHalf& A, float dxA, const RowColHalf& B, float dxB,
+                                                             const LaneBits& L, const RowColConstsPair& K) {
+    // even rows get A's, odd rows B's
+    const float b0 = pair_swap16(A.a0, B.a0), b1 = pair_swap16(A.a1, B.a1), b2 = pair_swap16(A.a2, B.a2);
+    // column weights, of the instance this row holds
+    // (rounded products: left contractable, o2 fuses into the add of its ror8 level — above it is the result of an FMA with a
+    //  zero addend, which cannot fuse again — and the moments differ from the unpaired network's in the last bit)
+    const float dx = L.odd_row ? dxB : dxA;
+    const float o1 = mul_rounded(b0, dx), o2 = mul_rounded(b0, mul_rounded(dx, dx));
+    // 16 lanes of the row: 5 -> 3 by b3, 3 -> 2 by b0, 2 -> 1 by b1, then the plain level
+    const float x0 = pair_level<2>(b0, o1, L), x1 = pair_level<2>(b1, b2, L), x2 = single_level<2>(o2, L);
+    const float y0 = pair_level<3>(x0, x1, L), y1 = single_level<3>(x2, L);
+    const float send = K.b1 ? y0 : y1, keep = K.b1 ? y1 : y0;
+    float r = keep + dpp_xor2(send);
     r = r + dpp_shr4(r);
     return r;
 }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Instruction budget of composite_bwd_kernel<3, false> from its ISA (round-2 verdict item 4-i).
+"""Instruction budget of composite_bwd_kernel<3, BG0> from its ISA (round-2 verdict item 4-i).
 
 Compiles composite.hip to an ISA listing exactly as the Makefile does (hipcc -S --cuda-device-only, same flags), splits the
 kernel into basic blocks (tools/isa_loop.py), assigns every block a ROLE from its content and position, multiplies its VALU
@@ -20,6 +20,10 @@ Roles (execution count on one view):
   active[q]       per visited group with >= 1 active lane      exp, alpha, rcp, T, A, P/U1/U2, colour sums
   skip[q]         per candidate whose mask misses group q      (scalar branch; the q = 0 path zero-fills 7 accumulators)
   reduce          per instance with >= 1 active lane           row-then-column wave64 reduction + LDS row store
+                  (--kernel bg0: the first level only; the rest is done for two instances at a time:)
+  pair            per two reduced instances of a ballot        the levels behind the first, both rows' LDS stores
+  park            per pair                                     the first instance's level-one sums moved to where they wait
+  alone           per ballot with an odd count (taken: 1 in 2) the instance left without a partner: the unpaired levels
   glue            per candidate                                loop control, ballot accumulation
   flush           per batch                                    sum slabs, apply -o/2 and conic factors, 48-byte row store
   tail            per tile                                     zero rows behind tile_last
@@ -36,7 +40,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from isa_loop import blocks, cost  # noqa: E402
 
-KERNEL = "composite_bwd_kernelILi3ELb0ELi3ELb0E"  # <C = 3, BG0 = false, VC = 3, ACC = false>: the kernel the :rgb launch takes
+# <C = 3, BG0, VC = 3, ACC = false>: the kernels of the :rgb launch, by background (--kernel general for a non-zero one)
+KERNELS = {"bg0": "composite_bwd_kernel_rgb_bg0", "general": "composite_bwd_kernelILi3ELb0ELi3ELb0E"}
 N_SIMD = 1024
 
 
@@ -44,7 +49,7 @@ def compile_asm():
     out = os.path.join(tempfile.mkdtemp(), "composite.s")
     src = os.path.join(ROOT, "gaussiansplatting.jl_amd", "csrc", "composite.hip")
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics",
-                    "-fno-slp-vectorize", "-S", "--cuda-device-only", "-o", out, src], check=True, stderr=subprocess.DEVNULL)
+                    "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-S", "--cuda-device-only", "-o", out, src], check=True, stderr=subprocess.DEVNULL)
     return out
 
 
@@ -92,10 +97,16 @@ def classify(blist):
                 role = f"test{q}"
             elif has(i, r"v_permlane32_swap") or (roles and roles[-1][2] == "reduce" and has(i, r"ds_write")):
                 role = "reduce"
+            elif has(i, r"v_permlane16_swap") or (roles and roles[-1][2] == "pair" and has(i, r"ds_write")):
+                role = "pair"    # the zero-background kernel: the levels behind the first, two instances at a time
+            elif roles and roles[-1][2] in ("pair", "reduce") and b and all(l.startswith(("v_mov_b32", "s_")) for l in b):
+                role = "park"    # ... and the first instance of a pair moved to the registers it waits in
             elif sum(l.startswith("v_mov_b32") for l in b) >= 5:
                 role = f"skip{q + 1}"
             else:
                 role = "glue"
+        elif has(i, r"v_permlane16_swap") or (roles and roles[-1][2] == "alone" and has(i, r"ds_write") and not has(i, r"global_load")):
+            role = "alone"       # the zero-background kernel: the instance a ballot leaves without a partner
         elif has(i, r"global_store_dwordx4") or (has(i, r"ds_read") and has(i, r"v_add_f32") and not has(i, r"global_load")):
             role = "flush"
         elif has(i, r"global_load_dwordx4") and has(i, r"ds_write_b128"):
@@ -114,15 +125,20 @@ def main():
     ap.add_argument("--pmc-key", default="N1000000_1920x1080_SH3_rgb_cull_loss")
     ap.add_argument("--json", default=None)
     ap.add_argument("--list", action="store_true", help="print every block with its role")
+    ap.add_argument("--kernel", default="bg0", choices=sorted(KERNELS), help="bg0: the zero-background kernel (the default); general: any background")
     a = ap.parse_args()
     asm = a.asm or compile_asm()
     c = json.load(open(a.counts))
-    blist = [(n, b) for n, b in blocks(asm, KERNEL) if b]
+    blist = [(n, b) for n, b in blocks(asm, KERNELS[a.kernel]) if b]
     roles = classify(blist)
     T, batches, cand = c["tiles_nonempty"], c["batches_of_64"], c["candidates_after_row_mask_ballot"]
     vq, aq = c["group_visits_by_q"], c["active_group_visits_by_q"]
     execs = {"prologue": T, "tail": T, "stage": batches, "ballot": batches, "flush": batches, "head": cand, "glue": cand,
              "reduce": c["instances_reduced"]}
+    # the zero-background kernel reduces in pairs per (wave, batch) ballot; the counts file has no pair census, so: every
+    # ballot with an odd number of reduced instances leaves one alone, taken as half of the batches
+    alone = c.get("instances_reduced_alone", batches // 2)
+    execs.update({"alone": alone, "pair": (c["instances_reduced"] - alone) // 2, "park": (c["instances_reduced"] - alone) // 2})
     for q in range(4):
         execs[f"test{q}"] = vq[q]
         execs[f"active{q}"] = aq[q]
@@ -136,7 +152,7 @@ def main():
         if a.list:
             print(f"{name:16s} {role:10s} {len(b):3d} instr {len(valu):3d} VALU")
     order = ["prologue", "stage", "ballot", "head", "test0", "active0", "skip0", "test1", "active1", "skip1", "test2", "active2",
-             "skip2", "test3", "active3", "skip3", "reduce", "glue", "flush", "tail"]
+             "skip2", "test3", "active3", "skip3", "reduce", "pair", "park", "alone", "glue", "flush", "tail"]
     print(f"{'role':10s} {'blocks':>6s} {'VALU':>5s} {'cycles':>7s} {'LDS':>4s} {'SALU':>5s} {'executions':>11s} {'VALU x exec (M)':>16s} {'cycles x exec (G)':>18s}")
     tot_v = tot_c = 0.0
     rows = []
@@ -160,7 +176,7 @@ def main():
     if measured:
         print(f"PMC:   {measured / 1e6:.1f} M SQ_INSTS_VALU per launch  ->  model / measured = {tot_v * 1e6 / measured:.3f}")
     if a.json:
-        json.dump({"kernel": KERNEL, "counts": a.counts, "rows": rows, "model_valu_M": round(tot_v, 2),
+        json.dump({"kernel": KERNELS[a.kernel], "counts": a.counts, "rows": rows, "model_valu_M": round(tot_v, 2),
                    "model_cycles_G": round(tot_c, 3), "measured_SQ_INSTS_VALU": measured,
                    "model_over_measured": round(tot_v * 1e6 / measured, 4) if measured else None}, open(a.json, "w"), indent=1)
 
