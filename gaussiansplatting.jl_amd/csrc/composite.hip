@@ -207,12 +207,8 @@ __global__ __launch_bounds__(64) void composite_fwd_strip_kernel(int W, int H, i
         if (slot >= grid_x * ((H + GSR_TILE - 1) / GSR_TILE)) return;
         tile = (int)tile_order[slot];
     } else {           // only the tiles of the scan's tier lists (the fused kernel did the others), longest tier first
-        uint32_t b = (uint32_t)slot;
-        if (b >= tiers.n_big + tiers.n_mid8 + tiers.n_mid4) return;
-        const uint32_t* list = tiers.lists;
-        if (b >= tiers.n_big) { b -= tiers.n_big; list = tiers.lists + tiers.n_tiles;
-            if (b >= tiers.n_mid8) { b -= tiers.n_mid8; list = tiers.lists + 2 * (size_t)tiers.n_tiles; } }
-        tile = (int)list[b];
+        if ((uint32_t)slot >= tiers.n_big + tiers.n_mid8 + tiers.n_mid4) return;
+        GSR_TIER_TILE(tile, tiers, (uint32_t)slot);
         // beside the fused launch (gsr_forward): these few waves are the forward's critical path and share their SIMDs with it
         if (tiers.split_len) __builtin_amdgcn_s_setprio(3);
     }
@@ -373,6 +369,20 @@ __device__ __forceinline__ void bwd_zero_rows(float4* rows, const GsrStream stre
     }
 }
 
+// Stream entry p into slot k of a batch's LDS planes.  Plane 2 is staged as (third colour, footprint mask, depth | :rgb blend
+// threshold, gradient-row slot): what a walk reads per splat is then one aligned 64-bit LDS read in :rgb mode.  Returns the
+// footprint mask's bits.
+template <int C>
+__device__ __forceinline__ uint32_t bwd_stage_entry(const GsrStream& stream, uint32_t p, int k, float4* l0, float4* l1,
+                                                    float4* l2, float4* l3) {
+    l0[k] = stream.s0[p];
+    l1[k] = stream.s1[p];
+    const float4 t2 = stream.s2[p];
+    l2[k] = make_float4(t2.x, t2.w, t2.z, t2.y);
+    if (C > 3) l3[k] = stream.s3[p];
+    return __float_as_uint(t2.w);
+}
+
 // The backward of a tile whose list is at most tiers.split_len long (the longer ones are composite_bwd_long_kernel's).
 // BG0: the background is exactly (0, 0, 0) — the reference's default (rasterizer.jl:209) and what a trainer without a sky
 // colour passes: the term -T_final/(1-α)·(bg·v) (render.jl:259) vanishes identically, and with it the per-pixel bgT state and
@@ -399,6 +409,9 @@ __device__ __forceinline__ void bwd_zero_rows(float4* rows, const GsrStream stre
 
 // The walk itself is composite_bwd_body.inc, the text of both kernels below: as a function it is inlined with one VGPR more
 // in six of the template's instantiations (profiles/bwd_zero_background/resource_usage.txt is taken with the text included).
+// What it shares with composite_bwd_long_kernel — the per-pixel state, the decode and the visit of an instance, the one-at-a-time
+// reduction — is text of its own (composite_bwd_state / _decode / _visit / _reduce.inc), included by both, for the same reason: each
+// was tried as a function and changed the code of kernels it must not change (profiles/bwd_shared_visit/codegen_compare.txt).
 template <int C, bool BG0, int VC = C, bool ACC = false>
 __global__ __launch_bounds__(64, 1) void composite_bwd_kernel(int W, int H, int grid_x,
                                                  const uint32_t* __restrict__ tile_start,
@@ -460,10 +473,14 @@ __global__ __launch_bounds__(64) void composite_bwd_long_kernel(int W, int H, in
                                                                 const uint32_t* __restrict__ n_contrib,
                                                                 const float* __restrict__ final_T, GsrInst inst,
                                                                 GsrTierLists tiers, float2* __restrict__ state) {
+    // the names composite_bwd_visit.inc / composite_bwd_reduce.inc read: every channel, the fast exp and reciprocal, y per row,
+    // one wave for all 16 rows of the tile
+    constexpr int VC = C, BB = 64, ROWS = 16, wave = 0;
+    constexpr bool ACC = false, FY_REBUILD = false;
     constexpr int NA = AccRow<C>::N, ST = AccRow<C>::STRIDE, PPL = 4;
-    __shared__ float4 l0[64], l1[64], l2[64];
-    __shared__ float4 l3[C > 3 ? 64 : 1];
-    __shared__ float my[64 * ST];
+    __shared__ float4 l0[BB], l1[BB], l2[BB];
+    __shared__ float4 l3[C > 3 ? BB : 1];
+    __shared__ float my[BB * ST];  // the wave's accumulator slab
     __builtin_amdgcn_s_setprio(3);  // these few waves are the critical path of the step; they share SIMDs with the main launch
     const int lane = threadIdx.x;
     const uint32_t listed = blockIdx.x / LONG_SEGS;
@@ -474,13 +491,7 @@ __global__ __launch_bounds__(64) void composite_bwd_long_kernel(int W, int H, in
     const gsr::RowColConsts rowcol(lane);
     const gsr::RowColConstsD rowcol_d(lane);
     int tile;
-    {
-        uint32_t b = listed;
-        const uint32_t* list = tiers.lists;                                              // lists > 8192
-        if (b >= tiers.n_big) { b -= tiers.n_big; list = tiers.lists + tiers.n_tiles;    // (4096, 8192]
-            if (b >= tiers.n_mid8) { b -= tiers.n_mid8; list = tiers.lists + 2 * (size_t)tiers.n_tiles; } }  // (1024, 4096]
-        tile = (int)list[b];
-    }
+    GSR_TIER_TILE(tile, tiers, listed);
     const int tile_x = tile % grid_x, tile_y = tile / grid_x;
     const int px = tile_x * GSR_TILE + (lane & 15);
     const int py0 = tile_y * GSR_TILE + (lane >> 4);
@@ -489,26 +500,8 @@ __global__ __launch_bounds__(64) void composite_bwd_long_kernel(int W, int H, in
     if (end == start) return;
     float fy[PPL], T[PPL], A[PPL], bgT[BG0 ? 1 : PPL], vp[PPL][C];
     int last_contributor[PPL];
-    int tile_last = 0;
-#pragma unroll
-    for (int q = 0; q < PPL; q++) {
-        const int py = py0 + 4 * q;
-        const bool inside = px < W && py < H;
-        const size_t pi = (size_t)px + (size_t)W * py;
-        fy[q] = (float)py;
-        const float T_final = inside ? final_T[pi] : 0.0f;
-        T[q] = T_final;
-        last_contributor[q] = inside ? (int)n_contrib[pi] : 0;
-        float bg_dot = 0.0f;
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            vp[q][c] = inside ? vpixels[(size_t)C * pi + c] : 0.0f;
-            bg_dot += bg.v[c] * vp[q][c];
-        }
-        if (!BG0) bgT[BG0 ? 0 : q] = -T_final * bg_dot;
-        A[q] = 0.0f;
-        tile_last = max(tile_last, last_contributor[q]);
-    }
+#include "composite_bwd_state.inc"
+    int tile_last = deepest;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) tile_last = max(tile_last, __shfl_xor(tile_last, off));
     tile_last = __builtin_amdgcn_readfirstlane(tile_last);  // list positions tile_last-1 ... 0 are walked (the wave holds all 256 pixels)
@@ -529,15 +522,7 @@ __global__ __launch_bounds__(64) void composite_bwd_long_kernel(int W, int H, in
     auto stage = [&](int top /* first (highest) position of the batch + 1 */, int cnt) -> unsigned long long {
         __builtin_amdgcn_wave_barrier();  // the previous batch's LDS reads are done (single wave, in order)
         uint32_t mask = 0u;
-        if (lane < cnt) {
-            const uint32_t idx = start + (uint32_t)(top - 1 - lane);
-            l0[lane] = stream.s0[idx];
-            l1[lane] = stream.s1[idx];
-            const float4 t2 = stream.s2[idx];
-            l2[lane] = make_float4(t2.x, t2.w, t2.z, t2.y);  // (third colour, footprint mask, depth | threshold, slot)
-            if (C > 3) l3[C > 3 ? lane : 0] = stream.s3[idx];
-            mask = __float_as_uint(t2.w);
-        }
+        if (lane < cnt) mask = bwd_stage_entry<C>(stream, start + (uint32_t)(top - 1 - lane), lane, l0, l1, l2, l3);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         return wave_ballot(lane < cnt && (mask & 0xFFFFu) != 0u);
@@ -555,20 +540,10 @@ __global__ __launch_bounds__(64) void composite_bwd_long_kernel(int W, int H, in
                 const int j = __builtin_ctzll(wl);
                 wl &= wl - 1;
                 const int contributor = top - 1 - j;
-                const float4 a = l0[j], b = l1[j];
-                const float4 t2 = l2[j];
-                const float4 c2 = make_float4(t2.x, 0.0f, t2.z, t2.y);
-                float4 t3 = t2;
-                if (C > 3) t3 = l3[C > 3 ? j : 0];
-                const uint32_t thr_bits = __float_as_uint(C == 3 ? t2.z : t3.w);
-                const float o = b.y, dx = a.x - fx;
-                const SigmaX sx = sigma_x(a.z, a.w, dx);
-                float f[C];
-                unpack_features<C>(b, c2, t3, f);
-                const uint32_t rowbits = __builtin_amdgcn_readfirstlane(__float_as_uint(t2.y));
+#include "composite_bwd_decode.inc"
 #pragma unroll
                 for (int q = 0; q < PPL; q++) {
-                    if (__builtin_amdgcn_readfirstlane((int)((rowbits >> (4 * q)) & 0xFu)) == 0) continue;
+                    if (__builtin_amdgcn_readfirstlane((int)((entry_rowbits >> (4 * q)) & 0xFu)) == 0) continue;
                     const float dy = a.y - fy[q], dy2 = __fmul_rn(dy, dy);
                     const float sigma = sigma_of(sx, b.x, dy, dy2);
                     if (contributor < last_contributor[q] && __float_as_uint(sigma) < thr_bits) {
@@ -596,89 +571,24 @@ __global__ __launch_bounds__(64) void composite_bwd_long_kernel(int W, int H, in
             A[q] = mc.x * A[q] + mc.y;
         }
     }
-    // ---- the gradient walk of the segment (the main kernel's arithmetic, ACC = false: one wave = the whole tile) ----
+    // ---- the gradient walk of the segment: the main kernel's visit and reduction, text for text (ACC = false: one wave = the whole tile) ----
     for (int top = hi; top > lo; top -= 64) {
         const int cnt = min(64, top - lo);
         unsigned long long wl = stage(top, cnt);
-        unsigned long long touched = 0ull;
+        unsigned long long touched[1] = {0ull};
         while (wl) {
             const int j = __builtin_ctzll(wl);
             wl &= wl - 1;
             const int contributor = top - 1 - j;
-            const float4 a = l0[j], b = l1[j];
-            const float4 t2 = l2[j];
-            const float4 c2 = make_float4(t2.x, 0.0f, t2.z, t2.y);
-            float4 t3 = t2;
-            if (C > 3) t3 = l3[C > 3 ? j : 0];
-            const uint32_t thr_bits = __float_as_uint(C == 3 ? t2.z : t3.w);
-            const float o = b.y, dx = a.x - fx;
-            const SigmaX sx = sigma_x(a.z, a.w, dx);
-            float f[C];
-            unpack_features<C>(b, c2, t3, f);
-            float P = 0.0f, U1 = 0.0f, U2 = 0.0f, col[C];
-#pragma unroll
-            for (int c = 0; c < C; c++) col[c] = 0.0f;
-            unsigned long long any_active = 0ull;
-            const uint32_t rowbits = __builtin_amdgcn_readfirstlane(__float_as_uint(t2.y));
-#pragma unroll
-            for (int q = 0; q < PPL; q++) {
-                if (__builtin_amdgcn_readfirstlane((int)((rowbits >> (4 * q)) & 0xFu)) == 0) continue;
-                const float dy = a.y - fy[q], dy2 = __fmul_rn(dy, dy);
-                const float sigma = sigma_of(sx, b.x, dy, dy2);
-                const bool c_live = contributor < last_contributor[q];
-                const bool c_touch = __float_as_uint(sigma) < thr_bits;
-                const bool active = c_live && c_touch;
-                any_active |= wave_ballot(c_live) & wave_ballot(c_touch);
-                if (active) {
-                    const float G = __expf(-sigma);
-                    const float alpha = alpha_of(o, G);
-                    const float rinv = __builtin_amdgcn_rcpf(1.0f - alpha);
-                    T[q] = T[q] * rinv;
-                    const float fac = alpha * T[q];
-                    float cv = f[0] * vp[q][0];
-#pragma unroll
-                    for (int c = 1; c < C; c++) cv += f[c] * vp[q][c];
-                    const float d = cv - A[q];
-                    const float valpha = BG0 ? d * T[q] : d * T[q] + bgT[BG0 ? 0 : q] * rinv;
-                    A[q] = A[q] + alpha * d;
-                    const float t = G * valpha;
-                    P += t;
-                    U1 += t * dy;
-                    U2 += t * dy2;
-#pragma unroll
-                    for (int c = 0; c < C; c++) col[c] += fac * vp[q][c];
-                }
-            }
-            if (any_active == 0ull) continue;
-            int jrow;
-            asm("s_mul_i32 %0, %1, %2" : "=s"(jrow) : "s"(j), "n"(ST));
-            float* const my_row = my + jrow;
-            touched |= 1ull << j;
-            if (C == 3) {
-                const float total = gsr::wave_reduce_rowcol_rgb(P, U1, U2, col[0], col[1], col[2], dx, lane_bits, rowcol);
-                if (rowcol.slot >= 0) my_row[rowcol.slot] = total;
-            } else if (C == 5) {
-                const float total = gsr::wave_reduce_rowcol_rgbd(P, U1, U2, col[0], col[1], col[2], col[C > 3 ? 3 : 0], dx, lane_bits, rowcol_d);
-                if (rowcol_d.slot >= 0) my_row[rowcol_d.slot] = total;
-            } else {
-                float part[16];
-#pragma unroll
-                for (int k = 0; k < 16; k++) part[k] = 0.0f;
-                const float dxp = dx * P;
-                part[0] = col[0]; part[1] = col[1]; part[2] = col[2];
-                part[3] = P; part[4] = dx * dxp; part[5] = dx * U1; part[6] = U2; part[7] = dxp; part[8] = U1;
-                if (C > 3) part[9] = col[3];
-                if (C > 5) { part[10] = col[5]; part[11] = col[6]; part[12] = col[7]; }
-                const float total = gsr::wave_reduce_transposed<NA>(part, lane_bits);
-                if (red_writer) my_row[red_slot] = total;
-            }
+#include "composite_bwd_visit.inc"
+#include "composite_bwd_reduce.inc"
         }
         // flush: one gradient row per staged instance (zeros when nothing touched it), the main kernel's row format
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
         if (lane < cnt) {
             float r[NA];
-            const bool hit = (touched >> lane) & 1ull;
+            const bool hit = (touched[0] >> lane) & 1ull;
 #pragma unroll
             for (int k = 0; k < NA; k++) r[k] = hit ? my[lane * ST + k] : 0.0f;
             bwd_store_row<C, C>(inst.rows, l0[lane], l1[lane], l2[lane].w, r);

@@ -164,6 +164,17 @@ struct GsrTierLists {  // the scan's tier lists: [0, T) lists > 8192, [T, 2T) (4
     uint32_t n_tiles, n_big, n_mid8, n_mid4;  // a tier that is not split has count 0 here
     uint32_t split_len;  // (forward launch over the lists: non-zero = its waves run at raised issue priority, beside another launch)
 };
+// tile = the tile of listed slot `slot` < n_big + n_mid8 + n_mid4 (the three lists back to back, longest tier first).  A statement,
+// not a function: composite.hip's forward kernel schedules its prologue differently around an inlined call, in every form tried
+// (profiles/bwd_shared_visit/codegen_compare.txt).
+#define GSR_TIER_TILE(tile, tiers, slot)                                                                                       \
+    do {                                                                                                                       \
+        uint32_t b_ = (slot);                                                                                                  \
+        const uint32_t* list_ = (tiers).lists;                                                            /* lists > 8192 */   \
+        if (b_ >= (tiers).n_big) { b_ -= (tiers).n_big; list_ = (tiers).lists + (tiers).n_tiles;          /* (4096, 8192] */   \
+            if (b_ >= (tiers).n_mid8) { b_ -= (tiers).n_mid8; list_ = (tiers).lists + 2 * (size_t)(tiers).n_tiles; } }  /* (1024, 4096] */ \
+        (tile) = (int)list_[b_];                                                                                               \
+    } while (0)
 void gsr_launch_composite_fwd(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrStream stream, GsrFrame frame,
                               const GsrTierLists* only_listed /* NULL: every tile, in tiles.order */);
 // sort + forward of every tile in one launch (fixed-capacity bins, no list beyond 1024 instances; checked on the
