@@ -9,6 +9,7 @@ from . import ply  # noqa: F401
 from . import checkpoint  # noqa: F401
 from . import _lib  # noqa: F401
 from . import evaluation  # noqa: F401
+from . import geometry_frames  # noqa: F401
 from .camera import Camera  # noqa: F401
 
 

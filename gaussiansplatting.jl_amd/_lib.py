@@ -198,6 +198,7 @@ EXPORTS = ["gsr_create", "gsr_destroy", "gsr_release_scene_buffers", "gsr_memory
            "gsr_depth_loss_scratch_bytes", "gsr_depth_target", "gsr_depth_loss_forward", "gsr_depth_loss_backward",
            "gsr_sky_scratch_bytes", "gsr_sky_composite_forward", "gsr_sky_composite_backward",
            "gsr_eval_scratch_bytes", "gsr_eval_metrics", "gsr_frame_rgb8",
+           "gsr_frames_scratch_bytes", "gsr_depth_scale", "gsr_frame_depth16", "gsr_frame_normal8", "gsr_pick_point",
            "gsr_mcmc_weights", "gsr_mcmc_sample_scratch_bytes", "gsr_mcmc_sample", "gsr_mcmc_split_sampled",
            "gsr_mcmc_relocation_params", "gsr_mcmc_relocate_rows", "gsr_mcmc_inject_noise",
            "gsr_mcmc_regularization_scratch_bytes", "gsr_mcmc_regularization"] + POLICY_EXPORTS
@@ -313,6 +314,12 @@ def load():
     lib.gsr_eval_scratch_bytes.restype = sz
     lib.gsr_eval_metrics.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.gsr_frame_rgb8.argtypes = [i32, i32, i32, vp, vp, i32, vp, vp]
+    lib.gsr_frames_scratch_bytes.argtypes = [i32, i32]
+    lib.gsr_frames_scratch_bytes.restype = sz
+    lib.gsr_depth_scale.argtypes = [i32, i32, i32, vp, f32, C.c_double, vp, vp, vp]
+    lib.gsr_frame_depth16.argtypes = [i32, i32, i32, vp, i32, f32, f32, vp, i32, vp, vp]
+    lib.gsr_frame_normal8.argtypes = [i32, i32, i32, vp, f32, C.POINTER(C.c_float * 9), vp, vp]
+    lib.gsr_pick_point.argtypes = [i32, i32, i32, vp, C.POINTER(CameraS), i32, i32, i32, vp, vp]
     u32 = C.c_uint32
     lib.gsr_mcmc_weights.argtypes = [i64, i32, vp, vp, f32, f32, vp, vp, vp]
     lib.gsr_mcmc_sample_scratch_bytes.argtypes = [i64]

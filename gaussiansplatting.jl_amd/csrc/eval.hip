@@ -28,6 +28,7 @@
 // reads was written by the scoring launch.
 #include "gsr_kernels.h"
 #include "block_reduce.h"
+#include "quant_level.h"
 #include "ssim_strip.h"
 
 namespace {
@@ -35,9 +36,7 @@ namespace {
 constexpr int STRIP_H = 32;  // output rows per wave: fixed, so that the scratch size depends on W and H alone
 constexpr int NSUM = 3;      // Σssim, Σd², Σ|d|
 
-// The integer level of `quantize8` (utils.jl:118) as a float: THE quantiser of both entry points.  Each operation is its own
-// fp32 operation (the product is rounded before the sum: not rintf, not a float -> integer conversion of x · 255).
-__device__ __forceinline__ float quant_level(float x) { return floorf(fminf(fmaxf(x, 0.0f), 1.0f) * 255.0f + 0.5f); }
+// quant_level (quant_level.h): the integer level of `quantize8` (utils.jl:118) as a float, THE quantiser of both entry points
 
 // what one lane loads of one row: untouched until the row is filtered
 template <bool SKY, bool U8>

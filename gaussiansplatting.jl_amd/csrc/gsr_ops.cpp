@@ -1,13 +1,14 @@
 // C ABI of libgsr_hip.so (include/gsr.h), the part without a handle: every entry point that checks its arguments, launches
 // its kernels on the caller's stream and keeps nothing — planar SSIM, the trainer's prologue / Adam / tail, row gathers, the
-// bilateral grid, the geometry, depth and sky losses, the evaluation head, densification, MCMC, Morton codes, k-NN, PLY rows,
-// the multi-view SH gradient, the all-reduce.  (The handle and its launch choreography are gsr_api.cpp's.)
+// bilateral grid, the geometry, depth and sky losses, the evaluation head, the geometry frames, densification, MCMC, Morton
+// codes, k-NN, PLY rows, the multi-view SH gradient, the all-reduce.  (The handle and its launch choreography are gsr_api.cpp's.)
 #include <dlfcn.h>
 
 #include <algorithm>
 #include <cmath>
 
 #include "gsr_kernels.h"
+#include "frames.h"
 #include "adam_math.h"
 #include "gsr_host.h"
 
@@ -435,6 +436,85 @@ int gsr_frame_rgb8(int32_t W, int32_t H, int32_t C, const float* image, const fl
     if ((rc = check_eval_frame(W, H, C, image, sky_rgb))) return rc;
     if (!rgb8_out) return fail(GSR_E_INVALID_ARG, "null rgb8_out");
     gsr_launch_frame_rgb8((hipStream_t)stream, W, H, C, image, sky_rgb, flip_rows != 0, rgb8_out);
+    return launched();
+}
+
+// ---- geometry frames: exact depth percentile, 16-bit depth, 8-bit normals, the pick (frames.hip; render-views.jl:264-308) ----
+namespace {
+int check_geometry_frame(int32_t W, int32_t H, int32_t C, int32_t c_min, const void* image) {
+    if (W < 1 || H < 1) return fail(GSR_E_INVALID_ARG, "image size %d x %d", W, H);
+    if (C < c_min) return fail(GSR_E_INVALID_ARG, "C = %d: this call reads channel %d of the frame (C >= %d)", C, c_min - 1, c_min);
+    if ((uint64_t)W * (uint64_t)H * (uint64_t)C > 0xFFFFFFFFull)
+        return fail(GSR_E_INVALID_ARG, "frame too large: %d x %d x %d is 2^32 elements or more", C, W, H);
+    if (!image) return fail(GSR_E_INVALID_ARG, "null image");
+    return GSR_OK;
+}
+int check_min_alpha(float min_alpha) {
+    if (!(min_alpha > 0.0f)) return fail(GSR_E_INVALID_ARG, "min_alpha = %g: must be > 0", (double)min_alpha);
+    return GSR_OK;
+}
+}  // namespace
+
+size_t gsr_frames_scratch_bytes(int32_t W, int32_t H) {
+    if (W < 1 || H < 1) return 0;
+    return gsr_frames_scratch_size(W, H);
+}
+
+int gsr_depth_scale(int32_t W, int32_t H, int32_t C, const float* image, float min_alpha, double percentile, void* stats_out,
+                    void* scratch, void* stream) {
+    int rc;
+    if ((rc = check_geometry_frame(W, H, C, 5, image))) return rc;
+    if ((rc = check_min_alpha(min_alpha))) return rc;
+    if (!(percentile > 0.0 && percentile <= 100.0)) return fail(GSR_E_INVALID_ARG, "percentile = %g: must be in (0, 100]", percentile);
+    if (!stats_out || !scratch) return fail(GSR_E_INVALID_ARG, "null stats_out or scratch");
+    if ((uintptr_t)scratch % 8) return fail(GSR_E_INVALID_ARG, "scratch must be 8-byte aligned");
+    gsr_launch_depth_scale((hipStream_t)stream, W, H, C, image, min_alpha, percentile, stats_out, scratch);
+    return launched();
+}
+
+int gsr_frame_depth16(int32_t W, int32_t H, int32_t C, const float* image, int32_t expected, float min_alpha, float depth_max,
+                      const float* scale_dev, int32_t flip_rows, uint16_t* depth16_out, void* stream) {
+    int rc;
+    if ((rc = check_geometry_frame(W, H, C, expected ? 5 : 4, image))) return rc;
+    if ((rc = check_min_alpha(min_alpha))) return rc;
+    if (!(depth_max >= 0.0f) || std::isinf(depth_max))
+        return fail(GSR_E_INVALID_ARG, "depth_max = %g: must be finite and >= 0", (double)depth_max);
+    if ((depth_max > 0.0f) == (scale_dev != nullptr))
+        return fail(GSR_E_INVALID_ARG, "exactly one of depth_max > 0 and scale_dev: %s given", scale_dev ? "both" : "neither");
+    if (!depth16_out) return fail(GSR_E_INVALID_ARG, "null depth16_out");
+    if ((uintptr_t)depth16_out % 2) return fail(GSR_E_INVALID_ARG, "depth16_out must be 2-byte aligned");
+    gsr_launch_frame_depth16((hipStream_t)stream, W, H, C, image, expected != 0, min_alpha, depth_max, scale_dev, flip_rows != 0,
+                             depth16_out);
+    return launched();
+}
+
+int gsr_frame_normal8(int32_t W, int32_t H, int32_t C, const float* image, float min_alpha, const float* R_c2w,
+                      uint8_t* normal8_out, void* stream) {
+    int rc;
+    if ((rc = check_geometry_frame(W, H, C, 8, image))) return rc;
+    if ((rc = check_min_alpha(min_alpha))) return rc;
+    if (!normal8_out) return fail(GSR_E_INVALID_ARG, "null normal8_out");
+    GsrRot rot = {};
+    if (R_c2w) {
+        std::copy(R_c2w, R_c2w + 9, rot.r);
+        rot.use = 1;
+    }
+    gsr_launch_frame_normal8((hipStream_t)stream, W, H, C, image, min_alpha, rot, normal8_out);
+    return launched();
+}
+
+int gsr_pick_point(int32_t W, int32_t H, int32_t C, const float* image, const gsr_camera* cam, int32_t px, int32_t py,
+                   int32_t half_window, float* out4, void* stream) {
+    int rc;
+    if ((rc = check_geometry_frame(W, H, C, 4, image))) return rc;
+    if (half_window < 0 || half_window > 16) return fail(GSR_E_INVALID_ARG, "half_window = %d: must be in [0, 16]", half_window);
+    if (!cam || !out4) return fail(GSR_E_INVALID_ARG, "null cam or out4");
+    GsrPickCam pc;
+    std::copy(cam->R, cam->R + 9, pc.R);
+    std::copy(cam->camera_center, cam->camera_center + 3, pc.center);
+    std::copy(cam->focal, cam->focal + 2, pc.focal);
+    std::copy(cam->principal, cam->principal + 2, pc.principal);
+    gsr_launch_pick_point((hipStream_t)stream, W, H, C, image, pc, px, py, half_window, out4);
     return launched();
 }
 

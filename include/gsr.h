@@ -832,6 +832,66 @@ GSR_API int gsr_eval_metrics(int32_t W, int32_t H, int32_t C, const float* image
 GSR_API int gsr_frame_rgb8(int32_t W, int32_t H, int32_t C, const float* image, const float* sky_rgb, int32_t flip_rows,
                            uint8_t* rgb8_out, void* stream);
 
+/* Geometry frames: the pictures the reference makes of the depth, alpha and normal channels of a frame — on the host, after
+ * copying the frame out and sorting its depths — (scripts/render-views.jl:264-308,390-407 `depth_image` / `normal_image`;
+ * src/rasterization/rasterizer.jl:163-198 `gl_depth` / `to_depth`; src/gui/worker.jl:688-726 `handle_pick!`).  New functions, no
+ * struct change: GSR_ABI_VERSION stays.  `image` is the rasterizer's frame (C,W,H), channel fastest: 0..2 rgb, 3 depth, 4
+ * alpha, 5..7 normal.  One arithmetic (csrc/frames.hip states it operation by operation): fp32 as written, IEEE divisions and
+ * square roots, no contraction.  Per pixel: covered = alpha >= min_alpha (a NaN alpha is not covered), e = depth /
+ * fmaxf(alpha, min_alpha).  All array pointers device unless said otherwise; every argument is checked before the device is
+ * touched; integer atomics only: results are run-to-run bit-identical.
+ *
+ * gsr_frames_scratch_bytes : bytes of `scratch` for gsr_depth_scale on a W x H frame (32 832 + 4·W·H, rounded up to 8); 0 for
+ *                            W, H < 1.
+ * gsr_depth_scale          : the white level of `depth_image` (render-views.jl:272-277), left on the device.  C >= 5;
+ *                            `percentile` in (0, 100].  stats_out, 16 bytes: {float scale; uint32 n; uint32 a_bits; uint32
+ *                            b_bits}.  v = the covered e in ascending order (Julia's `sort`: -0.0 < +0.0; NaN unspecified),
+ *                            n their number; Statistics.jl's definition 7 in double: p = percentile / 100, m = 1 - p,
+ *                            aleph = fma((double)n, p, m), j = clamp(trunc(aleph), 1, n - 1), γ = clamp(aleph - j, 0, 1);
+ *                            a = v[j], b = v[j+1] (1-based; n == 1: a = b = v[1]); d = b - a in fp32; q = (double)a + γ ·
+ *                            (double)d, two double operations; scale = fmaxf((float)q, 1e-6f).  n == 0: scale = 1, a_bits =
+ *                            b_bits = 0.  The selection is an exact radix select (11 + 11 + 10 key bits): one pass reads
+ *                            depth and alpha of every pixel and writes a 4-byte key, two more passes read only the keys;
+ *                            no host round trip between n and the rank.  This is a + γ·(b - a) as Statistics.jl evaluates
+ *                            it for a Float32 vector and a Float64 p; newer Statistics.jl versions take (1-γ)a + γb when
+ *                            a ≉ b, older ones n·p + m without the fma, and nobody has run Julia against this: n, a_bits
+ *                            and b_bits are the pinned part.  `scratch`: 8-byte aligned, gsr_frames_scratch_bytes(W, H).
+ * gsr_frame_depth16        : depth16_out (W,H) uint16, rows as the frame's rows, reversed with flip_rows != 0 (as
+ *                            gsr_frame_rgb8); 2-byte aligned.  x = covered ? e : 0 with expected != 0 (C >= 5: `depth_image`),
+ *                            x = depth with expected == 0 (C >= 4; with depth_max = 50 this is `to_depth` / `gl_depth`).
+ *                            Exactly one of depth_max > 0 (a host float) and scale_dev (device pointer to the float
+ *                            gsr_depth_scale wrote) is given.  inv = 1.0f / scale, one division; y = fminf(fmaxf(x · inv, 0),
+ *                            1); word = (uint16) floorf(y · 65535.0f + 0.5f): gsr_frame_rgb8's quantiser form at 16 bits.
+ *                            FixedPointNumbers' N0f16(y) rounds to nearest: the two can differ only on exact .5 ties.
+ * gsr_frame_normal8        : `normal_image` (render-views.jl:291-308).  C >= 8; normal8_out (3,W,H) bytes, channel fastest,
+ *                            any alignment.  n = N / fmaxf(alpha, min_alpha), three divisions; len = sqrtf((nx² + ny²) +
+ *                            nz²); degenerate = len < 1e-6f || !covered; n = n / fmaxf(len, 1e-6f); a degenerate pixel is
+ *                            (0,0,0).  R_c2w: nine HOST floats, column-major (transpose(camera.R)), or NULL; when given,
+ *                            row i of R_c2w·n = (r[i]·x + r[i+3]·y) + r[i+6]·z and a degenerate pixel stays zero — the
+ *                            reference multiplies through BLAS, whose order is not known: this order is ours.
+ *                            byte = (uint8) floorf(fminf(fmaxf(c · 0.5f + 0.5f, 0), 1) · 255.0f + 0.5f), the device function
+ *                            gsr_frame_rgb8 uses.
+ * gsr_pick_point           : `handle_pick!`: the orbit target under a pixel.  C >= 4; px, py 1-based; 0 <= half_window <= 16;
+ *                            out4: four device floats {x, y, z, count}.  Over the window [px-hw, px+hw] x [py-hw, py+hw]
+ *                            clipped to the frame, z = (Σ of the raw depths > 1e-2f, in fp32 in a fixed order: csrc/frames.hip)
+ *                            / count; p_cam = ((px - 0.5f - principal[0]·W)·z / fx, (py - 0.5f - principal[1]·H)·z / fy, z);
+ *                            target = Rᵀ·p_cam + camera_center from the host fields of `cam` (the reference inverts the
+ *                            4x4 pose; for a rigid pose that is the transpose).  count == 0 or a pixel outside the frame:
+ *                            {0,0,0,0} and GSR_OK (the reference returns silently).
+ * GSR_E_INVALID_ARG: W or H < 1; C below what the call needs; a frame of 2^32 elements or more; NULL image, output or `cam`,
+ * NULL scratch or stats_out; percentile outside (0, 100] or NaN; min_alpha not > 0; both depth_max > 0 and scale_dev, or
+ * neither; depth_max negative, NaN or Inf; half_window outside [0, 16]; a scratch that is not 8-byte aligned, a depth16_out
+ * that is not 2-byte aligned. */
+GSR_API size_t gsr_frames_scratch_bytes(int32_t W, int32_t H);
+GSR_API int gsr_depth_scale(int32_t W, int32_t H, int32_t C, const float* image, float min_alpha, double percentile,
+                            void* stats_out, void* scratch, void* stream);
+GSR_API int gsr_frame_depth16(int32_t W, int32_t H, int32_t C, const float* image, int32_t expected, float min_alpha,
+                              float depth_max, const float* scale_dev, int32_t flip_rows, uint16_t* depth16_out, void* stream);
+GSR_API int gsr_frame_normal8(int32_t W, int32_t H, int32_t C, const float* image, float min_alpha, const float* R_c2w,
+                              uint8_t* normal8_out, void* stream);
+GSR_API int gsr_pick_point(int32_t W, int32_t H, int32_t C, const float* image, const gsr_camera* cam, int32_t px, int32_t py,
+                           int32_t half_window, float* out4, void* stream);
+
 /* The MCMC densification strategy of the reference on the device (src/mcmc.jl, `strategy = :mcmc`, src/strategy.jl:16): the
  * number of Gaussians only grows (up to max_cap), dead Gaussians are relocated onto alive ones sampled ∝ opacity with the
  * Eq. 9 opacity / scale correction, position noise keeps the chain exploring and an L1 on opacity and scale produces the
