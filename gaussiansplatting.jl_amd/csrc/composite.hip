@@ -72,7 +72,7 @@ __device__ __forceinline__ void unpack_features(const float4& s1, const float4& 
 //   * sort_composite_fwd_kernel: the fused sort + forward, which composites straight from the 256-entry LDS chunk the
 //     workgroup has just emitted — the stream in HBM is written for the backward and never read back here.
 template <int C> struct FwdPixel {
-    bool done;
+    unsigned long long done;  // wave-level, in SGPRs: bit l <-> lane l has saturated or its pixel lies outside the image
     float T, unc;
     uint32_t last;
     float color[C];
@@ -80,14 +80,44 @@ template <int C> struct FwdPixel {
 
 template <int C>
 __device__ __forceinline__ void fwd_pixel_init(FwdPixel<C>& p, bool inside) {
-    p.done = !inside; p.T = 1.0f; p.unc = 0.0f; p.last = 0;
+    p.done = wave_ballot(!inside); p.T = 1.0f; p.unc = 0.0f; p.last = 0;
 #pragma unroll
     for (int c = 0; c < C; c++) p.color[c] = 0.0f;
 }
 
+// The state update of one visit for the lanes of `ok`, under EXEC narrowed to them:  T <- Tn,  last <- pos,
+// colour[c] += f[c]·w  (feature 4 of :rgbd / :rgbdn is the constant 1: an add),  unc += w  (AUX).
+// ONE asm statement per (C, AUX): between two statements the compiler may schedule VALU work of its own, which would then
+// run under the narrowed mask.  Inside are the two mask moves, v_mov_b32, v_fmac_f32 and v_add_f32 — no memory instruction,
+// nothing with a hazard against a scalar write of EXEC.  The saved mask is written before `ok` is read: early-clobber.
+#define GSR_FWD_REGION(BODY) \
+    "s_and_saveexec_b64 %[sv], %[ok]\n\tv_mov_b32 %[T], %[Tn]\n\tv_mov_b32 %[last], %[pos]\n\t" BODY "s_mov_b64 exec, %[sv]"
+#define GSR_FWD_RGB "v_fmac_f32 %[c0], %[f0], %[w]\n\tv_fmac_f32 %[c1], %[f1], %[w]\n\tv_fmac_f32 %[c2], %[f2], %[w]\n\t"
+#define GSR_FWD_D   "v_fmac_f32 %[c3], %[f3], %[w]\n\tv_add_f32 %[c4], %[c4], %[w]\n\t"
+#define GSR_FWD_N   "v_fmac_f32 %[c5], %[f5], %[w]\n\tv_fmac_f32 %[c6], %[f6], %[w]\n\tv_fmac_f32 %[c7], %[f7], %[w]\n\t"
+#define GSR_FWD_UNC "v_add_f32 %[unc], %[unc], %[w]\n\t"
+#define GSR_FWD_OUT      [sv] "=&s"(saved), [T] "+v"(p.T), [last] "+v"(p.last)
+#define GSR_FWD_OUT_RGB  GSR_FWD_OUT, [c0] "+v"(p.color[0]), [c1] "+v"(p.color[1]), [c2] "+v"(p.color[2])
+#define GSR_FWD_OUT_D    GSR_FWD_OUT_RGB, [c3] "+v"(p.color[3]), [c4] "+v"(p.color[4])
+#define GSR_FWD_OUT_N    GSR_FWD_OUT_D, [c5] "+v"(p.color[5]), [c6] "+v"(p.color[6]), [c7] "+v"(p.color[7])
+#define GSR_FWD_IN       [ok] "s"(ok), [Tn] "v"(Tn), [pos] "v"(pos), [w] "v"(w)
+#define GSR_FWD_IN_RGB   GSR_FWD_IN, [f0] "v"(f[0]), [f1] "v"(f[1]), [f2] "v"(f[2])
+#define GSR_FWD_IN_D     GSR_FWD_IN_RGB, [f3] "v"(f[3])
+#define GSR_FWD_IN_N     GSR_FWD_IN_D, [f5] "v"(f[5]), [f6] "v"(f[6]), [f7] "v"(f[7])
+template <int C, bool AUX>
+__device__ __forceinline__ void fwd_update_under_exec(FwdPixel<C>& p, unsigned long long ok, float Tn, float pos, float w, const float (&f)[C]) {
+    unsigned long long saved;
+    if constexpr (C == 3 && !AUX) asm volatile(GSR_FWD_REGION(GSR_FWD_RGB) : GSR_FWD_OUT_RGB : GSR_FWD_IN_RGB : "scc");
+    if constexpr (C == 3 && AUX)  asm volatile(GSR_FWD_REGION(GSR_FWD_RGB GSR_FWD_UNC) : GSR_FWD_OUT_RGB, [unc] "+v"(p.unc) : GSR_FWD_IN_RGB : "scc");
+    if constexpr (C == 5 && !AUX) asm volatile(GSR_FWD_REGION(GSR_FWD_RGB GSR_FWD_D) : GSR_FWD_OUT_D : GSR_FWD_IN_D : "scc");
+    if constexpr (C == 5 && AUX)  asm volatile(GSR_FWD_REGION(GSR_FWD_RGB GSR_FWD_D GSR_FWD_UNC) : GSR_FWD_OUT_D, [unc] "+v"(p.unc) : GSR_FWD_IN_D : "scc");
+    if constexpr (C == 8 && !AUX) asm volatile(GSR_FWD_REGION(GSR_FWD_RGB GSR_FWD_D GSR_FWD_N) : GSR_FWD_OUT_N : GSR_FWD_IN_N : "scc");
+    if constexpr (C == 8 && AUX)  asm volatile(GSR_FWD_REGION(GSR_FWD_RGB GSR_FWD_D GSR_FWD_N GSR_FWD_UNC) : GSR_FWD_OUT_N, [unc] "+v"(p.unc) : GSR_FWD_IN_N : "scc");
+}
+
 // Blend the LDS entries whose bits are set in `m` (bit k <-> entry e0 + k), front to back.  Plane 2 of an entry holds
-// (third colour, 1-BASED LIST POSITION, depth, -): `last` is then a select between two VGPRs, not a v_mov of the scalar
-// position + a select.  `ids`: Gaussian id of entry 0, 1, ... (only read for the covisibility output).
+// (third colour, 1-BASED LIST POSITION, depth, -): `last` is then a move between two VGPRs, not a v_mov of the scalar
+// position.  `ids`: Gaussian id of entry 0, 1, ... (only read for the covisibility output).
 template <int C, bool AUX, int N>
 __device__ __forceinline__ void fwd_blend_selected(FwdPixel<C>& p, unsigned long long m, const LdsSplats<C, N>& e, int e0, float fx, float fy,
                                                    const uint32_t* __restrict__ ids, uint8_t* __restrict__ covis) {
@@ -103,28 +133,28 @@ __device__ __forceinline__ void fwd_blend_selected(FwdPixel<C>& p, unsigned long
         const float dx = a.x - fx, dy = a.y - fy;
         const float sigma = sigma_of(sigma_x(a.z, a.w, dx), b.x, dy, __fmul_rn(dy, dy));
         const float alpha = alpha_of(b.y, __expf(-sigma));
-        // Branch-free body: a lane that is done, or whose pixel this splat does not touch, blends
-        // with weight 0 (what `continue`/`break` leave behind, render.jl:92-101).  (Handling the
-        // saturating lanes in a wave-uniform rare path instead measured 10 % slower.)
+        // Branch-free body: every lane computes the blend; the lanes that take it are a wave-level mask, built on the
+        // scalar unit from the ballots of the two bare compares (no per-lane bool in between: the compiler would
+        // materialise it with a v_cndmask and compare it back), and the state is updated under EXEC = that mask.  A lane
+        // that is done, or whose pixel this splat does not touch, keeps its state untouched (what `continue`/`break`
+        // leave behind, render.jl:92-101).  (As selects on the mask: three v_cndmask more per visit.  As `if (ok)`, or
+        // with the saturating lanes in a wave-uniform rare path: a branch per visit, measured 10 % slower.)
         const float Tn = p.T * (1.0f - alpha);
-        const bool small = Tn < 1e-4f;
+        const unsigned long long small = wave_ballot(Tn < 1e-4f);
         // sigma >= 0 && alpha >= 1/255 as one unsigned compare against the instance's threshold (tile_sort_device.h)
-        const bool touch = __float_as_uint(sigma) < __float_as_uint(C == 3 ? c2.z : c3.w);
-        bool ok = !p.done && touch;
-        const bool stop = ok && small;
-        p.done = p.done || stop;
-        ok = ok != stop;  // stop implies ok: the xor stays on the scalar unit (`ok && !small` costs a second v_cmp)
+        const unsigned long long touch = wave_ballot(__float_as_uint(sigma) < __float_as_uint(C == 3 ? c2.z : c3.w));
+        const unsigned long long okpre = touch & ~p.done;
+        const unsigned long long stop = okpre & small;
+        p.done |= stop;
+        const unsigned long long ok = okpre ^ stop;
         float f[C];
         unpack_features<C>(b, c2, c3, f);
-        const float w = ok ? alpha * p.T : 0.0f;
-#pragma unroll
-        for (int c = 0; c < C; c++) p.color[c] += f[c] * w;
-        if (AUX) {
-            p.unc += w;
-            if (covis && ok && p.T > 0.5f) covis[ids[jb]] = 1;
-        }
-        p.T = ok ? Tn : p.T;
-        p.last = ok ? __float_as_uint(c2.y) : p.last;
+        const float w = alpha * p.T;
+        // (covisibility: decided on the transmittance BEFORE the update)
+        // (a null `covis` empties the mask: as a test of its own in front of the store it is a second branch per visit)
+        const unsigned long long seen = AUX ? ok & wave_ballot(p.T > 0.5f) & (covis ? ~0ull : 0ull) : 0ull;
+        fwd_update_under_exec<C, AUX>(p, ok, Tn, c2.y, w, f);
+        if (AUX && __builtin_amdgcn_inverse_ballot_w64(seen)) covis[ids[jb]] = 1;
     }
 }
 
@@ -161,7 +191,7 @@ __device__ __forceinline__ void composite_fwd_quadrant(int W, int H, int grid_x,
     FwdPixel<C> p;
     fwd_pixel_init<C>(p, inside);
     for (int base = 0; base < to_do; base += 64) {
-        if (wave_ballot(!p.done) == 0ull) break;  // the whole quadrant has saturated
+        if (p.done == ~0ull) break;  // the whole quadrant has saturated (a scalar compare)
         const int jj = base + lane;
         float4 r2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (jj < to_do) r2 = stream.s2[start + jj];
@@ -301,7 +331,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void s
             __syncthreads();
             const int cnt = (int)min((uint32_t)CHUNK, n - cbase);
             for (int b = 0; b < cnt; b += 64) {
-                if (wave_ballot(!p.done) == 0ull) break;  // the whole quadrant has saturated
+                if (p.done == ~0ull) break;  // the whole quadrant has saturated (a scalar compare)
                 const int k = b + lane;
                 const bool cand = k < cnt && (__float_as_uint(e(2, k).w) & strip_bits) != 0u;
                 const unsigned long long m = wave_ballot(cand);
