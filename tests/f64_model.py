@@ -70,7 +70,9 @@ def render_dense(means, shs, opac, scales, rots, cam, sh_degree, background, mod
                  R_w2c=None, t_w2c=None, taps=None):
     """Full differentiable float64 model.  Discrete structure (which Gaussian is in
     which tile, in which order; who is culled) is taken from `values_sorted`,
-    `ranges`, `radii`; the per-pixel skip/stop decisions are re-derived in float64.
+    `ranges`, `radii` — the oracle's, or those definition_ref.tile_lists / decide derive
+    in float64 from the spec without keys, scan or sort (equal on every filtered scene:
+    tests/test_definition_cpu.py); the per-pixel skip/stop decisions are re-derived in float64.
     Returns image (H,W,C).  `taps`: a dict that receives the intermediate `m2` (N,2: the
     projected centres in pixels), so that the caller can `retain_grad()` it."""
     W, H = cam.width, cam.height
