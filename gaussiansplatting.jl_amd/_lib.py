@@ -22,10 +22,11 @@ GRAD_FP32_REFERENCE, GRAD_ACCURATE = 1, 2         # gsr_config.grad_precision
 MODES = {"rgb": 3, "rgbd": 5, "rgbdn": 8}
 FORWARD_ONLY = 1  # gsr_aux.flags: no backward state is kept (inference render)
 FLAG_REFERENCE_TILE_LISTS = 2  # flags = 0: exact footprint culling (the default); bit 1 is retired (rejected)
+FLAG_ANTIALIASED = 4           # opacity x add_blur's compensation, forward and backward (gsr.h)
 ABI_VERSION = 6  # GSR_ABI_VERSION of the include/gsr.h this mirror was written against
 
 (BUF_RADII, BUF_GRAD_MEANS2D, BUF_N_CONTRIB, BUF_FINAL_T, BUF_TILE_RANGES, BUF_VALUES_SORTED, BUF_GEOM, BUF_NORMALS,
- BUF_GRAD_ROWS, BUF_INSTANCE_AUX) = range(10)
+ BUF_GRAD_ROWS, BUF_INSTANCE_AUX, BUF_COMPENSATIONS) = range(11)
 
 
 class GsrError(RuntimeError):

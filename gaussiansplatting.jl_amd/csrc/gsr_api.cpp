@@ -46,7 +46,7 @@ struct TunerEvents {
     }
 };
 
-constexpr int kHandleBufs = 32;  // rows of kBufs, the table of the handle's buffers below the handle (checked there)
+constexpr int kHandleBufs = 33;  // rows of kBufs, the table of the handle's buffers below the handle (checked there)
 
 bool valid_mode(int m) { return m == GSR_MODE_RGB || m == GSR_MODE_RGBD || m == GSR_MODE_RGBDN; }
 
@@ -59,6 +59,7 @@ struct gsr_handle {
     DevBuf ranges, n_contrib, final_T, tile_count, tile_start, tile_order, totals;
     // GeometryState (states.jl:2-47), repacked as one 64-byte record per Gaussian
     DevBuf geo, gnormal, radii, bsum, bpre, bvis;
+    DevBuf comp;  // add_blur's compensations (float per Gaussian): GSR_FLAG_ANTIALIASED handles only, never allocated otherwise
     // BinningState (states.jl:66-85): unsorted keys (per-tile bins of bin_cap slots), sorted ids, sorted splat stream
     // everything gsr_forward carries from one view to the next lives in `pol`, and every decision taken from it is a pure
     // function of gsr_policy.cpp (include/gsr_policy.h): bins capacity / compact mode, the binning form and its tuner, the held
@@ -154,6 +155,7 @@ constexpr BufRow kBufs[] = {
     BUF(overflow_fill, false, false, 1u),
     BUF(dbg_flag, false, false, 1u),
     BUF(pose_part, true, true, 1u),       // per-workgroup pose-gradient partials: every slot is stored (zeros included) before it is summed
+    BUF(comp, true, true, 1u),            // compensations of an antialiased forward (float): stale where radii == 0, read behind radii > 0
 };
 #undef BUF
 template <class Pred> constexpr int count_bufs(Pred pred) {
@@ -162,9 +164,11 @@ template <class Pred> constexpr int count_bufs(Pred pred) {
     return n;
 }
 static_assert(sizeof(kBufs) / sizeof(kBufs[0]) == kHandleBufs, "gsr_handle::all holds one pointer per row");
-static_assert(count_bufs([](const BufRow& r) { return r.scene; }) == 17, "the scene buffers");
-static_assert(count_bufs([](const BufRow& r) { return r.fill_ok; }) == 10, "the GSR_DEBUG_FILL candidates");
+static_assert(count_bufs([](const BufRow& r) { return r.scene; }) == 18, "the scene buffers");
+static_assert(count_bufs([](const BufRow& r) { return r.fill_ok; }) == 11, "the GSR_DEBUG_FILL candidates");
 static_assert(count_bufs([](const BufRow& r) { return r.guard_word == 0u; }) == 3, "the id buffers whose guard word is 0");
+
+bool antialiased(const gsr_handle* h) { return (h->cfg.flags & GSR_FLAG_ANTIALIASED) != 0u; }
 
 GsrCam make_cam(const gsr_handle* h, const gsr_camera* c) {
     GsrCam k;
@@ -181,6 +185,8 @@ GsrCam make_cam(const gsr_handle* h, const gsr_camera* c) {
     return k;
 }
 
+// the compensations of an antialiased handle's forward, else NULL: WHAT the per-Gaussian kernels dispatch on
+float* comp_of(const gsr_handle* h) { return antialiased(h) ? h->comp.as<float>() : nullptr; }
 GsrGeom geom_of(const gsr_handle* h) {
     return GsrGeom{h->geo.as<GsrGeoRec>(), h->gnormal.as<float4>(), h->radii_cur, h->bsum.as<uint32_t>(),
                    h->bpre.as<uint32_t>()};
@@ -214,7 +220,7 @@ inline int preprocess_form_of(const gsr_handle* h) {  // -1 by scene and grid, 0
 
 // Byte sizes of the buffers an n-Gaussian view on this handle touches (gsr_sizes.h: the one place they are written)
 gsr_gaussian_bytes gaussian_bytes(const gsr_handle* h, int64_t n) {
-    return gsr_sizes_per_gaussian((size_t)n, h->cfg.mode, gsr_pose_partial_floats(n));
+    return gsr_sizes_per_gaussian((size_t)n, h->cfg.mode, gsr_pose_partial_floats(n), antialiased(h));
 }
 
 // gsr_stats' view-history block (ABI 6): the policy state's counters + the mechanism's own (buffer reallocations)
@@ -337,7 +343,7 @@ int gsr_create(const gsr_config* cfg, gsr_handle** out) {
     if (cfg->flags & GSR_FLAG_RETIRED_BIT0)
         return fail(GSR_E_INVALID_ARG, "flag bit 0x1 is retired (ABI 1's GSR_FLAG_EXACT_TILE_CULL): rebuild the caller against "
                                        "include/gsr.h ABI %d", GSR_ABI_VERSION);
-    if (cfg->flags & ~(uint32_t)GSR_FLAG_REFERENCE_TILE_LISTS) return fail(GSR_E_INVALID_ARG, "unknown flags 0x%x", cfg->flags);
+    if (cfg->flags & ~(uint32_t)(GSR_FLAG_REFERENCE_TILE_LISTS | GSR_FLAG_ANTIALIASED)) return fail(GSR_E_INVALID_ARG, "unknown flags 0x%x", cfg->flags);
     if (cfg->ssim_precision < 0 || cfg->ssim_precision > GSR_SSIM_EXACT)
         return fail(GSR_E_INVALID_ARG, "gsr_config.ssim_precision = %d: GSR_DEFAULT (0), GSR_SSIM_FAST (1) or GSR_SSIM_EXACT (2)",
                     cfg->ssim_precision);
@@ -472,7 +478,8 @@ int gsr_reserve(gsr_handle* h, int64_t n_gaussians, int64_t n_instances) {
         const gsr_gaussian_bytes b = gaussian_bytes(h, n_gaussians);
         if ((rc = h->geo.ensure(b.geo)) || (rc = h->radii.ensure(b.radii)) || (rc = h->bsum.ensure(b.block)) ||
             (rc = h->bpre.ensure(b.block)) || (rc = h->bvis.ensure(b.block)) || (rc = h->vmean2d.ensure(b.vmean2d)) ||
-            (rc = h->pose_part.ensure(b.pose_part)) || (C > 5 && (rc = h->gnormal.ensure(b.gnormal))))
+            (rc = h->pose_part.ensure(b.pose_part)) || (C > 5 && (rc = h->gnormal.ensure(b.gnormal))) ||
+            (b.comp && (rc = h->comp.ensure(b.comp))))
             return rc;
     }
     if (n_instances > 0) {
@@ -547,7 +554,8 @@ static int fwd_begin(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam,
     const float nslack = 1.25f;
     if ((rc = h->geo.ensure(b.geo, nslack)) || (own_radii && (rc = h->radii.ensure(b.radii, nslack))) ||
         (rc = h->bsum.ensure(b.block, nslack)) || (rc = h->bpre.ensure(b.block, nslack)) ||
-        (rc = h->bvis.ensure(b.block, nslack)) || (v.C > 5 && (rc = h->gnormal.ensure(b.gnormal, nslack))))
+        (rc = h->bvis.ensure(b.block, nslack)) || (v.C > 5 && (rc = h->gnormal.ensure(b.gnormal, nslack))) ||
+        (b.comp && (rc = h->comp.ensure(b.comp, nslack))))
         return rc;
     h->radii_cur = own_radii ? h->radii.as<int32_t>() : aux->radii;
     h->vmean2d_cur = nullptr;
@@ -599,7 +607,7 @@ static int fwd_plan_and_bin(gsr_handle* h, FwdView& v) {
     h->last_form = gsr_launch_preprocess(s, v.n, v.in->n_coeffs, v.in->sh_degree, v.C, v.in->means, v.in->scales,
                                          v.in->rotations, v.in->opacities, v.in->shs, v.k, geom_of(h), tiles_of(h),
                                          h->bvis.as<uint32_t>(), bins_of(h, bin_cap_view) /* 0: count only */,
-                                         /*aggregating=*/v.plan.form != GSR_FORM_DIRECT);
+                                         /*aggregating=*/v.plan.form != GSR_FORM_DIRECT, comp_of(h));
     if (timed >= 0) HIPCHK(hipEventRecord(h->tuner_ev.ev[2 * timed + 1], s));
     sc1.close();
     v.seq = ++h->totals_seq ? h->totals_seq : ++h->totals_seq;  // never 0
@@ -900,7 +908,8 @@ int gsr_backward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, con
     gsr_launch_pergauss_bwd(s, n, in->n_coeffs, in->sh_degree, C, in->means, in->scales, in->rotations, in->shs, k,
                             geom_of(h), inst_of(h), h->vmean2d_cur, g->vmeans, g->vshs, g->vopacities,
                             g->vscales, g->vrotations, g->vR, g->vt, h->pose_part.as<float>(), g->vcolors,
-                            /*fp32_chain=*/h->cfg.grad_precision == GSR_GRAD_FP32_REFERENCE);
+                            /*fp32_chain=*/h->cfg.grad_precision == GSR_GRAD_FP32_REFERENCE,
+                            antialiased(h) ? in->opacities : nullptr, comp_of(h));
     sc8.close();
     HIPCHK(hipGetLastError());
     h->bwd_valid = true;
@@ -922,6 +931,10 @@ static int buffer_lookup(const gsr_handle* h, int which, const void** dev_ptr, s
         case GSR_BUF_GRAD_MEANS2D:
             *dev_ptr = h->bwd_valid && n ? h->vmean2d_cur : nullptr;
             *bytes = *dev_ptr ? gb.vmean2d : 0;
+            return GSR_OK;
+        case GSR_BUF_COMPENSATIONS:  // per-forward state like the radii; a handle without GSR_FLAG_ANTIALIASED has none
+            *dev_ptr = h->fwd_valid && n && gb.comp && gb.comp <= h->comp.cap ? h->comp.p : nullptr;
+            *bytes = *dev_ptr ? gb.comp : 0;
             return GSR_OK;
         case GSR_BUF_N_CONTRIB: b = &h->n_contrib; sz = P * 4; break;
         case GSR_BUF_FINAL_T: b = &h->final_T; sz = P * 4; break;
@@ -1081,7 +1094,7 @@ int gsr_backward_trainer_tail(gsr_handle* h, const gsr_inputs* in, const gsr_cam
     const gsr::TailState S = gsr_make_tail_state(st->theta, st->mu, st->nu, lr_t, st->beta1, st->beta2, st->eps,
                                                  st->scale_dims, st->shs, st->opacities_act, st->scales_act);
     gsr_launch_pergauss_bwd_tail(s, n, K, in->sh_degree, C, k, geom_of(h), inst_of(h), h->vmean2d_cur, S,
-                                 /*fp32_chain=*/h->cfg.grad_precision == GSR_GRAD_FP32_REFERENCE);
+                                 /*fp32_chain=*/h->cfg.grad_precision == GSR_GRAD_FP32_REFERENCE, comp_of(h));
     sc12.close();
     HIPCHK(hipGetLastError());
     h->bwd_valid = true;

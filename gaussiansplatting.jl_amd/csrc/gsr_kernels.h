@@ -105,7 +105,9 @@ struct GsrFrame {
 int gsr_launch_preprocess(hipStream_t s, int n, int K, int degree, int channels, const float* means,
                           const float* scales, const float* rots, const float* opac, const float* shs, GsrCam cam,
                           GsrGeom geom, GsrTiles tiles, uint32_t* n_visible /* per 256-block */,
-                          GsrKeys keys /* (T+1) x cap keys; cap == 0: count only */, bool aggregating);
+                          GsrKeys keys /* (T+1) x cap keys; cap == 0: count only */, bool aggregating,
+                          float* comp /* antialiased handle: add_blur's compensations (N), written where radii > 0, and the
+                                         opacity of every later stage is opac * comp; NULL: the plain render */);
 struct GsrBg8 { float v[8]; };
 // compact binning mode: scatter the keys to tile_start[t] + arrival rank (tile_fill zeroed by the caller).
 // only_above > 0: only the tiles whose list is LONGER than that (the lists that overflowed fixed-capacity bins) — the others'
@@ -120,12 +122,15 @@ void gsr_launch_pergauss_bwd(hipStream_t s, int n, int K, int degree, int channe
                              float* vscales, float* vrots, float* vR, float* vt /* both or neither */,
                              float* pose_part /* scratch of gsr_pose_partial_floats(n) floats, needed when vR is given */,
                              float* vcolors /* (3,N) or NULL: factored SH gradient instead of vshs */,
-                             bool fp32_chain /* ∇scales / ∇rotations by the reference's fp32 trees (GSR_GRAD_FP32_REFERENCE) */);
+                             bool fp32_chain /* ∇scales / ∇rotations by the reference's fp32 trees (GSR_GRAD_FP32_REFERENCE) */,
+                             const float* opac, const float* comp /* antialiased handle: the caller's opacities and the forward's
+                                                                     compensations (∇add_blur joins both chains); else both NULL */);
 // backward epilogue = trainer tail (single-GPU step): no gradient arrays, the parameters / Adam states in S are
 // updated in place and the activated copies of the next forward written (adam_math.h)
 namespace gsr { struct TailState; }
 void gsr_launch_pergauss_bwd_tail(hipStream_t s, int n, int K, int degree, int channels, GsrCam cam, GsrGeom geom,
-                                  GsrInst inst, float2* vmean2d, const gsr::TailState& S, bool fp32_chain);
+                                  GsrInst inst, float2* vmean2d, const gsr::TailState& S, bool fp32_chain,
+                                  const float* comp /* antialiased handle (the opacities are S.opac_act), or NULL */);
 void gsr_launch_sh_grad_views(hipStream_t s, int n, int K, int degree, int n_views, const float* centers,
                               const float* means, const float* vc_all, float* vshs);
 // the same rebuild with the trainer tail applied in place of the ∇shs store (multi-GPU trainer step; S.points = the means)

@@ -12,11 +12,12 @@ struct gsr_gaussian_bytes {
     size_t gnormal;    // float4, :rgbdn only
     size_t vmean2d;    // float2 (the backward's)
     size_t pose_part;  // the backward's pose-gradient partials
+    size_t comp;       // float: add_blur's compensations, antialiased handles only
 };
 
 // n Gaussians in a C-channel mode; pose_partial_floats: pergauss.hip's gsr_pose_partial_floats(n).  The forward's arrays hold
-// at least one element (a view of no Gaussian still launches over them).
-inline gsr_gaussian_bytes gsr_sizes_per_gaussian(size_t n, int C, size_t pose_partial_floats) {
+// at least one element (a view of no Gaussian still launches over them).  antialiased: a GSR_FLAG_ANTIALIASED handle.
+inline gsr_gaussian_bytes gsr_sizes_per_gaussian(size_t n, int C, size_t pose_partial_floats, bool antialiased = false) {
     const size_t nn = n > 0 ? n : 1;
     gsr_gaussian_bytes b;
     b.geo = nn * 64;
@@ -25,6 +26,7 @@ inline gsr_gaussian_bytes gsr_sizes_per_gaussian(size_t n, int C, size_t pose_pa
     b.gnormal = C > 5 ? nn * 16 : 0;
     b.vmean2d = n * 8;
     b.pose_part = pose_partial_floats * 4;
+    b.comp = antialiased ? nn * 4 : 0;
     return b;
 }
 

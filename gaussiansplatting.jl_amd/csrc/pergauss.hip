@@ -463,7 +463,10 @@ template <int DEG, int AGG_NT /* 0: direct form, 256 threads; else the threads o
           bool SCATTER = false /* the compact binning mode's SECOND pass (duplicate_with_keys! as count -> scan -> scatter): no
                                   projection — the geometry records are read back —, keys go to tile_start[t] + arrival rank */,
           bool BANDED = false /* aggregating form over horizontal bands of the tile grid (n_bands > 1); false: ONE band = the whole
-                                 grid, the band loop and the rect clipping compile away (round 4's kernel, register for register) */>
+                                 grid, the band loop and the rect clipping compile away (round 4's kernel, register for register) */,
+          bool AA = false /* antialiased handle (GSR_FLAG_ANTIALIASED): the opacity every later stage sees is the caller's times the
+                             compensation of add_blur, which goes to `comp`; a template flag, so that the default kernels are the
+                             parent's register for register (the aggregating forms sit ON their occupancy step) */>
 // (direct form: AT MOST four waves per SIMD — with its per-lane walks gone it would fit five, and five waves of scattered returning
 //  atomics are slower than four: config 5 0.66-0.68 ms against 0.60-0.62)
 __global__ __launch_bounds__(AGG_NT ? AGG_NT : 256)
@@ -477,8 +480,10 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
                                                                       uint32_t* __restrict__ n_visible,
                                                                       uint64_t* __restrict__ bins, uint32_t bin_cap,
                                                                       int n_words, const uint32_t* __restrict__ tile_start,
-                                                                      int n_bands, int band_rows) {
+                                                                      int n_bands, int band_rows,
+                                                                      float* __restrict__ comp /* AA: compensations (N) */) {
     static_assert(!SCATTER || AGG_NT != 0, "the scatter pass exists in the aggregating form only");
+    static_assert(!SCATTER || !AA, "the scatter pass replays the record: the effective opacity is in it");
     static_assert(!BANDED || AGG_NT != 0, "bands are the aggregating form's");
     constexpr bool AGG = AGG_NT != 0;
     constexpr int NT = AGG ? AGG_NT : 256;
@@ -531,6 +536,7 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
         for (int r = 0; r < 3; r++) mc[r] = (R.m[r][0] * p[0] + R.m[r][1] * p[1] + R.m[r][2] * p[2]) + t[r];
         mc_z = mc[2];
         int radius = 0;
+        float rho = 0.0f;  // AA: add_blur's compensation
         M33 Rg; float s[3];
         if (cam.near_plane < mc[2] && mc[2] < cam.far_plane) {
             float qn[4], inv_norm;
@@ -559,10 +565,13 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
                 for (int b = 0; b < 2; b++)
                     S2.m[a][b] = JS[a][0] * pr.J[b][0] + JS[a][1] * pr.J[b][1] + JS[a][2] * pr.J[b][2];
             // add_blur (render.jl:387-396)
+            float det_orig = 0.0f;
+            if constexpr (AA) det_orig = S2.m[0][0] * S2.m[1][1] - S2.m[0][1] * S2.m[1][0];
             S2.m[0][0] = S2.m[0][0] + cam.blur_eps;
             S2.m[1][1] = S2.m[1][1] + cam.blur_eps;
             float det = S2.m[0][0] * S2.m[1][1] - S2.m[0][1] * S2.m[1][0];
             if (det > 0.0f) {
+                if constexpr (AA) rho = sqrtf(fmaxf(0.0f, det_orig / det));
                 // inverse (render.jl:368-381)
                 float det_inv = 1.0f / det;
                 float tmp = -S2.m[0][1] * det_inv;
@@ -589,7 +598,14 @@ __attribute__((amdgpu_waves_per_eu(AGG_NT ? 3 * AGG_NT / 256 : 1, AGG_NT ? 8 : 4
             sh_colour(p);
             get_rect(m2[0], m2[1], radius, cam.grid_x, cam.grid_y, rmin, rmax);
             area = (uint32_t)((rmax[0] - rmin[0]) * (rmax[1] - rmin[1]));
-            tau = footprint_tau(opac_in);
+            if constexpr (AA) {
+                // an antialiased render of opacities o IS the plain render of o * rho: every reader of the opacity below — the
+                // footprint test, the record, the blend threshold — takes the product.  rho == 0 (a footprint whose fp32
+                // det_orig is <= 0): tau = log(0) emits nothing.  comp[i] stays stale where radii == 0, like the record.
+                comp[i] = rho;
+                opac_v = opac_in * rho;
+            }
+            tau = footprint_tau(opac_v);
         }
     }
     // duplicate_with_keys! (utils.jl:85-120) restated per tile, fused into this kernel: the
@@ -847,9 +863,11 @@ __device__ __forceinline__ void unnorm_quat2rot_bwd(const T (&vR)[3][3], const T
 //   va, vb, vc: the summed conic cotangent (vb on both off-diagonal entries, as the reference places it); vRg: the normal
 //   channel's contribution to the rotation matrix cotangent (projection.jl:227-235), zero outside :rgbdn.
 // ---------------------------------------------------------------------------------
+//   AA: rho, vrho = the forward's compensation and its cotangent; ∇add_blur (render.jl:398-413) is added to vS2 below.
+template <bool AA>
 __device__ __forceinline__ void scales_rots_bwd_f64(const GsrCam& cam, const M33& Rf, const float tf[3], const float pf[3],
                                                     const float4 q4, const float sf[3], float va, float vb, float vc,
-                                                    const M33& vRg, float vs_out[3], float vq_out[4]) {
+                                                    const M33& vRg, float rho, float vrho, float vs_out[3], float vq_out[4]) {
     double R[3][3], mc[3];
 #pragma unroll
     for (int r = 0; r < 3; r++) {
@@ -898,7 +916,14 @@ __device__ __forceinline__ void scales_rots_bwd_f64(const GsrCam& cam, const M33
     // vS2 = -C vC C (render.jl:383-385), symmetric
     const double a_ = (double)va, b_ = (double)vb, c_ = (double)vc;
     const double P00 = Ca * a_ + Cb * b_, P01 = Ca * b_ + Cb * c_, P10 = Cb * a_ + Cc * b_, P11 = Cb * b_ + Cc * c_;
-    const double V00 = -(P00 * Ca + P01 * Cb), V01 = -(P00 * Cb + P01 * Cc), V11 = -(P10 * Cb + P11 * Cc);
+    double V00 = -(P00 * Ca + P01 * Cb), V01 = -(P00 * Cb + P01 * Cc), V11 = -(P10 * Cb + P11 * Cc);
+    if constexpr (AA) {
+        // ∇add_blur (render.jl:398-413) on the conic: vS2 += vs ((1 - rho²) C - eps det(C) I), the pullback of
+        // rho = sqrt(det S / det(S + eps I)) (adj(S) = adj(S + eps I) - eps I in 2 x 2), with the reference's 1e-6 under vs
+        const double r_ = (double)rho, vsq = 0.5 * (double)vrho / (r_ + 1e-6), ct = 1.0 - r_ * r_;
+        const double ed = (double)cam.blur_eps * (Ca * Cc - Cb * Cb);
+        V00 += vsq * (ct * Ca - ed); V01 += vsq * ct * Cb; V11 += vsq * (ct * Cc - ed);
+    }
     // vM = (vSigma + vSigma') M with vSigma = T' vS2 T:  vM = 2 T' (vS2 TM)
     double X[2][3], vM[3][3];
 #pragma unroll
@@ -1081,10 +1106,13 @@ struct ProjectBwd {
     float vmean[3];
     M33 vSigma;
 };
+//   AA: rho, vrho = the forward's compensation (GSR_BUF_COMPENSATIONS, re-read as the reference re-reads compensations[i]) and
+//   its cotangent; ∇add_blur is added to the 2-D covariance cotangent before anything reads it.  Depends on AA.
+template <bool AA>
 __device__ __forceinline__ ProjectBwd project_bwd(const GsrCam& cam, const M33& R, const float t[3], const float p[3],
                                                   const float4 q4, const float s[3], const GsrGeoRec& rec, const float4 a1,
-                                                  const float2 vm2, int channels, bool with_pose, float poseR[9],
-                                                  float poset[3]) {
+                                                  const float2 vm2, float rho, float vrho, int channels, bool with_pose,
+                                                  float poseR[9], float poset[3]) {
     ProjectBwd o;
     const float4 g0 = rec.q0, g1 = rec.q1;
     M22 Ci, vCi;
@@ -1096,6 +1124,17 @@ __device__ __forceinline__ ProjectBwd project_bwd(const GsrCam& cam, const M33& 
 #pragma unroll
         for (int b = 0; b < 2; b++) nC.m[a][b] = -Ci.m[a][b];
     M22 vS2 = mul22(mul22(nC, vCi), Ci);  // ∇inverse (render.jl:383-385)
+    if constexpr (AA) {
+        // ∇add_blur (render.jl:398-413).  The reference hands it the conic where its parameter is named Σ_2D_blur; the
+        // formula is the right one for the conic: vs ((1 - rho²) C - eps det(C) I).  rho == 0: finite (the 1e-6), times vrho = 0.
+        const float dc = Ci.m[0][0] * Ci.m[1][1] - Ci.m[0][1] * Ci.m[1][0];
+        const float vsq = 0.5f * vrho / (rho + 1e-6f);
+        const float ct = 1.0f - rho * rho;
+        vS2.m[0][0] = vS2.m[0][0] + vsq * (ct * Ci.m[0][0] - cam.blur_eps * dc);
+        vS2.m[1][0] = vS2.m[1][0] + vsq * ct * Ci.m[1][0];
+        vS2.m[0][1] = vS2.m[0][1] + vsq * ct * Ci.m[0][1];
+        vS2.m[1][1] = vS2.m[1][1] + vsq * (ct * Ci.m[1][1] - cam.blur_eps * dc);
+    }
     to_camera(R, t, p, o.mc);
     const float* mc = o.mc;
     const ForwardChain fc = forward_chain(R, mc, q4, s, cam);
@@ -1313,7 +1352,11 @@ __device__ __forceinline__ void store_or_apply_sh(int i, int n, int K, float* __
 // F32CHAIN (gsr_config.grad_precision = GSR_GRAD_FP32_REFERENCE): ∇scales / ∇rotations through the reference's own fp32
 // expression trees instead of the float64 chain — reference-parity runs; a template parameter, not a branch, so
 // that the default kernels are round 5's register for register.
-template <int DEG, bool FUSED, bool F32CHAIN = false>
+// AA (GSR_FLAG_ANTIALIASED): the row sum acc[3] is the cotangent of the EFFECTIVE opacity o * rho the forward put into the
+// record.  ∇opacity = acc[3] * rho is with respect to the caller's o; v rho = acc[3] * o goes through ∇add_blur into the 2-D
+// covariance cotangent of both chains (project_bwd, scales_rots_bwd_f64).  `comp` = the forward's compensations, `opac` = the
+// caller's opacities (FUSED: TS.opac_act): 8 more bytes per Gaussian.  A template parameter for the same reason.
+template <int DEG, bool FUSED, bool F32CHAIN = false, bool AA = false>
 __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int channels, const float* __restrict__ means,
                                                            const float* __restrict__ scales,
                                                            const float4* __restrict__ rots,
@@ -1323,7 +1366,9 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
                                                            float* __restrict__ vshs, float* __restrict__ vopac,
                                                            float* __restrict__ vscales, float4* __restrict__ vrots,
                                                            float* __restrict__ pose_part,
-                                                           float* __restrict__ vcolors, gsr::TailState TS) {
+                                                           float* __restrict__ vcolors, gsr::TailState TS,
+                                                           const float* __restrict__ opac,
+                                                           const float* __restrict__ comp) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     float poseR[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, poset[3] = {0, 0, 0};
     // The radius, the geometry record and the Gaussian's own inputs are all requested at once (the record and the
@@ -1334,6 +1379,7 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
     float p_in[3] = {0, 0, 0}, s_in[3] = {0, 0, 0};
     float4 q_in = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
     int radius_in = 0;
+    float o_in = 0.0f, rho_in = 0.0f;  // AA (comp[i] of a culled Gaussian is stale: read, never used)
     if (i < n) {
         radius_in = geom.radii[i];
         rec = geom.rec[i];
@@ -1344,6 +1390,10 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
         p_in[0] = mp[3 * i]; p_in[1] = mp[3 * i + 1]; p_in[2] = mp[3 * i + 2];
         s_in[0] = sp[3 * i]; s_in[1] = sp[3 * i + 1]; s_in[2] = sp[3 * i + 2];
         q_in = qp[i];
+        if constexpr (AA) {
+            o_in = FUSED ? TS.opac_act[i] : opac[i];
+            rho_in = comp[i];
+        }
     }
     const bool visible = radius_in > 0;
     // 1. the summed gradient row
@@ -1372,14 +1422,16 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
             const float4 a1 = make_float4(acc[4], acc[5], acc[6], acc[7]);
             const float2 vm2 = make_float2(acc[8], acc[9]);
             vmean2d_out[i] = vm2;  // gstate.∇means_2d, read by densification (strategy.jl:85-86)
-            if constexpr (FUSED) f_vopac = a0.w; else vopac[i] = a0.w;
+            const float vo = AA ? a0.w * rho_in : a0.w, vrho = AA ? a0.w * o_in : 0.0f;
+            if constexpr (FUSED) f_vopac = vo; else vopac[i] = vo;
             M33 R; float t[3];
             load_pose(cam, R, t);
             const float p[3] = {p_in[0], p_in[1], p_in[2]};
             const float4 q4 = q_in;
             const float s[3] = {s_in[0], s_in[1], s_in[2]};
             // 2. ∇project
-            const ProjectBwd pb = project_bwd(cam, R, t, p, q4, s, rec, a1, vm2, channels, pose_part != nullptr, poseR, poset);
+            const ProjectBwd pb = project_bwd<AA>(cam, R, t, p, q4, s, rec, a1, vm2, rho_in, vrho, channels, pose_part != nullptr,
+                                                  poseR, poset);
             // 3. the normal channel
             M33 vRg;
             normal_bwd(channels, acc, R, pb.Rg, s, pb.mc, vRg);
@@ -1389,7 +1441,7 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
             // reference's fp32 expression trees (gsr_config.grad_precision = GSR_GRAD_FP32_REFERENCE).
             float vs[3], vq[4];
             if constexpr (!F32CHAIN) {
-                scales_rots_bwd_f64(cam, R, t, p, q4, s, a1.x, a1.y, a1.z, vRg, vs, vq);
+                scales_rots_bwd_f64<AA>(cam, R, t, p, q4, s, a1.x, a1.y, a1.z, vRg, rho_in, vrho, vs, vq);
             } else {
                 // (inline, and pose partials below: as functions either takes instantiations of this kernel over their register
                 //  ceilings — profiles/pergauss_stages/codegen_compare.txt)
@@ -1625,7 +1677,7 @@ using gsr::dispatch_degree;
 // the form that ran (gsr_stats.preprocess_form = gsr_agg::form_code: the same number the policy announced).
 int gsr_launch_preprocess(hipStream_t s, int n, int K, int degree, int channels, const float* means,
                           const float* scales, const float* rots, const float* opac, const float* shs, GsrCam cam,
-                          GsrGeom geom, GsrTiles tiles, uint32_t* n_visible, GsrKeys keys, bool agg) {
+                          GsrGeom geom, GsrTiles tiles, uint32_t* n_visible, GsrKeys keys, bool agg, float* comp) {
     if (n <= 0) return 0;
     const float4* r4 = reinterpret_cast<const float4*>(rots);
     // The aggregating form keeps its counter words in LDS three times per CU: the whole grid up to ~21 500 tiles, bands of it
@@ -1635,20 +1687,23 @@ int gsr_launch_preprocess(hipStream_t s, int n, int K, int degree, int channels,
     const uint32_t* no_start = nullptr;
     dispatch_degree(degree, [&](auto d) {
         constexpr int DEG = d;
-        if (!agg) {
-            hipLaunchKernelGGL((preprocess_kernel<DEG, 0, false, false, false>), dim3((n + 255) / 256), dim3(256), 0, s, n, K,
-                               channels, means, scales, r4, opac, shs, cam, geom, tiles.count, n_visible, keys.bins, keys.cap,
-                               n_words, no_start, 1, cam.grid_y);
-            return;
-        }
-        dispatch_bool(pl.w32, [&](auto w) {
-            constexpr bool W32 = w;
-            dispatch_bool(pl.n_bands > 1, [&](auto b) {
-                constexpr bool BANDED = b;
-                hipLaunchKernelGGL((preprocess_kernel<DEG, kAggThreads, W32, false, BANDED>),
-                                   dim3((n + kAggThreads - 1) / kAggThreads), dim3(kAggThreads), pl.lds, s, n, K, channels,
-                                   means, scales, r4, opac, shs, cam, geom, tiles.count, n_visible, keys.bins, keys.cap, n_words,
-                                   no_start, pl.n_bands, pl.band_rows);
+        dispatch_bool(comp != nullptr, [&](auto a) {
+            constexpr bool AA = a;
+            if (!agg) {
+                hipLaunchKernelGGL((preprocess_kernel<DEG, 0, false, false, false, AA>), dim3((n + 255) / 256), dim3(256), 0, s, n,
+                                   K, channels, means, scales, r4, opac, shs, cam, geom, tiles.count, n_visible, keys.bins,
+                                   keys.cap, n_words, no_start, 1, cam.grid_y, comp);
+                return;
+            }
+            dispatch_bool(pl.w32, [&](auto w) {
+                constexpr bool W32 = w;
+                dispatch_bool(pl.n_bands > 1, [&](auto b) {
+                    constexpr bool BANDED = b;
+                    hipLaunchKernelGGL((preprocess_kernel<DEG, kAggThreads, W32, false, BANDED, AA>),
+                                       dim3((n + kAggThreads - 1) / kAggThreads), dim3(kAggThreads), pl.lds, s, n, K, channels,
+                                       means, scales, r4, opac, shs, cam, geom, tiles.count, n_visible, keys.bins, keys.cap,
+                                       n_words, no_start, pl.n_bands, pl.band_rows, comp);
+                });
             });
         });
     });
@@ -1675,7 +1730,7 @@ void gsr_launch_emit_compact(hipStream_t s, int n, GsrCam cam, GsrGeom geom, con
             constexpr bool BANDED = b;
             hipLaunchKernelGGL((preprocess_kernel<0, kAggThreads, W32, true, BANDED>), grid, block, pl.lds, s, n, 0, 3, nf,
                                nf, nq, nf, nf, cam, geom, tile_fill, (uint32_t*)nullptr, keys, only_above, n_words, tile_start,
-                               pl.n_bands, pl.band_rows);
+                               pl.n_bands, pl.band_rows, (float*)nullptr);
         });
     });
 }
@@ -1684,7 +1739,7 @@ void gsr_launch_pergauss_bwd(hipStream_t s, int n, int K, int degree, int channe
                              const float* scales, const float* rots, const float* shs, GsrCam cam, GsrGeom geom,
                              GsrInst inst, float2* vmean2d, float* vmeans, float* vshs, float* vopac,
                              float* vscales, float* vrots, float* vR, float* vt, float* pose_part, float* vcolors,
-                             bool fp32_chain) {
+                             bool fp32_chain, const float* opac, const float* comp) {
     if (n <= 0) return;
     dim3 grid((n + 255) / 256), block(256);
     const float4* r4 = reinterpret_cast<const float4*>(rots);
@@ -1694,15 +1749,19 @@ void gsr_launch_pergauss_bwd(hipStream_t s, int n, int K, int degree, int channe
         constexpr int DEG = d;
         dispatch_bool(fp32_chain, [&](auto f) {
             constexpr bool F32 = f;
-            hipLaunchKernelGGL((pergauss_bwd_kernel<DEG, false, F32>), grid, block, 0, s, n, K, channels, means, scales, r4,
-                               shs, cam, geom, inst, vmean2d, vmeans, vshs, vopac, vscales, vr4, vR ? pose_part : nullptr, vcolors, none);
+            dispatch_bool(comp != nullptr, [&](auto a) {
+                constexpr bool AA = a;
+                hipLaunchKernelGGL((pergauss_bwd_kernel<DEG, false, F32, AA>), grid, block, 0, s, n, K, channels, means, scales,
+                                   r4, shs, cam, geom, inst, vmean2d, vmeans, vshs, vopac, vscales, vr4,
+                                   vR ? pose_part : nullptr, vcolors, none, opac, comp);
+            });
         });
     });
     if (vR) hipLaunchKernelGGL(pose_final_kernel, dim3(1), dim3(256), 0, s, (int)grid.x, pose_part, vR, vt);
 }
 
 void gsr_launch_pergauss_bwd_tail(hipStream_t s, int n, int K, int degree, int channels, GsrCam cam, GsrGeom geom,
-                                  GsrInst inst, float2* vmean2d, const gsr::TailState& S, bool fp32_chain) {
+                                  GsrInst inst, float2* vmean2d, const gsr::TailState& S, bool fp32_chain, const float* comp) {
     if (n <= 0) return;
     dim3 grid((n + 255) / 256), block(256);
     const float4* r4 = reinterpret_cast<const float4*>(S.rots);
@@ -1711,9 +1770,12 @@ void gsr_launch_pergauss_bwd_tail(hipStream_t s, int n, int K, int degree, int c
         constexpr int DEG = d;
         dispatch_bool(fp32_chain, [&](auto f) {
             constexpr bool F32 = f;
-            hipLaunchKernelGGL((pergauss_bwd_kernel<DEG, true, F32>), grid, block, 0, s, n, K, channels, S.points,
-                               S.scales_act, r4, (const float*)nullptr, cam, geom, inst, vmean2d, no_f, no_f, no_f, no_f,
-                               (float4*)nullptr, no_f, no_f, S);
+            dispatch_bool(comp != nullptr, [&](auto a) {
+                constexpr bool AA = a;
+                hipLaunchKernelGGL((pergauss_bwd_kernel<DEG, true, F32, AA>), grid, block, 0, s, n, K, channels, S.points,
+                                   S.scales_act, r4, (const float*)nullptr, cam, geom, inst, vmean2d, no_f, no_f, no_f, no_f,
+                                   (float4*)nullptr, no_f, no_f, S, (const float*)nullptr, comp);
+            });
         });
     });
 }

@@ -95,7 +95,8 @@ class GaussianRasterizer:
     def __init__(self, width: int, height: int, mode: str = "rgbd", near_plane: float = 0.2,
                  far_plane: float = 1000.0, device="cuda", radius_clip: int = 3, blur_eps: float = 0.3,
                  exact_tile_cull: bool = True, bins_budget_bytes: int = 0, ssim_precision: Optional[str] = None,
-                 preprocess_form: Optional[str] = None, form_tuner: Optional[bool] = None, grad_precision: Optional[str] = None):
+                 preprocess_form: Optional[str] = None, form_tuner: Optional[bool] = None, grad_precision: Optional[str] = None,
+                 antialiased: bool = False):
         self.mode = mode
         self.channels = n_color_features(mode)
         self.width, self.height = int(width), int(height)
@@ -110,6 +111,11 @@ class GaussianRasterizer:
         # unchanged, only the internal lists (n_rendered, ranges, values_sorted, n_contrib positions) shrink.
         # False = GSR_FLAG_REFERENCE_TILE_LISTS: exactly the reference's lists (list-level parity checks).
         self.exact_tile_cull = bool(exact_tile_cull)
+        # antialiased (GSR_FLAG_ANTIALIASED; the Mip-Splatting 2-D filter, gsplat's rasterize_mode="antialiased"): every opacity
+        # is multiplied by add_blur's compensation sqrt(det S / det(S + blur_eps I)) of the view — the render IS the plain render
+        # of those effective opacities — and the backward returns the gradients of that image: ∇opacities w.r.t. the caller's
+        # opacity, the geometry gradients with the compensation's pullback.  `compensations` holds the factors.
+        self.antialiased = bool(antialiased)
         # The two behaviour switches are per handle (ABI 5), like the reference's constructor keywords
         # (rasterizer.jl:60-65): None = follow the process-wide default (gsr_ssim_precision / gsr_preprocess_form).
         #   ssim_precision : None | "fast" | "exact"   — arithmetic of the loss head on this rasterizer (fused_ssim.l1_ssim_loss)
@@ -134,7 +140,8 @@ class GaussianRasterizer:
         # always-state-keeping `rasterize` for callers of the manual rasterize / grad_rasterize pair
         self.forward_only_outside_ad = True
         cfg = L.Config(self.width, self.height, self.channels, self.near_plane, self.far_plane, int(radius_clip),
-                       float(blur_eps), 0 if exact_tile_cull else L.FLAG_REFERENCE_TILE_LISTS, int(bins_budget_bytes), sp, pf, ft, gp)
+                       float(blur_eps), (0 if exact_tile_cull else L.FLAG_REFERENCE_TILE_LISTS) |
+                       (L.FLAG_ANTIALIASED if self.antialiased else 0), int(bins_budget_bytes), sp, pf, ft, gp)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             L.check(self._lib.gsr_create(C.byref(cfg), C.byref(h)))
@@ -262,6 +269,18 @@ class GaussianRasterizer:
     def grad_means_2d(self):
         """gstate.∇means_2d (2,N) — valid after the backward"""
         return self.gstate.grad_means_2d
+
+    @property
+    def compensations(self):
+        """The reference's `compensations` (projection.jl:45) of the last forward, float (N), stale where radii == 0; None on a
+        rasterizer that is not antialiased, and while no forward is live."""
+        if not self.antialiased:
+            return None
+        p, sz = C.c_void_p(), C.c_size_t()
+        L.check(self._lib.gsr_buffer(self._h, L.BUF_COMPENSATIONS, C.byref(p), C.byref(sz)))
+        if not p.value:
+            return None
+        return self._buffer(L.BUF_COMPENSATIONS, torch.float32, (sz.value // 4,))
 
     @property
     def n_contrib(self):

@@ -116,6 +116,18 @@ enum { GSR_GRAD_FP32_REFERENCE = 1, GSR_GRAD_ACCURATE = 2 };
  * gsr_create rejects it with GSR_E_INVALID_ARG so that a caller built against the old header fails loudly instead of
  * silently getting the other list mode. */
 #define GSR_FLAG_RETIRED_BIT0 1u
+/* Antialiased rendering (the Mip-Splatting 2-D filter; the Inria code's `antialiasing`, gsplat's rasterize_mode="antialiased").
+ * The reference carries the mode dormant: add_blur returns compensation = sqrt(max(0, det S / det(S + blur_eps I)))
+ * (render.jl:387-396), project! / ∇project! take a `compensations` array (projection.jl:45,93,125,190-194), rasterize passes
+ * `nothing`.  With this flag every Gaussian's opacity is multiplied by its compensation of the view before anything reads it:
+ * the image, the lists and every side output are exactly those of the plain render of opacities o * compensation, so a splat
+ * the blur_eps dilation widened keeps the integrated contribution its 3-D Gaussian projects to.  Culling decisions that depend
+ * on the opacity see the product (a visible Gaussian whose effective opacity is below 1/255 emits no instance).  The
+ * compensations of the last forward are GSR_BUF_COMPENSATIONS.  The gradients gsr_backward / gsr_backward_trainer_tail return
+ * on such a handle are those of the ANTIALIASED image: vopacities is with respect to the caller's activated opacity (not the
+ * effective one), and vmeans / vscales / vrotations / vR / vt include the compensation's own pullback (∇add_blur,
+ * render.jl:398-413).  A per-handle mode like the other switches; no struct changed, GSR_ABI_VERSION stays. */
+#define GSR_FLAG_ANTIALIASED 4u
 
 /* ABI version of this header: bumped whenever a struct of this file changes size or a flag / enum value changes meaning.
  *   1: round-1 layout (flag bit 1u = exact tile cull, smaller gsr_config / gsr_aux / gsr_stats / gsr_grads)
@@ -219,6 +231,8 @@ typedef struct gsr_stats {
 /* Cotangents returned by `∇rasterize` (rasterizer.jl:549): caller-provided device
  * buffers, fully overwritten (culled Gaussians and SH bands above sh_degree get exact
  * zeros, projection.jl:172-176).  Gradients are w.r.t. the ACTIVATED opacity/scale.
+ * On a GSR_FLAG_ANTIALIASED handle they are the gradients of the antialiased image: vopacities is w.r.t. the caller's
+ * activated opacity, not the effective one (opacity x compensation), and the geometry gradients carry ∇add_blur.
  * vR/vt (pose optimisation, projection.jl:243-256) may be NULL. */
 typedef struct gsr_grads {
     float* vmeans;     /* (3,N) */
@@ -287,7 +301,7 @@ GSR_API int gsr_debug_check_guards(gsr_handle* h);
  * A call that has to REALLOCATE a buffer that already existed frees what the handle's last forward left in it, so it ENDS that
  * forward: until the next gsr_forward, gsr_backward / gsr_backward_trainer_tail / gsr_update_stats fail with GSR_E_STATE (before
  * any launch), gsr_buffer reports a null pointer and 0 bytes for the per-forward buffers (GSR_BUF_RADII, _GRAD_MEANS2D,
- * _VALUES_SORTED, _GEOM, _NORMALS, _GRAD_ROWS, _INSTANCE_AUX) and gsr_copy_buffer of any of their bytes fails with GSR_E_STATE.
+ * _VALUES_SORTED, _GEOM, _NORMALS, _GRAD_ROWS, _INSTANCE_AUX, _COMPENSATIONS) and gsr_copy_buffer of any of their bytes fails with GSR_E_STATE.
  * So reserve after gsr_update_stats, not between a forward and what reads it.  A call that reallocates nothing — sizes within
  * capacity, (0, 0), the first allocation of a buffer that did not exist, a repeat of an earlier call — leaves the forward live,
  * bit for bit.  The view history, the key bins and the loss head's scratch are not touched either way. */
@@ -362,11 +376,14 @@ enum {
     GSR_BUF_GRAD_ROWS = 8,     /* 12 (:rgb) or 16 x float per slot, Gaussian-major: the per-instance gradient rows of the last
                                 *   gsr_backward.  A Gaussian whose tile rect has at most 32 tiles owns one slot per tile it
                                 *   was binned into (in row-major tile order); larger rects one per tile of the rect */
-    GSR_BUF_INSTANCE_AUX = 9   /* 4 x 32-bit (D), sorted instance order (plane s2 of the splat stream):
+    GSR_BUF_INSTANCE_AUX = 9,  /* 4 x 32-bit (D), sorted instance order (plane s2 of the splat stream):
                                 *   [0] blue, [1] u32 Gaussian-major slot, [2] depth (:rgbd / :rgbdn) or, in :rgb mode, the u32 blend-test
                                 *   threshold X (bits(sigma) < X is the reference's blend test; 0: never blends), [3] u32 footprint masks
                                 *   (bits 0..15 tile rows, 16..19 8x8 quadrants the instance can touch; bit 20: the splat is a
                                 *   needle — 2-D axis ratio beyond 10 : 1 —, evaluated in the backward's accurate arithmetic) */
+    GSR_BUF_COMPENSATIONS = 10 /* float (N): the reference's `compensations` (projection.jl:45) of the last gsr_forward on a
+                                *   GSR_FLAG_ANTIALIASED handle, handle-owned, stale where radii == 0; the backward re-reads it.
+                                *   A handle without the flag has no such buffer: null pointer, 0 bytes */
 };
 GSR_API int gsr_buffer(const gsr_handle* h, int which, const void** dev_ptr, size_t* bytes);
 /* Copy of one of those buffers into caller memory, enqueued on `stream` by the library's own HIP

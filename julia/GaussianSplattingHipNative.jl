@@ -58,6 +58,8 @@ struct GsrCamera
     R_dev::Ptr{Float32}; t_dev::Ptr{Float32}
 end
 struct GsrAux; covisibilities::Ptr{UInt8}; uncertainties::Ptr{Float32}; radii::Ptr{Int32}; flags::UInt32; reserved::UInt32; end
+const GSR_FLAG_ANTIALIASED = 0x00000004          # gsr_config.flags: opacity x add_blur's compensation, forward and backward
+const GSR_BUF_COMPENSATIONS = Int32(10)          # gsr_buffer id: Float32 (N), the reference's `compensations` of the last forward
 const GSR_FORWARD_ONLY = 0x00000001  # gsr_aux.flags: this forward will not be differentiated (no backward state kept)
 struct GsrStats
     n_rendered::Int64; n_visible::Int32; max_tile_instances::Int32; generation::UInt64
@@ -118,7 +120,7 @@ native(rast::GaussianRasterizer) = lock(() -> get(NATIVE, rast, nothing), NATIVE
 
 """
     enable_hip_native!(rast; reference_tile_lists=false, forward_only_outside_ad=true, ssim_exact=nothing, preprocess_form=nothing,
-                       form_tuner=nothing, grad_precision=:default)
+                       form_tuner=nothing, grad_precision=:default, antialiased=false)
 
 Route `rasterize` / `∇rasterize` on this rasterizer through libgsr_hip.so.  Width / height / mode / near / far
 are the rasterizer's own (rasterizer.jl:60-90).  `forward_only_outside_ad`: a `rasterize` that is not being
@@ -131,17 +133,23 @@ way).  `grad_precision` (`:default` | `:accurate` | `:fp32_reference`): the back
 `:accurate` = libm exp + IEEE division per pixel (+12 % of ∇render!; ∇means of a 90 : 1 needle 4e-4 -> 2e-5 from float64),
 `:fp32_reference` = that and ∇scales / ∇rotations by the reference's own fp32 expression trees (projection.jl:132-257,
 render.jl:302-366) instead of the library's float64 chain — for reference-parity runs.
+`antialiased` (GSR_FLAG_ANTIALIASED): the Mip-Splatting 2-D filter the reference carries dormant — every opacity is multiplied by
+`add_blur`'s compensation (render.jl:387-396) of the view, and `∇rasterize` returns the gradients of that image (∇opacities with
+respect to the caller's opacity; ∇means / ∇scales / ∇rotations / the pose with `∇add_blur`, render.jl:398-413).  The factors of
+the last forward are the handle's buffer `GSR_BUF_COMPENSATIONS`.
 Returns `rast`.
 """
 function enable_hip_native!(rast::GaussianRasterizer; reference_tile_lists::Bool = false, forward_only_outside_ad::Bool = true,
                             ssim_exact::Union{Nothing, Bool} = nothing, preprocess_form::Union{Nothing, Integer} = nothing,
-                            form_tuner::Union{Nothing, Bool} = nothing, grad_precision::Symbol = :default)
+                            form_tuner::Union{Nothing, Bool} = nothing, grad_precision::Symbol = :default,
+                            antialiased::Bool = false)
     native(rast) === nothing || return rast
     check_abi()
     c, w, h = size(rast.image)
     href = Ref{Ptr{Cvoid}}()
     check(ccall((:gsr_create, LIB), Cint, (Ref{GsrConfig}, Ref{Ptr{Cvoid}}),
-        GsrConfig(w, h, c, rast.near_plane, rast.far_plane, 3, 0.3f0, reference_tile_lists ? 0x2 : 0x0, 0,
+        GsrConfig(w, h, c, rast.near_plane, rast.far_plane, 3, 0.3f0,
+                  UInt32(reference_tile_lists ? 0x2 : 0x0) | (antialiased ? GSR_FLAG_ANTIALIASED : 0x00000000), 0,
                   # ABI 6: 0 = default, 1 / 2 the explicit choices
                   ssim_exact === nothing ? Int32(0) : Int32(ssim_exact ? 2 : 1),
                   preprocess_form === nothing ? Int32(0) : Int32(preprocess_form != 0 ? 2 : 1),

@@ -79,6 +79,7 @@ class Protocol:
                                       # the reference's own fp32 expression trees (what an oracle-chain comparison runs with: an
                                       # isotropic Gaussian's rotation gradient is then EXACTLY zero on both sides, where the float64
                                       # chain leaves 1e-17-level noise that NU.Adam's eps = 1e-15 turns into visible steps)
+    antialiased: bool = False         # GaussianRasterizer(antialiased=True): the training handle renders with the opacity compensation
     init_jitter: float = 0.01
     init_color_noise: float = 0.05
     torch_pool_gb: int = 8            # device memory the harness takes from the driver ONCE, up front, and hands to torch's caching
@@ -193,7 +194,7 @@ class Harness:
             self.focal = (float(np.float32(fx)), float(np.float32(fx)))
         self.cams = [pkg.Camera(W, H, self.focal, (0.5, 0.5), Rm, t) for Rm, t in self.poses]
         self.rast = R.GaussianRasterizer(W, H, mode=p.mode, device=self.dev, bins_budget_bytes=p.bins_budget_bytes,
-                                         grad_precision=p.grad_precision)
+                                         grad_precision=p.grad_precision, antialiased=p.antialiased)
         if p.torch_pool_gb and torch.cuda.memory_reserved(self.dev) < (p.torch_pool_gb << 30):
             pool = [torch.empty(1 << 30, dtype=torch.uint8, device=self.dev) for _ in range(p.torch_pool_gb)]
             del pool
@@ -527,9 +528,11 @@ if __name__ == "__main__":
     ap.add_argument("--from-iter", type=int, default=500)
     ap.add_argument("--ply", default=None)
     ap.add_argument("--history-out", default=None, help="write the per-view history (tests/golden/train_history.json format)")
+    ap.add_argument("--antialiased", action="store_true", help="train on an antialiased rasterizer (GSR_FLAG_ANTIALIASED)")
     a = ap.parse_args()
     pr = Protocol(width=a.width, height=a.height, mode=a.mode, n_gt=a.n_gt, n_init=a.n_init, n_views=a.views,
-                  densify_grad_threshold=a.grad_threshold, densification_interval=a.interval, densify_from_iter=a.from_iter)
+                  densify_grad_threshold=a.grad_threshold, densification_interval=a.interval, densify_from_iter=a.from_iter,
+                  antialiased=a.antialiased)
     rec, hh = protocol_run(gsr_pkg.load(), pr, a.warmup, a.steps, ply_out=a.ply, verbose=True)
     print(json.dumps(rec))
     if a.history_out:
