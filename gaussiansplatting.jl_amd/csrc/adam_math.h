@@ -1,7 +1,7 @@
 // The NU.Adam update and the per-Gaussian part of the trainer tail, shared by the stand-alone tail
-// kernels (trainer.hip) and the backward kernel that applies the tail in its epilogue (pergauss.hip):
-// ONE definition of every expression, so the fused and the unfused step give the same bits.
-// Both translation units are compiled with -ffp-contract=off.
+// kernels (trainer.hip), the backward kernel that applies the tail in its epilogue (pergauss.hip) and the
+// multi-view SH tail (sh_views.hip): ONE definition of every expression, so the fused and the unfused step
+// give the same bits.  All three translation units are compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 

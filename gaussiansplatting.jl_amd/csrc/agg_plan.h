@@ -1,4 +1,4 @@
-// The aggregating binning form's LDS plan — shared by the kernels' launcher (pergauss.hip) and the GPU-free policy layer
+// The aggregating binning form's LDS plan — shared by the kernels' launcher (preprocess.hip) and the GPU-free policy layer
 // (gsr_policy.cpp), so that the form the policy announces is the form the launcher runs.  Plain C++, no HIP.
 #pragma once
 #include <stddef.h>

@@ -4,7 +4,7 @@
 // per-tile LDS sort.
 //
 //   preprocess     : each visible Gaussian drops (depth_bits<<32 | id) into the bins of its
-//                    tiles (returning atomics on the tile counters; pergauss.hip)
+//                    tiles (returning atomics on the tile counters; preprocess.hip)
 //   tile_scan      : exclusive scan over the T tile counts  -> tile ranges, D, max count
 //   tile_sort      : one workgroup per tile sorts its bin in LDS by (depth, id) and writes
 //                    the sorted ids plus the packed, sorted splat stream the composite

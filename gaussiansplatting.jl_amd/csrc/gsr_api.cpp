@@ -360,7 +360,7 @@ int gsr_create(const gsr_config* cfg, gsr_handle** out) {
     h->cfg = *cfg;
     h->grid_x = (cfg->width + GSR_TILE - 1) / GSR_TILE;
     h->grid_y = (cfg->height + GSR_TILE - 1) / GSR_TILE;
-    // (8 192 tiles = 131 072 pixels wide: one row of the tile grid must fit the aggregating binning's LDS band, pergauss.hip)
+    // (8 192 tiles = 131 072 pixels wide: one row of the tile grid must fit the aggregating binning's LDS band, preprocess.hip)
     if (h->grid_x > 8192 || h->grid_y > 65535) { delete h; return fail(GSR_E_INVALID_ARG, "resolution too large"); }
     h->n_tiles = h->grid_x * h->grid_y;
     // the handle's policies: configuration (constructor fields, then the tuner's process default) and the view-history state

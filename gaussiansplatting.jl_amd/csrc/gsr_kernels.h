@@ -32,10 +32,10 @@ struct GsrCam {
 //   q2 = b, clamped bits (u32), depth, lpre (u32: exclusive prefix of tile-rect areas inside the
 //        Gaussian's 256-wide block; + bpre[i >> 8] = Gaussian-major slot of its first instance)
 //   q3 = rect xmin | ymin << 16, rect xmax | ymax << 16 (u32), blend-test threshold bits X (u32, tile_mask.h),
-//        emitted-tile mask of the rect (u32, row-major bit per tile; meaningful for rects of <= 32 tiles: pergauss.hip DENSE_RECT)
+//        emitted-tile mask of the rect (u32, row-major bit per tile; meaningful for rects of <= 32 tiles: preprocess.hip DENSE_RECT)
 struct GsrGeoRec { float4 q0, q1, q2, q3; };
 // Tile rects of at most this many tiles get one gradient-row slot per EMITTED tile (ranked through the record's mask);
-// larger ones one per tile of the rect (pergauss.hip: preprocess, pergauss_bwd; tile_sort_device.h: the emit's slot).
+// larger ones one per tile of the rect (preprocess.hip: preprocess; pergauss.hip: pergauss_bwd; tile_sort_device.h: the emit's slot).
 constexpr uint32_t GSR_DENSE_RECT = 32;
 struct GsrGeom {
     GsrGeoRec* rec;
@@ -99,7 +99,7 @@ struct GsrFrame {
     uint8_t* covis; float* uncert;  // gsr_aux.covisibilities / uncertainties, or NULL
 };
 
-// ---- pergauss.hip (compiled with -ffp-contract=off: bit-reproducible fp32) ----
+// ---- preprocess.hip (compiled with -ffp-contract=off: bit-reproducible fp32) ----
 // aggregating: the binning form gsr_policy_begin_view chose for this view (false = the direct form);
 // returns the form that ran (gsr_stats.preprocess_form: 0 direct, 1 / 2 aggregating with 2 x 32 / 2 x 16-bit LDS words, 3 banded)
 int gsr_launch_preprocess(hipStream_t s, int n, int K, int degree, int channels, const float* means,
@@ -114,6 +114,8 @@ struct GsrBg8 { float v[8]; };
 // segments of `keys` and their fill cursors are not touched
 void gsr_launch_emit_compact(hipStream_t s, int n, GsrCam cam, GsrGeom geom, const uint32_t* tile_start, uint32_t* tile_fill,
                              uint64_t* keys, uint32_t max_list /* longest tile list of the view */, uint32_t only_above);
+
+// ---- pergauss.hip (-ffp-contract=off) ----
 // per-workgroup partials of the pose gradient (12 floats per 256 Gaussians), summed in a fixed order by a finishing launch
 inline size_t gsr_pose_partial_floats(int64_t n) { return n <= 0 ? 0 : (size_t)((n + 255) / 256) * 12; }
 void gsr_launch_pergauss_bwd(hipStream_t s, int n, int K, int degree, int channels, const float* means,
@@ -131,15 +133,16 @@ namespace gsr { struct TailState; }
 void gsr_launch_pergauss_bwd_tail(hipStream_t s, int n, int K, int degree, int channels, GsrCam cam, GsrGeom geom,
                                   GsrInst inst, float2* vmean2d, const gsr::TailState& S, bool fp32_chain,
                                   const float* comp /* antialiased handle (the opacities are S.opac_act), or NULL */);
+void gsr_launch_update_stats(hipStream_t s, int n, const int32_t* radii, const float2* vmean2d, int width, int height,
+                             int32_t* max_radii, float* accum, float* denom);
+
+// ---- sh_views.hip (-ffp-contract=off) ----
 void gsr_launch_sh_grad_views(hipStream_t s, int n, int K, int degree, int n_views, const float* centers,
                               const float* means, const float* vc_all, float* vshs);
 // the same rebuild with the trainer tail applied in place of the ∇shs store (multi-GPU trainer step; S.points = the means)
 void gsr_launch_sh_views_tail(hipStream_t s, int n, int K, int degree, int n_views, const float* centers,
                               const float* vc_all, const float* vmeans, const float* vopac_act, const float* vscales_act,
                               const float* vrot, const gsr::TailState& S);
-
-void gsr_launch_update_stats(hipStream_t s, int n, const int32_t* radii, const float2* vmean2d, int width, int height,
-                             int32_t* max_radii, float* accum, float* denom);
 
 // ---- binning.hip ----
 // exclusive scan of tiles.count -> tiles.start[T+1], and of the per-block rect-area sums geom.bsum[n_blocks] -> geom.bpre;

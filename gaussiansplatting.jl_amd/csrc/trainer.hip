@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamGroups G, float beta1, fl
 // writes), the chain rule of the prologue is applied in registers, the six NU.Adam states are
 // advanced, and the activated copies the next rasterize() consumes are written straight away.
 // Same fp32 expression trees as the three separate kernels (bit-identical θ, μ, ν).
-// (AdamHyper, adam_update and the per-Gaussian block live in adam_math.h, shared with pergauss.hip)
+// (AdamHyper, adam_update and the per-Gaussian block live in adam_math.h, shared with pergauss.hip and sh_views.hip)
 // SH block: one thread per coefficient float of shs (N x 3K); element j of a Gaussian's row
 // belongs to sh_color (j < 3) or sh_remainder — two optimizers, two learning rates.
 __global__ __launch_bounds__(256) void tail_sh_kernel(size_t total, int K3, const float* __restrict__ vshs,

@@ -4,7 +4,7 @@ torch's caching allocator rounds every request up to 512 bytes inside a segment 
 a few elements past an array neither faults nor, as a rule, changes a compared value.  The callers of include/gsr.h pack their
 arrays differently.  Here every case runs FIVE times on identical inputs — plain (each buffer its own torch allocation, as the
 rest of the suite), and the two placements ("aligned": 16-byte aligned data pointers, the vector paths; "worst": the weakest
-alignment the interface allows, the scalar paths of pergauss.hip / trainer.hip) times the two guard fills — and asserts
+alignment the interface allows, the scalar paths of sh_rows.h / trainer.hip) times the two guard fills — and asserts
   1. every call returns GSR_OK;
   2. no guard word changed (a store outside an array);
   3. every output, in-place buffer and returned scalar is bit-identical in all five runs (a load outside an array follows the
@@ -356,7 +356,7 @@ def test_trainer_tail_step(pkg, n, k_rest, sd):
 @pytest.mark.parametrize("mode,n,wh,k_rest,deg", [("rgb", 257, (55, 33), 3, 1), ("rgbd", 1031, (130, 70), 15, 2), ("rgbdn", 65, (55, 33), 0, 0)])
 def test_backward_trainer_tail(pkg, mode, n, wh, k_rest, deg):
     """The fused step with θ, μ, ν of the six groups and the activated copies at 4 mod 16 (rotations at 16 mod 32, as the
-    interface demands): the scalar branches of tail_sh_group and store_sh_rows (pergauss.hip)."""
+    interface demands): the scalar branches of tail_sh_group and store_sh_rows (sh_rows.h)."""
     L, lib = pkg._lib, pkg._lib.load()
     (W, H), Cn, K = wh, CH[mode], k_rest + 1
     s = pkg.synthetic.make_scene(n, W, H, deg, 500 + n, sigma_px=5.0, K=K)

@@ -364,7 +364,7 @@ NAMED |= {main_bwd(3, False, None, False)}
 @pytest.mark.parametrize("prec", [None, "accurate"])
 def test_large_rects_under_exact_cull(pkg, orc, prec):
     """Footprints of more than GSR_DENSE_RECT (32) tiles under exact culling: one row slot per tile of the rect, the culled
-    tiles' slots never written nor read (pergauss.hip)."""
+    tiles' slots never written nor read (preprocess.hip, pergauss.hip)."""
     sc = make(pkg, orc, "rgb", 1500, 320, 208, 1, 61, (0.1, 0.2, 0.3), sigma_px=45.0, view=0)
     vp = np.random.default_rng(3).standard_normal((sc.H, sc.W, 3)).astype(np.float32)
     st, g = oracle(orc, sc, vp)

@@ -24,7 +24,7 @@ from test_gpu_preprocess_forms import form
 
 pytestmark = pytest.mark.gpu
 
-FLAT_MAX, DENSE_RECT, EMIT_COOP = 16, 32, 48   # csrc/pergauss.hip, gsr_kernels.h
+FLAT_MAX, DENSE_RECT, EMIT_COOP = 16, 32, 48   # csrc/preprocess.hip, gsr_kernels.h
 N, DEGREES, SIGMA_PX, BG = 3000, (0, 1, 3), 9.0, (0.1, 0.3, 0.2)
 SCENES = {"odd_21x13": (328, 200, 5100), "even_20x12": (320, 192, 5101)}
 CELLS = {"direct": (0, 0), "aggregating": (1, 0), "compact": (1, 1)}   # (gsr_preprocess_form, bins_budget_bytes)
