@@ -110,6 +110,7 @@ class DepthAnchorS(C.Structure):  # gsr_depth_anchor
 
 
 COMPOSE_MAX_GROUPS = 24
+FILTER3D_CAMERA_FLOATS = 22  # GSR_FILTER3D_CAMERA_FLOATS: one row of gsr_filter3d_compute's camera table
 DENSIFY_CLONE, DENSIFY_SPLIT, DENSIFY_PRUNE = 0, 1, 2
 
 
@@ -191,6 +192,7 @@ EXPORTS = ["gsr_create", "gsr_destroy", "gsr_release_scene_buffers", "gsr_memory
            "gsr_backward_trainer_tail",
            "gsr_densify_grad_mean", "gsr_densify_mask", "gsr_compose_rows", "gsr_split_transform", "gsr_reset_opacity", "gsr_morton_codes",
            "gsr_knn_scratch_bytes", "gsr_knn_scales",
+           "gsr_filter3d_scratch_bytes", "gsr_filter3d_compute", "gsr_filter3d_apply", "gsr_filter3d_apply_backward",
            "gsr_ply_pack_rows", "gsr_ply_unpack_rows", "gsr_count_nonfinite",
            "gsr_bilateral_scratch_bytes", "gsr_bilateral_tv_scratch_bytes", "gsr_bilateral_slice_forward",
            "gsr_bilateral_slice_backward", "gsr_bilateral_tv", "gsr_bilateral_adam_tail",
@@ -276,6 +278,11 @@ def load():
     lib.gsr_knn_scratch_bytes.argtypes = [i64]
     lib.gsr_knn_scratch_bytes.restype = C.c_size_t
     lib.gsr_knn_scales.argtypes = [i64, vp, vp, f32, C.c_int32, vp, vp, vp, C.c_size_t, vp]
+    lib.gsr_filter3d_scratch_bytes.argtypes = [i64]
+    lib.gsr_filter3d_scratch_bytes.restype = C.c_size_t
+    lib.gsr_filter3d_compute.argtypes = [i64, vp, C.c_int32, vp, f32, f32, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.gsr_filter3d_apply.argtypes = [i64, vp, vp, vp, C.c_int32, vp, vp, vp]
+    lib.gsr_filter3d_apply_backward.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.gsr_count_nonfinite.argtypes = [C.POINTER(vp), C.POINTER(C.c_int32), C.c_int32, i64, vp, vp, vp]
     lib.gsr_ply_pack_rows.argtypes = [i64, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.gsr_ply_unpack_rows.argtypes = [i64, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -336,3 +336,12 @@ void gsr_launch_frame_rgb8(hipStream_t s, int W, int H, int C, const float* imag
 size_t gsr_knn_scratch_size(long long n);
 void gsr_launch_knn_scales(hipStream_t s, long long n, const float* points, const int32_t* order, float point_size,
                            int scale_dims, float* scales_out, float* dist2_out, void* scratch);
+
+// ---- filter3d.hip (compiled with -ffp-contract=off): the 3-D smoothing filter — camera sweep, apply and its pullback ----
+size_t gsr_filter3d_scratch_size(long long n);
+void gsr_launch_filter3d_compute(hipStream_t s, long long n, const float* points, int n_cameras, const float* cams,
+                                 float near_plane, float k, float* filter, uint8_t* seen, uint32_t* count, void* scratch);
+void gsr_launch_filter3d_apply(hipStream_t s, long long n, const float* opac, const float* scales, const float* filter, int raw,
+                               float* opac_out, float* scales_out);
+void gsr_launch_filter3d_apply_bwd(hipStream_t s, long long n, const float* opac, const float* scales, const float* filter,
+                                   const float* g_opac, const float* g_scales, float* v_opac, float* v_scales);

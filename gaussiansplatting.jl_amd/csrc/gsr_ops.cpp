@@ -1,7 +1,7 @@
 // C ABI of libgsr_hip.so (include/gsr.h), the part without a handle: every entry point that checks its arguments, launches
 // its kernels on the caller's stream and keeps nothing — planar SSIM, the trainer's prologue / Adam / tail, row gathers, the
 // bilateral grid, the geometry, depth and sky losses, the evaluation head, the geometry frames, densification, MCMC, Morton
-// codes, k-NN, PLY rows, the multi-view SH gradient, the all-reduce.  (The handle and its launch choreography are gsr_api.cpp's.)
+// codes, k-NN, the 3-D smoothing filter, PLY rows, the multi-view SH gradient, the all-reduce.  (The handle and its launch choreography are gsr_api.cpp's.)
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -717,6 +717,56 @@ int gsr_knn_scales(int64_t n, const float* points, const int32_t* order, float p
     if (scratch_bytes < need) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: scratch_bytes = %zu, the search needs %zu", scratch_bytes, need);
     if ((uintptr_t)scratch % 16) return fail(GSR_E_INVALID_ARG, "gsr_knn_scales: scratch must be 16-byte aligned");
     gsr_launch_knn_scales((hipStream_t)stream, n, points, order, point_size, scale_dims, scales_out, dist2_out, scratch);
+    return launched();
+}
+
+// ---- the 3-D smoothing filter: camera sweep, apply, pullback (filter3d.hip; Mip-Splatting §4.1) ----
+static int check_filter3d_rows(int64_t n) {
+    if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
+    if (n > 0x7FFFFFFFll) return fail(GSR_E_INVALID_ARG, "n = %lld: rows are indexed with 31 bits", (long long)n);
+    return GSR_OK;
+}
+
+size_t gsr_filter3d_scratch_bytes(int64_t n) {
+    if (n <= 0 || n > 0x7FFFFFFFll) return 0;
+    return gsr_filter3d_scratch_size(n);
+}
+
+int gsr_filter3d_compute(int64_t n, const float* points, int32_t n_cameras, const float* camera_table, float near_plane, float k,
+                         float* filter, uint8_t* seen, uint32_t* count, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc;
+    if ((rc = check_filter3d_rows(n))) return rc;
+    if (n_cameras < 1) return fail(GSR_E_INVALID_ARG, "n_cameras = %d: the sweep needs at least one camera", n_cameras);
+    if (!(near_plane >= 0.0f) || !(k >= 0.0f))
+        return fail(GSR_E_INVALID_ARG, "near_plane = %g, k = %g: neither may be negative or NaN", (double)near_plane, (double)k);
+    if (n == 0) return GSR_OK;
+    if (!points || !camera_table || !filter || !scratch) return fail(GSR_E_INVALID_ARG, "null points, camera_table, filter or scratch");
+    if ((rc = check_scratch(scratch_bytes, gsr_filter3d_scratch_bytes(n), "camera sweep"))) return rc;
+    if ((uintptr_t)scratch % 8) return fail(GSR_E_INVALID_ARG, "scratch must be 8-byte aligned");
+    gsr_launch_filter3d_compute((hipStream_t)stream, n, points, n_cameras, camera_table, near_plane, k, filter, seen, count, scratch);
+    return launched();
+}
+
+int gsr_filter3d_apply(int64_t n, const float* opacities_act, const float* scales_act, const float* filter, int32_t raw,
+                       float* opacities_out, float* scales_out, void* stream) {
+    int rc;
+    if ((rc = check_filter3d_rows(n))) return rc;
+    if (n == 0) return GSR_OK;
+    if (!opacities_act || !scales_act || !filter || !opacities_out || !scales_out) return fail(GSR_E_INVALID_ARG, "null array");
+    if (opacities_out == opacities_act || scales_out == scales_act) return fail(GSR_E_INVALID_ARG, "the outputs must not be the inputs");
+    gsr_launch_filter3d_apply((hipStream_t)stream, n, opacities_act, scales_act, filter, raw != 0, opacities_out, scales_out);
+    return launched();
+}
+
+int gsr_filter3d_apply_backward(int64_t n, const float* opacities_act, const float* scales_act, const float* filter,
+                                const float* g_opacities, const float* g_scales, float* v_opacities, float* v_scales, void* stream) {
+    int rc;
+    if ((rc = check_filter3d_rows(n))) return rc;
+    if (n == 0) return GSR_OK;
+    if (!opacities_act || !scales_act || !filter || !g_opacities || !g_scales || !v_opacities || !v_scales)
+        return fail(GSR_E_INVALID_ARG, "null array");
+    gsr_launch_filter3d_apply_bwd((hipStream_t)stream, n, opacities_act, scales_act, filter, g_opacities, g_scales, v_opacities,
+                                  v_scales);
     return launched();
 }
 

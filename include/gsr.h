@@ -632,6 +632,57 @@ GSR_API size_t gsr_knn_scratch_bytes(int64_t n);
 GSR_API int gsr_knn_scales(int64_t n, const float* points, const int32_t* order, float point_size, int32_t scale_dims,
                            float* scales_out, float* dist2_out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* The 3-D smoothing filter of Mip-Splatting (Yu et al., CVPR 2024, §4.1): the world-space companion of
+ * GSR_FLAG_ANTIALIASED.  Every Gaussian is low-pass filtered by the highest rate at which any training camera samples it;
+ * the filter is folded into the ACTIVATED scales and opacities in front of gsr_forward.  No handle, no struct, nothing read
+ * back to the host.  Arrays are device, contiguous float32 unless stated.
+ *
+ * gsr_filter3d_compute: the sweep of n points against n_cameras cameras, redone when the points change (after every
+ * densification round).  camera_table: n_cameras rows of GSR_FILTER3D_CAMERA_FLOATS floats,
+ *     R[9] (column-major) t[3]   as in gsr_camera
+ *     focal[2]
+ *     pp[2]    = principal · resolution
+ *     lo[2]    = -margin · resolution         hi[2] = (1 + margin) · resolution
+ *     inv_f    = 1 / max(focal)
+ *     one pad word
+ * Per point p and camera v, every operation ONE rounded fp32 operation in this association:
+ *     xc[i] = ((R[i]*p0 + R[i+3]*p1) + R[i+6]*p2) + t[i]     i = 0,1,2 ;  z = xc[2]
+ *     u[j]  = focal[j]*xc[j] + pp[j]*z                         j = 0,1
+ *     valid = (z > near_plane) && (lo[j]*z <= u[j]) && (u[j] <= hi[j]*z) for both j      (any NaN: not valid)
+ *     tau   = z * inv_f
+ *     tmin(p) = min of tau over the valid cameras ;  seen(p) = some camera is valid
+ *     filter(p) = k * tmin(p) where seen(p), else the maximum of filter over the seen points (0 when no point is seen)
+ * — the paper's highest sampling rate max_v focal_v / depth_v, inverted; k = sqrt(variance), 0.2 in the paper.  Minimum and
+ * maximum are exact in any order: the output is the same bits in every run.
+ *   filter : (n), fully overwritten.      seen : (n) bytes, 1 / 0, or NULL.      count : one uint32, the seen points, or NULL.
+ *   scratch: gsr_filter3d_scratch_bytes(n) bytes (1 per point, 8 per 1024 points, 8 more), 8-byte aligned.
+ * GSR_E_INVALID_ARG: n < 0 or n >= 2^31, n_cameras < 1, near_plane or k negative or NaN, a null points / camera_table /
+ * filter / scratch, scratch_bytes too small, a misaligned scratch.  n == 0: GSR_OK, nothing is launched.
+ *
+ * gsr_filter3d_apply: opacities_act (n), scales_act (n,3) — what gsr_prologue_forward wrote, scales > 0 — and filter (n) to
+ *     f2 = f*f ;  se[i] = sqrtf(s[i]*s[i] + f2) ;  r[i] = s[i] / se[i] ;  c = (r[0]*r[1])*r[2] ;  o_eff = o * c
+ * in scales_out / opacities_out (other arrays than the inputs).  c = sqrt(det S / det(S + f2 I)) of the paper, as a product
+ * of ratios that cannot underflow for small scales; o_eff · Π se = o · Π s.  A row with f == 0 passes through bit for bit.
+ * raw != 0: logf(se[i]) and logit(o_eff) instead, the values a .ply stores — an exported model renders filtered in any
+ * viewer.  (1 - o_eff is formed as (1 - o) + o·(1 - c), 1 - c from 1 - r[i] = f2 / (se[i]·(se[i] + s[i])): no cancellation.)
+ *
+ * gsr_filter3d_apply_backward: the pullback, the filter a constant.  g_opacities (n) / g_scales (n,3): the cotangents
+ * w.r.t. the EFFECTIVE values, as gsr_backward wrote them;
+ *     vo = g_o * c ;  vs[i] = g_s[i]*r[i] + ((g_o*o)*P[i]) * (f2 / ((se[i]*se[i])*se[i])),  P[i] = product of the other two r
+ * w.r.t. the activated values, for gsr_prologue_backward / gsr_trainer_tail_step.  v_opacities / v_scales may be
+ * g_opacities / g_scales (in place).  The fused gsr_backward_trainer_tail cannot carry this step: a filtered training step
+ * runs gsr_backward + gsr_filter3d_apply_backward + gsr_trainer_tail_step, as with gsr_flatten_loss. */
+#define GSR_FILTER3D_CAMERA_FLOATS 22
+GSR_API size_t gsr_filter3d_scratch_bytes(int64_t n);
+GSR_API int gsr_filter3d_compute(int64_t n, const float* points, int32_t n_cameras, const float* camera_table, float near_plane,
+                                 float k, float* filter, uint8_t* seen, uint32_t* count, void* scratch, size_t scratch_bytes,
+                                 void* stream);
+GSR_API int gsr_filter3d_apply(int64_t n, const float* opacities_act, const float* scales_act, const float* filter, int32_t raw,
+                               float* opacities_out, float* scales_out, void* stream);
+GSR_API int gsr_filter3d_apply_backward(int64_t n, const float* opacities_act, const float* scales_act, const float* filter,
+                                        const float* g_opacities, const float* g_scales, float* v_opacities, float* v_scales,
+                                        void* stream);
+
 /* The non-finite gradient guard of `step!` under GSP_DEBUG (src/training.jl:772-777: `isfinite(sum(∇ᵢ))` per parameter)
  * and the per-parameter counts of `nonfinite_gradient_report` (:534-552), in one pass over up to GSR_ADAM_MAX_GROUPS
  * gradient arrays of n_rows Gaussians each (rows of row_words floats; row_words = 0 skips an empty array):
