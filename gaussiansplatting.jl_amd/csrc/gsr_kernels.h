@@ -345,3 +345,23 @@ void gsr_launch_filter3d_apply(hipStream_t s, long long n, const float* opac, co
                                float* opac_out, float* scales_out);
 void gsr_launch_filter3d_apply_bwd(hipStream_t s, long long n, const float* opac, const float* scales, const float* filter,
                                    const float* g_opac, const float* g_scales, float* v_opac, float* v_scales);
+
+// ---- tsdf.hip (compiled with -ffp-contract=off): TSDF fusion of a rendered frame, surface-nets count and emit ----
+// the volume: nx x ny x nz samples, sample (i, j, k) at o + h*(i, j, k)
+struct GsrTsdfGrid {
+    int nx, ny, nz;
+    float o[3];
+    float h;
+};
+// world->camera R (column-major as in the ABI) and t, the focal lengths, the principal point in pixels
+struct GsrTsdfCam {
+    float R[9];
+    float t[3];
+    float fx, fy, cx, cy;
+};
+size_t gsr_mesh_scratch_size(int nx, int ny, int nz);
+void gsr_launch_tsdf_integrate(hipStream_t s, const GsrTsdfGrid& g, const GsrTsdfCam& c, int W, int H, int C, const float* image,
+                               float min_alpha, float near_plane, float trunc, float* volume, float* color);
+void gsr_launch_mesh_count(hipStream_t s, const GsrTsdfGrid& g, const float* volume, uint32_t* counts, void* scratch);
+void gsr_launch_mesh_emit(hipStream_t s, const GsrTsdfGrid& g, const float* volume, const float* color, const void* scratch,
+                          long long max_vertices, long long max_faces, float* vertices, float* vertex_colors, int32_t* faces);

@@ -1,7 +1,7 @@
 // C ABI of libgsr_hip.so (include/gsr.h), the part without a handle: every entry point that checks its arguments, launches
 // its kernels on the caller's stream and keeps nothing — planar SSIM, the trainer's prologue / Adam / tail, row gathers, the
 // bilateral grid, the geometry, depth and sky losses, the evaluation head, the geometry frames, densification, MCMC, Morton
-// codes, k-NN, the 3-D smoothing filter, PLY rows, the multi-view SH gradient, the all-reduce.  (The handle and its launch choreography are gsr_api.cpp's.)
+// codes, k-NN, the 3-D smoothing filter, TSDF fusion and mesh extraction, PLY rows, the multi-view SH gradient, the all-reduce.  (The handle and its launch choreography are gsr_api.cpp's.)
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -767,6 +767,99 @@ int gsr_filter3d_apply_backward(int64_t n, const float* opacities_act, const flo
         return fail(GSR_E_INVALID_ARG, "null array");
     gsr_launch_filter3d_apply_bwd((hipStream_t)stream, n, opacities_act, scales_act, filter, g_opacities, g_scales, v_opacities,
                                   v_scales);
+    return launched();
+}
+
+// ---- TSDF fusion of rendered depth and surface-nets mesh extraction (tsdf.hip) ----
+namespace {
+constexpr int kTsdfMaxDim = 65535;              // a (j, k) row is one workgroup row of the launch grid
+constexpr long long kMeshMaxSamples = 1ll << 30;  // vertex ids are int32, 3 quads per sample are counted in 32 bits
+
+int check_tsdf_grid(int32_t nx, int32_t ny, int32_t nz, const void* volume) {
+    if (nx < 1 || ny < 1 || nz < 1) return fail(GSR_E_INVALID_ARG, "volume of %d x %d x %d samples: every side must be >= 1", nx, ny, nz);
+    if (nx > kTsdfMaxDim || ny > kTsdfMaxDim || nz > kTsdfMaxDim)
+        return fail(GSR_E_INVALID_ARG, "volume of %d x %d x %d samples: a side may not exceed %d", nx, ny, nz, kTsdfMaxDim);
+    if (!volume) return fail(GSR_E_INVALID_ARG, "null volume");
+    if ((uintptr_t)volume % 8) return fail(GSR_E_INVALID_ARG, "the volume must be 8-byte aligned: {tsdf, weight} pairs");
+    return GSR_OK;
+}
+int check_mesh_grid(int32_t nx, int32_t ny, int32_t nz, const void* volume) {
+    if (int rc = check_tsdf_grid(nx, ny, nz, volume)) return rc;
+    if ((long long)nx * ny * nz > kMeshMaxSamples)
+        return fail(GSR_E_INVALID_ARG, "volume of %d x %d x %d samples: the extraction indexes at most 2^30", nx, ny, nz);
+    return GSR_OK;
+}
+int check_mesh_scratch(int32_t nx, int32_t ny, int32_t nz, const void* scratch, size_t scratch_bytes) {
+    const size_t need = gsr_mesh_scratch_size(nx, ny, nz);
+    if (need == 0) return GSR_OK;   // no cell: nothing is launched, nothing is touched
+    if (!scratch) return fail(GSR_E_INVALID_ARG, "null scratch");
+    if (int rc = check_scratch(scratch_bytes, need, "mesh extraction")) return rc;
+    if ((uintptr_t)scratch % 8) return fail(GSR_E_INVALID_ARG, "scratch must be 8-byte aligned");
+    return GSR_OK;
+}
+GsrTsdfGrid tsdf_grid(int32_t nx, int32_t ny, int32_t nz, const float* origin, float h) {
+    GsrTsdfGrid g = {nx, ny, nz, {0.0f, 0.0f, 0.0f}, h};
+    if (origin) std::copy(origin, origin + 3, g.o);
+    return g;
+}
+}  // namespace
+
+int gsr_tsdf_integrate(int32_t nx, int32_t ny, int32_t nz, const float* origin, float voxel_size, float trunc, int32_t W, int32_t H,
+                       int32_t C, const float* image, const gsr_camera* cam, float min_alpha, float near_plane, float* volume,
+                       float* color, void* stream) {
+    int rc;
+    if ((rc = check_tsdf_grid(nx, ny, nz, volume))) return rc;
+    if (!origin || !cam) return fail(GSR_E_INVALID_ARG, "null origin or cam");
+    if (!(voxel_size > 0.0f) || !std::isfinite(voxel_size)) return fail(GSR_E_INVALID_ARG, "voxel_size = %g: must be finite and > 0", (double)voxel_size);
+    if (!(trunc > 0.0f) || !std::isfinite(trunc)) return fail(GSR_E_INVALID_ARG, "trunc = %g: must be finite and > 0", (double)trunc);
+    if ((rc = check_geometry_frame(W, H, C, 5, image))) return rc;
+    if ((rc = check_min_alpha(min_alpha))) return rc;
+    if (std::isnan(near_plane)) return fail(GSR_E_INVALID_ARG, "near_plane is NaN");
+    if (!(cam->focal[0] > 0.0f) || !(cam->focal[1] > 0.0f)) return fail(GSR_E_INVALID_ARG, "focal lengths must be positive");
+    GsrTsdfCam c;
+    std::copy(cam->R, cam->R + 9, c.R);
+    std::copy(cam->t, cam->t + 3, c.t);
+    c.fx = cam->focal[0];
+    c.fy = cam->focal[1];
+    c.cx = cam->principal[0] * (float)W;
+    c.cy = cam->principal[1] * (float)H;
+    gsr_launch_tsdf_integrate((hipStream_t)stream, tsdf_grid(nx, ny, nz, origin, voxel_size), c, W, H, C, image, min_alpha,
+                              near_plane, trunc, volume, color);
+    return launched();
+}
+
+size_t gsr_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz) {
+    if (nx < 1 || ny < 1 || nz < 1 || nx > kTsdfMaxDim || ny > kTsdfMaxDim || nz > kTsdfMaxDim ||
+        (long long)nx * ny * nz > kMeshMaxSamples)
+        return 0;
+    return gsr_mesh_scratch_size(nx, ny, nz);
+}
+
+int gsr_mesh_count(int32_t nx, int32_t ny, int32_t nz, const float* volume, uint32_t* counts, void* scratch, size_t scratch_bytes,
+                   void* stream) {
+    int rc;
+    if ((rc = check_mesh_grid(nx, ny, nz, volume))) return rc;
+    if (!counts) return fail(GSR_E_INVALID_ARG, "null counts");
+    if ((rc = check_mesh_scratch(nx, ny, nz, scratch, scratch_bytes))) return rc;
+    gsr_launch_mesh_count((hipStream_t)stream, tsdf_grid(nx, ny, nz, nullptr, 0.0f), volume, counts, scratch);
+    return launched();
+}
+
+int gsr_mesh_emit(int32_t nx, int32_t ny, int32_t nz, const float* origin, float voxel_size, const float* volume, const float* color,
+                  const void* scratch, size_t scratch_bytes, int64_t max_vertices, int64_t max_faces, float* vertices,
+                  float* vertex_colors, int32_t* faces, void* stream) {
+    int rc;
+    if ((rc = check_mesh_grid(nx, ny, nz, volume))) return rc;
+    if (!origin) return fail(GSR_E_INVALID_ARG, "null origin");
+    if (!(voxel_size > 0.0f) || !std::isfinite(voxel_size)) return fail(GSR_E_INVALID_ARG, "voxel_size = %g: must be finite and > 0", (double)voxel_size);
+    if (max_vertices < 0 || max_faces < 0) return fail(GSR_E_INVALID_ARG, "negative capacity");
+    if ((max_vertices > 0 && !vertices) || (max_faces > 0 && !faces)) return fail(GSR_E_INVALID_ARG, "null vertices or faces");
+    if ((color != nullptr) != (vertex_colors != nullptr) && max_vertices > 0)
+        return fail(GSR_E_INVALID_ARG, "color and vertex_colors go together: %s given", color ? "only color" : "only vertex_colors");
+    if ((rc = check_mesh_scratch(nx, ny, nz, scratch, scratch_bytes))) return rc;
+    if (max_vertices == 0 && max_faces == 0) return GSR_OK;
+    gsr_launch_mesh_emit((hipStream_t)stream, tsdf_grid(nx, ny, nz, origin, voxel_size), volume, color, scratch, max_vertices,
+                         max_faces, vertices, vertex_colors, faces);
     return launched();
 }
 

@@ -683,6 +683,56 @@ GSR_API int gsr_filter3d_apply_backward(int64_t n, const float* opacities_act, c
                                         const float* g_opacities, const float* g_scales, float* v_opacities, float* v_scales,
                                         void* stream);
 
+/* TSDF fusion of rendered depth frames and surface-nets mesh extraction: one surface of the scene from the :rgbd / :rgbdn
+ * frames, made on the device.  No handle, no struct, nothing read back to the host.
+ *
+ * The volume: nx x ny x nz samples; sample (i, j, k) sits at world origin + voxel_size*(i, j, k), each coordinate computed as
+ * origin[a] + voxel_size*(float)idx; linear index l = i + nx*(j + ny*k), x fastest.
+ *   volume : (nz, ny, nx, 2) float32, {tsdf, weight} per sample, 8-byte aligned.  A fresh volume is tsdf = 1, weight = 0.
+ *   color  : (nz, ny, nx, 3) float32 or NULL.
+ * Every side is in [1, 65535]; the extraction also asks for nx*ny*nz <= 2^30.
+ *
+ * gsr_tsdf_integrate: fuses one frame into the volume.  image: the rasterizer's frame (H, W, C >= 5), channel fastest:
+ * channels 0..2 rgb, 3 the depth sum D, 4 alpha.  cam: R (column-major), t, focal and principal are read.  Per sample, in fp32,
+ * every operation ONE rounded operation in this association:
+ *     p = sample position ;  pc[r] = ((R[r]*px + R[r+3]*py) + R[r+6]*pz) + t[r] ;  z = pc[2]
+ *     skip unless z > near_plane
+ *     u = (fx*pc[0])/z + cx ;  v = (fy*pc[1])/z + cy ;  cx = principal[0]*(float)W, cy = principal[1]*(float)H
+ *     iu = floor(u + 0.5), iv = floor(v + 0.5)       (the rasterizer's convention: 0-based pixel i samples u = i)
+ *     skip unless 0 <= iu < W, 0 <= iv < H, alpha >= min_alpha       (a NaN anywhere skips)
+ *     d = D/alpha ;  sdf = d - z ;  skip unless sdf >= -trunc ;  s = min(1, sdf/trunc)
+ *     tsdf' = (tsdf*w + s)/(w + 1) ;  w' = w + 1 ;  colour' = (colour*w + clamp(rgb/alpha, 0, 1))/(w + 1) per channel
+ * A skipped sample's entry is neither read nor written.  Views are fused in call order: run-to-run bit-identical.
+ * GSR_E_INVALID_ARG: a side < 1 or > 65535, a null origin / cam / image / volume, a misaligned volume, voxel_size, trunc or
+ * min_alpha not > 0, W or H < 1, C < 5, a non-positive focal length, a NaN near_plane.  A refused call touches nothing.
+ *
+ * Extraction, naive surface nets.  A sample is inside when tsdf < 0 and observed when weight > 0.  Cell (i, j, k) (i < nx-1,
+ * ...) is active when its 8 corners are observed and not all on one side; every active cell gives one vertex, in ascending
+ * cell index i + (nx-1)*(j + (ny-1)*k): local = the mean of the crossing points a + s*(b - a), s = Ta/(Ta - Tb), over the
+ * cell's sign-changing edges, summed in this order: the 4 x-edges, then the y-edges, then the z-edges, within an axis the two
+ * fixed coordinates counting up with the lower axis fastest; world = origin + voxel_size*((float)idx + local).  The vertex
+ * colour is the sum of the 8 corners' colours in corner order (corner = dx + 2*dy + 4*dz) times 0.125.  Every grid edge
+ * p -> p + e_a (a = 0, 1, 2) whose ends are observed and on different sides gives one quad when the four cells around it
+ * exist and are active: with (b, c) = (a+1, a+2) mod 3, c0 = p - e_b - e_c, c1 = p - e_c, c2 = p, c3 = p - e_b, written as the
+ * triangles (c0, c1, c2), (c0, c2, c3) of vertex ids when p is inside and (c3, c2, c1), (c3, c1, c0) when p + e_a is: the normal
+ * points from inside to outside.  Quads ascend in 3*l(p) + a.
+ *   gsr_mesh_scratch_bytes: 4 bytes per cell, 8 per run of whole rows of about 2048 cells, 8 more; 0 when the volume has no cell (or is refused).
+ *   gsr_mesh_count : counts[0] <- the vertices, counts[1] <- the quads (two uint32 on the device); leaves in the scratch what
+ *                    gsr_mesh_emit needs.  scratch: gsr_mesh_scratch_bytes, 8-byte aligned.
+ *   gsr_mesh_emit  : after gsr_mesh_count on the same volume and scratch.  Writes the first min(vertices, max_vertices) rows of
+ *                    vertices (x, y, z) and vertex_colors, and the first min(2*quads, max_faces) rows of faces (int32 x 3), and
+ *                    nothing beyond them.  color and vertex_colors are given together or both NULL.
+ * A volume without a cell (a side of 1) is an empty mesh: counts <- {0, 0}, no scratch is needed, nothing else is written. */
+GSR_API int gsr_tsdf_integrate(int32_t nx, int32_t ny, int32_t nz, const float* origin, float voxel_size, float trunc, int32_t W,
+                               int32_t H, int32_t C, const float* image, const gsr_camera* cam, float min_alpha, float near_plane,
+                               float* volume, float* color, void* stream);
+GSR_API size_t gsr_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
+GSR_API int gsr_mesh_count(int32_t nx, int32_t ny, int32_t nz, const float* volume, uint32_t* counts, void* scratch,
+                           size_t scratch_bytes, void* stream);
+GSR_API int gsr_mesh_emit(int32_t nx, int32_t ny, int32_t nz, const float* origin, float voxel_size, const float* volume,
+                          const float* color, const void* scratch, size_t scratch_bytes, int64_t max_vertices, int64_t max_faces,
+                          float* vertices, float* vertex_colors, int32_t* faces, void* stream);
+
 /* The non-finite gradient guard of `step!` under GSP_DEBUG (src/training.jl:772-777: `isfinite(sum(∇ᵢ))` per parameter)
  * and the per-parameter counts of `nonfinite_gradient_report` (:534-552), in one pass over up to GSR_ADAM_MAX_GROUPS
  * gradient arrays of n_rows Gaussians each (rows of row_words floats; row_words = 0 skips an empty array):
