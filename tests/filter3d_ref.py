@@ -197,6 +197,36 @@ def unseen_points(n, seed=0):
     return pts
 
 
+# ---- the final fold past two partials: (n, the workgroup of the sweep that holds the largest filter) ----
+WG_POINTS = 1024                        # points per workgroup of the sweep: one partial maximum and count each
+FOLD_V = 2
+FOLD_CASES = ((64 * 1024 + 1, 64),      # 65 partials: the final's wave 1 holds one, the LAST, and with it the maximum
+              (257 * 1024 + 1, 257),    # 258 partials: threads 0 and 1 take a second trip; the maximum comes in on thread 1's
+              (257 * 1024 + 1, 200))    # ... and from thread 200 (wave 3) on the first trip
+FOLD_FAR = 64.0                         # make_points stays within z < 20 (1.5 + 6 sigma)
+
+
+def fold_points(n, wg, table):
+    """make_points with the hand rows, and ONE point far out on camera 0's axis — seen, with the largest filter of all — in
+    workgroup `wg` of the sweep: the last point of the array when that is the last workgroup (which holds nothing else)."""
+    pts = make_points(n, table, seed=3)
+    at = min(wg * WG_POINTS + 517, n - 1)
+    pts[at] = (0.0, 0.0, FOLD_FAR)
+    return pts, at
+
+
+_fold = {}
+
+
+def fold_case(n, wg):
+    """-> (table, points, the index of the far point, the fp32 sweep) of a FOLD_CASES entry; computed once, read-only."""
+    if (n, wg) not in _fold:
+        table = camera_table(make_rig(FOLD_V))
+        pts, at = fold_points(n, wg, table)
+        _fold[n, wg] = table, pts, at, sweep(pts, table, dtype=f32)
+    return _fold[n, wg]
+
+
 # ---- the rows of the apply tests ----
 def apply_rows(n, seed=0):
     """o in [0.004, 0.999], s log-uniform in [1e-4, 10], f log-uniform in [1e-4, 1], normal cotangents."""

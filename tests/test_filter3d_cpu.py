@@ -65,6 +65,31 @@ def test_no_point_seen_is_all_zeros():
     assert s.count == 0 and not s.filter.any() and not s.seen.any()
 
 
+# (n, workgroup) -> (seen points, seen points of the workgroup that holds the maximum)
+FOLD_FIGURES = {(65537, 64): (14474, 1), (263169, 257): (58201, 1), (263169, 200): (58200, 257)}
+
+
+@pytest.mark.parametrize("n,wg", fr.FOLD_CASES)
+def test_fold_points_put_the_maximum_where_they_say(n, wg):
+    """The inputs of the final fold's GPU cases: ceil(n / 1024) partials (65: wave 1 of the final holds one; 258: a second trip
+    for threads 0 and 1), some points seen by no camera — the fill is written — and the largest filter among the seen points on
+    ONE point, in workgroup `wg`: the last one, or number 200."""
+    table, pts, at, s = fr.fold_case(n, wg)
+    n_wg = (n + fr.WG_POINTS - 1) // fr.WG_POINTS
+    assert n_wg in (65, 258) and at // fr.WG_POINTS == wg < n_wg and (wg == n_wg - 1) == (at == n - 1)
+    assert table.shape[0] == 2 and pts.shape == (n, 3)
+    assert s.seen[at] and 0 < s.count < n and s.count == int(s.seen.sum())
+    top = np.flatnonzero(s.seen & (s.filter == s.filter[at]))
+    assert list(top) == [at] and s.filter[at] == s.filter[s.seen].max(), "one point holds the maximum"
+    assert (s.filter[~s.seen].view(np.int32) == s.filter[at].view(np.int32)).all() and (~s.seen).sum() > 1000, "the fill is that point's filter"
+    per_wg = np.bincount(np.arange(n) // fr.WG_POINTS, weights=s.seen, minlength=n_wg).astype(int)
+    assert (per_wg[:-1] > 0).all(), "every partial count matters"
+    print(n, wg, s.count, int(per_wg[wg]))
+    assert (s.count, int(per_wg[wg])) == FOLD_FIGURES[n, wg]
+    # and the hand rows are still in front
+    assert not s.seen[6] and not s.seen[7] and np.isfinite(s.filter).all()
+
+
 # ---- apply and its pullback ----
 def test_analytic_backward_is_autograd_of_the_forward():
     o, s, f, g_o, g_s = fr.apply_rows(2000)

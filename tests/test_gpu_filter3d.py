@@ -1,6 +1,7 @@
 """-m gpu: the 3-D smoothing filter on the MI355X (csrc/filter3d.hip through smoothing_filter).
   1. the camera sweep against the fp32 restatement of tests/filter3d_ref.py, bit for bit — filter, seen flags and count as
-     integers, every N x V of the restatement's cases, the hand-placed rows, a scene nobody sees, two runs;
+     integers, every N x V of the restatement's cases, the hand-placed rows, a scene nobody sees, two runs; 65 and 258
+     partials into the final fold;
   2. the sweep against the float64 twin;
   3. apply, its pullback and the raw (export) values against the float64 twin, the zero-filter pass-through, in place ==
      out of place;
@@ -60,6 +61,25 @@ def test_sweep_is_the_fp32_restatement_bit_for_bit(pkg, n, V):
         assert not got[1][6] and not got[1][7]
         if V == 1:
             assert not got[1][0] and bool(got[1][1:6].all())
+
+
+@pytest.mark.parametrize("n,wg", fr.FOLD_CASES)
+def test_final_fold_past_one_wave_and_one_trip(pkg, n, wg):
+    """65 and 258 partial maxima and counts into filter3d_final_kernel — the earlier cases stop at 2, which threads 0 and 1 of
+    wave 0 hold after one trip of the loop.  The largest filter sits on ONE seen point of workgroup `wg` of the sweep (the
+    last, which is wave 1's only partial of 65 and thread 1's second trip of 258; or number 200, in wave 3), and every unseen
+    point carries it as the fill: a fold that loses a wave or a trip shows in thousands of rows and in the count
+    (tests/test_filter3d_cpu.py holds the inputs to this)."""
+    SF = pkg.smoothing_filter
+    table, pts_h, at, want = fr.fold_case(n, wg)
+    assert want.seen[at] and want.filter[at] == want.filter[want.seen].max() and (~want.seen).sum() > 1000
+    pts = dev(pts_h)
+    got = SF.compute_filter_3d(pts, table, return_seen=True)
+    _same_sweep(got, want, (n, wg))
+    assert int(got[2].item()) == int(want.seen.sum())
+    again = SF.compute_filter_3d(pts, table, return_seen=True)
+    assert all(torch.equal(a, b) for a, b in zip(got, again)), "two runs"
+    assert np.array_equal(bits(SF.compute_filter_3d(pts, table)), bits(want.filter)), "the seen flags in the scratch"
 
 
 @pytest.mark.parametrize("n", [1, 257, 1025])

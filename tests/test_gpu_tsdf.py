@@ -1,8 +1,10 @@
 """-m gpu: TSDF fusion and surface-nets extraction on the MI355X (csrc/tsdf.hip through surface_mesh).
   1. `integrate` against the fp32 restatement of tests/tsdf_ref.py, bit for bit — tsdf, weight and colour as integers, after the
-     first and after all 14 views of the sphere cases, on random frames over the four odd volumes, two runs;
+     first and after all 14 views of the sphere cases, on random frames over the four odd volumes, two runs; over volumes of two
+     to four 256-blocks of x under cameras that see their whole length;
   2. against the float64 twin;
-  3. the extraction against the restatement: counts, vertices and colours as bits, faces as integers; one read-back;
+  3. the extraction against the restatement: counts, vertices and colours as bits, faces as integers; one read-back; the volumes
+     of tsdf_ref.MULTI_RUN_CASES among them (several runs per slab, several workgroups, a second round of the scan);
   4. the mesh conditions on the device's meshes of the sphere cases;
   5. gsr_mesh_emit with capacities below the counts, on guarded buffers;
   6. through the rasterizer: fuse_views on a small :rgbd scene;
@@ -116,6 +118,32 @@ def test_integrate_random_frames_bit_for_bit(pkg, dims):
     assert int((runs[0].volume[..., 1] > 0).sum()) > 0
 
 
+@pytest.mark.parametrize("dims", tr.WIDE_DIMS)
+def test_integrate_past_the_first_256_samples_of_x(pkg, dims):
+    """Volumes of two, three and four workgroups in x (blockIdx.x·256 beyond 0), the last with 1, 44, 1 and 2 live lanes, under
+    cameras that see the whole length of the box (tests/test_tsdf_cpu.py: every 256-block holds fused samples in the
+    restatement; random_views' cameras reach none past i = 255): compared after every view, two runs, and the device's own
+    weights are non-zero in every block."""
+    ref, views = tr.wide_views(dims, True)
+    runs = [device_volume(pkg, ref), device_volume(pkg, ref)]
+    for n, (frame, cam) in enumerate(views):
+        tr.integrate(ref, frame, cam)
+        for vol in runs:
+            vol.integrate(dev(frame), pkg_cam(pkg, cam))
+        assert_same_volume(runs[0], ref, (dims, n))
+    assert torch.equal(runs[0].volume.view(I32), runs[1].volume.view(I32)) and torch.equal(runs[0].color.view(I32), runs[1].color.view(I32))
+    weight = runs[0].volume[..., 1]
+    blocks = [int((weight[..., b:b + 256] > 0).sum()) for b in range(0, dims[0], 256)]
+    sizes = [weight[..., b:b + 256].numel() for b in range(0, dims[0], 256)]
+    print(dims, list(zip(blocks, sizes)))
+    assert len(blocks) == (dims[0] + 255) // 256 >= 2 and all(n >= min(30, size) for n, size in zip(blocks, sizes)), (blocks, sizes)
+    # without colour: the same {tsdf, weight} bits
+    plain = device_volume(pkg, tr.Volume(dims, ref.origin, ref.h, ref.trunc, False))
+    for frame, cam in views:
+        plain.integrate(dev(frame), pkg_cam(pkg, cam))
+    assert plain.color is None and torch.equal(plain.volume.view(I32), runs[0].volume.view(I32))
+
+
 def test_min_alpha_and_near_reach_the_kernel(pkg):
     ref, views = tr.random_views((41, 13, 11), True)
     vol = device_volume(pkg, ref)
@@ -188,14 +216,20 @@ def _extraction_cases():
     cases["one active cell"] = tr.one_cell_volume
     cases["no cell (1, 4, 4)"] = lambda: tr.random_volume((1, 4, 4), 15)
     cases["no cell (2, 2, 1)"] = lambda: tr.random_volume((2, 2, 1), 16)
+    for case in tr.MULTI_RUN_CASES:   # past one step of 63 cells, one run per slab, one workgroup, one round of the scan
+        cases[tr.multi_run_name(case)] = lambda case=case: tr.multi_run(case)[0]
     return cases
+
+
+_MULTI_RUN = {tr.multi_run_name(case): case for case in tr.MULTI_RUN_CASES}
 
 
 @pytest.mark.parametrize("name", list(_extraction_cases()))
 def test_extraction_is_the_restatement(pkg, name, monkeypatch):
     SM = pkg.surface_mesh
     ref = _extraction_cases()[name]()
-    want = tr.extract_volume(ref)
+    want = tr.multi_run(_MULTI_RUN[name])[1] if name in _MULTI_RUN else tr.extract_volume(ref)
+    assert SM.mesh_scratch_bytes(ref.dims) == tr.mesh_scratch_bytes(ref.dims), "the plan of the library is the restated one"
     vol = device_volume(pkg, ref, load=True)
     calls = []
     real = SM._read_back
@@ -211,6 +245,10 @@ def test_extraction_is_the_restatement(pkg, name, monkeypatch):
         assert (want.n_vertices, want.n_quads) == (1, 0)
     if name.startswith("no cell"):
         assert (want.n_vertices, want.n_quads) == (0, 0) and SM.mesh_scratch_bytes(ref.dims) == 0
+    if name in _MULTI_RUN:
+        rows, nruns, nblk, ncells = tr.mesh_plan(ref.dims)
+        assert (rows, nruns, nblk) == _MULTI_RUN[name].plan and SM.mesh_scratch_bytes(ref.dims) == 4 * ncells + 8 * (nblk + 1)
+        assert want.n_vertices > 300 and want.n_quads > 100
     assert_same_volume(vol, ref, "the volume is an input")
 
 
@@ -242,21 +280,21 @@ def _origin(ref):
     return (C.c_float * 3)(*[float(x) for x in ref.origin])
 
 
-@pytest.mark.parametrize("skew", ["aligned", "worst"])
-def test_emit_below_capacity_on_guarded_buffers(pkg, skew):
-    """max_vertices = M // 2 and an odd max_faces (the last quad written as ONE triangle): the first rows are the full mesh's,
-    the output arrays end where the capacities do and their guards are intact, the counts are the true ones."""
+def _arena_bytes(*nbytes):
+    """Room for placements of these sizes: each with its guards and the skew of its start."""
+    return sum(int(n) for n in nbytes) + len(nbytes) * (2 * 1024 + 64)
+
+
+def _emit_below_capacity(pkg, skew, ref, want, capacities):
+    """gsr_mesh_count + gsr_mesh_emit per (max_vertices, max_faces) of `capacities`, on an arena sized from the case."""
     lib = pkg._lib.load()
-    ref = tr.random_volume((41, 13, 11), 12, p_zero=0.05)
-    want = tr.extract_volume(ref)
     M, Q = want.n_vertices, want.n_quads
-    cap_v, cap_f = M // 2, (2 * Q) // 2 | 1
-    assert 0 < cap_v < M and 0 < cap_f < 2 * Q
     nx, ny, nz = ref.dims
     nb = int(lib.gsr_mesh_scratch_bytes(nx, ny, nz))
+    assert nb == tr.mesh_scratch_bytes(ref.dims)
     st = _stream()
-    for caps in ((cap_v, cap_f), (M, 0), (0, 2 * Q), (1, 1)):
-        P = Arena(1 << 20, "cuda", skew, 1)
+    for caps in capacities:
+        P = Arena(max(1 << 20, _arena_bytes(ref.packed().nbytes, ref.color.nbytes, nb, 8, 12 * caps[0], 12 * caps[0], 12 * caps[1])), "cuda", skew, 1)
         volume, color = P.place("volume", ref.packed(), align=8), P.place("color", ref.color)
         scratch = P.place("scratch", (nb,), U8, align=8, role="scratch")
         counts = P.place("counts", (2,), I32)
@@ -275,6 +313,42 @@ def test_emit_below_capacity_on_guarded_buffers(pkg, skew):
         assert counts.tolist() == [M, Q], caps
         assert np.array_equal(bits(vertices), bits(want.vertices[:caps[0]])) and np.array_equal(bits(vcolors), bits(want.colors[:caps[0]]))
         assert np.array_equal(faces.cpu().numpy(), want.faces[:caps[1]]), caps
+
+
+@pytest.mark.parametrize("skew", ["aligned", "worst"])
+def test_emit_below_capacity_on_guarded_buffers(pkg, skew):
+    """max_vertices = M // 2 and an odd max_faces (the last quad written as ONE triangle): the first rows are the full mesh's,
+    the output arrays end where the capacities do and their guards are intact, the counts are the true ones."""
+    ref = tr.random_volume((41, 13, 11), 12, p_zero=0.05)
+    want = tr.extract_volume(ref)
+    M, Q = want.n_vertices, want.n_quads
+    cap_v, cap_f = M // 2, (2 * Q) // 2 | 1
+    assert 0 < cap_v < M and 0 < cap_f < 2 * Q
+    _emit_below_capacity(pkg, skew, ref, want, ((cap_v, cap_f), (M, 0), (0, 2 * Q), (1, 1)))
+
+
+@pytest.mark.parametrize("skew", ["aligned", "worst"])
+def test_emit_below_capacity_inside_a_second_run(pkg, skew):
+    """(130, 40, 5), three runs per slab.  The capacities M // 2 and Q | 1 of the test above end inside the short last run of
+    slab 1 and inside run 0 of slab 2; a second pair ends in the MIDDLE of run 1 of slab 1, the last quad as one triangle — a
+    wave of a workgroup stops writing while its neighbours write all or nothing; a third with the last vertex and the last
+    whole quad of run 0 of slab 2 (all of a run is written, nothing of its successor); and (M, 0), (0, 2Q), (1, 1)."""
+    case = next(c for c in tr.MULTI_RUN_CASES if c.dims == (130, 40, 5))
+    ref, want = tr.multi_run(case)
+    M, Q = want.n_vertices, want.n_quads
+    nruns = case.plan[1]
+    run, _, _ = tr.vertex_runs(ref)
+    quad_run = run[want.faces[0::2]].max(1)          # the run that emits a quad is the run of its cell p, the last of its four
+    assert (np.diff(quad_run) >= 0).all()
+    first_v, first_q = (lambda r: int(np.searchsorted(run, r))), (lambda r: int(np.searchsorted(quad_run, r)))
+    cap_v, cap_f = M // 2, (2 * Q) // 2 | 1
+    assert run[cap_v] == run[cap_v - 1] == nruns + 2 and quad_run[cap_f // 2] == 2 * nruns
+    mid_v = (first_v(nruns + 1) + first_v(nruns + 2)) // 2
+    mid_f = (first_q(nruns + 1) + first_q(nruns + 2)) | 1
+    assert run[mid_v] == run[mid_v - 1] == nruns + 1 and quad_run[mid_f // 2] == quad_run[mid_f // 2 - 1] == quad_run[mid_f // 2 + 1] == nruns + 1
+    edge_v, edge_q = first_v(2 * nruns + 1), first_q(2 * nruns + 1)
+    assert 0 < edge_v < M and 0 < edge_q < Q and run[edge_v - 1] == 2 * nruns == quad_run[edge_q - 1]
+    _emit_below_capacity(pkg, skew, ref, want, ((cap_v, cap_f), (mid_v, mid_f), (M, 0), (0, 2 * Q), (1, 1), (edge_v, 2 * edge_q)))
 
 
 # ---- 6. through the rasterizer ----
@@ -313,11 +387,11 @@ def test_fuse_views_through_the_rasterizer(pkg):
 G_DIMS, G_W, G_H = (41, 13, 11), 64, 48
 
 
-def _guarded_inputs(pkg):
-    ref = tr.Volume(G_DIMS, (-2.0, -1.0, -1.0625), 1.0 / 16.0, 0.25, True)
-    cam = tr.oblique_camera(77, G_W, G_H, ref)
+def _guarded_inputs(pkg, dims=G_DIMS, wide=False):
+    ref = tr.Volume(dims, (-2.0, -1.0, -1.0625), 1.0 / 16.0, 0.25, True)
+    cam = tr.wide_camera(ref, +1, 1.0, 0.5, G_W, G_H) if wide else tr.oblique_camera(77, G_W, G_H, ref)
     frame = tr.random_frame(78, G_W, G_H, 8)
-    start = tr.random_volume(G_DIMS, 12, p_zero=0.05)        # a volume in mid-fusion: weights 0..8, colours
+    start = tr.random_volume(dims, 12, p_zero=0.05)          # a volume in mid-fusion: weights 0..8, colours
     ref.tsdf, ref.weight, ref.color = start.tsdf.copy(), start.weight.copy(), start.color.copy()
     before = ref.packed().copy(), ref.color.copy()
     tr.integrate(ref, frame, cam)
@@ -329,7 +403,10 @@ def _guarded_calls(lib, P, inputs, tag):
     ref, cam, frame_h, before, want, cs = inputs
     nx, ny, nz = ref.dims
     nb = int(lib.gsr_mesh_scratch_bytes(nx, ny, nz))
-    assert nb == 4 * 40 * 12 * 10 + 8 * (10 + 1)      # 4 bytes per cell; one run of 12 rows of 40 cells per slab, 10 slabs; the total
+    if ref.dims == G_DIMS:
+        assert nb == 4 * 40 * 12 * 10 + 8 * (10 + 1)      # 4 bytes per cell; one run of 12 rows of 40 cells per slab, 10 slabs; the total
+    rows, nruns, nblk, ncells = tr.mesh_plan(ref.dims)
+    assert nb == 4 * ncells + 8 * (nblk + 1)
     M, Q = want.n_vertices, want.n_quads
     frame = P.place("frame", frame_h)
     volume, color = P.place("volume", before[0], align=8, role="inout"), P.place("color", before[1], role="inout")
@@ -380,6 +457,77 @@ def test_entry_points_on_guarded_buffers(pkg):
             continue
         for k in got:
             assert torch.equal(got[k].contiguous().view(-1).view(U8), ref[k].contiguous().view(-1).view(U8)), (tag, k)
+
+
+W_DIMS = (513, 12, 4)
+
+
+def test_entry_points_on_guarded_buffers_across_runs_and_blocks(pkg):
+    """(513, 12, 4) on the five placements: three workgroups of the integration in x (the last with one live lane), three runs
+    per slab in one workgroup of the extraction, the last run with 3 rows of 4.  The volume starts in mid-fusion and the camera
+    sees its whole length; the scratch is 4 bytes per cell and 8 per run and for the total."""
+    lib = pkg._lib.load()
+    inputs = _guarded_inputs(pkg, W_DIMS, wide=True)
+    ref, want, before = inputs[0], inputs[4], inputs[3]
+    assert tr.mesh_plan(W_DIMS)[:3] == (4, 3, 9) and int(lib.gsr_mesh_scratch_bytes(*W_DIMS)) == 4 * 512 * 11 * 3 + 8 * (9 + 1)
+    assert want.n_vertices > 1000 and want.n_quads > 500
+    fused = ref.packed()[..., 1] != before[0][..., 1]
+    assert all(fused[..., b:b + 256].sum() >= min(30, fused[..., b:b + 256].size) for b in (0, 256, 512)), "the view fuses samples of every block of x"
+    run, K, _ = tr.vertex_runs(ref)
+    f_run, f_k = run[want.faces], K[want.faces]
+    assert ((f_k.max(1) == f_k.min(1)) & (f_run.max(1) != f_run.min(1))).sum() >= 100 and len(np.unique(run)) == 9
+    volume_b, scratch_b = before[0].nbytes, tr.mesh_scratch_bytes(W_DIMS)
+    mesh_b = 12 * want.n_vertices, 24 * want.n_quads
+    need = _arena_bytes(inputs[2].nbytes, volume_b, before[1].nbytes, volume_b, scratch_b, 8, mesh_b[0], mesh_b[0], mesh_b[1], scratch_b, 8,
+                        mesh_b[0], mesh_b[1])
+    first = None
+    for P in placements(need, "cuda"):
+        tag = f"{P.skew}/{P.fill}"
+        got = _guarded_calls(lib, P, inputs, tag)
+        if first is None:
+            first = got
+            continue
+        for k in got:
+            assert torch.equal(got[k].contiguous().view(-1).view(U8), first[k].contiguous().view(-1).view(U8)), (tag, k)
+
+
+def test_second_round_of_the_scan(pkg):
+    """(1026, 42, 26): 1025 runs, one past a round of the 1024-thread scan — the last run's offset is the carry that crossed the
+    rounds through LDS plus nothing, and the totals are the packed {vertices, quads << 32} word after that carry.  Through the
+    entry points, on poisoned outputs: the counts read back, the LAST vertex and the LAST face (both of run 1024, by
+    tests/test_tsdf_cpu.py: their ids and position come from that offset), then every row."""
+    lib = pkg._lib.load()
+    case = tr.MULTI_RUN_CASES[-1]
+    ref, want = tr.multi_run(case)
+    nx, ny, nz = ref.dims
+    M, Q = want.n_vertices, want.n_quads
+    rows, nruns, nblk, ncells = tr.mesh_plan(ref.dims)
+    assert nblk == 1025 and (nx, ny, nz) == (1026, 42, 26)
+    nb = int(lib.gsr_mesh_scratch_bytes(nx, ny, nz))
+    assert nb == 4 * ncells + 8 * (nblk + 1)
+    volume, color = dev(ref.packed()), dev(ref.color)
+    scratch, counts = torch.empty(nb, dtype=U8, device="cuda"), torch.empty(2, dtype=I32, device="cuda")
+    vertices, vcolors = torch.empty(M, 3, device="cuda"), torch.empty(M, 3, device="cuda")
+    faces = torch.empty(2 * Q, 3, dtype=I32, device="cuda")
+    for t in (scratch, counts, vertices, vcolors, faces):
+        t.view(-1).view(U8).fill_(0xFF)
+    st = _stream()
+    rc = lib.gsr_mesh_count(nx, ny, nz, _ptr(volume), _ptr(counts), _ptr(scratch), nb, st)
+    rc2 = lib.gsr_mesh_emit(nx, ny, nz, _origin(ref), float(ref.h), _ptr(volume), _ptr(color), _ptr(scratch), nb, M, 2 * Q,
+                            _ptr(vertices), _ptr(vcolors), _ptr(faces), st)
+    assert (rc, rc2) == (0, 0), lib.gsr_last_error_string().decode()
+    torch.cuda.synchronize()
+    assert counts.tolist() == [M, Q]
+    run, _, _ = tr.vertex_runs(ref)
+    assert run[-1] == 1024 and run[want.faces[-1]].max() == 1024 and run[want.faces[-1]].min() < 1024
+    assert np.array_equal(bits(vertices[-1]), bits(want.vertices[-1])), (vertices[-1].tolist(), want.vertices[-1])
+    assert faces[-1].tolist() == want.faces[-1].tolist()
+    first_v = int(np.searchsorted(run, 1024))
+    assert np.array_equal(bits(vertices[first_v:]), bits(want.vertices[first_v:])), "the vertices of run 1024"
+    assert np.array_equal(bits(vertices), bits(want.vertices)) and np.array_equal(bits(vcolors), bits(want.colors))
+    bad = np.flatnonzero((faces.cpu().numpy() != want.faces).any(1))
+    assert bad.size == 0, (len(bad), bad[:4], faces[int(bad[0])].tolist(), want.faces[bad[0]])
+    assert np.array_equal(bits(volume), bits(ref.packed()))
 
 
 def test_error_codes(pkg):

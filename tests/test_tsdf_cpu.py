@@ -1,6 +1,7 @@
 """No GPU: the numpy restatement of the TSDF fusion and the surface-nets extraction (tests/tsdf_ref.py) against
 its float64 twin, the mesh conditions on the analytic sphere scenes, the random frames' coverage of every branch, the PLY
-bytes parsed back, and the declarations of the new entry points."""
+bytes parsed back, the declarations of the new entry points, and the conditions on the inputs that take the GPU tests past one
+run per slab, one workgroup, one round of the scan (MULTI_RUN_CASES) and one 256-block of x (wide_views)."""
 import os
 import re
 
@@ -112,6 +113,121 @@ def test_extraction_fp32_against_float64_and_small_volumes():
     for dims in ((1, 4, 4), (2, 2, 1)):
         e = tr.extract_volume(tr.random_volume(dims, 4))
         assert e.n_vertices == 0 and e.n_quads == 0 and e.vertices.shape == (0, 3)
+
+
+# ---- the inputs that take the kernels past one run, one workgroup, one scan round, one 256-block of x ----
+# dims -> (vertices, quads, triangles with vertices in two runs of ONE slab, active cells in the last run of a slab)
+MULTI_RUN_FIGURES = {(64, 5, 3): (311, 150, 0, 311), (65, 5, 3): (327, 138, 0, 327), (127, 4, 3): (484, 238, 0, 484),
+                     (130, 40, 5): (12839, 9075, 362, 3116), (513, 12, 4): (11111, 7237, 1246, 3045),
+                     (1025, 7, 3): (8051, 4260, 1556, 2643), (1026, 10, 3): (12204, 6792, 6588, 1372),
+                     (2050, 4, 3): (8111, 3687, 3276, 2717), (1026, 42, 26): (60044, 2480, 1626, 1494)}
+
+
+def test_mesh_plan_is_the_formula():
+    """rows = max(1, 2048 // (nx - 1)), nruns = ceil((ny - 1) / rows), nblk = nruns·(nz - 1); every volume of the earlier
+    extraction tests has ONE run per slab and at most 25 runs — what MULTI_RUN_CASES is there to leave."""
+    for dims, want in (((9, 8, 7), (256, 1, 6, 336)), ((41, 13, 11), (51, 1, 10, 4800)), ((300, 4, 3), (6, 1, 2, 1794)),
+                       ((17, 18, 19), (128, 1, 18, 4896)), ((24, 25, 26), (89, 1, 25, 13800)), ((2, 2, 2), (2048, 1, 1, 1)),
+                       ((1025, 7, 3), (2, 3, 6, 12288)), ((1026, 7, 3), (1, 6, 12, 12300)), ((2049, 3, 2), (1, 2, 2, 4096)),
+                       ((2050, 3, 2), (1, 2, 2, 4098)), ((256, 256, 256), (8, 32, 8160, 255 ** 3))):
+        assert tr.mesh_plan(dims) == want, dims
+        assert tr.mesh_scratch_bytes(dims) == 4 * want[3] + 8 * (want[2] + 1)
+    for dims in ((1, 4, 4), (2, 2, 1), (5, 1, 5)):
+        assert tr.mesh_plan(dims)[1:] == (0, 0, 0) and tr.mesh_scratch_bytes(dims) == 0
+    assert tr.run_of((130, 40, 5), 14, 0) == 0 and tr.run_of((130, 40, 5), 15, 0) == 1 and tr.run_of((130, 40, 5), 38, 3) == 2 + 3 * 3
+    assert any(not c.color and c.plan[1] >= 2 for c in tr.MULTI_RUN_CASES), "one multi-run case without colour"
+
+
+@pytest.mark.parametrize("case", tr.MULTI_RUN_CASES, ids=tr.multi_run_name)
+def test_multi_run_volumes_reach_what_they_are_for(case):
+    """The plan of the case; its counts; fp32 against float64 as for the small volumes; and, where a slab has two runs or
+    more: at least 100 triangles take vertices from two runs of ONE slab (mesh_vertex_id's j / rows and the run stride), an
+    active cell lies in the last run of a slab — the shorter one where the rows do not divide — and for the 1025-run case a
+    cell has run id 1024, the one entry of the scan's second round, with triangles joining it to earlier runs."""
+    rows, nruns, nblk, ncells = tr.mesh_plan(case.dims)
+    assert (rows, nruns, nblk) == case.plan
+    nx, ny, nz = case.dims
+    vol, a = tr.multi_run(case)
+    assert (vol.color is not None) == case.color
+    b = tr.extract_volume(vol, np.float64)
+    assert a.n_vertices == b.n_vertices and a.n_quads == b.n_quads and np.array_equal(a.faces, b.faces)
+    assert a.faces.min() >= 0 and a.faces.max() < a.n_vertices
+    assert np.abs(a.vertices - b.vertices).max() <= 16 * tr.EPS * (np.abs(vol.origin).max() + float(vol.h) * max(case.dims))
+    if case.color:
+        assert np.abs(a.colors - b.colors).max() <= 8 * tr.EPS
+    else:
+        assert a.colors is None and b.colors is None
+    run, K, J = tr.vertex_runs(vol)
+    assert len(run) == a.n_vertices and (np.diff(run) >= 0).all(), "the runs ascend with the vertex order"
+    f_run, f_k = run[a.faces], K[a.faces]
+    cross = int(((f_k.max(1) == f_k.min(1)) & (f_run.max(1) != f_run.min(1))).sum())
+    in_last = int((J // rows == nruns - 1).sum())
+    print(f"{case.dims}: plan {case.plan}, {a.n_vertices} vertices, {a.n_quads} quads, {cross} triangles across runs of one slab, "
+          f"{in_last} active cells in the last run of a slab")
+    assert (a.n_vertices, a.n_quads, cross, in_last) == MULTI_RUN_FIGURES[case.dims]
+    if nruns >= 2:
+        assert cross >= 100 and in_last > 0
+        assert run.max() == nblk - 1 and len(np.unique(run)) == nblk, "every run has a vertex"
+    if case.dims in ((130, 40, 5), (513, 12, 4)):
+        assert 0 < (ny - 1) - (nruns - 1) * rows < rows, "the last run is shorter"
+    if nblk > tr.SCAN_ROUND:
+        assert nblk == tr.SCAN_ROUND + 1 and (run == 1024).sum() > 0
+        joins = (f_run.max(1) == 1024) & (f_run.min(1) < 1024)
+        assert joins.sum() >= 2 and (f_run[-1] == 1024).any() and run[-1] == 1024, "the last vertex and the last face come from run 1024"
+
+
+# dims -> samples whose weight changes in some view, per 256-block of x
+WIDE_FIGURES = {(257, 3, 2): [1510, 6], (300, 4, 3): [3041, 521], (513, 5, 3): [3806, 3779, 15], (770, 3, 2): [1507, 1516, 1516, 12]}
+
+
+@pytest.mark.parametrize("dims", tr.WIDE_DIMS)
+def test_wide_views_reach_every_block_and_every_branch(dims):
+    """Every 256-block of x, the partly filled last one included, holds at least 30 samples whose weight changes in some view —
+    all of its samples where the block has fewer than 30 ((257, 3, 2): 6, (513, 5, 3): 15, (770, 3, 2): 12) — and the views
+    reach what test_random_views_reach_every_branch lists.  random_views' cameras update no sample past i = 255 of such a box:
+    they see 3.25 deep at most."""
+    nx, ny, nz = dims
+    old, old_views = tr.random_views(dims)
+    for frame, cam in old_views:
+        tr.integrate(old, frame, cam)
+    if dims in ((257, 3, 2), (300, 4, 3)):
+        assert not old.weight[..., 256:].any(), "the cameras of random_views stop short of the second block"
+    vol, views = tr.wide_views(dims, True)
+    assert len(views) >= 3 and vol.dims == dims and float(vol.h) == 1.0 / 16.0
+    changed = np.zeros(vol.weight.shape, bool)
+    for frame, cam in views:
+        changed |= tr.integrate(vol, frame, cam)
+    assert np.array_equal(changed, vol.weight > 0)
+    blocks = [changed[..., b:b + 256] for b in range(0, nx, 256)]
+    print(dims, [(int(b.sum()), b.size) for b in blocks])
+    assert len(blocks) == (nx + 255) // 256 >= 2
+    for b in blocks:
+        assert b.sum() >= min(30, b.size)
+    assert [int(b.sum()) for b in blocks] == WIDE_FIGURES[dims]
+    # the branches
+    assert vol.weight.max() >= 2 and (vol.weight == 0).any() and (vol.weight == 1).any()
+    assert ((vol.tsdf < 1) & (vol.weight > 0)).sum() > 50 and (vol.tsdf < 0).sum() > 10
+    assert np.isfinite(vol.tsdf).all() and np.isfinite(vol.color).all()
+    (frame, cam), (frame_o, cam_o) = views[0], views[1]
+    k, j, i = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    p = vol.origin.astype(np.float64) + float(vol.h) * np.stack([i, j, k], -1)
+    z = p @ np.asarray(cam_o.R, np.float64)[2] + float(cam_o.t[2])
+    assert (z <= tr.NEAR).sum() > 100 and (z > tr.NEAR).sum() > 100, "samples on both sides of the oblique camera"
+    ok, iu, iv = vol.views[0]
+    assert ok[1].any() and (iu[1][ok[1]] == i[1][ok[1]]).all() and (iv[1][ok[1]] == j[1][ok[1]]).all()   # u = i - 0.5, v = j - 0.5 exactly
+    for fr_ in (frame, views[2][0]):
+        a = fr_[..., 4]
+        d = fr_[..., 3] / np.where(a > 0, a, 1)
+        assert (a == 0).any() and ((a > 0) & (a < tr.MIN_ALPHA)).any() and np.isnan(a).any() and np.isnan(fr_[..., 3]).any() and (d < 0).any()
+    assert ok[1][:, 0].any() and ok[1][0, :].any(), "the low edges are inside"
+    fresh, _ = tr.wide_views(dims)
+    full = np.zeros((tr.EDGE_H, tr.EDGE_W, 5), f32)
+    full[..., 3:] = (3.0, 1.0)
+    ok_full = tr.integrate(fresh, full, cam)
+    assert not ok_full[1, :, 64:].any() and ok_full[1, :, :64].all(), "u + 0.5 = W exactly is outside"
+    # every kind of skip happens in the far blocks too: outside the frame, an unusable pixel, behind the truncation
+    far = [v[0][..., 256:] for v in vol.views[2:]]
+    assert any((~o).any() for o in far) and all(o.any() for o in far)
 
 
 @pytest.mark.parametrize("colors", [True, False])

@@ -109,6 +109,18 @@ def _corner(a, dx, dy, dz):
     return a[dz:dz + nz - 1, dy:dy + ny - 1, dx:dx + nx - 1]
 
 
+_CORNERS = [(c & 1, (c >> 1) & 1, c >> 2) for c in range(8)]
+
+
+def active_cells(tsdf, weight):
+    """(nz-1, ny-1, nx-1) bool: the cells with a vertex — all 8 corners observed, not all on one side.  Vertex ids count the
+    True entries in C order."""
+    inside, obs = np.asarray(tsdf) < 0, np.asarray(weight) > 0
+    all_obs = np.logical_and.reduce([_corner(obs, *c) for c in _CORNERS])
+    n_in = np.sum([_corner(inside, *c) for c in _CORNERS], 0)
+    return all_obs & (n_in > 0) & (n_in < 8)
+
+
 def extract(tsdf, weight, color, origin, h, dtype=f32):
     """gsr_mesh_count + gsr_mesh_emit -> Mesh(vertices (M, 3), faces (F, 3) int32, colors (M, 3) | None, M, quads)."""
     T = dtype
@@ -119,10 +131,8 @@ def extract(tsdf, weight, color, origin, h, dtype=f32):
         return empty
     o, h = np.asarray(origin, f32).astype(T), T(f32(h))
     inside, obs = tsdf < 0, weight > 0
-    corners = [(c & 1, (c >> 1) & 1, c >> 2) for c in range(8)]
-    all_obs = np.logical_and.reduce([_corner(obs, *c) for c in corners])
-    n_in = np.sum([_corner(inside, *c) for c in corners], 0)
-    active = all_obs & (n_in > 0) & (n_in < 8)                                   # (nz-1, ny-1, nx-1)
+    corners = _CORNERS
+    active = active_cells(tsdf, weight)                                         # (nz-1, ny-1, nx-1)
     M = int(active.sum())
     vid = np.full(active.shape, -1, np.int64)
     vid[active] = np.arange(M)                                                  # ascending i + (nx-1)·(j + (ny-1)·k)
@@ -337,6 +347,45 @@ def random_views(dims, color=False):
     return vol, views
 
 
+WIDE_DIMS = [(257, 3, 2), (300, 4, 3), (513, 5, 3), (770, 3, 2)]      # more than one 256-sample block of the integration in x
+WIDE_W, WIDE_H = 512, 32
+WIDE_POSES = ((+1, 1.0, 0.5), (-1, 1.5, -0.5), (+1, 0.7, 1.0), (-1, 1.2, 0.75), (+1, 0.9, -1.0))     # side, distance, turn in degrees
+# the first seed offset with which the case meets the conditions of tests/test_tsdf_cpu.py: with 0 no sample of the low edge
+# i = 0 of plane k = 1 is fused ((257, 3, 2), (770, 3, 2)), two of the 15 samples of column 512 meet a usable pixel in no view
+WIDE_RESEED = {(257, 3, 2): 100, (513, 5, 3): 100, (770, 3, 2): 100}
+
+
+def wide_camera(vol, side, dist, turn, W=WIDE_W, H=WIDE_H):
+    """A camera `dist` in front of the box's long face, looking across it (side = +1: along +z from below, -1: along -z from
+    above), turned `turn` degrees about its axis, with a focal length so short that the whole length of the box projects into
+    the frame: every sample is dist .. dist + 0.2 deep, within the truncation of most of random_frame's depths (0.3 .. 3.0) —
+    the oblique cameras of random_views see 3.25 deep at most, 52 samples of x."""
+    nx, ny, nz = vol.dims
+    ext = np.array([nx - 1, ny - 1, nz - 1]) * float(vol.h)
+    c = vol.origin.astype(np.float64) + 0.5 * ext
+    c[2] = float(vol.origin[2]) + (-dist if side > 0 else ext[2] + dist)
+    a = math.radians(turn)
+    z = np.array([0.0, 0.0, float(side)])
+    x = np.array([math.cos(a), math.sin(a), 0.0])
+    R = np.stack([x, np.cross(z, x), z])
+    fx = 0.46 * W * dist / (0.5 * ext[0])          # the ends of the box at 0.46·W from the centre at depth `dist`
+    return Cam(W, H, (fx, 12.0), (0.5, 0.45), R.astype(f32), (-R @ c).astype(f32))
+
+
+def wide_views(dims, color=False):
+    """-> (fresh fp32 volume, [(frame, camera)] x 7) for a volume longer than 256 samples in x: the exact-edge camera of
+    edge_setup (binary fractions; it sees i < 64), an oblique camera inside the box, and the five wide_cameras of WIDE_POSES,
+    which reach every 256-block of x; random frames with all their populations, one of them with 8 channels."""
+    vol, cam = edge_setup(dims)
+    vol = Volume(dims, vol.origin, vol.h, vol.trunc, color)
+    seed = 1000 * dims[0] + 10 * dims[1] + dims[2] + WIDE_RESEED.get(tuple(dims), 0)
+    views = [(random_frame(seed, EDGE_W, EDGE_H), cam),
+             (random_frame(seed + 1, 48, 40), oblique_camera(seed + 1, 48, 40, vol))]
+    for n, pose in enumerate(WIDE_POSES):
+        views.append((random_frame(seed + 2 + n, WIDE_W, WIDE_H, 8 if n == 0 else 5), wide_camera(vol, *pose)))
+    return vol, views
+
+
 def random_volume(dims, seed, color=True, p_zero=0.3):
     """tsdf uniform in [-1, 1], 30 % of the weights zero: ambiguous faces, missing cells, every edge case of the indexing
     (at 30 % one cell in 17 is active and quads are rare; p_zero = 0.05 gives the dense counterpart)."""
@@ -348,6 +397,66 @@ def random_volume(dims, seed, color=True, p_zero=0.3):
     if color:
         vol.color = rng.uniform(0, 1, (nz, ny, nx, 3)).astype(f32)
     return vol
+
+
+# ---- the extraction's plan, restated, and the volumes that take it past one run, one workgroup, one scan round ----
+MESH_RUN_CELLS, SCAN_ROUND = 2048, 1024
+
+
+def mesh_plan(dims):
+    """-> (rows, nruns, nblk, ncells): a wave walks a run of `rows` whole x-rows of cells of one slab k, `nruns` runs per slab,
+    `nblk` runs in all (the length of the scan)."""
+    nx, ny, nz = (int(d) for d in dims)
+    if min(nx, ny, nz) < 2:
+        return 1, 0, 0, 0
+    rows = max(1, MESH_RUN_CELLS // (nx - 1))
+    nruns = (ny - 1 + rows - 1) // rows
+    return rows, nruns, nruns * (nz - 1), (nx - 1) * (ny - 1) * (nz - 1)
+
+
+def run_of(dims, j, k):
+    """The index of the run of cell row (j, k) in the per-run words; j and k may be arrays."""
+    rows, nruns, _, _ = mesh_plan(dims)
+    return j // rows + nruns * k
+
+
+def mesh_scratch_bytes(dims):
+    """gsr_mesh_scratch_bytes: one 4-byte word per cell, one 8-byte word per run and the 8-byte total."""
+    _, _, nblk, ncells = mesh_plan(dims)
+    return 4 * ncells + 8 * (nblk + 1) if ncells else 0
+
+
+MultiRun = collections.namedtuple("MultiRun", "dims seed p_zero color plan")      # plan = (rows, nruns, nblk)
+MULTI_RUN_CASES = (
+    MultiRun((64, 5, 3), 21, 0.05, True, (32, 1, 2)),          # nx - 1 = 63: the cells fill one step, lane 63 carries the last column
+    MultiRun((65, 5, 3), 22, 0.05, True, (32, 1, 2)),          # 64: the second step holds one cell
+    MultiRun((127, 4, 3), 23, 0.05, True, (16, 1, 2)),         # 126: two full steps
+    MultiRun((130, 40, 5), 24, 0.05, True, (15, 3, 12)),       # three waves live, the fourth leaves; the last run has 9 rows of 15
+    MultiRun((513, 12, 4), 25, 0.05, True, (4, 3, 9)),         # the last run has 3 rows of 4
+    MultiRun((1025, 7, 3), 26, 0.05, False, (2, 3, 6)),        # nx - 1 = 1024: the last width with rows = 2; no colour
+    MultiRun((1026, 10, 3), 27, 0.05, True, (1, 9, 18)),       # rows = 1; three workgroups, the last with one live wave
+    MultiRun((2050, 4, 3), 28, 0.05, True, (1, 3, 6)),         # nx - 1 > 2048: the clamp of rows
+    MultiRun((1026, 42, 26), 29, 0.3, True, (1, 41, 1025)),    # nblk = 1024 + 1: a second scan round, the carry into one entry
+)
+_multi = {}
+
+
+def multi_run_name(case):
+    return f"multi-run {case.dims}" + ("" if case.color else ", no colour")
+
+
+def multi_run(case):
+    """-> (volume, its fp32 mesh) of a MULTI_RUN_CASES entry; computed once, treat as read-only."""
+    if case.dims not in _multi:
+        vol = random_volume(case.dims, case.seed, case.color, case.p_zero)
+        _multi[case.dims] = vol, extract_volume(vol)
+    return _multi[case.dims]
+
+
+def vertex_runs(vol):
+    """-> (run, slab, j) per vertex of `vol`'s mesh, in vertex order: the run id (run_of), the slab k and the cell row j."""
+    K, J, _ = np.nonzero(active_cells(vol.tsdf, vol.weight))
+    return run_of(vol.dims, J, K), K, J
 
 
 def one_cell_volume():
