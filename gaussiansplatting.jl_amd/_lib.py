@@ -153,8 +153,13 @@ class BwdSplit(C.Structure):
     _fields_ = [("n_big", C.c_uint32), ("n_mid8", C.c_uint32), ("n_mid4", C.c_uint32), ("split_len", C.c_uint32)]
 
 
+class BwdRowJob(C.Structure):
+    _fields_ = [("n_wg", C.c_uint32), ("slice", C.c_uint32)]
+
+
 POLICY_EXPORTS = ["gsr_policy_config_init", "gsr_policy_state_init", "gsr_policy_agg_plan", "gsr_policy_preprocess_form",
-                  "gsr_policy_form_is_open", "gsr_policy_begin_view", "gsr_policy_end_view", "gsr_policy_bwd_split"]
+                  "gsr_policy_form_is_open", "gsr_policy_begin_view", "gsr_policy_end_view", "gsr_policy_bwd_split",
+                  "gsr_policy_bwd_row_job"]
 
 
 def bind_policy(lib):
@@ -177,6 +182,8 @@ def bind_policy(lib):
     lib.gsr_policy_end_view.restype = None
     lib.gsr_policy_bwd_split.argtypes = [P(PolicyConfig), C.c_uint32, C.c_uint32, C.c_uint32, P(BwdSplit)]
     lib.gsr_policy_bwd_split.restype = None
+    lib.gsr_policy_bwd_row_job.argtypes = [P(PolicyConfig), C.c_int32, P(BwdRowJob)]
+    lib.gsr_policy_bwd_row_job.restype = None
     lib.gsr_bins_capacity_after.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32]
     lib.gsr_bins_capacity_after.restype = C.c_uint32
     return lib

@@ -459,6 +459,12 @@ __global__ __launch_bounds__(64, 1) void composite_bwd_kernel(int W, int H, int 
 // for at least the 73 that keep a seventh wave off the SIMD, so the kernel runs at the occupancy measured best for this walk
 // whatever its register count.  (A kernel of its own, not an instantiation of the template above: the occupancy attribute
 // __launch_bounds__(64, 1) expands to would win over a second one.)
+// THE ROW-INDEPENDENT JOB: workgroups from job.first_wg on (none when job.n_wg == 0: the grid ends there) walk no tile.  They
+// run bwd_row_job.h over a slice of the Gaussians — the direction Jacobian of the SH colour and the zero rows of culled
+// Gaussians, for the per-Gaussian backward behind this launch — and return.  Launched behind the tile workgroups, which go
+// longest list first, they take the wave slots that drain in the launch's last third and use the memory pipe this walk leaves
+// idle.  (Defined at the end of this file, under `#pragma clang fp contract(off)`: pergauss.hip's floats.)
+__device__ void bwd_row_job(const GsrRowJob& job, uint32_t w, int lane);
 __global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_eu(6, 6)))
 void composite_bwd_kernel_rgb_bg0(int W, int H, int grid_x,
                                                  const uint32_t* __restrict__ tile_start,
@@ -467,9 +473,13 @@ void composite_bwd_kernel_rgb_bg0(int W, int H, int grid_x,
                                                  const float* __restrict__ vpixels,
                                                  const uint32_t* __restrict__ n_contrib,
                                                  const float* __restrict__ final_T, GsrInst inst,
-                                                 GsrTierLists tiers) {
+                                                 GsrTierLists tiers, GsrRowJob job) {
     constexpr int C = 3, VC = 3;
     constexpr bool BG0 = true, ACC = false;
+    if (blockIdx.x >= job.first_wg) {
+        bwd_row_job(job, blockIdx.x - job.first_wg, (int)threadIdx.x);
+        return;
+    }
 #include "composite_bwd_body.inc"
 }
 
@@ -679,9 +689,11 @@ void gsr_launch_sort_composite_fwd(hipStream_t s, int channels, GsrCam cam, GsrT
     });
 }
 
-void gsr_launch_composite_bwd(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrStream stream, GsrFrame frame,
-                              const float* vpixels, GsrInst inst, uint32_t split_len, bool color_only, bool accurate) {
+bool gsr_launch_composite_bwd(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrStream stream, GsrFrame frame,
+                              const float* vpixels, GsrInst inst, const GsrRowJob* job, uint32_t split_len, bool color_only,
+                              bool accurate) {
     dim3 grid(cam.grid_x * cam.grid_y), block(64);
+    bool carried = false;
     Bg bg = make_bg(frame.background, channels);
     GsrTierLists none{};
     none.split_len = split_len;
@@ -697,9 +709,14 @@ void gsr_launch_composite_bwd(hipStream_t s, int channels, GsrCam cam, GsrTiles 
 #define LAUNCH3(CC, ZZ) do { if (accurate) LAUNCH_K(CC, false, 3, true); else LAUNCH_K(CC, ZZ, 3, false); } while (0)
     // (written out: the instantiation set is irregular on purpose — no BG0 with ACC or for colour-only, VC = 3 only for colour-only)
     if (channels == 3) {
-        if (bg0 && !accurate)
-            hipLaunchKernelGGL(composite_bwd_kernel_rgb_bg0, grid, block, 0, s, cam.width, cam.height, cam.grid_x, tiles.start, tiles.order,
-                               stream, bg, vpixels, frame.n_contrib, frame.final_T, inst, none);
+        if (bg0 && !accurate) {
+            // the row-independent job rides this launch: job.n_wg workgroups behind the tiles'
+            GsrRowJob j{};
+            if (job && job->n > 0 && job->n_wg > 0) { j = *job; carried = true; }
+            j.first_wg = grid.x;
+            hipLaunchKernelGGL(composite_bwd_kernel_rgb_bg0, dim3(grid.x + j.n_wg), block, 0, s, cam.width, cam.height, cam.grid_x,
+                               tiles.start, tiles.order, stream, bg, vpixels, frame.n_contrib, frame.final_T, inst, none, j);
+        }
         else LAUNCH2(3, false);
     }
     else if (color_only) {
@@ -713,6 +730,7 @@ void gsr_launch_composite_bwd(hipStream_t s, int channels, GsrCam cam, GsrTiles 
 #undef LAUNCH_K
 #undef LAUNCH2
 #undef LAUNCH3
+    return carried;
 }
 
 void gsr_launch_composite_bwd_listed(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrTierLists tiers,
@@ -733,3 +751,13 @@ void gsr_launch_composite_bwd_listed(hipStream_t s, int channels, GsrCam cam, Gs
         });
     });
 }
+
+// ---------------------------------------------------------------------------------
+// The row-independent job of composite_bwd_kernel_rgb_bg0 (declared above it).  Last in the file: from here on no expression is
+// contracted into FMAs, as in pergauss.hip, whose floats these are (bwd_row_job.h).
+// ---------------------------------------------------------------------------------
+#pragma clang fp contract(off)
+#include "bwd_row_job.h"
+namespace {
+__device__ void bwd_row_job(const GsrRowJob& job, uint32_t w, int lane) { gsr::bwd_row_job_run(job, w, lane); }
+}  // namespace

@@ -46,7 +46,7 @@ struct TunerEvents {
     }
 };
 
-constexpr int kHandleBufs = 33;  // rows of kBufs, the table of the handle's buffers below the handle (checked there)
+constexpr int kHandleBufs = 34;  // rows of kBufs, the table of the handle's buffers below the handle (checked there)
 
 bool valid_mode(int m) { return m == GSR_MODE_RGB || m == GSR_MODE_RGBD || m == GSR_MODE_RGBDN; }
 
@@ -75,6 +75,7 @@ struct gsr_handle {
     DevBuf overflow_fill;           // fill cursors of the scatter pass restricted to the lists beyond the bins' capacity
     // backward: per-instance gradient rows + instance position map; gstate.∇means_2d
     DevBuf rows, vmean2d;
+    DevBuf sh_jac;  // d rgb / d dir per Gaussian (9 floats): written by the row-independent job of composite_bwd's launch, read by pergauss_bwd
     DevBuf pose_part;  // pose gradient: 12 partial sums per workgroup of pergauss_bwd, added in a fixed order by its finishing launch
     // loss-head scratch
     DevBuf d0, d1, d2, partial;
@@ -156,6 +157,7 @@ constexpr BufRow kBufs[] = {
     BUF(dbg_flag, false, false, 1u),
     BUF(pose_part, true, true, 1u),       // per-workgroup pose-gradient partials: every slot is stored (zeros included) before it is summed
     BUF(comp, true, true, 1u),            // compensations of an antialiased forward (float): stale where radii == 0, read behind radii > 0
+    BUF(sh_jac, true, true, 1u),          // the backward's SH direction Jacobians (9 floats): written and read behind radii > 0 in one gsr_backward
 };
 #undef BUF
 template <class Pred> constexpr int count_bufs(Pred pred) {
@@ -164,8 +166,8 @@ template <class Pred> constexpr int count_bufs(Pred pred) {
     return n;
 }
 static_assert(sizeof(kBufs) / sizeof(kBufs[0]) == kHandleBufs, "gsr_handle::all holds one pointer per row");
-static_assert(count_bufs([](const BufRow& r) { return r.scene; }) == 18, "the scene buffers");
-static_assert(count_bufs([](const BufRow& r) { return r.fill_ok; }) == 11, "the GSR_DEBUG_FILL candidates");
+static_assert(count_bufs([](const BufRow& r) { return r.scene; }) == 19, "the scene buffers");
+static_assert(count_bufs([](const BufRow& r) { return r.fill_ok; }) == 12, "the GSR_DEBUG_FILL candidates");
 static_assert(count_bufs([](const BufRow& r) { return r.guard_word == 0u; }) == 3, "the id buffers whose guard word is 0");
 
 bool antialiased(const gsr_handle* h) { return (h->cfg.flags & GSR_FLAG_ANTIALIASED) != 0u; }
@@ -822,8 +824,9 @@ int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, floa
 // handle's second stream, forked from and joined back into the caller's stream.  The cut is a tier boundary of the
 // scan (> 8192, > 4096 or > 1024 instances): the deepest tiers first, as many as fit the limit.  Four waves cost
 // ~20 % more work per instance, so when long tiles are plentiful they stay with the main launch.
+// job: the row-independent job for the tile-walk launch to carry, or NULL; *job_carried: whether it did (gsr_launch_composite_bwd).
 static int launch_composite_bwd(gsr_handle* h, hipStream_t s, int C, const GsrCam& k, const float* background,
-                                const float* vpixels, bool color_only) {
+                                const float* vpixels, bool color_only, const GsrRowJob* job, bool* job_carried) {
     color_only = color_only && C > 3;
     // which tiers leave the main launch: gsr_policy_bwd_split (its limit: gsr_policy_config.bwd_split_max_tiles)
     gsr_bwd_split sp;
@@ -844,7 +847,8 @@ static int launch_composite_bwd(gsr_handle* h, hipStream_t s, int C, const GsrCa
                                         h->long_state.as<float>());
         HIPCHK(hipEventRecord(h->ev_join, h->aux_stream));
     }
-    gsr_launch_composite_bwd(s, C, k, tiles_of(h), stream_of(h), frame, vpixels, inst_of(h), tiers.split_len, color_only, accurate);
+    *job_carried = gsr_launch_composite_bwd(s, C, k, tiles_of(h), stream_of(h), frame, vpixels, inst_of(h), job, tiers.split_len,
+                                            color_only, accurate);
     if (n > 0) HIPCHK(hipStreamWaitEvent(s, h->ev_join, 0));
     return GSR_OK;
 }
@@ -866,16 +870,41 @@ static int check_backward_state(const gsr_handle* h, const gsr_inputs* in, const
 
 // ... and what both do once their arguments are checked: ∇means_2d goes to the caller's array or the handle's scratch, a
 // cotangent declared colour-only is checked where asked (GSR_CHECK_COLOR_COTANGENT), the compositing backward runs as its stage.
+// grads: gsr_backward's gradient arrays — the row-independent job of the :rgb tile walk writes the zero rows of culled Gaussians
+// into them and the SH direction Jacobians into the handle's sh_jac; NULL (the trainer tail): no job.  *job_carried: the per-
+// Gaussian kernel behind may read sh_jac and leave those rows alone (false wherever no launch carried the job: an empty view,
+// another mode or background, the accurate kernels, the factored SH gradient).
 static int composite_bwd_stage(gsr_handle* h, hipStream_t s, const gsr_inputs* in, const gsr_camera* cam, const float* vpixels,
-                               float* vmeans2d, uint32_t flags, GsrCam* k) {
+                               float* vmeans2d, uint32_t flags, GsrCam* k, const gsr_grads* grads, bool* job_carried) {
     int rc;
+    *job_carried = false;
     if (!vmeans2d && (rc = h->vmean2d.ensure(gaussian_bytes(h, in->n).vmean2d, 1.25f))) return rc;
     h->vmean2d_cur = vmeans2d ? reinterpret_cast<float2*>(vmeans2d) : h->vmean2d.as<float2>();
     const bool color_only = (flags & GSR_GRADS_COLOR_COTANGENT) != 0u;
     if (color_only && (rc = check_color_cotangent(h, vpixels, s))) return rc;
     *k = make_cam(h, cam);
+    GsrRowJob job{};
+    // (the conditions of the one launch that carries it — composite_bwd_kernel_rgb_bg0 — so that no other backward allocates sh_jac.
+    //  It grows here, with the slack of the forward's per-Gaussian scratch, not in gsr_reserve: what a reserve allocates per mode is
+    //  pinned byte for byte by tests/test_gpu_handle_bytes.py, and most :rgb handles — a background, another precision — never use it)
+    const bool bg_zero = in->background[0] == 0.0f && in->background[1] == 0.0f && in->background[2] == 0.0f;
+    if (grads && grads->vshs && !grads->vcolors && h->cfg.mode == 3 && bg_zero && h->cfg.grad_precision == GSR_DEFAULT &&
+        h->last_D > 0) {
+        gsr_bwd_row_job rj;
+        gsr_policy_bwd_row_job(&h->pcfg, in->n, &rj);
+        if ((rc = h->sh_jac.ensure(gaussian_bytes(h, in->n).sh_jac, 1.25f))) return rc;
+        job.n_wg = rj.n_wg; job.slice = rj.slice;
+        job.n = in->n; job.K = in->n_coeffs; job.degree = in->sh_degree;
+        job.means = in->means; job.shs = in->shs; job.radii = h->radii_cur;
+        for (int c = 0; c < 3; c++) job.center[c] = k->center[c];
+        job.jac = h->sh_jac.as<float>();
+        job.vmeans = grads->vmeans; job.vshs = grads->vshs; job.vopac = grads->vopacities; job.vscales = grads->vscales;
+        job.vrots = reinterpret_cast<float4*>(grads->vrotations);
+    }
     StageScope sc(h->prof, ST_COMPOSITE_BWD, s);
-    if (h->last_D > 0 && (rc = launch_composite_bwd(h, s, h->cfg.mode, *k, in->background, vpixels, color_only))) return rc;
+    if (h->last_D > 0 &&
+        (rc = launch_composite_bwd(h, s, h->cfg.mode, *k, in->background, vpixels, color_only, job.n_wg ? &job : nullptr, job_carried)))
+        return rc;
     sc.close();
     return GSR_OK;
 }
@@ -903,13 +932,14 @@ int gsr_backward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, con
     // in a fixed order — the "zero_acc" stage stays in the table, empty)
     if (g->vR && (rc = h->pose_part.ensure(gaussian_bytes(h, n).pose_part, 1.25f))) return rc;
     GsrCam k;
-    if ((rc = composite_bwd_stage(h, s, in, cam, vpixels, g->vmeans2d, g->flags, &k))) return rc;
+    bool job_carried = false;
+    if ((rc = composite_bwd_stage(h, s, in, cam, vpixels, g->vmeans2d, g->flags, &k, g, &job_carried))) return rc;
     StageScope sc8(h->prof, ST_PERGAUSS_BWD, s);
     gsr_launch_pergauss_bwd(s, n, in->n_coeffs, in->sh_degree, C, in->means, in->scales, in->rotations, in->shs, k,
                             geom_of(h), inst_of(h), h->vmean2d_cur, g->vmeans, g->vshs, g->vopacities,
                             g->vscales, g->vrotations, g->vR, g->vt, h->pose_part.as<float>(), g->vcolors,
                             /*fp32_chain=*/h->cfg.grad_precision == GSR_GRAD_FP32_REFERENCE,
-                            antialiased(h) ? in->opacities : nullptr, comp_of(h));
+                            antialiased(h) ? in->opacities : nullptr, comp_of(h), job_carried ? h->sh_jac.as<float>() : nullptr);
     sc8.close();
     HIPCHK(hipGetLastError());
     h->bwd_valid = true;
@@ -1089,7 +1119,8 @@ int gsr_backward_trainer_tail(gsr_handle* h, const gsr_inputs* in, const gsr_cam
     hipStream_t s = (hipStream_t)stream_v;
     const int C = h->cfg.mode;
     GsrCam k;
-    if ((rc = composite_bwd_stage(h, s, in, cam, vpixels, st->vmeans2d, st->flags, &k))) return rc;
+    bool no_job = false;
+    if ((rc = composite_bwd_stage(h, s, in, cam, vpixels, st->vmeans2d, st->flags, &k, nullptr, &no_job))) return rc;
     StageScope sc12(h->prof, ST_PERGAUSS_BWD, s);
     const gsr::TailState S = gsr_make_tail_state(st->theta, st->mu, st->nu, lr_t, st->beta1, st->beta2, st->eps,
                                                  st->scale_dims, st->shs, st->opacities_act, st->scales_act);

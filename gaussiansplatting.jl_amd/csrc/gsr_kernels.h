@@ -126,7 +126,10 @@ void gsr_launch_pergauss_bwd(hipStream_t s, int n, int K, int degree, int channe
                              float* vcolors /* (3,N) or NULL: factored SH gradient instead of vshs */,
                              bool fp32_chain /* ∇scales / ∇rotations by the reference's fp32 trees (GSR_GRAD_FP32_REFERENCE) */,
                              const float* opac, const float* comp /* antialiased handle: the caller's opacities and the forward's
-                                                                     compensations (∇add_blur joins both chains); else both NULL */);
+                                                                     compensations (∇add_blur joins both chains); else both NULL */,
+                             const float* sh_jac /* the composite_bwd launch before carried the row-independent job (GsrRowJob): its
+                                                    Jacobian buffer, read instead of the SH bands, and the rows of culled Gaussians
+                                                    are left to the job; NULL: everything is this launch's */);
 // backward epilogue = trainer tail (single-GPU step): no gradient arrays, the parameters / Adam states in S are
 // updated in place and the activated copies of the next forward written (adam_math.h)
 namespace gsr { struct TailState; }
@@ -190,8 +193,22 @@ void gsr_launch_composite_fwd(hipStream_t s, int channels, GsrCam cam, GsrTiles 
 void gsr_launch_sort_composite_fwd(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrKeys keys, GsrGeom geom,
                                    GsrStream stream, GsrFrame frame, uint32_t cap_instances,
                                    bool keep_backward_state /* false (GSR_FORWARD_ONLY): the sorted stream and ids are not stored */);
-void gsr_launch_composite_bwd(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrStream stream, GsrFrame frame,
-                              const float* vpixels, GsrInst inst,
+// The row-independent job (bwd_row_job.h): n_wg extra single-wave workgroups behind the tile workgroups of the :rgb
+// zero-background launch, `slice` Gaussians each (gsr_policy_bwd_row_job).  Of a visible Gaussian they store the nine floats of
+// d rgb / d dir (splat_math.h: sh_dir_jacobian) into jac, of a culled one the zero rows of every gradient array — what the
+// per-Gaussian backward otherwise does from the SH bands, in a kernel that leaves the memory pipe idle.
+struct GsrRowJob {
+    uint32_t first_wg;      // the tile workgroups of the launch: the job's are first_wg ... first_wg + n_wg - 1
+    uint32_t n_wg, slice;   // n_wg * slice >= n
+    int n, K, degree;
+    const float* means; const float* shs; const int32_t* radii;
+    float center[3];        // the camera centre (view_dir)
+    float* jac;             // 9 floats per Gaussian, written where radii > 0 (degree > 0)
+    float* vmeans; float* vshs; float* vopac; float* vscales; float4* vrots;  // zeros where radii <= 0
+};
+// returns whether the launch carried `job` (the :rgb zero-background kernel at the default precision only; else it is ignored)
+bool gsr_launch_composite_bwd(hipStream_t s, int channels, GsrCam cam, GsrTiles tiles, GsrStream stream, GsrFrame frame,
+                              const float* vpixels, GsrInst inst, const GsrRowJob* job /* or NULL */,
                               uint32_t split_len /* tiles with a longer list are left to the listed launch */,
                               bool color_only /* channels >= 3 of vpixels are zeros (the loss head's cotangent) */,
                               bool accurate /* libm exp + IEEE division per pixel (gsr_config.grad_precision); the caller then

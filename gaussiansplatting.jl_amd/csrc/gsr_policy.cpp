@@ -264,4 +264,19 @@ void gsr_policy_bwd_split(const gsr_policy_config* cfg, uint32_t n_mid4, uint32_
     if (n == 0) out->split_len = 0xFFFFFFFFu;  // nothing to split (or the deepest tier alone is already plentiful)
 }
 
+// The job's workgroups are single waves that stream a slice of the Gaussians, 64 per trip.  About 512 of them: enough to keep
+// the memory pipe busy from the wave slots the tile walk's last third frees, each short against that third.  A slice is at
+// least 256 Gaussians (four trips: a small scene does not pay a launch slot per 64) and at most 2048 (a large one gets more
+// workgroups, not longer ones).
+void gsr_policy_bwd_row_job(const gsr_policy_config* cfg, int32_t n, gsr_bwd_row_job* out) {
+    (void)cfg;
+    out->n_wg = out->slice = 0;
+    if (n <= 0) return;
+    const uint32_t un = (uint32_t)n, target_wg = 512u;
+    uint32_t trips = (un + 64u * target_wg - 1u) / (64u * target_wg);
+    trips = trips < 4u ? 4u : trips > 32u ? 32u : trips;
+    out->slice = 64u * trips;
+    out->n_wg = (un + out->slice - 1u) / out->slice;
+}
+
 }  // extern "C"

@@ -13,6 +13,7 @@ struct gsr_gaussian_bytes {
     size_t vmean2d;    // float2 (the backward's)
     size_t pose_part;  // the backward's pose-gradient partials
     size_t comp;       // float: add_blur's compensations, antialiased handles only
+    size_t sh_jac;     // 9 floats: d rgb / d dir of the backward's row-independent job, :rgb only; grown by that backward, not by gsr_reserve
 };
 
 // n Gaussians in a C-channel mode; pose_partial_floats: pergauss.hip's gsr_pose_partial_floats(n).  The forward's arrays hold
@@ -27,6 +28,7 @@ inline gsr_gaussian_bytes gsr_sizes_per_gaussian(size_t n, int C, size_t pose_pa
     b.vmean2d = n * 8;
     b.pose_part = pose_partial_floats * 4;
     b.comp = antialiased ? nn * 4 : 0;
+    b.sh_jac = C == 3 ? n * 36 : 0;
     return b;
 }
 

@@ -445,13 +445,24 @@ __device__ __forceinline__ void normal_bwd(int channels, const float acc[16], co
 //   in: sh = the coefficients of band 1 on (3 floats per band; band 0 has no directional gradient), p, the camera centre,
 //   vc = the colour cotangent with the clamp mask applied.  out: b = the SH basis at the view direction (the coefficient
 //   gradient is the outer product b x vc, stored by store_or_apply_sh), vmsh = the SH stage's share of ∇means.  Depends on DEG.
-template <int DEG>
+//   JAC: sh = the nine floats of d rgb / d dir that the row-independent job of composite_bwd's launch stored for this Gaussian
+//   (splat_math.h: sh_dir_jacobian, the expression evaluated here otherwise — the same bits), read instead of the SH bands.
+template <int DEG, bool JAC = false>
 __device__ __forceinline__ void sh_bwd(const float* sh, const float p[3], const GsrCam& cam, const float vc[3], float b[16],
                                        float vmsh[3]) {
     float d0[3], dir[3];
     view_dir(p, cam.center, d0, dir);
     sh_basis<DEG>(dir, b);
     float dcx[3] = {0, 0, 0}, dcy[3] = {0, 0, 0}, dcz[3] = {0, 0, 0};
+    if constexpr (JAC) {
+        // (sh = the Gaussian's nine floats, as the row-independent job of composite_bwd's launch stored them)
+        if (DEG > 0) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) { dcx[c] = sh[c]; dcy[c] = sh[3 + c]; dcz[c] = sh[6 + c]; }
+        }
+    } else {
+    // (the text of splat_math.h's sh_dir_jacobian, kept here: through the function the compiler folds the negated constants of
+    //  band 3 another way — the same floats, but not this kernel's instructions)
     if (DEG > 0) {
         const float x = dir[0], y = dir[1], z = dir[2];
 #pragma unroll
@@ -487,6 +498,7 @@ __device__ __forceinline__ void sh_bwd(const float* sh, const float p[3], const 
             }
         }
     }
+    }
     float vdir[3];
     vdir[0] = dcx[0] * vc[0] + dcx[1] * vc[1] + dcx[2] * vc[2];
     vdir[1] = dcy[0] * vc[0] + dcy[1] * vc[1] + dcy[2] * vc[2];
@@ -504,7 +516,8 @@ __device__ __forceinline__ void sh_bwd(const float* sh, const float p[3], const 
 //   in: per thread, the factors f_b (basis), f_vc (colour cotangent), f_nb (bands carrying a gradient; 0: culled), and for
 //   FUSED the Gaussian's own gradients f_vmean, f_vopac, f_vs, f_vq.  out: !FUSED: vshs (unless vcolors: the factored
 //   form left the kernel already); FUSED: the trainer tail applied to TS (adam_math.h).  Depends on FUSED.
-template <bool FUSED>
+//   JAC (!FUSED, no vcolors): the rows of culled Gaussians are not this launch's — the row-independent job wrote their zeros.
+template <bool FUSED, bool JAC = false>
 __device__ __forceinline__ void store_or_apply_sh(int i, int n, int K, float* __restrict__ vshs, const float* vcolors,
                                                   const gsr::TailState& TS, const float f_b[16], const float f_vc[3],
                                                   int f_nb, const float f_vmean[3], float f_vopac, const float f_vs[3],
@@ -525,10 +538,12 @@ __device__ __forceinline__ void store_or_apply_sh(int i, int n, int K, float* __
     if constexpr (!FUSED) {
         if (!vcolors) {
             __syncthreads();
-            store_sh_rows(vshs, i0, cnt, K3, [&](int il, int j) {
+            auto value = [&](int il, int j) {
                 const int k = j / 3, c = j - 3 * k;
                 return k < tail_nb[il] ? tail_b[il][k] * tail_vc[il][c] : 0.0f;
-            });
+            };
+            if constexpr (JAC) gsr::store_sh_rows_where(vshs, i0, cnt, K3, value, [&](int il) { return tail_nb[il] != 0; });
+            else store_sh_rows(vshs, i0, cnt, K3, value);
         }
     }
     if constexpr (FUSED) {
@@ -566,7 +581,11 @@ __device__ __forceinline__ void store_or_apply_sh(int i, int n, int K, float* __
 // record.  ∇opacity = acc[3] * rho is with respect to the caller's o; v rho = acc[3] * o goes through ∇add_blur into the 2-D
 // covariance cotangent of both chains (project_bwd, scales_rots_bwd_f64).  `comp` = the forward's compensations, `opac` = the
 // caller's opacities (FUSED: TS.opac_act): 8 more bytes per Gaussian.  A template parameter for the same reason.
-template <int DEG, bool FUSED, bool F32CHAIN = false, bool AA = false>
+// JAC (!FUSED, !F32CHAIN, no vcolors; gsr_launch_pergauss_bwd): the launch behind a composite_bwd launch that carried the
+// row-independent job (bwd_row_job.h).  `shs` is then the job's Jacobian buffer, nine floats per Gaussian (the SH bands are not
+// read at all: 36 bytes instead of up to 180 per visible Gaussian), and the gradient rows of a culled Gaussian are left alone:
+// the job wrote their zeros.  ∇means_2d is still written for every Gaussian here.  A template parameter for the same reason.
+template <int DEG, bool FUSED, bool F32CHAIN = false, bool AA = false, bool JAC = false>
 __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int channels, const float* __restrict__ means,
                                                            const float* __restrict__ scales,
                                                            const float4* __restrict__ rots,
@@ -619,7 +638,7 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
     if (i < n) {
         if (!visible) {
             vmean2d_out[i] = make_float2(0.0f, 0.0f);
-            if constexpr (!FUSED) {
+            if constexpr (!FUSED && !JAC) {
 #pragma unroll
                 for (int c = 0; c < 3; c++) { vmeans[3 * i + c] = 0.0f; vscales[3 * i + c] = 0.0f; }
                 vrots[i] = make_float4(0, 0, 0, 0);
@@ -681,12 +700,12 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
 
             // 5. ∇SH
             // coefficients of band k >= 1 (band 0 has no directional gradient)
-            const float* sh = FUSED ? TS.rest + (size_t)3 * (K - 1) * i : shs + (size_t)3 * K * i + 3;
+            const float* sh = JAC ? shs + (size_t)9 * i : FUSED ? TS.rest + (size_t)3 * (K - 1) * i : shs + (size_t)3 * K * i + 3;
             const uint32_t clamp_bits = __float_as_uint(rec.q2.y);
             float vc[3] = {a0.x * (1.0f - (float)(clamp_bits & 1u)), a0.y * (1.0f - (float)((clamp_bits >> 1) & 1u)),
                            a0.z * (1.0f - (float)((clamp_bits >> 2) & 1u))};
             float b[16], vmsh[3];
-            sh_bwd<DEG>(sh, p, cam, vc, b, vmsh);
+            sh_bwd<DEG, JAC>(sh, p, cam, vc, b, vmsh);
             constexpr int NB = (DEG + 1) * (DEG + 1);
             if (!FUSED && vcolors) {
                 // factored form for the multi-view exchange: ∇shs of a view is the outer product
@@ -709,7 +728,7 @@ __global__ __launch_bounds__(256, 1) void pergauss_bwd_kernel(int n, int K, int 
         }
     }
     // 6. the epilogues: ∇shs stored (FUSED: the trainer tail applied) by the whole workgroup, then the pose partials
-    store_or_apply_sh<FUSED>(i, n, K, vshs, vcolors, TS, f_b, f_vc, f_nb, f_vmean, f_vopac, f_vs, f_vq);
+    store_or_apply_sh<FUSED, JAC>(i, n, K, vshs, vcolors, TS, f_b, f_vc, f_nb, f_vmean, f_vopac, f_vs, f_vq);
     if (pose_part) {  // projection.jl:243-256: thresholded per Gaussian, then summed
         // wave sum -> workgroup sum in LDS -> the workgroup's 12 partials (∇R column-major, ∇t) to ITS slot of pose_part, zeros
         // included (the scratch needs no clearing); pose_final_kernel adds the slots in a fixed order — float atomics onto the 12
@@ -782,7 +801,7 @@ void gsr_launch_pergauss_bwd(hipStream_t s, int n, int K, int degree, int channe
                              const float* scales, const float* rots, const float* shs, GsrCam cam, GsrGeom geom,
                              GsrInst inst, float2* vmean2d, float* vmeans, float* vshs, float* vopac,
                              float* vscales, float* vrots, float* vR, float* vt, float* pose_part, float* vcolors,
-                             bool fp32_chain, const float* opac, const float* comp) {
+                             bool fp32_chain, const float* opac, const float* comp, const float* sh_jac) {
     if (n <= 0) return;
     dim3 grid((n + 255) / 256), block(256);
     const float4* r4 = reinterpret_cast<const float4*>(rots);
@@ -794,6 +813,16 @@ void gsr_launch_pergauss_bwd(hipStream_t s, int n, int K, int degree, int channe
             constexpr bool F32 = f;
             dispatch_bool(comp != nullptr, [&](auto a) {
                 constexpr bool AA = a;
+                // sh_jac: the composite_bwd launch before this one carried the row-independent job (default precision, ∇shs
+                // in full): the Jacobian buffer takes the place of `shs`
+                if constexpr (!F32) {
+                    if (sh_jac && !vcolors) {
+                        hipLaunchKernelGGL((pergauss_bwd_kernel<DEG, false, false, AA, true>), grid, block, 0, s, n, K, channels, means,
+                                           scales, r4, sh_jac, cam, geom, inst, vmean2d, vmeans, vshs, vopac, vscales, vr4,
+                                           vR ? pose_part : nullptr, vcolors, none, opac, comp);
+                        return;
+                    }
+                }
                 hipLaunchKernelGGL((pergauss_bwd_kernel<DEG, false, F32, AA>), grid, block, 0, s, n, K, channels, means, scales,
                                    r4, shs, cam, geom, inst, vmean2d, vmeans, vshs, vopac, vscales, vr4,
                                    vR ? pose_part : nullptr, vcolors, none, opac, comp);

@@ -70,4 +70,24 @@ __device__ __forceinline__ void store_sh_rows(float* __restrict__ vshs, int i0, 
     for (int e = 4 * total4 + threadIdx.x; e < total; e += 256) dst[e] = element(e);
 }
 
+// ... where only some rows are this launch's to write: keep(il) says whether Gaussian il's row is.  A float4 that spans the
+// rows of two Gaussians goes out when either is kept (value() of the other's floats is what its own writer stores).
+template <class Value, class Keep>
+__device__ __forceinline__ void store_sh_rows_where(float* __restrict__ vshs, int i0, int cnt, int K3, Value value, Keep keep) {
+    const uint32_t inv = (1u << 20) / (uint32_t)K3 + 1u;
+    float* __restrict__ dst = vshs + (size_t)i0 * K3;
+    const int total = cnt * K3;
+    auto owner = [&](int e) { return (int)(((uint32_t)e * inv) >> 20); };
+    auto element = [&](int e) {
+        const int il = owner(e);
+        return value(il, e - il * K3);
+    };
+    const int total4 = (((uintptr_t)dst & 15) == 0) ? total >> 2 : 0;
+    for (int f = threadIdx.x; f < total4; f += 256)
+        if (keep(owner(4 * f)) || keep(owner(4 * f + 3)))
+            reinterpret_cast<float4*>(dst)[f] = make_float4(element(4 * f), element(4 * f + 1), element(4 * f + 2), element(4 * f + 3));
+    for (int e = 4 * total4 + threadIdx.x; e < total; e += 256)
+        if (keep(owner(e))) dst[e] = element(e);
+}
+
 }  // namespace gsr

@@ -170,4 +170,50 @@ __device__ __forceinline__ void view_dir(const float p[3], const float* center, 
     dir[0] = d0[0] * inv; dir[1] = d0[1] * inv; dir[2] = d0[2] * inv;
 }
 
+// The direction Jacobian of the SH colour before the clamp (spherical_harmonics.jl:76-172): dcx[c], dcy[c], dcz[c] =
+// d rgb_c / d dir_x, _y, _z.  sh = the coefficients of band 1 on (3 floats per band; band 0 has no directional gradient).
+// It depends on nothing the compositing backward produces: the per-Gaussian backward evaluates it in place, or reads the nine
+// floats the row-independent job of composite_bwd's launch left for it (bwd_row_job.h) — one definition, the same bits.
+template <int DEG>
+__device__ __forceinline__ void sh_dir_jacobian(const float* sh, const float dir[3], float dcx[3], float dcy[3], float dcz[3]) {
+    auto coeff = [&](int k, int c) { return sh[3 * (k - 1) + c]; };  // band k >= 1, channel c
+#pragma unroll
+    for (int c = 0; c < 3; c++) { dcx[c] = 0.0f; dcy[c] = 0.0f; dcz[c] = 0.0f; }
+    if (DEG > 0) {
+        const float x = dir[0], y = dir[1], z = dir[2];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            dcx[c] = -SH1 * coeff(3, c); dcy[c] = -SH1 * coeff(1, c); dcz[c] = SH1 * coeff(2, c);
+        }
+        if (DEG > 1) {
+            float x2 = x * x, y2 = y * y, z2 = z * z, xy = x * y, xz = x * z, yz = y * z;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                dcx[c] = dcx[c] + SH2C1 * y * coeff(4, c) + SH2C3 * 2.0f * -x * coeff(6, c) +
+                         SH2C4 * z * coeff(7, c) + SH2C5 * 2.0f * x * coeff(8, c);
+                dcy[c] = dcy[c] + SH2C1 * x * coeff(4, c) + SH2C2 * z * coeff(5, c) +
+                         SH2C3 * 2.0f * -y * coeff(6, c) + SH2C5 * 2.0f * -y * coeff(8, c);
+                dcz[c] = dcz[c] + SH2C2 * y * coeff(5, c) + SH2C3 * 4.0f * z * coeff(6, c) +
+                         SH2C4 * x * coeff(7, c);
+            }
+            if (DEG > 2) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    dcx[c] = dcx[c] + SH3C1 * coeff(9, c) * 3.0f * 2.0f * xy + SH3C2 * coeff(10, c) * yz +
+                             SH3C3 * coeff(11, c) * -2.0f * xy + SH3C4 * coeff(12, c) * -3.0f * 2.0f * xz +
+                             SH3C5 * coeff(13, c) * (-3.0f * x2 + 4.0f * z2 - y2) +
+                             SH3C6 * coeff(14, c) * 2.0f * xz + SH3C7 * coeff(15, c) * 3.0f * (x2 - y2);
+                    dcy[c] = dcy[c] + SH3C1 * coeff(9, c) * 3.0f * (x2 - y2) + SH3C2 * coeff(10, c) * xz +
+                             SH3C3 * coeff(11, c) * (-3.0f * y2 + 4.0f * z2 - x2) +
+                             SH3C4 * coeff(12, c) * -3.0f * 2.0f * yz + SH3C5 * coeff(13, c) * -2.0f * xy +
+                             SH3C6 * coeff(14, c) * -2.0f * yz + SH3C7 * coeff(15, c) * -3.0f * 2.0f * xy;
+                    dcz[c] = dcz[c] + SH3C2 * coeff(10, c) * xy + SH3C3 * coeff(11, c) * 4.0f * 2.0f * yz +
+                             SH3C4 * coeff(12, c) * 3.0f * (2.0f * z2 - x2 - y2) +
+                             SH3C5 * coeff(13, c) * 4.0f * 2.0f * xz + SH3C6 * coeff(14, c) * (x2 - y2);
+                }
+            }
+        }
+    }
+}
+
 }  // namespace gsr::splat

@@ -160,6 +160,13 @@ GSR_API void gsr_policy_end_view(const gsr_policy_config* cfg, gsr_policy_state*
 GSR_API void gsr_policy_bwd_split(const gsr_policy_config* cfg, uint32_t n_mid4, uint32_t n_mid8, uint32_t n_big,
                                   gsr_bwd_split* out);
 
+/* The row-independent job that rides the :rgb backward's tile-walk launch: n_wg single-wave workgroups behind the tiles', each
+ * over `slice` Gaussians (a multiple of 64), n_wg * slice >= n; n <= 0: none (n_wg = slice = 0). */
+typedef struct gsr_bwd_row_job {
+    uint32_t n_wg, slice;
+} gsr_bwd_row_job;
+GSR_API void gsr_policy_bwd_row_job(const gsr_policy_config* cfg, int32_t n, gsr_bwd_row_job* out);
+
 #ifdef __cplusplus
 }
 #endif
