@@ -58,6 +58,14 @@ class Aux(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Scores(C.Structure):  # gsr_scores
+    _fields_ = [("max_weight", C.c_void_p), ("hits", C.c_void_p), ("weight_sum", C.c_void_p), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+SCORE_MAX_WEIGHT, SCORE_WEIGHT_SUM, SCORE_HITS = 0, 1, 2  # gsr_contribution_mask's rules
+
+
 class Stats(C.Structure):
     _fields_ = [("n_rendered", C.c_int64), ("n_visible", C.c_int32), ("max_tile_instances", C.c_int32),
                 ("generation", C.c_uint64), ("bins_bytes", C.c_int64), ("compact_binning", C.c_int32), ("preprocess_form", C.c_int32),
@@ -190,6 +198,7 @@ def bind_policy(lib):
 
 
 EXPORTS = ["gsr_create", "gsr_destroy", "gsr_release_scene_buffers", "gsr_memory_usage", "gsr_debug_check_guards", "gsr_reserve", "gsr_drop_forward", "gsr_bins_capacity_after", "gsr_forward",
+           "gsr_forward_scored", "gsr_contribution_mask",
            "gsr_backward", "gsr_host_wait_policy", "gsr_buffer", "gsr_copy_buffer", "gsr_ssim_forward", "gsr_ssim_backward", "gsr_loss_l1_ssim",
            "gsr_ssim_precision", "gsr_get_ssim_precision", "gsr_preprocess_form", "gsr_get_preprocess_form",
            "gsr_allreduce_grads", "gsr_last_error_string", "gsr_version", "gsr_abi_version", "gsr_check_abi", "gsr_profile_enable",
@@ -260,6 +269,9 @@ def load():
     lib.gsr_drop_forward.argtypes = [vp]  # ends the live forward as a reallocating gsr_reserve does (gsr.h)
     bind_policy(lib)
     lib.gsr_forward.argtypes = [vp, C.POINTER(Inputs), C.POINTER(CameraS), vp, C.POINTER(Aux), vp, C.POINTER(Stats)]
+    lib.gsr_forward_scored.argtypes = [vp, C.POINTER(Inputs), C.POINTER(CameraS), vp, C.POINTER(Aux), C.POINTER(Scores), vp,
+                                       C.POINTER(Stats)]
+    lib.gsr_contribution_mask.argtypes = [C.c_int64, C.c_int, C.c_double, vp, vp, vp, vp, vp]
     lib.gsr_backward.argtypes = [vp, C.POINTER(Inputs), C.POINTER(CameraS), vp, C.POINTER(Grads), vp]
     lib.gsr_host_wait_policy.argtypes = [i32, i32, i32]
     lib.gsr_buffer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]

@@ -115,12 +115,66 @@ __device__ __forceinline__ void fwd_update_under_exec(FwdPixel<C>& p, unsigned l
     if constexpr (C == 8 && AUX)  asm volatile(GSR_FWD_REGION(GSR_FWD_RGB GSR_FWD_D GSR_FWD_N GSR_FWD_UNC) : GSR_FWD_OUT_N, [unc] "+v"(p.unc) : GSR_FWD_IN_N : "scc");
 }
 
+// ---- per-Gaussian contribution scores (gsr_scores; the SCORED instantiations) ----
+// What a set of views uses of a Gaussian, from the blend weights w = alpha·T of the visits that blend it: max_p w is RadSplat's
+// pruning score (Niemeyer et al. 2024, eq. 7-8: prune below 0.01), sum_p w and the hit count are the importance terms of
+// LightGaussian (Fan et al. 2023, global significance) and Mini-Splatting (Fang & Wang 2024).  No reference counterpart: the
+// reference exports the per-PIXEL sum of the same w (uncertainties, render.jl:109) and nothing per Gaussian.
+// All three are INTEGERS — max of the bits of w (w > 0: float order is unsigned order), a count, and the sum of
+// q = rne(w · 2^24) (w <= 0.99: q < 2^24, a wave's 64 of them < 2^30, the four waves of a tile < 2^32) — so every grouping of
+// the updates gives the same bits: per wave by DPP (gsr::wave_max_u32 / wave_sum_u32), per tile instance in N x 3 words of LDS
+// (ds_max_u32 / ds_add_u32 from one lane of each quadrant wave), per Gaussian by ONE triple of non-returning global integer
+// atomics per tile instance that was blended at all.  No float atomic anywhere.
+// (SCORED inside the kernel bodies shared as text — composite_fwd_*_body.inc: dependent on the kernel's template parameters, so
+// that the discarded branches of the unscored kernels are not instantiated)
+template <int C, bool S> inline constexpr bool scored_form = S;
+template <bool ON, int N> struct ScoreLds {};
+template <int N> struct ScoreLds<true, N> { uint32_t v[3][N]; };  // [0] max of bits(w), [1] hits, [2] sum of q — per staged entry
+// the byte address of an LDS object, as the DS instructions take it
+__device__ __forceinline__ uint32_t lds_address(const void* p) {
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
+}
+// One visit's update of entry `j`'s three words (sc = LDS address of word [0][0]): the wave's totals are wave-uniform, so ONE
+// lane issues the three DS atomics — under EXEC = lane 0, set and restored on the scalar unit like fwd_update_under_exec's
+// region, not as `if (lane == 0)`: a branch per visit.  (The DS unit takes EXEC at issue; nothing in the region depends on a
+// VALU write of EXEC or of an SGPR.  The compiler does not count these DS operations: score_drain waits for them.)
+template <int N>
+__device__ __forceinline__ void score_visit(uint32_t sc, int j, unsigned long long ok, float w) {
+    const bool mine = __builtin_amdgcn_inverse_ballot_w64(ok);
+    const uint32_t wmax = gsr::wave_max_u32(mine ? __float_as_uint(w) : 0u);
+    const uint32_t qsum = gsr::wave_sum_u32(mine ? __float2uint_rn(__fmul_rn(w, 16777216.0f)) : 0u);
+    const uint32_t hits = (uint32_t)__builtin_popcountll(ok);
+    const uint32_t addr = sc + 4u * (uint32_t)j;
+    unsigned long long saved;
+    asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, 1\n\t"
+                 "ds_max_u32 %[a], %[m]\n\tds_add_u32 %[a], %[h] offset:%[o1]\n\tds_add_u32 %[a], %[q] offset:%[o2]\n\t"
+                 "s_mov_b64 exec, %[sv]"
+                 : [sv] "=&s"(saved)
+                 : [a] "v"(addr), [m] "v"(wmax), [h] "v"(hits), [q] "v"(qsum), [o1] "n"(4 * N), [o2] "n"(8 * N)
+                 : "memory");
+}
+// Entry `k`'s words to its Gaussian `id`, by one thread, and zero again for the next chunk / batch.  Called behind a barrier
+// of every wave that updates the words; the inline DS atomics are invisible to the compiler's counters, hence the explicit wait
+// in front of that barrier (score_drain).
+__device__ __forceinline__ void score_drain() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+template <int N>
+__device__ __forceinline__ void score_flush(ScoreLds<true, N>& sl, int k, uint32_t id, const GsrScores& out) {
+    const uint32_t hits = sl.v[1][k];
+    if (hits) {
+        if (out.max_weight) atomicMax(out.max_weight + id, sl.v[0][k]);
+        if (out.hits) atomicAdd(out.hits + id, (unsigned long long)hits);
+        if (out.weight_sum) atomicAdd(out.weight_sum + id, (unsigned long long)sl.v[2][k]);
+        sl.v[0][k] = 0u; sl.v[1][k] = 0u; sl.v[2][k] = 0u;
+    }
+}
+
 // Blend the LDS entries whose bits are set in `m` (bit k <-> entry e0 + k), front to back.  Plane 2 of an entry holds
 // (third colour, 1-BASED LIST POSITION, depth, -): `last` is then a move between two VGPRs, not a v_mov of the scalar
 // position.  `ids`: Gaussian id of entry 0, 1, ... (only read for the covisibility output).
-template <int C, bool AUX, int N>
+// SCORED: every visit also updates the three score words of its entry (`sc`: LDS address of ScoreLds::v, score_visit).
+template <int C, bool AUX, int N, bool SCORED = false>
 __device__ __forceinline__ void fwd_blend_selected(FwdPixel<C>& p, unsigned long long m, const LdsSplats<C, N>& e, int e0, float fx, float fy,
-                                                   const uint32_t* __restrict__ ids, uint8_t* __restrict__ covis) {
+                                                   const uint32_t* __restrict__ ids, uint8_t* __restrict__ covis, uint32_t sc = 0u) {
     while (m) {
         const int jb = __builtin_ctzll(m), j = e0 + jb;
         m &= m - 1;
@@ -155,6 +209,7 @@ __device__ __forceinline__ void fwd_blend_selected(FwdPixel<C>& p, unsigned long
         const unsigned long long seen = AUX ? ok & wave_ballot(p.T > 0.5f) & (covis ? ~0ull : 0ull) : 0ull;
         fwd_update_under_exec<C, AUX>(p, ok, Tn, c2.y, w, f);
         if (AUX && __builtin_amdgcn_inverse_ballot_w64(seen)) covis[ids[jb]] = 1;
+        if constexpr (SCORED) score_visit<N>(sc, j, ok, w);
     }
 }
 
@@ -173,14 +228,15 @@ __device__ __forceinline__ void fwd_pixel_store(const FwdPixel<C>& p, bool insid
 }
 
 // One quadrant wave walking its tile's slice of the GLOBAL stream (e: its 64-entry LDS staging array).
-template <int C, bool AUX>
+template <int C, bool AUX, bool SCORED = false>
 __device__ __forceinline__ void composite_fwd_quadrant(int W, int H, int grid_x, int tile, int quad, int lane,
                                                        const uint32_t* __restrict__ tile_start, GsrStream stream,
                                                        const Bg& bg, float* __restrict__ image,
                                                        uint32_t* __restrict__ n_contrib, float* __restrict__ final_T,
                                                        const uint32_t* __restrict__ values_sorted,
                                                        uint8_t* __restrict__ covis, float* __restrict__ uncert,
-                                                       LdsSplats<C, 64>& e) {
+                                                       LdsSplats<C, 64>& e, ScoreLds<SCORED, 64>* sl = nullptr,
+                                                       GsrScores scores = GsrScores{nullptr, nullptr, nullptr}) {
     const int tile_x = tile % grid_x, tile_y = tile / grid_x;
     const uint32_t strip_bits = 0x10000u << quad;  // the instance's quadrant bit (tile_mask.h)
     const int px = tile_x * GSR_TILE + 8 * (quad & 1) + (lane & 7), py = tile_y * GSR_TILE + 8 * (quad >> 1) + (lane >> 3);
@@ -190,6 +246,9 @@ __device__ __forceinline__ void composite_fwd_quadrant(int W, int H, int grid_x,
     const int to_do = (int)(end - start);
     FwdPixel<C> p;
     fwd_pixel_init<C>(p, inside);
+    if constexpr (SCORED) {  // (single wave, in-order LDS: visible to the first batch's atomics)
+        sl->v[0][lane] = 0u; sl->v[1][lane] = 0u; sl->v[2][lane] = 0u;
+    }
     for (int base = 0; base < to_do; base += 64) {
         if (p.done == ~0ull) break;  // the whole quadrant has saturated (a scalar compare)
         const int jj = base + lane;
@@ -210,10 +269,21 @@ __device__ __forceinline__ void composite_fwd_quadrant(int W, int H, int grid_x,
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
+        if constexpr (SCORED) {
+            // the batch's words, per staged entry: lane <-> entry, flushed per batch — one triple of global atomics per
+            // (quadrant, instance) this wave blended: the tier walk is the rare path
+            fwd_blend_selected<C, AUX, 64, true>(p, m, e, 0, fx, fy, values_sorted + start + base, covis, lds_address(&sl->v[0][0]));
+            score_drain();
+            __builtin_amdgcn_wave_barrier();
+            if (cand) score_flush<64>(*sl, lane, values_sorted[start + jj], scores);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        } else
         fwd_blend_selected<C, AUX, 64>(p, m, e, 0, fx, fy, values_sorted + start + base, covis);
     }
     fwd_pixel_store<C, AUX>(p, inside, px, py, W, bg, image, n_contrib, final_T, uncert);
 }
+
 
 template <int C, bool AUX>
 __global__ __launch_bounds__(64) void composite_fwd_strip_kernel(int W, int H, int grid_x,
@@ -225,25 +295,24 @@ __global__ __launch_bounds__(64) void composite_fwd_strip_kernel(int W, int H, i
                                                                  const uint32_t* __restrict__ values_sorted,
                                                                  uint8_t* __restrict__ covis,
                                                                  float* __restrict__ uncert, GsrTierLists tiers) {
-    __shared__ LdsSplats<C, 64> e;
-    // 1-D grid, workgroup id -> (launch slot, strip).  Workgroups are dealt round-robin to the 8
-    // XCDs (each with its own L2): the 4 strips of a tile get ids that are equal mod 8, so a tile's
-    // splat stream is fetched into ONE L2; slots follow tile_order (longest lists first).
-    const int id = blockIdx.x, k = id >> 3;
-    const int quad = k & 3;  // 8x8 quadrant (qx = quad & 1, qy = quad >> 1) of the tile
-    const int slot = ((k >> 2) << 3) | (id & 7);
-    int tile;
-    if (tile_order) {  // every tile, in launch order
-        if (slot >= grid_x * ((H + GSR_TILE - 1) / GSR_TILE)) return;
-        tile = (int)tile_order[slot];
-    } else {           // only the tiles of the scan's tier lists (the fused kernel did the others), longest tier first
-        if ((uint32_t)slot >= tiers.n_big + tiers.n_mid8 + tiers.n_mid4) return;
-        GSR_TIER_TILE(tile, tiers, (uint32_t)slot);
-        // beside the fused launch (gsr_forward): these few waves are the forward's critical path and share their SIMDs with it
-        if (tiers.split_len) __builtin_amdgcn_s_setprio(3);
-    }
-    composite_fwd_quadrant<C, AUX>(W, H, grid_x, tile, quad, (int)threadIdx.x, tile_start, stream, bg, image,
-                                   n_contrib, final_T, values_sorted, covis, uncert, e);
+    constexpr bool SCORED = scored_form<C, false>;
+    const GsrScores scores{nullptr, nullptr, nullptr};
+#include "composite_fwd_strip_body.inc"
+}
+// The scored twin: the same walk with the per-Gaussian contribution scores (gsr_scores).  A kernel NAME of its own, not a
+// template argument of the kernel above: the unscored instantiations keep their names, parameter lists and code.
+template <int C, bool AUX>
+__global__ __launch_bounds__(64) void composite_fwd_strip_scored_kernel(int W, int H, int grid_x,
+                                                                 const uint32_t* __restrict__ tile_start,
+                                                                 const uint32_t* __restrict__ tile_order,
+                                                                 GsrStream stream, Bg bg, float* __restrict__ image,
+                                                                 uint32_t* __restrict__ n_contrib,
+                                                                 float* __restrict__ final_T,
+                                                                 const uint32_t* __restrict__ values_sorted,
+                                                                 uint8_t* __restrict__ covis,
+                                                                 float* __restrict__ uncert, GsrTierLists tiers, GsrScores scores) {
+    constexpr bool SCORED = scored_form<C, true>;
+#include "composite_fwd_strip_body.inc"
 }
 
 // Sort + forward of a tile in ONE workgroup (fixed-capacity bins; a tile with more than 1024 instances is left to the
@@ -260,6 +329,7 @@ __global__ __launch_bounds__(64) void composite_fwd_strip_kernel(int W, int H, i
 // separate sort and forward launches).
 // KEEP = false (GSR_FORWARD_ONLY, the reference's non-AD branch rasterizer.jl:214-248): the emitted chunk lives in LDS only —
 // the 52-68 bytes per instance of stream + id that nothing but the backward reads are not stored.
+
 template <int C, bool AUX, bool KEEP>
 // (8 waves per SIMD: the sort needs 66 VGPRs left to itself; at 64 it does not spill and an eighth workgroup fits the CU)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void sort_composite_fwd_kernel(int W, int H, int grid_x,
@@ -276,72 +346,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void s
                                                                  uint8_t* __restrict__ covis, float* __restrict__ uncert,
                                                                  const uint32_t* __restrict__ totals,
                                                                  uint32_t cap_instances) {
-    // instances resident in LDS at a time: one per thread and round (512 / 1024 — whole lists — cost 5 / 3 workgroups per CU
-    // instead of 8: +13 % / +48 %, profiles/r03/experiments/small_ab_notes.txt)
-    constexpr int CHUNK = 256;
-    __shared__ uint32_t ids[1024];
-    __shared__ LdsSplats<C, CHUNK> e;
-    // Bins of >= 1024 keys hold every list this launch takes complete whatever the longest one
-    // is (lists beyond the capacity are tier tiles; the host scatters their keys again) — smaller bins must hold them all
-    if (totals[GSR_TOTAL_D] > cap_instances || (totals[GSR_TOTAL_MAX_LIST] > bin_cap && bin_cap < 1024u)) return;
-    const int tile = (int)tile_order[blockIdx.x];  // launch order: longest lists first
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t start = tile_start[tile], end = tile_start[tile + 1];
-    const uint32_t n = end - start;
-    if (tid == 0) {
-        tile_count[tile] = 0u;  // counter ready for the next view
-        // identify_tile_range! (utils.jl:56-78): empty tiles keep the (0,0) of the prior fill!
-        ranges[2 * tile] = n ? start : 0u;
-        ranges[2 * tile + 1] = n ? end : 0u;
-    }
-    if (n > 1024u) return;  // a tier launch's tile (sort and forward)
-    const int tile_x = tile % grid_x, tile_y = tile / grid_x;
-    const int X0 = tile_x * GSR_TILE, Y0 = tile_y * GSR_TILE;
-    const int quad = wave;  // 8x8 quadrant (qx = quad & 1, qy = quad >> 1) of the tile
-    const uint32_t strip_bits = 0x10000u << quad;
-    const int px = X0 + 8 * (quad & 1) + (lane & 7), py = Y0 + 8 * (quad >> 1) + (lane >> 3);
-    const bool inside = px < W && py < H;
-    float fx = (float)px, fy = (float)py;
-    // (opaque to the optimiser: left alone it re-converts px / py inside the per-visit loop to save two registers —
-    // two more VALU instructions per visit in a VALU-bound loop)
-    asm volatile("" : "+v"(fx), "+v"(fy));
-    FwdPixel<C> p;
-    fwd_pixel_init<C>(p, inside);
-    if (n > 0) {
-        // (the sorting wave rotates with the workgroup id: wave w of every workgroup sits on SIMD w of its CU, and a fixed
-        // sorter would load one SIMD of four with all the sorting)
-        if (wave == (int)(blockIdx.x & 3u)) gsr_sort::wave_sort_ids_any(ids, n, lane, bins + (size_t)tile * bin_cap);
-        __syncthreads();
-        for (uint32_t cbase = 0; cbase < n; cbase += CHUNK) {
-            const uint32_t i = cbase + (uint32_t)tid;
-            if (i < n) {
-                const uint32_t id = ids[i];
-                const gsr_sort::InstanceVals v = gsr_sort::instance_vals<C>(id, X0, Y0, geom);
-                if (KEEP) {
-                    const uint32_t pos = start + i;
-                    values_sorted[pos] = id;
-                    stream.s0[pos] = v.v0; stream.s1[pos] = v.v1; stream.s2[pos] = v.v2;
-                    if (C > 3) stream.s3[pos] = v.v3;
-                }
-                e(0, tid) = v.v0; e(1, tid) = v.v1;
-                // LDS copy: (third colour, 1-based list position, depth | :rgb blend threshold, footprint masks)
-                e(2, tid) = make_float4(v.v2.x, __uint_as_float(i + 1u), v.v2.z, v.v2.w);
-                if (C > 3) e(C > 3 ? 3 : 0, tid) = v.v3;
-            }
-            __syncthreads();
-            const int cnt = (int)min((uint32_t)CHUNK, n - cbase);
-            for (int b = 0; b < cnt; b += 64) {
-                if (p.done == ~0ull) break;  // the whole quadrant has saturated (a scalar compare)
-                const int k = b + lane;
-                const bool cand = k < cnt && (__float_as_uint(e(2, k).w) & strip_bits) != 0u;
-                const unsigned long long m = wave_ballot(cand);
-                if (m == 0ull) continue;
-                fwd_blend_selected<C, AUX, CHUNK>(p, m, e, b, fx, fy, ids + cbase + b, covis);
-            }
-            if (cbase + CHUNK < n) __syncthreads();  // the chunk is consumed before the next one overwrites it
-        }
-    }
-    fwd_pixel_store<C, AUX>(p, inside, px, py, W, bg, image, n_contrib, final_T, uncert);
+    constexpr bool SCORED = scored_form<C, false>;
+    const GsrScores scores{nullptr, nullptr, nullptr};
+#include "composite_fwd_fused_body.inc"
+}
+// The scored twin (a kernel name of its own, like composite_fwd_strip_scored_kernel).  :rgbd / :rgbdn fit six workgroups per CU
+// with the score words in LDS and are compiled for six waves per SIMD.
+template <int C, bool AUX, bool KEEP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C > 3 ? 6 : 8))) void sort_composite_fwd_scored_kernel(int W, int H, int grid_x,
+                                                                 const uint32_t* __restrict__ tile_start,
+                                                                 const uint32_t* __restrict__ tile_order,
+                                                                 uint32_t* __restrict__ tile_count,
+                                                                 const uint64_t* __restrict__ bins, uint32_t bin_cap,
+                                                                 GsrGeom geom, GsrStream stream, Bg bg,
+                                                                 float* __restrict__ image,
+                                                                 uint32_t* __restrict__ n_contrib,
+                                                                 float* __restrict__ final_T,
+                                                                 uint32_t* __restrict__ values_sorted,
+                                                                 uint32_t* __restrict__ ranges,
+                                                                 uint8_t* __restrict__ covis, float* __restrict__ uncert,
+                                                                 const uint32_t* __restrict__ totals,
+                                                                 uint32_t cap_instances, GsrScores scores) {
+    constexpr bool SCORED = scored_form<C, true>;
+#include "composite_fwd_fused_body.inc"
 }
 
 // ---------------------------------------------------------------------------------
@@ -663,6 +690,11 @@ void gsr_launch_composite_fwd(hipStream_t s, int channels, GsrCam cam, GsrTiles 
         constexpr int CH = c;
         gsr::dispatch_bool(frame.covis || frame.uncert, [&](auto a) {
             constexpr bool AUX = a;
+            if (frame.scores.any())
+                hipLaunchKernelGGL((composite_fwd_strip_scored_kernel<CH, AUX>), grid, block, 0, s, cam.width, cam.height,
+                                   cam.grid_x, tiles.start, tile_order, stream, bg, frame.image, frame.n_contrib, frame.final_T,
+                                   frame.values_sorted, frame.covis, frame.uncert, tiers, frame.scores);
+            else
             hipLaunchKernelGGL((composite_fwd_strip_kernel<CH, AUX>), grid, block, 0, s, cam.width, cam.height, cam.grid_x,
                                tiles.start, tile_order, stream, bg, frame.image, frame.n_contrib, frame.final_T,
                                frame.values_sorted, frame.covis, frame.uncert, tiers);
@@ -680,6 +712,12 @@ void gsr_launch_sort_composite_fwd(hipStream_t s, int channels, GsrCam cam, GsrT
             constexpr bool AUX = a;
             gsr::dispatch_bool(keep_backward_state, [&](auto k) {
                 constexpr bool KEEP = k;
+                if (frame.scores.any())
+                    hipLaunchKernelGGL((sort_composite_fwd_scored_kernel<CH, AUX, KEEP>), grid, block, 0, s, cam.width,
+                                       cam.height, cam.grid_x, tiles.start, tiles.order, tiles.count, keys.bins, keys.cap, geom,
+                                       stream, bg, frame.image, frame.n_contrib, frame.final_T, frame.values_sorted, tiles.ranges,
+                                       frame.covis, frame.uncert, tiles.totals, cap_instances, frame.scores);
+                else
                 hipLaunchKernelGGL((sort_composite_fwd_kernel<CH, AUX, KEEP>), grid, block, 0, s, cam.width, cam.height,
                                    cam.grid_x, tiles.start, tiles.order, tiles.count, keys.bins, keys.cap, geom, stream, bg,
                                    frame.image, frame.n_contrib, frame.final_T, frame.values_sorted, tiles.ranges,

@@ -285,6 +285,22 @@ void gsr_launch_densify_mask(hipStream_t s, int kind, long long n, long long n_g
                        scale_dims, opacities, max_radii, thr, gamma, min_opacity, max_screen_size, mask);
 }
 
+// gsr_contribution_mask: the keep mask of one integer compare per Gaussian.  words = 1: 32-bit scores (the bits of max_weight),
+// 2: 64-bit (hits, weight_sum).
+__global__ __launch_bounds__(256) void contribution_mask_kernel(long long n, int words, const void* __restrict__ score,
+                                                                unsigned long long threshold, uint8_t* __restrict__ valid) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long v = words == 1 ? (unsigned long long)((const uint32_t*)score)[i] : ((const unsigned long long*)score)[i];
+    valid[i] = v >= threshold ? 1 : 0;
+}
+
+void gsr_launch_contribution_mask(hipStream_t s, long long n, int words, const void* score, unsigned long long threshold,
+                                  uint8_t* valid) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(contribution_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, words, score, threshold, valid);
+}
+
 void gsr_launch_compose_rows(hipStream_t s, int n_groups, const void* const* src, void* const* dst, const int* row_words,
                              const int* new_zero, const uint32_t* keep_idx, long long n_keep, const uint32_t* sel_idx,
                              long long n_sel, int reps) {

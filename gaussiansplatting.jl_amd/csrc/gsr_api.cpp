@@ -203,9 +203,12 @@ GsrTiles tiles_of(const gsr_handle* h) {
 }
 // the handle's fixed-capacity bins (cap == 0: preprocess only counts)
 GsrKeys bins_of(const gsr_handle* h, uint32_t cap) { return GsrKeys{h->bins.as<uint64_t>(), cap, nullptr}; }
-GsrFrame frame_of(const gsr_handle* h, const float* background, float* image, const gsr_aux* aux) {
+GsrFrame frame_of(const gsr_handle* h, const float* background, float* image, const gsr_aux* aux,
+                  const gsr_scores* scores = nullptr) {
     return GsrFrame{background, image, h->n_contrib.as<uint32_t>(), h->final_T.as<float>(), h->values_sorted.as<uint32_t>(),
-                    aux ? aux->covisibilities : nullptr, aux ? aux->uncertainties : nullptr};
+                    aux ? aux->covisibilities : nullptr, aux ? aux->uncertainties : nullptr,
+                    scores ? GsrScores{scores->max_weight, (unsigned long long*)scores->hits, (unsigned long long*)scores->weight_sum}
+                           : GsrScores{nullptr, nullptr, nullptr}};
 }
 
 // gsr_preprocess_form: -1 by scene and grid size (default), 0 direct, 1 aggregating wherever its LDS fits; the same rule as
@@ -518,6 +521,7 @@ struct FwdView {
     hipStream_t s;
     int C, n;
     const gsr_inputs* in; float* image_out; const gsr_aux* aux; gsr_stats* stats;  // the caller's
+    const gsr_scores* scores;  // gsr_forward_scored's, or NULL
     bool fwd_only;
     GsrCam k;
     gsr_view_plan plan;
@@ -532,13 +536,20 @@ struct FwdView {
 
 // Argument checks and per-Gaussian scratch; a call that gets through them is the handle's forward number `generation`.
 static int fwd_begin(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, float* image_out, const gsr_aux* aux,
-                     void* stream_v, gsr_stats* stats, FwdView& v) {
+                     const gsr_scores* scores, void* stream_v, gsr_stats* stats, FwdView& v) {
+    // (the scores' own checks first: they need no handle)
+    if (scores && (scores->flags || scores->reserved))
+        return fail(GSR_E_INVALID_ARG, "unknown gsr_scores.flags 0x%x / reserved 0x%x", scores->flags, scores->reserved);
+    if (scores && ((uintptr_t)scores->max_weight % 4 || (uintptr_t)scores->hits % 8 || (uintptr_t)scores->weight_sum % 8))
+        return fail(GSR_E_INVALID_ARG, "gsr_scores: max_weight must be 4-byte, hits and weight_sum 8-byte aligned");
     int rc = check_inputs(h, in, cam);
     if (rc) return rc;
     if (!image_out) return fail(GSR_E_INVALID_ARG, "null image_out");
     if (aux && ((aux->flags & ~(uint32_t)GSR_FORWARD_ONLY) || aux->reserved))
         return fail(GSR_E_INVALID_ARG, "unknown gsr_aux.flags 0x%x / reserved 0x%x", aux->flags, aux->reserved);
-    v.in = in; v.image_out = image_out; v.aux = aux; v.stats = stats;
+    // (no array asked for: the unscored kernels, as with scores == NULL)
+    if (scores && !scores->max_weight && !scores->hits && !scores->weight_sum) scores = nullptr;
+    v.in = in; v.image_out = image_out; v.aux = aux; v.stats = stats; v.scores = scores;
     v.fwd_only = aux && (aux->flags & GSR_FORWARD_ONLY);
     v.s = (hipStream_t)stream_v;
     v.C = h->cfg.mode; v.n = in->n;
@@ -571,7 +582,7 @@ static int fwd_begin(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam,
 static void launch_fused(gsr_handle* h, const FwdView& v, hipStream_t fs) {
     StageScope sc3(h->prof, ST_SORT_COMPOSITE_FWD, fs);
     gsr_launch_sort_composite_fwd(fs, v.C, v.k, tiles_of(h), bins_of(h, v.plan.bin_cap_view), geom_of(h), stream_of(h),
-                                  frame_of(h, v.in->background, v.image_out, v.aux), (uint32_t)v.cap_instances,
+                                  frame_of(h, v.in->background, v.image_out, v.aux, v.scores), (uint32_t)v.cap_instances,
                                   /*keep_backward_state=*/!v.fwd_only);
     sc3.close();
 }
@@ -790,7 +801,7 @@ static int fwd_sort_and_walk(gsr_handle* h, const FwdView& v) {
     StageScope sc5(h->prof, ST_COMPOSITE_FWD, ws);
     // after the fused launch only the tiles of the tier lists are left; otherwise every tile
     const GsrTierLists tiers{h->big_list.as<uint32_t>(), (uint32_t)h->n_tiles, v.n_big, v.n_mid8, v.n_mid4, beside ? 1u : 0u};
-    gsr_launch_composite_fwd(ws, v.C, v.k, tiles_of(h), stream_of(h), frame_of(h, v.in->background, v.image_out, v.aux),
+    gsr_launch_composite_fwd(ws, v.C, v.k, tiles_of(h), stream_of(h), frame_of(h, v.in->background, v.image_out, v.aux, v.scores),
                              fused_done ? &tiers : nullptr);
     sc5.close();
     if (beside) {
@@ -803,9 +814,15 @@ static int fwd_sort_and_walk(gsr_handle* h, const FwdView& v) {
 
 int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, float* image_out, const gsr_aux* aux,
                 void* stream_v, gsr_stats* stats) {
+    return gsr_forward_scored(h, in, cam, image_out, aux, nullptr, stream_v, stats);
+}
+
+// The forward, with or without gsr_scores (the scored kernels of composite.hip only where an array was asked for).
+int gsr_forward_scored(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, float* image_out, const gsr_aux* aux,
+                       const gsr_scores* scores, void* stream_v, gsr_stats* stats) {
     FwdView v;
     int rc;
-    if ((rc = fwd_begin(h, in, cam, image_out, aux, stream_v, stats, v))) return rc;
+    if ((rc = fwd_begin(h, in, cam, image_out, aux, scores, stream_v, stats, v))) return rc;
     if ((rc = fwd_plan_and_bin(h, v))) return rc;
     if ((rc = fwd_read_back(h, v))) return rc;
     if (v.D == 0) return fwd_empty_view(h, v);

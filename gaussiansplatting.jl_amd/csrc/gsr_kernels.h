@@ -90,6 +90,11 @@ struct GsrTiles {
 // Where a view's unsorted keys are.  cap > 0: keys of tile t at bins + t * cap — unless its list is longer than cap: the complete
 // list is then at overflow + start[t]; cap == 0: compact layout, keys of tile t at bins + start[t].
 struct GsrKeys { uint64_t* bins; uint32_t cap; const uint64_t* overflow /* or NULL */; };
+// gsr_scores: the per-Gaussian contribution scores a scored forward accumulates into (composite.hip); any of them NULL
+struct GsrScores {
+    uint32_t* max_weight; unsigned long long* hits; unsigned long long* weight_sum;
+    __host__ __device__ bool any() const { return max_weight || hits || weight_sum; }
+};
 // The frame a view renders into, and what the backward reads of it.
 struct GsrFrame {
     const float* background;  // host, 3 floats
@@ -97,6 +102,7 @@ struct GsrFrame {
     uint32_t* n_contrib; float* final_T;
     uint32_t* values_sorted;  // sorted ids, per instance
     uint8_t* covis; float* uncert;  // gsr_aux.covisibilities / uncertainties, or NULL
+    GsrScores scores;               // gsr_forward_scored's, or all NULL: the unscored kernels
 };
 
 // ---- preprocess.hip (compiled with -ffp-contract=off: bit-reproducible fp32) ----
@@ -245,6 +251,9 @@ void gsr_launch_grad_mean(hipStream_t s, long long n, const float* accum, const 
 void gsr_launch_densify_mask(hipStream_t s, int kind, long long n, long long n_grad, const float* grad, const float* scales,
                              int scale_dims, const float* opacities, const int32_t* max_radii, float thr, float gamma,
                              float min_opacity, int max_screen_size, uint8_t* mask);
+// valid[i] = score[i] >= threshold as unsigned integers; words = 1: uint32 scores, 2: uint64 (gsr_contribution_mask)
+void gsr_launch_contribution_mask(hipStream_t s, long long n, int words, const void* score, unsigned long long threshold,
+                                  uint8_t* valid);
 void gsr_launch_compose_rows(hipStream_t s, int n_groups, const void* const* src, void* const* dst, const int* row_words,
                              const int* new_zero, const uint32_t* keep_idx, long long n_keep, const uint32_t* sel_idx,
                              long long n_sel, int reps);

@@ -542,6 +542,35 @@ int gsr_densify_mask(int32_t kind, int64_t n, int64_t n_grad, const float* grad,
     return launched();
 }
 
+int gsr_contribution_mask(int64_t n, int rule, double threshold, const uint32_t* max_weight, const uint64_t* hits,
+                          const uint64_t* weight_sum, uint8_t* valid_out, void* stream) {
+    if (rule < GSR_SCORE_MAX_WEIGHT || rule > GSR_SCORE_HITS) return fail(GSR_E_INVALID_ARG, "unknown score rule %d", rule);
+    if (n < 0) return fail(GSR_E_INVALID_ARG, "negative n");
+    if (!(threshold >= 0.0) || !std::isfinite(threshold)) return fail(GSR_E_INVALID_ARG, "threshold must be finite and >= 0");
+    // the threshold in the score's own integers (gsr.h): the bits of the fp32 threshold | ceil(t · 2^24) | ceil(t)
+    unsigned long long thr;
+    const void* score;
+    if (rule == GSR_SCORE_MAX_WEIGHT) {
+        const float t = (float)threshold;
+        if (!std::isfinite(t)) return fail(GSR_E_INVALID_ARG, "threshold does not fit fp32");
+        uint32_t bits;
+        __builtin_memcpy(&bits, &t, 4);
+        thr = bits;
+        score = max_weight;
+    } else {
+        const double t = std::ceil(rule == GSR_SCORE_WEIGHT_SUM ? threshold * 16777216.0 : threshold);
+        if (!(t < 18446744073709551616.0)) return fail(GSR_E_INVALID_ARG, "threshold beyond 64 bits");
+        thr = (unsigned long long)t;
+        score = rule == GSR_SCORE_WEIGHT_SUM ? (const void*)weight_sum : (const void*)hits;
+    }
+    if (n == 0) return GSR_OK;
+    if (!score || !valid_out) return fail(GSR_E_INVALID_ARG, "null array");
+    if ((uintptr_t)score % (rule == GSR_SCORE_MAX_WEIGHT ? 4 : 8))
+        return fail(GSR_E_INVALID_ARG, "max_weight must be 4-byte, hits and weight_sum 8-byte aligned");
+    gsr_launch_contribution_mask((hipStream_t)stream, n, rule == GSR_SCORE_MAX_WEIGHT ? 1 : 2, score, thr, valid_out);
+    return launched();
+}
+
 int gsr_compose_rows(const gsr_compose_group* groups, int32_t n_groups, const uint32_t* keep_idx, int64_t n_keep,
                      const uint32_t* sel_idx, int64_t n_sel, int32_t reps, void* stream) {
     if (n_groups < 0 || n_groups > GSR_COMPOSE_MAX_GROUPS || (n_groups > 0 && !groups))

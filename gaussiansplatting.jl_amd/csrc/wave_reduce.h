@@ -43,6 +43,27 @@ __device__ __forceinline__ float dpp_shr4(float v) {  // lane i <- lane i-4 with
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xF, 0xF, true));
 }
 
+// Integer max / sum over the 64 lanes of a wave, the result wave-uniform (in SGPRs): four DPP steps inside the rows of 16 —
+// xor 1, xor 2, row_half_mirror, row_mirror: max and + are commutative, so a mirror pairs as well as an xor — with the
+// identity 0 for the lanes a row shift leaves out (the compiler folds each into one v_max_u32_dpp / v_add_u32_dpp), then the
+// four row totals through v_readlane and three scalar operations.  Integer results: no order to state.
+#define GSR_DPP_U32(v, ctrl) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), (ctrl), 0xF, 0xF, true))
+__device__ __forceinline__ uint32_t umax32(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    v = umax32(v, GSR_DPP_U32(v, 0xB1)); v = umax32(v, GSR_DPP_U32(v, 0x4E));
+    v = umax32(v, GSR_DPP_U32(v, 0x141)); v = umax32(v, GSR_DPP_U32(v, 0x140));
+    const uint32_t r0 = __builtin_amdgcn_readlane((int)v, 0), r1 = __builtin_amdgcn_readlane((int)v, 16);
+    const uint32_t r2 = __builtin_amdgcn_readlane((int)v, 32), r3 = __builtin_amdgcn_readlane((int)v, 48);
+    return umax32(umax32(r0, r1), umax32(r2, r3));
+}
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+    v += GSR_DPP_U32(v, 0xB1); v += GSR_DPP_U32(v, 0x4E);
+    v += GSR_DPP_U32(v, 0x141); v += GSR_DPP_U32(v, 0x140);
+    const uint32_t r0 = __builtin_amdgcn_readlane((int)v, 0), r1 = __builtin_amdgcn_readlane((int)v, 16);
+    const uint32_t r2 = __builtin_amdgcn_readlane((int)v, 32), r3 = __builtin_amdgcn_readlane((int)v, 48);
+    return (r0 + r1) + (r2 + r3);
+}
+
 // sum over the lane pair (i, i^32): lanes 0-31 get a's, lanes 32-63 get b's
 __device__ __forceinline__ float pair_swap32(float a, float b) {
     auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);

@@ -363,10 +363,13 @@ class GaussianRasterizer:
         return cs
 
     def forward_raw(self, means_3d, shs, opacities, scales, rotations, camera, sh_degree, background, R_w2c=None,
-                    t_w2c=None, covisibilities=None, uncertainties=None, image_out=None, forward_only: bool = False):
+                    t_w2c=None, covisibilities=None, uncertainties=None, image_out=None, forward_only: bool = False,
+                    scores=None):
         """`rasterize` (rasterizer.jl:255-408).  forward_only=True (GSR_FORWARD_ONLY): the render of the reference's non-AD
         branch (rasterizer.jl:214-248: `validate`, GUI, render-views) — same image bit for bit, no backward state kept
-        (a third of the forward's HBM traffic); `backward_raw` after it raises GSR_E_STATE."""
+        (a third of the forward's HBM traffic); `backward_raw` after it raises GSR_E_STATE.
+        scores: a `contribution.ContributionScores` of this model's N — the view's per-Gaussian contribution scores are
+        accumulated into it (gsr_forward_scored); the image and every other output are those of the plain call, bit for bit."""
         inp = self._inputs(means_3d, shs, opacities, scales, rotations, sh_degree, background)
         cs = self._camera(camera, R_w2c, t_w2c)
         img = self.image if image_out is None else _chk(image_out, "image_out", (self.height, self.width, self.channels))
@@ -375,8 +378,14 @@ class GaussianRasterizer:
                     None if uncertainties is None else uncertainties.data_ptr(),
                     self.gstate._radii.data_ptr() if inp.n else None, L.FORWARD_ONLY if forward_only else 0, 0)
         with torch.cuda.device(self.device):
-            L.check(self._lib.gsr_forward(self._h, C.byref(inp), C.byref(cs), L.ptr(img), C.byref(aux), L.stream(),
-                                          C.byref(self.stats)))
+            if scores is None:
+                L.check(self._lib.gsr_forward(self._h, C.byref(inp), C.byref(cs), L.ptr(img), C.byref(aux), L.stream(),
+                                              C.byref(self.stats)))
+            else:
+                sc = scores.as_struct(inp.n, self.device)
+                L.check(self._lib.gsr_forward_scored(self._h, C.byref(inp), C.byref(cs), L.ptr(img), C.byref(aux), C.byref(sc),
+                                                     L.stream(), C.byref(self.stats)))
+                scores.n_views += 1
         self._n = inp.n
         return img
 
@@ -528,11 +537,11 @@ class _Rasterize(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means_3d, shs, opacities, scales, rotations, R_w2c, t_w2c, rast, camera, sh_degree, background,
-                covisibilities, uncertainties):
+                covisibilities, uncertainties, scores=None):
         args = [a.detach().contiguous() for a in (means_3d, shs, opacities, scales, rotations)]
         Rd = None if R_w2c is None else R_w2c.detach().contiguous()
         td = None if t_w2c is None else t_w2c.detach().contiguous()
-        img = rast.forward_raw(*args, camera, sh_degree, background, Rd, td, covisibilities, uncertainties)
+        img = rast.forward_raw(*args, camera, sh_degree, background, Rd, td, covisibilities, uncertainties, scores=scores)
         ctx.generation = int(rast.stats.generation)  # an eval render in between is reported, not silently used
         ctx.rast, ctx.camera, ctx.sh_degree, ctx.background = rast, camera, sh_degree, background
         ctx.pose = (Rd, td)
@@ -546,12 +555,12 @@ class _Rasterize(torch.autograd.Function):
         vm, vs, vo, vsc, vr, vR, vt = ctx.rast.backward_raw(
             vpixels.contiguous(), means_3d, shs, opacities, scales, rotations, ctx.camera, ctx.sh_degree,
             ctx.background, Rd, td, forward_generation=ctx.generation)
-        return vm, vs, vo, vsc, vr, vR, vt, None, None, None, None, None, None
+        return vm, vs, vo, vsc, vr, vR, vt, None, None, None, None, None, None, None
 
 
 def rasterize(means_3d, shs, opacities, scales, rotations, R_w2c=None, t_w2c=None, *, rast: GaussianRasterizer,
               camera: Camera, sh_degree: int, background=(0.0, 0.0, 0.0), covisibilities=None, uncertainties=None,
-              forward_only: Optional[bool] = None):
+              forward_only: Optional[bool] = None, scores=None):
     """rasterize(means_3d, shs, opacities, scales, rotations, R_w2c, t_w2c; rast, camera,
     sh_degree, background, covisibilities, uncertainties) — rasterizer.jl:255-408.
     opacities / scales are the activated values.  Returns `rast.image` (aliased, overwritten by
@@ -562,7 +571,8 @@ def rasterize(means_3d, shs, opacities, scales, rotations, R_w2c=None, t_w2c=Non
     after it raise GSR_E_STATE.  The manual pair the reference also offers — a bare `rasterize` followed by `∇rasterize` on
     plain arrays, no autograd (rasterizer.jl:255,416) — asks for a state-keeping forward explicitly: `forward_only=False`
     here, or `rast.forward_only_outside_ad = False` once (the Julia binding's `enable_hip_native!(rast;
-    forward_only_outside_ad=false)`); `forward_only=True` forces the inference render.  None (default): decided as above."""
+    forward_only_outside_ad=false)`); `forward_only=True` forces the inference render.  None (default): decided as above.
+    `scores` (a `contribution.ContributionScores`): passed through to `forward_raw`."""
     diff = (means_3d, shs, opacities, scales, rotations, R_w2c, t_w2c)
     outside_ad = not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in diff))
     if forward_only is None:
@@ -573,15 +583,16 @@ def rasterize(means_3d, shs, opacities, scales, rotations, R_w2c=None, t_w2c=Non
         args = [a.detach().contiguous() for a in diff[:5]]
         return rast.forward_raw(*args, camera, sh_degree, tuple(float(b) for b in background),
                                 None if R_w2c is None else R_w2c.detach().contiguous(),
-                                None if t_w2c is None else t_w2c.detach().contiguous(), covisibilities, uncertainties)
+                                None if t_w2c is None else t_w2c.detach().contiguous(), covisibilities, uncertainties,
+                                scores=scores)
     if forward_only:
         args = [a.detach().contiguous() for a in diff[:5]]
         return rast.forward_raw(*args, camera, sh_degree, tuple(float(b) for b in background),
                                 None if R_w2c is None else R_w2c.detach().contiguous(),
                                 None if t_w2c is None else t_w2c.detach().contiguous(), covisibilities, uncertainties,
-                                forward_only=True)
+                                forward_only=True, scores=scores)
     return _Rasterize.apply(means_3d, shs, opacities, scales, rotations, R_w2c, t_w2c, rast, camera, sh_degree,
-                            tuple(float(b) for b in background), covisibilities, uncertainties)
+                            tuple(float(b) for b in background), covisibilities, uncertainties, scores)
 
 
 def grad_rasterize(vpixels, means_3d, shs, scales, rotations, opacities, radii=None, R_w2c=None, t_w2c=None, *,

@@ -333,6 +333,44 @@ GSR_API uint32_t gsr_bins_capacity_after(int64_t n_rendered, int32_t max_tile_in
 GSR_API int gsr_forward(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, float* image_out,
                         const gsr_aux* aux, void* stream, gsr_stats* stats);
 
+/* Per-Gaussian contribution scores: which Gaussians a set of views actually uses.  No reference counterpart — the reference
+ * exports the per-PIXEL sum of the blend weights (gsr_aux.uncertainties) and nothing per Gaussian.  The quantities are those of
+ *   RadSplat        (Niemeyer et al., 2024, eq. 7-8): h_g = max over pixels and views of the blend weight w = alpha·T; prune h_g < 0.01
+ *   LightGaussian   (Fan et al., 2023) / Mini-Splatting (Fang & Wang, 2024): the sum of w over the pixels that blend g, and the hit count
+ * without the volume weighting and the keep-fraction rules, which are the caller's.
+ * For every (pixel, list entry) that render! BLENDS (alpha >= 1/255, sigma >= 0, the pixel not stopped, and not the entry that
+ * stops it with T' < 1e-4 — exactly the entries that add to the image), with w the fp32 alpha·T the pixel's colour is scaled by:
+ *   max_weight[g]  max=  the bits of w            (w > 0: float order is unsigned order; read the word back as a float)
+ *   hits[g]        +=    1
+ *   weight_sum[g]  +=    q = round-to-nearest-even(w · 2^24)     (w <= 0.99 and w >= 1e-4 / 255: 6 <= q < 2^24; value = sum / 2^24)
+ * All three are integers, so the result is bit-identical from run to run and across the default / reference tile lists, the
+ * binning forms, compact mode, the fused launch and the tier walk, and GSR_FORWARD_ONLY.  The arrays are the caller's, device,
+ * (N) each, ACCUMULATED INTO AND NEVER CLEARED (like covisibilities): scoring V views is V calls on the same arrays.  Any of the
+ * three pointers may be NULL; culled Gaussians and instances no pixel blends are not touched.  On a GSR_FLAG_ANTIALIASED handle w
+ * is that of the effective opacity.  hits and weight_sum must be 8-byte aligned; flags and reserved must be 0. */
+typedef struct gsr_scores {
+    uint32_t* max_weight; /* device (N) or NULL */
+    uint64_t* hits;       /* device (N) or NULL */
+    uint64_t* weight_sum; /* device (N) or NULL */
+    uint32_t flags;       /* 0 */
+    uint32_t reserved;    /* 0 */
+} gsr_scores;
+/* gsr_forward with the scores of this view accumulated into `scores`.  scores == NULL, or all three pointers NULL: gsr_forward
+ * itself (the same launches of the same kernels) — gsr_forward(...) IS gsr_forward_scored(..., NULL, ...).  Works together with
+ * every gsr_aux member.  The scored kernels do one wave reduction pair per visit and one triple of integer atomics per blended
+ * tile instance more than the plain ones: an offline pass over the training views, not a training forward. */
+GSR_API int gsr_forward_scored(gsr_handle* h, const gsr_inputs* in, const gsr_camera* cam, float* image_out,
+                               const gsr_aux* aux, const gsr_scores* scores, void* stream, gsr_stats* stats);
+/* The keep mask of a pruning rule on accumulated scores, compared in integers: valid_out[i] = 1 where Gaussian i is KEPT, else 0.
+ *   GSR_SCORE_MAX_WEIGHT  bits(max_weight[i]) >= bits((float)threshold)     (RadSplat: threshold 0.01)
+ *   GSR_SCORE_WEIGHT_SUM  weight_sum[i] >= ceil(threshold · 2^24)
+ *   GSR_SCORE_HITS        hits[i] >= ceil(threshold)
+ * Only the rule's own array is read (the others may be NULL).  threshold must be finite and >= 0 (and its fixed-point form must
+ * fit 64 bits).  valid_out feeds gsr_mask_findall / gsr_compose_rows like gsr_densify_mask's GSR_DENSIFY_PRUNE mask. */
+enum { GSR_SCORE_MAX_WEIGHT = 0, GSR_SCORE_WEIGHT_SUM = 1, GSR_SCORE_HITS = 2 };
+GSR_API int gsr_contribution_mask(int64_t n, int rule, double threshold, const uint32_t* max_weight, const uint64_t* hits,
+                                  const uint64_t* weight_sum, uint8_t* valid_out, void* stream);
+
 /* ∇rasterize(vpixels, ...) — rasterizer.jl:416-550 (the pullback of the rrule,
  * rasterizer.jl:552-573): ∇render! + ∇project! + ∇spherical_harmonics!.
  * vpixels: device (C,W,H).  `in`/`cam` must be the ones given to gsr_forward.

@@ -1,0 +1,121 @@
+"""No GPU: the premises of the contribution-score comparator (tests/scores_ref.py) and the argument contracts of the new entry
+points that fail before any launch.
+
+  per scene of scores_ref.SCENES: the interval caps (total slack of the hit counts <= 2 %, at least 40 % of the Gaussians that can
+      be hit at all have a one-value interval), printed;
+  the comparator's own test: scores made from the definition pass; four mutations fail — one Gaussian's hits beyond its slack, a
+      max_weight raised by 2 tol on a Gaussian with sure hits only, a view dropped from a two-view accumulation, two rows swapped;
+  gsr_forward_scored / gsr_contribution_mask reject NULL, misaligned and unknown arguments with GSR_E_INVALID_ARG, and the Python
+      layer rejects CPU tensors, unknown rules and bad thresholds."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import definition_ref as dr
+import scores_ref as sr
+
+
+@pytest.mark.parametrize("name", sr.SCENES)
+def test_scene_meets_the_interval_caps(pkg, name):
+    defn = dr.definition(pkg, name)
+    dr.conditions(defn)
+    iv = sr.scene_intervals(pkg, name)
+    sr.conditions(iv, name)
+    assert (iv.hits_lo <= iv.hits).all() and (iv.hits <= iv.hits_hi).all()
+    assert not iv.hits_hi[~defn.d.visible].any(), "a culled Gaussian cannot be hit"
+
+
+def test_tier_scenes_have_the_lists_they_are_there_for(pkg):
+    assert dr.definition(pkg, "deep-276").shares["longest"] > 1024
+    assert dr.definition(pkg, "deep-5911").shares["longest"] > 4096
+
+
+@pytest.mark.parametrize("name", sr.SCENES)
+def test_definitions_own_scores_pass(pkg, name):
+    iv = sr.scene_intervals(pkg, name)
+    m = sr.check_scores(iv, *sr.got_from_definition(iv))
+    assert m["worst_max_weight"] == 0.0 and m["worst_weight_sum_per_hit"] == 0.0
+    two = sr.accumulate(iv, iv)
+    bits, hits, q = sr.got_from_definition(iv)
+    sr.check_scores(two, bits, 2 * hits, 2 * q)
+
+
+def _sure_gaussian(iv):
+    """A Gaussian with sure hits only whose max_weight interval is the plain +- tol (nothing widened it)."""
+    mw = iv.bits.view(np.float32).astype(np.float64)
+    ok = np.flatnonzero((iv.hits_hi == iv.hits_lo) & (iv.hits_lo > 0) & (iv.mw_hi - mw <= 1.5 * sr.TOL))
+    assert ok.size, "no Gaussian with an unwidened interval"
+    return int(ok[0])
+
+
+@pytest.mark.parametrize("name", ["sweep-3", "ragged", "deep-276"])
+def test_mutations_fail(pkg, name):
+    iv = sr.scene_intervals(pkg, name)
+    g = _sure_gaussian(iv)
+    # one Gaussian's hits beyond its slack
+    bits, hits, q = sr.got_from_definition(iv)
+    worst = int(np.argmax(iv.hits_hi - iv.hits_lo))
+    hits[worst] = iv.hits_lo[worst] + (iv.hits_hi[worst] - iv.hits_lo[worst]) + 1
+    with pytest.raises(AssertionError, match="hits outside"):
+        sr.check_scores(iv, bits, hits, q)
+    # a max_weight raised by 2 tol on a sure Gaussian
+    bits, hits, q = sr.got_from_definition(iv)
+    w = np.float32(bits[g:g + 1].view(np.float32)[0] + np.float32(2 * sr.TOL))
+    bits[g] = np.array([w], np.float32).view(np.uint32)[0]
+    with pytest.raises(AssertionError, match="max_weight outside"):
+        sr.check_scores(iv, bits, hits, q)
+    # a dropped view in a two-view accumulation
+    two = sr.accumulate(iv, iv)
+    with pytest.raises(AssertionError, match="hits outside"):
+        sr.check_scores(two, *sr.got_from_definition(iv))
+    # two Gaussians' rows swapped
+    a = int(np.argmax(iv.hits_lo))
+    below = np.flatnonzero(iv.hits_hi < iv.hits_lo[a])
+    assert below.size, "no two Gaussians with disjoint hit intervals"
+    b = int(below[0])
+    got = sr.got_from_definition(iv)
+    for arr in got:
+        arr[[a, b]] = arr[[b, a]]
+    with pytest.raises(AssertionError, match="hits outside"):
+        sr.check_scores(iv, *got)
+
+
+def test_scored_entry_points_reject_bad_arguments_before_any_launch(pkg):
+    L = pkg._lib
+    lib = L.load()
+    assert C.sizeof(L.Scores) == 32
+    assert lib.gsr_forward_scored(None, None, None, None, None, None, None, None) == L.GSR_E_INVALID_ARG
+    ok = L.Scores(None, None, None, 0, 0)
+    assert lib.gsr_forward_scored(None, None, None, None, None, C.byref(ok), None, None) == L.GSR_E_INVALID_ARG
+    for sc, word in ((L.Scores(None, None, None, 1, 0), b"gsr_scores.flags"), (L.Scores(None, None, None, 0, 7), b"gsr_scores.flags"),
+                     (L.Scores(None, 0x1004, None, 0, 0), b"aligned"), (L.Scores(None, None, 0x1004, 0, 0), b"aligned"),
+                     (L.Scores(0x1002, None, None, 0, 0), b"aligned")):
+        assert lib.gsr_forward_scored(None, None, None, None, None, C.byref(sc), None, None) == L.GSR_E_INVALID_ARG
+        assert word in lib.gsr_last_error_string(), lib.gsr_last_error_string()
+    mask = lib.gsr_contribution_mask
+    assert mask(4, 3, 0.5, None, None, None, None, None) == L.GSR_E_INVALID_ARG and b"rule" in lib.gsr_last_error_string()
+    assert mask(4, -1, 0.5, None, None, None, None, None) == L.GSR_E_INVALID_ARG
+    assert mask(-1, 0, 0.5, None, None, None, None, None) == L.GSR_E_INVALID_ARG
+    for bad in (-0.5, float("nan"), float("inf")):
+        assert mask(4, 0, bad, None, None, None, None, None) == L.GSR_E_INVALID_ARG and b"threshold" in lib.gsr_last_error_string()
+    assert mask(4, L.SCORE_HITS, 1e30, None, None, None, None, None) == L.GSR_E_INVALID_ARG
+    for rule in (L.SCORE_MAX_WEIGHT, L.SCORE_WEIGHT_SUM, L.SCORE_HITS):
+        assert mask(4, rule, 0.5, None, None, None, None, None) == L.GSR_E_INVALID_ARG and b"null" in lib.gsr_last_error_string()
+        assert mask(0, rule, 0.5, None, None, None, None, None) == L.GSR_OK            # nothing to do
+    assert mask(4, L.SCORE_HITS, 1.0, None, 0x1004, None, 0x2000, None) == L.GSR_E_INVALID_ARG and b"aligned" in lib.gsr_last_error_string()
+    assert mask(4, L.SCORE_WEIGHT_SUM, 1.0, None, None, 0x1004, 0x2000, None) == L.GSR_E_INVALID_ARG
+
+
+def test_python_layer_rejects_cpu_tensors_and_bad_rules(pkg):
+    K = pkg.contribution
+    with pytest.raises(ValueError, match="HIP device"):
+        K.ContributionScores(8, "cpu")
+    with pytest.raises(ValueError, match="unknown rule"):
+        K._check_rule("median", 0.1)
+    for bad in (-1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="threshold"):
+            K._check_rule("hits", bad)
+    with pytest.raises(TypeError):
+        K.prune_mask(np.zeros(4), "hits", 1)
+    assert K.RULES == {"max_weight": 0, "weight_sum": 1, "hits": 2}
