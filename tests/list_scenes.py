@@ -59,12 +59,14 @@ class ListScene:
         return self.means, self.shs, self.opac, self.scales, self.rots
 
 
-def boundary_positions(L, stop=None):
-    """Sorted positions within 2 of a boundary <= L (and of `stop`), plus the first and the last of the list."""
+def boundary_positions(L, stop=None, slack=0):
+    """Sorted positions within 2 of a boundary <= L (and of `stop`), plus the first and the last of the list.
+    slack = s: the positions that can END within 2 of a boundary, first or last once up to s entries of the list are dropped
+    (an entry at p moves to p - s .. p): each window reaches s positions further back, the last entry's s further to the front."""
     edges = [b for b in BOUNDARIES if b <= L] + ([stop] if stop is not None else [])
-    P = {0, L - 1}
+    P = set(range(0, slack + 1)) | set(range(L - 1 - slack, L))
     for b in edges:
-        P.update(range(b - 2, b + 3))
+        P.update(range(b - 2, b + 3 + slack))
     return np.array(sorted(p for p in P if 0 <= p < L), np.int64)
 
 
@@ -250,7 +252,7 @@ def tied_tile_scene(L, groups, seed, deg=0):
 MANY_FAINT_ABOVE = 64   # lists beyond this many entries get the faint front (opacity 0.0042), shorter ones 0.05
 
 
-def many_tile_scene(gx, gy, lengths, seed, deg=0):
+def many_tile_scene(gx, gy, lengths, seed, deg=0, slack=0):
     """A 16 gx x 16 gy image whose tile t (row-major) has a list of exactly lengths[t] entries: two_tile_scene on a grid.  Front
     splats of sigma 1.05 px, projected centres within [6, 10] px of their tile's origin in x and y — every 3-sigma square
     (radius 5) inside its own tile; distinct depths in [2, 8] whose ranks are dealt to the tiles at random; ids a random
@@ -258,7 +260,9 @@ def many_tile_scene(gx, gy, lengths, seed, deg=0):
     contributor of every tile is its last entry.  Opacity 0.0042 U(1, 1.5) in lists of more than MANY_FAINT_ABOVE entries, 0.05
     U(1, 1.5) in shorter ones (a 1024-entry list at 0.05 would saturate after some 300 entries; at 0.0042 its walk ends with
     T ~ 0.4).  Principal point in the image centre, focal length 2 W: at _camera()'s 13.9 px a splat 150 px off the axis is
-    stretched over several tiles.  No per-tile Python loop over Gaussians: one pass per DISTINCT length."""
+    stretched over several tiles.  No per-tile Python loop over Gaussians: one pass per DISTINCT length.
+    slack: pin boundary_positions(length, slack=slack) instead — for a caller that drops up to `slack` entries per list afterwards
+    (tests/score_scenes.py) and needs the pinned ones at the boundaries of the lists that remain."""
     lengths = np.asarray(lengths, np.int64)
     assert lengths.shape == (gx * gy,) and (lengths >= 1).all()
     rng = np.random.default_rng([int(seed), gx, gy, int(lengths.sum()), 0x3A9])
@@ -274,7 +278,7 @@ def many_tile_scene(gx, gy, lengths, seed, deg=0):
     starts = np.concatenate([[0], np.cumsum(lengths)])
     pinned = np.zeros(n, bool)
     for Lk in np.unique(lengths):
-        pinned[(starts[:-1][lengths == Lk][:, None] + boundary_positions(int(Lk))[None, :]).reshape(-1)] = True
+        pinned[(starts[:-1][lengths == Lk][:, None] + boundary_positions(int(Lk), slack=slack)[None, :]).reshape(-1)] = True
     ox, oy = 16.0 * (tile % gx), 16.0 * (tile // gx)
     base = np.where(lengths[tile] > MANY_FAINT_ABOVE, 0.0042, 0.05)
     parts = _front(rng, n, depths[by_pos], 1.05, base, fx, pinned, deg, lo=(ox + 6.0, oy + 6.0), hi=(ox + 10.0, oy + 10.0),

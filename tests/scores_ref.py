@@ -19,6 +19,8 @@ relative weight tolerance of every later entry of the pixel widens by that much 
   hits        in [#sure, #sure + #unsure]
   max_weight  in [max_sure(w (1 - widen)) - tol, max(max_sure(w (1 + widen)), max_unsure alpha) + tol]       (w <= alpha)
   weight_sum  in [sum_sure w (1 - widen) - (tol + 2^-25) hits_lo, sum_sure w (1 + widen) + sum_unsure alpha + (tol + 2^-25) hits_hi]
+On the list scenes of tests/score_scenes.py (tile lists of a chosen length) the hit interval is ONE value for 99.9 % of the Gaussians:
+there "inside the interval" is the exact hit count, at every boundary of the scored kernels (tests/test_gpu_score_boundaries.py).
 tol = 1e-4: what the suite grants the per-PIXEL sums of the same w (test_gpu_definition.test_covisibility_and_uncertainty,
 hip_helpers.compare_forward) — a single w cannot be further off than a sum of them; 2^-25 per term: the fixed point's rounding."""
 from types import SimpleNamespace

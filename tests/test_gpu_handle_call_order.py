@@ -26,6 +26,8 @@ torch.equal with a fresh handle's F + B on the same inputs and cotangent (five g
      ∇means_2d (gsr_aux.radii = NULL)           GSR_E_STATE
   8  R(4n, 4D) in the library only, F,          memory_usage unchanged (the library reallocates      test_grow_of_the_mirror_alone_...
      rast.reserve(4n, 4D)                       nothing), gstate replaced its arrays: as 3
+  9  rows 1 and 3 with F = gsr_forward_scored,  as 1 and 3: a scored forward is a forward; its score   test_scored_forward_in_the_orders_...
+     and F(scored) drop | B                     set keeps what it got, the pair after it = ref
 
 Every refusal is reached through a host-side check that returns before any launch — named at each assertion: the rows 3, 4, 6,
 7, 8 never put a backward kernel over the fresh allocations of a reserve.  Sequences 3 and 5 also run once with GSR_DEBUG_GUARD=1
@@ -49,9 +51,9 @@ NAMES = ("vmeans", "vshs", "vopacities", "vscales", "vrotations", "grad_means_2d
 _CASES = {}
 
 
-def _pair(rast, c):
-    """forward + backward on the case's inputs and cotangent: clones of what `ref` holds."""
-    rast.forward_raw(*c.t, c.cam, DEG, BG)
+def _pair(rast, c, scores=None):
+    """forward (scored into `scores` if given) + backward on the case's inputs and cotangent: clones of what `ref` holds."""
+    rast.forward_raw(*c.t, c.cam, DEG, BG, scores=scores)
     out = rast.backward_raw(c.vp, *c.t, c.cam, DEG, BG)
     return [o.clone() for o in out[:5]] + [rast.gstate.grad_means_2d.clone(), rast.gstate.radii.clone()]
 
@@ -138,10 +140,10 @@ def forward_is_dropped(pkg, rast, c):
     assert L.load().gsr_copy_buffer(rast._h, L.BUF_GEOM, word.data_ptr(), 0, L.stream()) == 0   # (nothing asked: nothing refused)
 
 
-def fresh_pair_equals_ref(rast, c):
+def fresh_pair_equals_ref(rast, c, scores=None):
     """... and the handle is as good as new: forward + backward = ref, and that forward regrows no scratch."""
     regrowths = int(rast.stats.scratch_regrowths)
-    got = _pair(rast, c)
+    got = _pair(rast, c, scores)
     assert int(rast.stats.scratch_regrowths) == regrowths and int(rast.stats.n_rendered) == c.D
     same(got, c.ref)
 
@@ -182,13 +184,13 @@ def test_reserve_within_capacity_between_forward_and_backward(pkg, orc, mode):
 
 
 # ---- 3, 4, 5: a reserve that reallocates --------------------------------------------------------------------------------------
-def sequence_3(pkg, c, check=None):
+def sequence_3(pkg, c, check=None, scores=None):
     rast = new(pkg, c)
     try:
-        rast.forward_raw(*c.t, c.cam, DEG, BG)
+        rast.forward_raw(*c.t, c.cam, DEG, BG, scores=scores)
         grow(rast, c)
         forward_is_dropped(pkg, rast, c)
-        fresh_pair_equals_ref(rast, c)
+        fresh_pair_equals_ref(rast, c, scores)
         if check:
             check(pkg, rast)
     finally:
@@ -245,6 +247,41 @@ def test_sequences_3_and_5_on_a_guarded_handle(pkg, orc, mode):
     with debug_guard(True):
         sequence_3(pkg, c, check=guards_ok)
         sequence_5(pkg, c, check=guards_ok)
+
+
+# ---- 9: the scored forward in the orders above --------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", MODES)
+def test_scored_forward_in_the_orders_of_rows_1_and_3(pkg, orc, mode):
+    """gsr_forward_scored where rows 1 and 3 have gsr_forward, and gsr_drop_forward behind it.  The score set of one view, taken
+    on a handle nothing happened to, is what every scored forward here adds: a dropped forward's scores are not taken back."""
+    c = case(pkg, orc, mode)
+    K = pkg.contribution
+    one = K.ContributionScores(N, "cuda")
+    rast = new(pkg, c)
+    try:
+        # row 1: F(scored) R(0, 0) B = ref
+        rast.forward_raw(*c.t, c.cam, DEG, BG, scores=one)
+        before = rast.memory_usage()
+        rast.reserve(0, 0)
+        assert rast.memory_usage() == before and rast.gstate.radii.numel() == N
+        out = rast.backward_raw(c.vp, *c.t, c.cam, DEG, BG)
+        same(list(out[:5]) + [rast.gstate.grad_means_2d, rast.gstate.radii], c.ref)
+        same(_stats(rast), c.ref_stats, ("max_radii", "accum", "denom"))
+        assert int(one.hits.sum()) > 0 and not one.hits[::7].any()
+        # F(scored) drop | B: refused before any launch (check_backward_state), then a scored pair = ref
+        two = K.ContributionScores(N, "cuda")
+        rast.forward_raw(*c.t, c.cam, DEG, BG, scores=two)
+        pkg._lib.check(pkg._lib.load().gsr_drop_forward(rast._h))
+        refused(pkg, rast.backward_raw, c.vp, *c.t, c.cam, DEG, BG)
+        same(_pair(rast, c, two), c.ref)
+        assert two.n_views == 2 and torch.equal(two.hits, 2 * one.hits) and torch.equal(two.q, 2 * one.q) and torch.equal(two.bits, one.bits)
+    finally:
+        rast.close()
+    # row 3: F(scored) grow | B, U refused; F(scored) B = ref
+    three = K.ContributionScores(N, "cuda")
+    sequence_3(pkg, c, scores=three)
+    assert three.n_views == 2 and torch.equal(three.hits, 2 * one.hits) and torch.equal(three.q, 2 * one.q)
+    assert torch.equal(three.bits, one.bits)
 
 
 # ---- 6: the fused backward + trainer tail ------------------------------------------------------------------------------------

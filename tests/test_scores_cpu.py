@@ -5,6 +5,9 @@ points that fail before any launch.
       be hit at all have a one-value interval), printed;
   the comparator's own test: scores made from the definition pass; four mutations fail — one Gaussian's hits beyond its slack, a
       max_weight raised by 2 tol on a Gaussian with sure hits only, a view dropped from a two-view accumulation, two rows swapped;
+  the list scenes of tests/score_scenes.py (the cases of tests/test_gpu_score_boundaries.py): the seeds re-derived, the post-filter
+      list lengths the ones asked for, nothing removed, slack <= 1e-3 and exact share >= 0.99, every entry next to a boundary surely
+      hit, nothing behind a stop hit — printed per case; five mutations the scored kernels could produce fail check_scores;
   gsr_forward_scored / gsr_contribution_mask reject NULL, misaligned and unknown arguments with GSR_E_INVALID_ARG, and the Python
       layer rejects CPU tensors, unknown rules and bad thresholds."""
 import ctypes as C
@@ -13,6 +16,8 @@ import numpy as np
 import pytest
 
 import definition_ref as dr
+import list_scenes as ls
+import score_scenes as ss
 import scores_ref as sr
 
 
@@ -79,6 +84,83 @@ def test_mutations_fail(pkg, name):
         arr[[a, b]] = arr[[b, a]]
     with pytest.raises(AssertionError, match="hits outside"):
         sr.check_scores(iv, *got)
+
+
+@pytest.mark.parametrize("case", ss.CASES, ids=ss.case_id)
+def test_list_scene_has_the_lengths_asked_for_and_exact_hit_counts(case):
+    if case[0] != "grid" and not (case[0] == "full" and case[1] in ss.TRIMMED_FULL):
+        assert ss.smallest_whole_seed(case) == ss.seed_of(case), "SEEDS must hold the smallest seed the filter leaves whole"
+    defn = ss.definition(case)
+    again = dr.robust_scene(defn.fs)
+    assert again.note["removed"] == (0, sum(ss.lengths_of(case))), "robust_scene removes nothing from the delivered scene"
+    ss.conditions(case, defn, ss.intervals(case))
+
+
+@pytest.mark.parametrize("mode", ["rgbd", "rgbdn"])
+@pytest.mark.parametrize("L", ss.MODE_LENGTHS)
+def test_list_scene_mode_twins_are_the_same_lists(L, mode):
+    a, b = ss.definition(("full", L)), ss.definition(("full", L), mode)
+    assert b.fs.mode == mode and b.lengths == (L,) and np.array_equal(a.tl.values_sorted, b.tl.values_sorted)
+    assert np.array_equal(a.fs.opac, b.fs.opac) and np.array_equal(a.d.conic, b.d.conic)   # the intervals read nothing else
+
+
+def test_trimmed_scenes_lose_only_what_was_built_on_top():
+    """The trimming of ss.fuzz_scene: every fragile Gaussian goes, and with the others dropped exactly extra(L) entries per list."""
+    want = ss.GRID_LENGTHS
+    slack = max(ss.extra(L) for L in want)
+    built = tuple(L + ss.extra(L) for L in want)
+    sc = ls.many_tile_scene(*ss.GRID, built, ss.GRID_SEED, 0, slack=slack)
+    frag = ss._fragile(sc)
+    assert frag.any(), "the grid is trimmed because the filter takes some of it"
+    args = ss.trim(sc, built, want, slack)
+    assert args[0].shape[0] == sum(want)
+    kept = {a.tobytes() for a in args[0]}
+    assert not any(m.tobytes() in kept for m in sc.means[frag]), "a fragile Gaussian stayed"
+
+
+def _list_ids(case):
+    return ss.definition(case).tl.lists[0]
+
+
+def test_mutations_of_the_scored_kernels_fail():
+    # a dropped chunk flush: positions 256 .. 511 of a list of 1025 never reach the arrays
+    case = ("full", 1025)
+    iv, ids = ss.intervals(case), _list_ids(case)
+    sr.check_scores(iv, *sr.got_from_definition(iv))
+    got = sr.got_from_definition(iv)
+    for a in got:
+        a[ids[256:512]] = 0
+    with pytest.raises(AssertionError, match="hits outside"):
+        sr.check_scores(iv, *got)
+    # position 255's words credited to position 256
+    bits, hits, q = sr.got_from_definition(iv)
+    a, b = ids[255], ids[256]
+    bits[b], hits[b], q[b] = max(bits[a], bits[b]), hits[a] + hits[b], q[a] + q[b]
+    bits[a] = hits[a] = q[a] = 0
+    with pytest.raises(AssertionError, match="hits outside"):
+        sr.check_scores(iv, bits, hits, q)
+    # every count doubled: a view taken twice
+    bits, hits, q = sr.got_from_definition(iv)
+    with pytest.raises(AssertionError, match="hits outside"):
+        sr.check_scores(iv, bits, 2 * hits, 2 * q)
+    # one hit behind the stop
+    case = ("walled", 1000, 257)
+    iv, ids = ss.intervals(case), _list_ids(case)
+    bits, hits, q = sr.got_from_definition(iv)
+    g = ids[257 + 1]
+    assert hits[g] == 0
+    bits[g], hits[g], q[g] = np.float32(0.004).view(np.uint32), 1, int(0.004 * sr.Q_ONE)
+    with pytest.raises(AssertionError, match="hits outside"):
+        sr.check_scores(iv, bits, hits, q)
+    # max_weight of the last entry of a 64-entry batch of the tier walk (position 1024 + 63) swapped with the next batch's first
+    case = ("full", 1089)
+    iv, ids = ss.intervals(case), _list_ids(case)
+    bits, hits, q = sr.got_from_definition(iv)
+    a, b = ids[1087], ids[1088]
+    assert abs(float(bits[a:a + 1].view(np.float32)[0]) - float(bits[b:b + 1].view(np.float32)[0])) > 4 * sr.TOL
+    bits[a], bits[b] = bits[b], bits[a]
+    with pytest.raises(AssertionError, match="max_weight outside"):
+        sr.check_scores(iv, bits, hits, q)
 
 
 def test_scored_entry_points_reject_bad_arguments_before_any_launch(pkg):
