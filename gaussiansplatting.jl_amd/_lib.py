@@ -209,6 +209,7 @@ EXPORTS = ["gsr_create", "gsr_destroy", "gsr_release_scene_buffers", "gsr_memory
            "gsr_densify_grad_mean", "gsr_densify_mask", "gsr_compose_rows", "gsr_split_transform", "gsr_reset_opacity", "gsr_morton_codes",
            "gsr_knn_scratch_bytes", "gsr_knn_scales",
            "gsr_filter3d_scratch_bytes", "gsr_filter3d_compute", "gsr_filter3d_apply", "gsr_filter3d_apply_backward",
+           "gsr_vq_scratch_bytes", "gsr_vq_assign", "gsr_vq_accumulate", "gsr_vq_update", "gsr_vq_decode",
            "gsr_tsdf_integrate", "gsr_mesh_scratch_bytes", "gsr_mesh_count", "gsr_mesh_emit",
            "gsr_ply_pack_rows", "gsr_ply_unpack_rows", "gsr_count_nonfinite",
            "gsr_bilateral_scratch_bytes", "gsr_bilateral_tv_scratch_bytes", "gsr_bilateral_slice_forward",
@@ -303,6 +304,12 @@ def load():
     lib.gsr_filter3d_compute.argtypes = [i64, vp, C.c_int32, vp, f32, f32, vp, vp, vp, vp, C.c_size_t, vp]
     lib.gsr_filter3d_apply.argtypes = [i64, vp, vp, vp, C.c_int32, vp, vp, vp]
     lib.gsr_filter3d_apply_backward.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gsr_vq_scratch_bytes.argtypes = [i64, C.c_int32, C.c_int32]
+    lib.gsr_vq_scratch_bytes.restype = C.c_size_t
+    lib.gsr_vq_assign.argtypes = [i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.gsr_vq_accumulate.argtypes = [i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
+    lib.gsr_vq_update.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+    lib.gsr_vq_decode.argtypes = [i64, C.c_int32, C.c_int32, vp, vp, vp, vp]
     lib.gsr_tsdf_integrate.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, f32, f32, C.c_int32, C.c_int32, C.c_int32, vp,
                                        C.POINTER(CameraS), f32, f32, vp, vp, vp]
     lib.gsr_mesh_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

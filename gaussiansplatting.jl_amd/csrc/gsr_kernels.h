@@ -372,6 +372,17 @@ void gsr_launch_filter3d_apply(hipStream_t s, long long n, const float* opac, co
 void gsr_launch_filter3d_apply_bwd(hipStream_t s, long long n, const float* opac, const float* scales, const float* filter,
                                    const float* g_opac, const float* g_scales, float* v_opac, float* v_scales);
 
+// ---- vq.hip (compiled with -ffp-contract=off): SH codebook k-means — nearest code on the f32 MFMA, integer sums, update, decode ----
+size_t gsr_vq_scratch_size(int n_codes, int dim);
+void gsr_launch_vq_assign(hipStream_t s, int n, int n_codes, int dim, const float* rows, const float* codebook,
+                          const uint16_t* prev, uint16_t* indices, float* err, uint32_t* changed, void* scratch);
+void gsr_launch_vq_accumulate(hipStream_t s, int n, int n_codes, int dim, const float* rows, const uint16_t* indices,
+                              const uint8_t* wq, long long* sums, unsigned long long* wsum);
+void gsr_launch_vq_update(hipStream_t s, int n_codes, int dim, const long long* sums, const unsigned long long* wsum,
+                          float* codebook, uint32_t* empty);
+void gsr_launch_vq_decode(hipStream_t s, int n, int n_codes, int dim, const float* codebook, const uint16_t* indices,
+                          float* rows_out);
+
 // ---- tsdf.hip (compiled with -ffp-contract=off): TSDF fusion of a rendered frame, surface-nets count and emit ----
 // the volume: nx x ny x nz samples, sample (i, j, k) at o + h*(i, j, k)
 struct GsrTsdfGrid {

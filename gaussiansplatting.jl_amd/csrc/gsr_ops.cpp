@@ -1,7 +1,7 @@
 // C ABI of libgsr_hip.so (include/gsr.h), the part without a handle: every entry point that checks its arguments, launches
 // its kernels on the caller's stream and keeps nothing — planar SSIM, the trainer's prologue / Adam / tail, row gathers, the
 // bilateral grid, the geometry, depth and sky losses, the evaluation head, the geometry frames, densification, MCMC, Morton
-// codes, k-NN, the 3-D smoothing filter, TSDF fusion and mesh extraction, PLY rows, the multi-view SH gradient, the all-reduce.  (The handle and its launch choreography are gsr_api.cpp's.)
+// codes, k-NN, the 3-D smoothing filter, the SH codebook k-means, TSDF fusion and mesh extraction, PLY rows, the multi-view SH gradient, the all-reduce.  (The handle and its launch choreography are gsr_api.cpp's.)
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -796,6 +796,69 @@ int gsr_filter3d_apply_backward(int64_t n, const float* opacities_act, const flo
         return fail(GSR_E_INVALID_ARG, "null array");
     gsr_launch_filter3d_apply_bwd((hipStream_t)stream, n, opacities_act, scales_act, filter, g_opacities, g_scales, v_opacities,
                                   v_scales);
+    return launched();
+}
+
+// ---- SH codebook compression: exact k-means, the nearest-code search on the f32 MFMA (vq.hip) ----
+static int check_vq_shape(int64_t n, int32_t n_codes, int32_t dim) {
+    if (n < 0 || n >= (1ll << 24)) return fail(GSR_E_INVALID_ARG, "n = %lld: 0 <= n < 2^24 rows", (long long)n);
+    if (n_codes < 1 || n_codes > 65536) return fail(GSR_E_INVALID_ARG, "n_codes = %d: 1 .. 65536 (indices are uint16)", n_codes);
+    if (dim < 1 || dim > 48) return fail(GSR_E_INVALID_ARG, "dim = %d: 1 .. 48", dim);
+    return GSR_OK;
+}
+
+size_t gsr_vq_scratch_bytes(int64_t n, int32_t n_codes, int32_t dim) {
+    if (n <= 0 || n >= (1ll << 24) || n_codes < 1 || n_codes > 65536 || dim < 1 || dim > 48) return 0;
+    return gsr_vq_scratch_size(n_codes, dim);
+}
+
+int gsr_vq_assign(int64_t n, int32_t n_codes, int32_t dim, const float* rows, const float* codebook, const uint16_t* prev,
+                  uint16_t* indices, float* err, uint32_t* changed, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc;
+    if ((rc = check_vq_shape(n, n_codes, dim))) return rc;
+    if (n == 0) return GSR_OK;
+    if (!rows || !codebook || !indices || !scratch) return fail(GSR_E_INVALID_ARG, "null rows, codebook, indices or scratch");
+    if ((uintptr_t)indices % 2 || (uintptr_t)prev % 2) return fail(GSR_E_INVALID_ARG, "indices and prev must be 2-byte aligned");
+    if ((uintptr_t)changed % 4) return fail(GSR_E_INVALID_ARG, "changed must be 4-byte aligned");
+    if ((rc = check_scratch(scratch_bytes, gsr_vq_scratch_bytes(n, n_codes, dim), "nearest-code search"))) return rc;
+    if ((uintptr_t)scratch % 16) return fail(GSR_E_INVALID_ARG, "scratch must be 16-byte aligned");
+    gsr_launch_vq_assign((hipStream_t)stream, (int)n, n_codes, dim, rows, codebook, prev, indices, err, changed, scratch);
+    return launched();
+}
+
+int gsr_vq_accumulate(int64_t n, int32_t n_codes, int32_t dim, const float* rows, const uint16_t* indices, const uint8_t* wq,
+                      int64_t* sums, uint64_t* wsum, void* stream) {
+    int rc;
+    if ((rc = check_vq_shape(n, n_codes, dim))) return rc;
+    if (n == 0) return GSR_OK;
+    if (!rows || !indices || !sums || !wsum) return fail(GSR_E_INVALID_ARG, "null rows, indices, sums or wsum");
+    if ((uintptr_t)indices % 2) return fail(GSR_E_INVALID_ARG, "indices must be 2-byte aligned");
+    if ((uintptr_t)sums % 8 || (uintptr_t)wsum % 8) return fail(GSR_E_INVALID_ARG, "sums and wsum must be 8-byte aligned");
+    gsr_launch_vq_accumulate((hipStream_t)stream, (int)n, n_codes, dim, rows, indices, wq, reinterpret_cast<long long*>(sums),
+                             reinterpret_cast<unsigned long long*>(wsum));
+    return launched();
+}
+
+int gsr_vq_update(int32_t n_codes, int32_t dim, const int64_t* sums, const uint64_t* wsum, float* codebook, uint32_t* empty,
+                  void* stream) {
+    int rc;
+    if ((rc = check_vq_shape(0, n_codes, dim))) return rc;
+    if (!sums || !wsum || !codebook) return fail(GSR_E_INVALID_ARG, "null sums, wsum or codebook");
+    if ((uintptr_t)sums % 8 || (uintptr_t)wsum % 8) return fail(GSR_E_INVALID_ARG, "sums and wsum must be 8-byte aligned");
+    if ((uintptr_t)empty % 4) return fail(GSR_E_INVALID_ARG, "empty must be 4-byte aligned");
+    gsr_launch_vq_update((hipStream_t)stream, n_codes, dim, reinterpret_cast<const long long*>(sums),
+                         reinterpret_cast<const unsigned long long*>(wsum), codebook, empty);
+    return launched();
+}
+
+int gsr_vq_decode(int64_t n, int32_t n_codes, int32_t dim, const float* codebook, const uint16_t* indices, float* rows_out,
+                  void* stream) {
+    int rc;
+    if ((rc = check_vq_shape(n, n_codes, dim))) return rc;
+    if (n == 0) return GSR_OK;
+    if (!codebook || !indices || !rows_out) return fail(GSR_E_INVALID_ARG, "null codebook, indices or rows_out");
+    if ((uintptr_t)indices % 2) return fail(GSR_E_INVALID_ARG, "indices must be 2-byte aligned");
+    gsr_launch_vq_decode((hipStream_t)stream, (int)n, n_codes, dim, codebook, indices, rows_out);
     return launched();
 }
 

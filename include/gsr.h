@@ -721,6 +721,52 @@ GSR_API int gsr_filter3d_apply_backward(int64_t n, const float* opacities_act, c
                                         const float* g_opacities, const float* g_scales, float* v_opacities, float* v_scales,
                                         void* stream);
 
+/* SH codebook compression: exact k-means (Lloyd) over (n, dim) rows, the vector quantisation of features_rest that
+ * LightGaussian, Compact3D and "Compressed 3D Gaussian Splatting" apply after pruning.  features_rest in
+ * the (3, k_rest, N) layout is such a matrix with dim = 3*k_rest.  No handle, no struct, nothing read back to the host.
+ * Arrays are device, contiguous, float32 unless stated.  1 <= dim <= 48, 1 <= n_codes <= 65536, 0 <= n < 2^24 (the integer
+ * sums below cannot overflow); indices are uint16.
+ *
+ * gsr_vq_assign: the nearest code of every row.  Every operation ONE rounded fp32 operation:
+ *     n2_j  = fmaf(c_jd, c_jd, n2_j)      d = 0 .. dim-1, from 0
+ *     h_j   = 0.5f * n2_j
+ *     t_ij  = fmaf(x_id, c_jd, t_ij)      d ascending, from -h_j          ( = x.c - |c|^2/2: its maximum is the nearest code)
+ *     index_i = the lowest j whose t_ij is not NaN and is >= every non-NaN t_ik ;  0 when every t_ik is NaN
+ *     err_i   = sum over d of (x_id - c_jd)^2 for that j:  r = x_id - c_jd ;  err = fmaf(r, r, err), d ascending, from 0
+ * The chain t_ij is what the f32-input matrix instruction computes with C = -h_j (two steps of d per instruction; dim is
+ * padded with zero columns, and fmaf(0, 0, acc) changes at most the sign of a zero), so the search runs on the matrix cores
+ * and is still this definition bit for bit, whatever the reduction order of the arg-max.
+ *   indices : (n) uint16, fully overwritten.     err : (n), or NULL.
+ *   prev    : (n) uint16 or NULL; may be `indices` itself.
+ *   changed : one uint32, overwritten: the number of rows whose index differs from prev (all n when prev is NULL); or NULL.
+ *   scratch : gsr_vq_scratch_bytes(n, n_codes, dim) bytes, 16-byte aligned (the codebook re-laid for the search: up to 220
+ *             bytes per code, whole chunks of 256 codes).
+ *
+ * gsr_vq_accumulate: per-code INTEGER sums — any order of the rows gives the same bits, no float atomics:
+ *     sums[j][d] += wq_i * rne(clamp(x_id, -128, 128) * 2^24)   as int64, j = indices[i] ;  a NaN x_id counts as 0
+ *     wsum[j]    += wq_i                                        as uint64
+ *   wq : (n) uint8 weights, NULL: every weight is 1.  sums (n_codes, dim) int64 and wsum (n_codes) uint64 are the caller's:
+ *   accumulated into, never cleared.  255 * 2^31 * 2^24 < 2^63.
+ *
+ * gsr_vq_update: c_jd = (float)((double)sums[j][d] / ((double)wsum[j] * 16777216.0)) where wsum[j] > 0; a code with
+ *   wsum[j] == 0 keeps its row bit for bit.  empty : one uint32, overwritten: the number of such codes; or NULL.
+ *
+ * gsr_vq_decode: rows_out[i] = codebook[indices[i]], (n, dim).
+ *
+ * An index >= n_codes (accumulate, decode) is read as n_codes - 1: wrong numbers, never an access outside the arrays.
+ * GSR_E_INVALID_ARG, before anything touches the device: n, n_codes or dim out of range, a null array that is not optional,
+ * a misaligned array (uint16: 2, uint32: 4, 64-bit sums: 8, scratch: 16 bytes), scratch_bytes too small.  n == 0: GSR_OK,
+ * nothing is launched.  gsr_vq_scratch_bytes is 0 for n <= 0 and for sizes out of range. */
+GSR_API size_t gsr_vq_scratch_bytes(int64_t n, int32_t n_codes, int32_t dim);
+GSR_API int gsr_vq_assign(int64_t n, int32_t n_codes, int32_t dim, const float* rows, const float* codebook, const uint16_t* prev,
+                          uint16_t* indices, float* err, uint32_t* changed, void* scratch, size_t scratch_bytes, void* stream);
+GSR_API int gsr_vq_accumulate(int64_t n, int32_t n_codes, int32_t dim, const float* rows, const uint16_t* indices,
+                              const uint8_t* wq, int64_t* sums, uint64_t* wsum, void* stream);
+GSR_API int gsr_vq_update(int32_t n_codes, int32_t dim, const int64_t* sums, const uint64_t* wsum, float* codebook,
+                          uint32_t* empty, void* stream);
+GSR_API int gsr_vq_decode(int64_t n, int32_t n_codes, int32_t dim, const float* codebook, const uint16_t* indices,
+                          float* rows_out, void* stream);
+
 /* TSDF fusion of rendered depth frames and surface-nets mesh extraction: one surface of the scene from the :rgbd / :rgbdn
  * frames, made on the device.  No handle, no struct, nothing read back to the host.
  *
