@@ -172,8 +172,55 @@ def read_sky(sky, ckpt: Checkpoint, prefix: str) -> None:
         sky._refresh_activations()
 
 
+# ---- the SH codebook under fine-tuning (sh_codebook.SHCodebookFineTuner; no reference counterpart) ----
+def _u16_host(x) -> np.ndarray:
+    """uint16 indices (a torch.uint16 tensor, or a numpy array) as a numpy uint16 array."""
+    if hasattr(x, "detach"):
+        import torch
+        return np.ascontiguousarray(x.detach().cpu().view(torch.int16).numpy().view(np.uint16))
+    return np.ascontiguousarray(x, dtype=np.uint16)
+
+
+def write_sh_codebook(tensors, meta, prefix: str, tuner) -> None:
+    """`tuner`: a SHCodebookFineTuner (`sh`, `optimizer`), or a bare SHCodebook (no moments are written).  The group:
+    `{prefix}.codebook` float32 (K, D), `.indices` uint16 (n), `.shape` int64 — the features_rest the codebook stands for —
+    and the code rows' optimizer under `{prefix}.optimizer` (write_adam)."""
+    sh = getattr(tuner, "sh", tuner)
+    cb = _host(sh.codebook).astype(np.float32, copy=False)
+    tensors[f"{prefix}.codebook"] = cb
+    tensors[f"{prefix}.indices"] = _u16_host(sh.indices)
+    tensors[f"{prefix}.shape"] = np.asarray(tuple(sh.shape), np.int64)
+    opt = getattr(tuner, "optimizer", None)
+    if opt is not None:
+        write_adam(tensors, meta, f"{prefix}.optimizer", opt, shape=cb.shape)
+
+
+def read_sh_codebook(tuner, ckpt: Checkpoint, prefix: str) -> None:
+    """In place: the code rows are copied into `sh.codebook` (the tensor the optimizer and autograd know), `sh.indices` is
+    replaced — so `sh.groups()` is built again — and the optimizer's moments are restored when the object has an optimizer
+    and the file its moments.  The file's codebook must have the object's shape."""
+    import torch
+    sh = getattr(tuner, "sh", tuner)
+    cb = np.ascontiguousarray(ckpt.tensor(f"{prefix}.codebook"), dtype=np.float32)
+    idx = np.ascontiguousarray(ckpt.tensor(f"{prefix}.indices"))
+    shape = tuple(int(v) for v in ckpt.tensor(f"{prefix}.shape").reshape(-1))
+    if idx.dtype != np.uint16 or idx.ndim != 1 or cb.ndim != 2:
+        raise ValueError(f"{prefix}: not an SH codebook group")
+    if tuple(cb.shape) != tuple(sh.codebook.shape):
+        raise ValueError(f"{prefix}.codebook: {cb.shape} in the file, the object's codebook is {tuple(sh.codebook.shape)}")
+    if not shape or idx.size != shape[0] or int(np.prod(shape[1:])) != cb.shape[1]:
+        raise ValueError(f"{prefix}.shape: {shape} does not match its codebook and indices")
+    with torch.no_grad():
+        sh.codebook.copy_(torch.from_numpy(cb))
+    sh.indices = torch.from_numpy(idx.view(np.int16).copy()).view(torch.uint16).to(sh.indices.device)
+    sh.shape = shape
+    opt = getattr(tuner, "optimizer", None)
+    if opt is not None and f"{prefix}.optimizer.n_moments" in ckpt.meta:
+        read_adam(opt, ckpt, f"{prefix}.optimizer", numel=int(cb.size))
+
+
 def save_state(filename: str, gaussians, optimizers: Dict[str, object], step: int, strategy=None,
-               extra_meta: Optional[Dict[str, str]] = None, bilateral_grid=None, sky=None) -> None:
+               extra_meta: Optional[Dict[str, str]] = None, bilateral_grid=None, sky=None, sh_codebook=None) -> None:
     """The Gaussian + optimizer part of `save_state` (training.jl:418-445).  `strategy` (a densification.DefaultStrategy):
     its split-noise position is added as two metadata scalars (`strategy.split_seed_base`, `strategy.split_rounds`; an
     mcmc.MCMCStrategy: `strategy.seed_base`, `strategy.sample_rounds`, `strategy.noise_steps` — its `state_dict()`) —
@@ -182,7 +229,9 @@ def save_state(filename: str, gaussians, optimizers: Dict[str, object], step: in
     `extra_meta`: more string scalars of the same kind — e.g. {"gsr.ssim_precision": "fast"}: the arithmetic of the loss head the
     run trained with (the library default is the contracted build, not bit-identical to the exact twin).
     `sky` (a sky_dome.SkyDome): the reference's `sky.*` group (sky_dome.jl:322-327) — `sky.gaussians.*`, the colour
-    optimizer `sky.optimizer.{mu.1,nu.1,n_moments,current_step}` and the scalar `sky.radius`."""
+    optimizer `sky.optimizer.{mu.1,nu.1,n_moments,current_step}` and the scalar `sky.radius`.
+    `sh_codebook` (a sh_codebook.SHCodebookFineTuner): the group `sh_codebook.{codebook, indices, shape}` and the code rows'
+    optimizer `sh_codebook.optimizer.*` (write_sh_codebook) — tensors the reference's reader never asks for."""
     tensors, meta = {}, {}
     write_gaussians(tensors, meta, "gaussians", gaussians)
     for name in OPTIMIZER_NAMES:
@@ -205,18 +254,21 @@ def save_state(filename: str, gaussians, optimizers: Dict[str, object], step: in
         write_adam(tensors, meta, "bilateral.opt", bilateral_grid.optimizer, shape=grids.shape)
     if sky is not None:
         write_sky(tensors, meta, "sky", sky)
+    if sh_codebook is not None:
+        write_sh_codebook(tensors, meta, "sh_codebook", sh_codebook)
     for k, v in (extra_meta or {}).items():
         meta[str(k)] = str(v)
     save_checkpoint(filename, tensors, meta)
 
 
-def load_state(filename: str, optimizers: Dict[str, object], strategy=None, bilateral_grid=None, sky=None):
+def load_state(filename: str, optimizers: Dict[str, object], strategy=None, bilateral_grid=None, sky=None, sh_codebook=None):
     """Counterpart (training.jl:447-470): returns (GaussianModel, step); optimizers are filled in place, and so is
     `strategy`'s split-noise position when the file carries one.  `bilateral_grid` (a bilateral_grid.BilateralGrid): its
     grids and optimizer are restored in place when the file has them (training.jl:452-459, `haskey` semantics: a file
     without them leaves the grids as they are).  `sky` (a sky_dome.SkyDome): restored in place when the file has
     `sky.gaussians.points` (training.jl:463-465, the same semantics: a file without the group leaves the dome as built, and
-    without `sky` the group is ignored)."""
+    without `sky` the group is ignored).  `sh_codebook` (a sh_codebook.SHCodebookFineTuner): restored in place when the file
+    has `sh_codebook.codebook`, the same semantics."""
     ckpt = load_checkpoint(filename)
     g = read_gaussians(ckpt, "gaussians")
     for name in OPTIMIZER_NAMES:
@@ -247,4 +299,6 @@ def load_state(filename: str, optimizers: Dict[str, object], strategy=None, bila
         read_adam(bilateral_grid.optimizer, ckpt, "bilateral.opt", numel=int(host.size))
     if sky is not None and "sky.gaussians.points" in ckpt:
         read_sky(sky, ckpt, "sky")
+    if sh_codebook is not None and "sh_codebook.codebook" in ckpt:
+        read_sh_codebook(sh_codebook, ckpt, "sh_codebook")
     return g, ckpt.read_scalar("step")

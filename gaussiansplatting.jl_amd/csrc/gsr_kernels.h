@@ -383,6 +383,14 @@ void gsr_launch_vq_update(hipStream_t s, int n_codes, int dim, const long long* 
 void gsr_launch_vq_decode(hipStream_t s, int n, int n_codes, int dim, const float* codebook, const uint16_t* indices,
                           float* rows_out);
 
+// ---- vq_grad.hip (compiled with -ffp-contract=off): SH codebook fine-tuning — the stable grouping of the rows by code, the fixed-order per-code gradient sums ----
+size_t gsr_vq_group_scratch_size(long long n, int n_codes);
+void gsr_launch_vq_group(hipStream_t s, int n, int n_codes, const uint16_t* indices, uint32_t* order, uint32_t* offsets,
+                         void* scratch);
+size_t gsr_vq_codebook_grad_scratch_size(long long n, int n_codes, int dim);
+void gsr_launch_vq_codebook_grad(hipStream_t s, int n, int n_codes, int dim, const float* g_rows, long long row_stride,
+                                 const uint32_t* order, const uint32_t* offsets, float* g_codebook, void* scratch);
+
 // ---- tsdf.hip (compiled with -ffp-contract=off): TSDF fusion of a rendered frame, surface-nets count and emit ----
 // the volume: nx x ny x nz samples, sample (i, j, k) at o + h*(i, j, k)
 struct GsrTsdfGrid {

@@ -1,7 +1,7 @@
 // C ABI of libgsr_hip.so (include/gsr.h), the part without a handle: every entry point that checks its arguments, launches
 // its kernels on the caller's stream and keeps nothing — planar SSIM, the trainer's prologue / Adam / tail, row gathers, the
 // bilateral grid, the geometry, depth and sky losses, the evaluation head, the geometry frames, densification, MCMC, Morton
-// codes, k-NN, the 3-D smoothing filter, the SH codebook k-means, TSDF fusion and mesh extraction, PLY rows, the multi-view SH gradient, the all-reduce.  (The handle and its launch choreography are gsr_api.cpp's.)
+// codes, k-NN, the 3-D smoothing filter, the SH codebook k-means and its fine-tuning gradient, TSDF fusion and mesh extraction, PLY rows, the multi-view SH gradient, the all-reduce.  (The handle and its launch choreography are gsr_api.cpp's.)
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -859,6 +859,48 @@ int gsr_vq_decode(int64_t n, int32_t n_codes, int32_t dim, const float* codebook
     if (!codebook || !indices || !rows_out) return fail(GSR_E_INVALID_ARG, "null codebook, indices or rows_out");
     if ((uintptr_t)indices % 2) return fail(GSR_E_INVALID_ARG, "indices must be 2-byte aligned");
     gsr_launch_vq_decode((hipStream_t)stream, (int)n, n_codes, dim, codebook, indices, rows_out);
+    return launched();
+}
+
+// ---- SH codebook fine-tuning: rows grouped by code, fixed-order per-code gradient sums (vq_grad.hip) ----
+size_t gsr_vq_group_scratch_bytes(int64_t n, int32_t n_codes) {
+    if (n <= 0 || n >= (1ll << 24) || n_codes < 1 || n_codes > 65536) return 0;
+    return gsr_vq_group_scratch_size(n, n_codes);
+}
+
+int gsr_vq_group(int64_t n, int32_t n_codes, const uint16_t* indices, uint32_t* order, uint32_t* offsets, void* scratch,
+                 size_t scratch_bytes, void* stream) {
+    int rc;
+    if ((rc = check_vq_shape(n, n_codes, 1))) return rc;
+    if (n == 0) return GSR_OK;
+    if (!indices || !order || !offsets || !scratch) return fail(GSR_E_INVALID_ARG, "null indices, order, offsets or scratch");
+    if ((uintptr_t)indices % 2) return fail(GSR_E_INVALID_ARG, "indices must be 2-byte aligned");
+    if ((uintptr_t)order % 4 || (uintptr_t)offsets % 4) return fail(GSR_E_INVALID_ARG, "order and offsets must be 4-byte aligned");
+    if ((rc = check_scratch(scratch_bytes, gsr_vq_group_scratch_bytes(n, n_codes), "grouping of the rows by code"))) return rc;
+    if ((uintptr_t)scratch % 16) return fail(GSR_E_INVALID_ARG, "scratch must be 16-byte aligned");
+    gsr_launch_vq_group((hipStream_t)stream, (int)n, n_codes, indices, order, offsets, scratch);
+    return launched();
+}
+
+size_t gsr_vq_codebook_grad_scratch_bytes(int64_t n, int32_t n_codes, int32_t dim) {
+    if (n <= 0 || n >= (1ll << 24) || n_codes < 1 || n_codes > 65536 || dim < 1 || dim > 48) return 0;
+    return gsr_vq_codebook_grad_scratch_size(n, n_codes, dim);
+}
+
+int gsr_vq_codebook_grad(int64_t n, int32_t n_codes, int32_t dim, const float* g_rows, int64_t row_stride, const uint32_t* order,
+                         const uint32_t* offsets, float* g_codebook, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc;
+    if ((rc = check_vq_shape(n, n_codes, dim))) return rc;
+    if (row_stride < dim) return fail(GSR_E_INVALID_ARG, "row_stride = %lld floats: at least dim = %d", (long long)row_stride, dim);
+    if (n == 0) return GSR_OK;
+    if (!g_rows || !order || !offsets || !g_codebook || !scratch)
+        return fail(GSR_E_INVALID_ARG, "null g_rows, order, offsets, g_codebook or scratch");
+    if ((uintptr_t)g_rows % 4 || (uintptr_t)g_codebook % 4) return fail(GSR_E_INVALID_ARG, "g_rows and g_codebook must be 4-byte aligned");
+    if ((uintptr_t)order % 4 || (uintptr_t)offsets % 4) return fail(GSR_E_INVALID_ARG, "order and offsets must be 4-byte aligned");
+    if ((rc = check_scratch(scratch_bytes, gsr_vq_codebook_grad_scratch_bytes(n, n_codes, dim), "per-code gradient sums"))) return rc;
+    if ((uintptr_t)scratch % 16) return fail(GSR_E_INVALID_ARG, "scratch must be 16-byte aligned");
+    gsr_launch_vq_codebook_grad((hipStream_t)stream, (int)n, n_codes, dim, g_rows, (long long)row_stride, order, offsets, g_codebook,
+                                scratch);
     return launched();
 }
 

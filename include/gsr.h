@@ -767,6 +767,46 @@ GSR_API int gsr_vq_update(int32_t n_codes, int32_t dim, const int64_t* sums, con
 GSR_API int gsr_vq_decode(int64_t n, int32_t n_codes, int32_t dim, const float* codebook, const uint16_t* indices,
                           float* rows_out, void* stream);
 
+/* SH codebook fine-tuning: training THROUGH the codebook, the indices fixed and the code rows the parameters (DESIGN.md
+ * section 24).  The pullback of rows[i] = codebook[indices[i]] is a scatter-add of n gradient rows into n_codes rows; here it
+ * is a sum in a FIXED order, with no float atomics: the same bits in every run.  Same ranges and conventions as gsr_vq_*.
+ *
+ * Grouping (gsr_vq_group, once per set of indices).  Let c_i = min(indices[i], n_codes - 1).
+ *     offsets[j] = #{ i : c_i < j },  j = 0 .. n_codes          (uint32, n_codes + 1 entries; offsets[n_codes] = n)
+ *     order      = the row numbers 0 .. n-1 sorted by (c_i, i)   (uint32, n entries: the STABLE counting sort)
+ * Both are uniquely determined: any correct implementation gives the same integers.
+ *
+ * Gradient (gsr_vq_codebook_grad, every step).  For code j, L_0 is the list of rows g[order[offsets[j]]], ...,
+ * g[order[offsets[j+1] - 1]] — ascending row numbers.  With the radix R = GSR_VQ_SUM_RADIX:
+ *     reduce(L):  if |L| = 1, that value, bit for bit (no add)
+ *                 else reduce([chunk_0, chunk_1, ...]), chunk_c the serial fp32 sum of L[R c .. R c + R - 1]:
+ *                      s = L[R c];  s = s + L[R c + 1];  s = s + L[R c + 2]; ...     (one rounded fp32 add each, ascending)
+ *     g_codebook[j][d] = reduce(L_0)[d];   an empty code gets +0.0f
+ * Every column d by itself; no fused operation, no double precision.  With n < 2^24 the recursion has at most four levels.
+ * A NaN or Inf in a row reaches its own code and column only.  g_codebook is fully overwritten, whatever it held.
+ * Error bound: a serial fp32 sum of at most 64 terms is within 63 * 2^-24 * sum|x| of the exact sum to first order; four
+ * levels compound to less than 256 * 2^-24:  |g_codebook[j][d] - exact| <= 2^-16 * sum over the code's rows of |g[i][d]|.
+ *
+ *   g_rows     : row i starts at g_rows + i * row_stride floats; row_stride >= dim, 4-byte alignment is enough.  The (N, K, 3)
+ *                vshs that gsr_backward writes is read in place with g_rows = vshs + 3, row_stride = 3 * K.
+ *   order, offsets : as above, 4-byte aligned.  An order entry >= n is read as n - 1, offsets[j] as min(offsets[j], n), a code
+ *                whose end lies before its start is empty: wrong numbers, never an access outside the arrays.
+ *   g_codebook : (n_codes, dim).
+ *   scratch    : gsr_vq_group_scratch_bytes(n, n_codes) / gsr_vq_codebook_grad_scratch_bytes(n, n_codes, dim) bytes, 16-byte
+ *                aligned, written before it is read.  The gradient's holds the per-level slot prefixes (n_codes + 1 uint32 per
+ *                level, made per call from offsets) and the partial rows: at level l at most floor(n / R^l) + min(n_codes, n).
+ * Nothing is read back to the host; the launches are sized from n and n_codes alone, ceil(log_R n) levels (at least one).
+ * GSR_E_INVALID_ARG, before anything touches the device, as for gsr_vq_*; also row_stride < dim.  n == 0: GSR_OK, nothing is
+ * launched and nothing written.  The scratch sizes are 0 for n <= 0 and for sizes out of range. */
+#define GSR_VQ_SUM_RADIX 64
+GSR_API size_t gsr_vq_group_scratch_bytes(int64_t n, int32_t n_codes);
+GSR_API int gsr_vq_group(int64_t n, int32_t n_codes, const uint16_t* indices, uint32_t* order, uint32_t* offsets,
+                         void* scratch, size_t scratch_bytes, void* stream);
+GSR_API size_t gsr_vq_codebook_grad_scratch_bytes(int64_t n, int32_t n_codes, int32_t dim);
+GSR_API int gsr_vq_codebook_grad(int64_t n, int32_t n_codes, int32_t dim, const float* g_rows, int64_t row_stride,
+                                 const uint32_t* order, const uint32_t* offsets, float* g_codebook,
+                                 void* scratch, size_t scratch_bytes, void* stream);
+
 /* TSDF fusion of rendered depth frames and surface-nets mesh extraction: one surface of the scene from the :rgbd / :rgbdn
  * frames, made on the device.  No handle, no struct, nothing read back to the host.
  *
