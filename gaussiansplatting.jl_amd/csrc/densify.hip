@@ -14,11 +14,13 @@ namespace {
 
 __device__ __forceinline__ float sigmoid_(float x) { return 1.0f / (1.0f + expf(-x)); }  // NU.sigmoid
 
-// maximum(exp.(gs.scales); dims=1) of Gaussian i (densification.jl:36-38,79-80,22)
+// maximum(exp.(gs.scales); dims=1) of Gaussian i (densification.jl:36-38,79-80,22).  Julia's `maximum` propagates a NaN
+// and fmaxf drops it: one select puts it back, so every comparison on a row with a NaN axis is false.
 __device__ __forceinline__ float max_exp_scale(const float* __restrict__ scales, int scale_dims, long long i) {
     if (scale_dims == 1) return expf(scales[i]);
     const float a = expf(scales[3 * i]), b = expf(scales[3 * i + 1]), c = expf(scales[3 * i + 2]);
-    return fmaxf(fmaxf(a, b), c);
+    const float m = fmaxf(fmaxf(a, b), c);
+    return (a != a || b != b || c != c) ? __builtin_nanf("") : m;
 }
 
 // ∇means_2d = accum ./ denom with NaN -> 0 (densification.jl:7-10)
@@ -150,7 +152,8 @@ __global__ __launch_bounds__(256) void split_transform_kernel(long long n_new, i
 __global__ __launch_bounds__(256) void reset_opacity_kernel(long long n, float* __restrict__ opacities) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float o = fminf(0.1f, sigmoid_(opacities[i]));
+    const float sg = sigmoid_(opacities[i]);
+    const float o = sg != sg ? sg : fminf(0.1f, sg);  // Julia's `min` propagates a NaN, fminf drops it
     opacities[i] = logf(o / (1.0f - o));
 }
 

@@ -610,7 +610,10 @@ GSR_API int gsr_gather_rows(const gsr_gather_group* groups, int32_t n_groups, co
  *                                                 holds n_grad <= n entries, rows beyond it count as 0: padded_grad)
  *                              GSR_DENSIFY_PRUNE  mask = sigmoid(opacity) > min_opacity, and when max_screen_size > 0
  *                                                 && max_radii < max_screen_size && max(exp(scales)) < gamma  (:18-25)
- *                         scales are the RAW log-scales (scale_dims = 3, or 1 for an isotropic model).
+ *                         scales are the RAW log-scales (scale_dims = 3, or 1 for an isotropic model).  Every comparison
+ *                         is the reference's own: strict where it is strict, and false on a NaN — a NaN grad, opacity or
+ *                         scale on ANY axis (Julia's `maximum` propagates it) leaves the row out of all three masks.  With
+ *                         max_screen_size = 0 the prune mask reads neither scales nor max_radii (both may be NULL).
  * gsr_compose_rows      : the row surgery of append_gaussians! / _append_optimizer! / prune_points! /
  *                         _prune_optimizer! (:138-297) for up to GSR_COMPOSE_MAX_GROUPS arrays in one launch:
  *                           dst[r]                      = src[keep_idx[r]]                 r < n_keep (keep_idx NULL: r)
@@ -621,7 +624,10 @@ GSR_API int gsr_gather_rows(const gsr_gather_group* groups, int32_t n_groups, co
  * gsr_split_transform   : on the 2m rows a split appended: sigma = exp(scale); point += R(q)·(sigma .* randn3);
  *                         scale = log(sigma / 1.6)   (:81-104, _add_split_noise! :121-135).  The normals come from a
  *                         counter-based generator keyed by (seed, row) — the reference uses the backend's device RNG.
- * gsr_reset_opacity     : opacity = inverse_sigmoid(min(0.1, sigmoid(opacity)))  (gaussians.jl:119-126,137). */
+ * gsr_reset_opacity     : opacity = inverse_sigmoid(min(0.1, sigmoid(opacity)))  (gaussians.jl:119-126,137).  `min` is Julia's:
+ *                         a NaN opacity stays a NaN (gsr_count_nonfinite still sees it); an opacity whose fp32 sigmoid
+ *                         underflows to 0 becomes -Inf, as log(0 / 1) is.
+ * tests/densify_ref.py states all of this in float64; tests/test_gpu_density_edges.py holds the kernels to it. */
 enum { GSR_DENSIFY_CLONE = 0, GSR_DENSIFY_SPLIT = 1, GSR_DENSIFY_PRUNE = 2 };
 #define GSR_COMPOSE_MAX_GROUPS 24
 typedef struct gsr_compose_group {

@@ -75,7 +75,8 @@ def new_optimizers(gs: Model):
 
 
 def max_exp_scale(scales):
-    """reshape(maximum(exp.(gs.scales); dims=1), :)"""
+    """reshape(maximum(exp.(gs.scales); dims=1), :) — np.max, like Julia's maximum, gives NaN for a row with a NaN on any
+    axis, so every mask comparison on such a row is false"""
     return np.exp(np.asarray(scales, f32), dtype=f32).max(axis=1)
 
 
@@ -178,6 +179,20 @@ def densify_clone(strategy, gs, optimizers, grad, grad_threshold, extent, dense_
     return mask
 
 
+def split_transform(points, rotations, scales, seed, n_split=2):
+    """What densify_split! does to the rows it appends (densification.jl:80,86,92-100; _add_split_noise! :121-135), given the
+    parents' repeated points, rotations and raw scales: (children's points, children's raw scales)."""
+    stds = np.exp(np.asarray(scales, f32), dtype=f32)                                 # exp.(gs.scales)[:, mask], repeated
+    new_scales = np.log(stds / (f32(0.8) * f32(n_split)), dtype=f32)
+    m = points.shape[0]
+    if m == 0:
+        return points, new_scales
+    xi = stds * randn3(seed, m)                                                       # σ .* randn3 (isotropic: σ broadcasts)
+    R = unnorm_quat2rot(rotations)
+    step = (R[:, :, 0] * xi[:, 0:1] + R[:, :, 1] * xi[:, 1:2]) + R[:, :, 2] * xi[:, 2:3]
+    return (points + step).astype(f32), new_scales
+
+
 def densify_split(strategy, gs, optimizers, grad, grad_threshold, extent, dense_percent, seed):
     """densification.jl:64-119 (+ _add_split_noise! :121-135)"""
     n, n_split = len(gs), 2
@@ -185,15 +200,9 @@ def densify_split(strategy, gs, optimizers, grad, grad_threshold, extent, dense_
     padded[:grad.shape[0]] = grad
     gamma = f32(extent) * f32(dense_percent)
     mask = (padded >= f32(grad_threshold)) & (max_exp_scale(gs.scales) > gamma)
-    stds = np.tile(np.exp(gs.scales[mask], dtype=f32), (n_split, 1))             # repeat(..., 1, n_split): block repeat
-    new = {k: _sel(gs, k, mask, n_split) for k in PARAMS}
-    new["scales"] = np.log(stds / (f32(0.8) * f32(n_split)), dtype=f32)
+    new = {k: _sel(gs, k, mask, n_split) for k in PARAMS}                             # repeat(..., 1, n_split): block repeat
+    new["points"], new["scales"] = split_transform(new["points"], new["rotations"], new["scales"], seed, n_split)
     m = new["points"].shape[0]
-    if m > 0:
-        xi = stds * randn3(seed, m)                                                   # σ .* randn3 (isotropic: σ broadcasts)
-        R = unnorm_quat2rot(new["rotations"])
-        step = (R[:, :, 0] * xi[:, 0:1] + R[:, :, 1] * xi[:, 1:2]) + R[:, :, 2] * xi[:, 2:3]
-        new["points"] = (new["points"] + step).astype(f32)
     densification_postfix(strategy, gs, optimizers, new)
     valid = np.concatenate([~mask, np.ones(m, bool)])
     prune_points(strategy, gs, optimizers, valid)
@@ -219,7 +228,7 @@ def densify_and_prune(strategy: Strategy, gs: Model, optimizers, extent, pruning
 
 
 def reset_opacity(gs: Model):
-    """gaussians.jl:115-126"""
+    """gaussians.jl:115-126; np.minimum, like Julia's min, keeps a NaN opacity a NaN"""
     gs.opacities = inverse_sigmoid(np.minimum(f32(0.1), sigmoid(gs.opacities))).astype(f32)
 
 

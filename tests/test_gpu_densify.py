@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from densify_ref import morton
 from hip_helpers import dev, rel_l2
 from oracle import densify as dz
 from test_oracle_densify import fill_stats, make_model
@@ -188,20 +189,6 @@ def test_default_split_seed_differs_between_rounds(pkg):
     assert s3.split_rounds == 1 and s3.next_split_seed() == s1.next_split_seed()
 
 
-def _morton_ref(points, bits=21):
-    """numpy restatement of gsr_morton_codes (float32 arithmetic as the kernel's)."""
-    lo, hi = points.min(0), points.max(0)
-    ext = (hi - lo).astype(f32)
-    inv = np.where(ext > 0, f32(1.0) / np.where(ext > 0, ext, f32(1.0)), f32(0.0)).astype(f32)
-    t = np.clip(((points - lo).astype(f32) * inv).astype(f32), f32(0.0), f32(1.0))
-    cells = (t * f32(2 ** bits - 1)).astype(f32).astype(np.uint64)
-    codes = np.zeros(len(points), np.uint64)
-    for b in range(bits):
-        for a in range(3):
-            codes |= ((cells[:, a] >> np.uint64(b)) & np.uint64(1)) << np.uint64(3 * b + a)
-    return codes
-
-
 def test_reorder_spatially_is_a_consistent_permutation_and_leaves_the_render_unchanged(pkg, orc):
     """densification.reorder_spatially (not a reference function; DefaultStrategy(spatial_reorder=True) runs it after each
     densification): every per-Gaussian array — parameters, Adam moments, ids, statistics — is permuted by ONE permutation,
@@ -226,7 +213,8 @@ def test_reorder_spatially_is_a_consistent_permutation_and_leaves_the_render_unc
     perm = Dz.reorder_spatially(st, gs_d, opt_d).cpu().numpy()
     torch.cuda.synchronize()
     assert np.array_equal(np.sort(perm), np.arange(n))
-    codes = _morton_ref(before["points"].reshape(n, 3))
+    pts = before["points"].reshape(n, 3)
+    codes = morton(pts, pts.min(0), pts.max(0))                # the box reorder_spatially takes: the finite extent
     assert np.array_equal(perm, np.argsort(codes, kind="stable"))
     assert np.array_equal(gs_d.ids.cpu().numpy(), perm)
     for k in dz.PARAMS:
