@@ -17,7 +17,7 @@ def __getattr__(name):
     # torch-dependent modules are imported lazily
     if name in ("rasterizer", "fused_ssim", "distributed", "optim", "densification", "bilateral_grid",
                 "geometry_regularization", "mcmc", "depth_supervision", "sky_dome", "point_cloud", "training_loss",
-                "smoothing_filter", "surface_mesh", "contribution", "sh_codebook"):
+                "smoothing_filter", "surface_mesh", "contribution", "sh_codebook", "quantised_model"):
         import importlib
         return importlib.import_module(f"{__name__}.{name}")   # (training_loss: a callable module, the function and its specs)
     if name in ("GaussianRasterizer", "rasterize", "grad_rasterize", "n_color_features"):

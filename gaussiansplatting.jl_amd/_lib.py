@@ -117,6 +117,13 @@ class DepthAnchorS(C.Structure):  # gsr_depth_anchor
     _fields_ = [("a", C.c_float), ("b", C.c_float), ("floor", C.c_float), ("disparity", C.c_float), ("p_far", C.c_float)]
 
 
+class QuantGroup(C.Structure):  # gsr_quant_group
+    _fields_ = [("rows_in", C.c_void_p), ("rows_out", C.c_void_p), ("cols", C.c_int32), ("bits", C.c_int32), ("kind", C.c_int32),
+                ("block_rows", C.c_int32), ("ranges", C.c_void_p)]
+
+
+QUANT_LINEAR, QUANT_UNIT_QUAT = 0, 1   # gsr_quant_group.kind
+QUANT_MAX_GROUPS = 8                   # GSR_QUANT_MAX_GROUPS
 COMPOSE_MAX_GROUPS = 24
 VQ_SUM_RADIX = 64            # GSR_VQ_SUM_RADIX: the chunk length of gsr_vq_codebook_grad's fixed-order sums
 FILTER3D_CAMERA_FLOATS = 22  # GSR_FILTER3D_CAMERA_FLOATS: one row of gsr_filter3d_compute's camera table
@@ -212,6 +219,7 @@ EXPORTS = ["gsr_create", "gsr_destroy", "gsr_release_scene_buffers", "gsr_memory
            "gsr_filter3d_scratch_bytes", "gsr_filter3d_compute", "gsr_filter3d_apply", "gsr_filter3d_apply_backward",
            "gsr_vq_scratch_bytes", "gsr_vq_assign", "gsr_vq_accumulate", "gsr_vq_update", "gsr_vq_decode",
            "gsr_vq_group_scratch_bytes", "gsr_vq_group", "gsr_vq_codebook_grad_scratch_bytes", "gsr_vq_codebook_grad",
+           "gsr_quant_ranges", "gsr_quant_encode", "gsr_quant_decode", "gsr_quant_fake",
            "gsr_tsdf_integrate", "gsr_mesh_scratch_bytes", "gsr_mesh_count", "gsr_mesh_emit",
            "gsr_ply_pack_rows", "gsr_ply_unpack_rows", "gsr_count_nonfinite",
            "gsr_bilateral_scratch_bytes", "gsr_bilateral_tv_scratch_bytes", "gsr_bilateral_slice_forward",
@@ -318,6 +326,10 @@ def load():
     lib.gsr_vq_codebook_grad_scratch_bytes.argtypes = [i64, C.c_int32, C.c_int32]
     lib.gsr_vq_codebook_grad_scratch_bytes.restype = C.c_size_t
     lib.gsr_vq_codebook_grad.argtypes = [i64, C.c_int32, C.c_int32, vp, i64, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.gsr_quant_ranges.argtypes = [i64, C.c_int32, vp, C.c_int32, vp, vp]
+    lib.gsr_quant_encode.argtypes = [i64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp]
+    lib.gsr_quant_decode.argtypes = [i64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp]
+    lib.gsr_quant_fake.argtypes = [C.POINTER(QuantGroup), C.c_int32, i64, vp]
     lib.gsr_tsdf_integrate.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, f32, f32, C.c_int32, C.c_int32, C.c_int32, vp,
                                        C.POINTER(CameraS), f32, f32, vp, vp, vp]
     lib.gsr_mesh_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

@@ -391,6 +391,15 @@ size_t gsr_vq_codebook_grad_scratch_size(long long n, int n_codes, int dim);
 void gsr_launch_vq_codebook_grad(hipStream_t s, int n, int n_codes, int dim, const float* g_rows, long long row_stride,
                                  const uint32_t* order, const uint32_t* offsets, float* g_codebook, void* scratch);
 
+// ---- quant.hip (compiled with -ffp-contract=off): the quantised model container — block ranges, 8/16-bit codes, the decode, the one-launch fake pass ----
+void gsr_launch_quant_ranges(hipStream_t s, long long n, int cols, const float* rows, int block_rows, float* ranges);
+void gsr_launch_quant_encode(hipStream_t s, long long n, int cols, int bits, int kind, const float* rows, int block_rows,
+                             const float* ranges, void* codes);
+void gsr_launch_quant_decode(hipStream_t s, long long n, int cols, int bits, int kind, const void* codes, int block_rows,
+                             const float* ranges, float* rows_out);
+void gsr_launch_quant_fake(hipStream_t s, int n_groups, long long n, const float* const* in, float* const* out,
+                           const float* const* ranges, const int* cols, const int* bits, const int* kind, const int* block_rows);
+
 // ---- tsdf.hip (compiled with -ffp-contract=off): TSDF fusion of a rendered frame, surface-nets count and emit ----
 // the volume: nx x ny x nz samples, sample (i, j, k) at o + h*(i, j, k)
 struct GsrTsdfGrid {

@@ -1,7 +1,7 @@
 // C ABI of libgsr_hip.so (include/gsr.h), the part without a handle: every entry point that checks its arguments, launches
 // its kernels on the caller's stream and keeps nothing — planar SSIM, the trainer's prologue / Adam / tail, row gathers, the
 // bilateral grid, the geometry, depth and sky losses, the evaluation head, the geometry frames, densification, MCMC, Morton
-// codes, k-NN, the 3-D smoothing filter, the SH codebook k-means and its fine-tuning gradient, TSDF fusion and mesh extraction, PLY rows, the multi-view SH gradient, the all-reduce.  (The handle and its launch choreography are gsr_api.cpp's.)
+// codes, k-NN, the 3-D smoothing filter, the SH codebook k-means and its fine-tuning gradient, the quantised model container, TSDF fusion and mesh extraction, PLY rows, the multi-view SH gradient, the all-reduce.  (The handle and its launch choreography are gsr_api.cpp's.)
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -901,6 +901,82 @@ int gsr_vq_codebook_grad(int64_t n, int32_t n_codes, int32_t dim, const float* g
     if ((uintptr_t)scratch % 16) return fail(GSR_E_INVALID_ARG, "scratch must be 16-byte aligned");
     gsr_launch_vq_codebook_grad((hipStream_t)stream, (int)n, n_codes, dim, g_rows, (long long)row_stride, order, offsets, g_codebook,
                                 scratch);
+    return launched();
+}
+
+// ---- the quantised model container: block ranges, 8/16-bit codes, the decode, the fake pass (quant.hip) ----
+static int check_quant_shape(int64_t n, int32_t cols, int32_t block_rows) {
+    if (n < 0 || n >= (1ll << 31)) return fail(GSR_E_INVALID_ARG, "n = %lld: 0 <= n < 2^31 rows", (long long)n);
+    if (cols < 1 || cols > 48) return fail(GSR_E_INVALID_ARG, "cols = %d: 1 .. 48", cols);
+    if (block_rows != 0 && (block_rows < 64 || block_rows > 1024 || block_rows % 64))
+        return fail(GSR_E_INVALID_ARG, "block_rows = %d: 0, or a multiple of 64 in [64, 1024]", block_rows);
+    return GSR_OK;
+}
+
+static int check_quant_code(int32_t cols, int32_t bits, int32_t kind) {
+    if (bits < 1 || bits > 16) return fail(GSR_E_INVALID_ARG, "bits = %d: 1 .. 16", bits);
+    if (kind != GSR_QUANT_LINEAR && kind != GSR_QUANT_UNIT_QUAT) return fail(GSR_E_INVALID_ARG, "kind = %d: GSR_QUANT_LINEAR or GSR_QUANT_UNIT_QUAT", kind);
+    if (kind == GSR_QUANT_UNIT_QUAT && cols != 4) return fail(GSR_E_INVALID_ARG, "GSR_QUANT_UNIT_QUAT needs cols = 4, not %d", cols);
+    return GSR_OK;
+}
+
+int gsr_quant_ranges(int64_t n, int32_t cols, const float* rows, int32_t block_rows, float* ranges, void* stream) {
+    int rc;
+    if ((rc = check_quant_shape(n, cols, block_rows))) return rc;
+    if (n == 0 && block_rows != 0) return GSR_OK;
+    if ((n > 0 && !rows) || !ranges) return fail(GSR_E_INVALID_ARG, "null rows or ranges");
+    if ((uintptr_t)rows % 4 || (uintptr_t)ranges % 4) return fail(GSR_E_INVALID_ARG, "rows and ranges must be 4-byte aligned");
+    gsr_launch_quant_ranges((hipStream_t)stream, n, cols, rows, block_rows, ranges);
+    return launched();
+}
+
+int gsr_quant_encode(int64_t n, int32_t cols, int32_t bits, int32_t kind, const float* rows, int32_t block_rows, const float* ranges,
+                     void* codes, void* stream) {
+    int rc;
+    if ((rc = check_quant_shape(n, cols, block_rows))) return rc;
+    if ((rc = check_quant_code(cols, bits, kind))) return rc;
+    if (n == 0) return GSR_OK;
+    if (!rows || !codes || (kind == GSR_QUANT_LINEAR && !ranges)) return fail(GSR_E_INVALID_ARG, "null rows, codes or ranges");
+    if ((uintptr_t)rows % 4 || (uintptr_t)ranges % 4) return fail(GSR_E_INVALID_ARG, "rows and ranges must be 4-byte aligned");
+    if (bits > 8 && (uintptr_t)codes % 2) return fail(GSR_E_INVALID_ARG, "uint16 codes must be 2-byte aligned");
+    gsr_launch_quant_encode((hipStream_t)stream, n, cols, bits, kind, rows, block_rows, ranges, codes);
+    return launched();
+}
+
+int gsr_quant_decode(int64_t n, int32_t cols, int32_t bits, int32_t kind, const void* codes, int32_t block_rows, const float* ranges,
+                     float* rows_out, void* stream) {
+    int rc;
+    if ((rc = check_quant_shape(n, cols, block_rows))) return rc;
+    if ((rc = check_quant_code(cols, bits, kind))) return rc;
+    if (n == 0) return GSR_OK;
+    if (!codes || !rows_out || (kind == GSR_QUANT_LINEAR && !ranges)) return fail(GSR_E_INVALID_ARG, "null codes, rows_out or ranges");
+    if ((uintptr_t)rows_out % 4 || (uintptr_t)ranges % 4) return fail(GSR_E_INVALID_ARG, "rows_out and ranges must be 4-byte aligned");
+    if (bits > 8 && (uintptr_t)codes % 2) return fail(GSR_E_INVALID_ARG, "uint16 codes must be 2-byte aligned");
+    gsr_launch_quant_decode((hipStream_t)stream, n, cols, bits, kind, codes, block_rows, ranges, rows_out);
+    return launched();
+}
+
+int gsr_quant_fake(const gsr_quant_group* groups, int32_t n_groups, int64_t n, void* stream) {
+    if (n_groups < 0 || n_groups > GSR_QUANT_MAX_GROUPS || (n_groups > 0 && !groups))
+        return fail(GSR_E_INVALID_ARG, "n_groups must be in [0, %d]", GSR_QUANT_MAX_GROUPS);
+    const float* in[GSR_QUANT_MAX_GROUPS]; float* out[GSR_QUANT_MAX_GROUPS]; const float* ranges[GSR_QUANT_MAX_GROUPS];
+    int cols[GSR_QUANT_MAX_GROUPS], bits[GSR_QUANT_MAX_GROUPS], kind[GSR_QUANT_MAX_GROUPS], block_rows[GSR_QUANT_MAX_GROUPS];
+    int rc;
+    if (n_groups == 0 && (rc = check_quant_shape(n, 1, 0))) return rc;
+    for (int g = 0; g < n_groups; g++) {
+        const gsr_quant_group& a = groups[g];
+        if ((rc = check_quant_shape(n, a.cols, a.block_rows))) return rc;
+        if ((rc = check_quant_code(a.cols, a.bits, a.kind))) return rc;
+        if (n > 0) {
+            if (!a.rows_in || !a.rows_out || (a.kind == GSR_QUANT_LINEAR && !a.ranges)) return fail(GSR_E_INVALID_ARG, "group %d: null array", g);
+            if ((uintptr_t)a.rows_in % 4 || (uintptr_t)a.rows_out % 4 || (uintptr_t)a.ranges % 4)
+                return fail(GSR_E_INVALID_ARG, "group %d: the arrays must be 4-byte aligned", g);
+        }
+        in[g] = a.rows_in; out[g] = a.rows_out; ranges[g] = a.ranges;
+        cols[g] = a.cols; bits[g] = a.bits; kind[g] = a.kind; block_rows[g] = a.block_rows;
+    }
+    if (n == 0 || n_groups == 0) return GSR_OK;
+    gsr_launch_quant_fake((hipStream_t)stream, n_groups, n, in, out, ranges, cols, bits, kind, block_rows);
     return launched();
 }
 

@@ -813,6 +813,63 @@ GSR_API int gsr_vq_codebook_grad(int64_t n, int32_t n_codes, int32_t dim, const 
                                  const uint32_t* order, const uint32_t* offsets, float* g_codebook,
                                  void* scratch, size_t scratch_bytes, void* stream);
 
+/* The quantised model container: per-(block, column) ranges of an (n, cols) float32 group, 8- or 16-bit codes, the decode,
+ * and the per-step quantise-dequantise pass - the last step of LightGaussian, Compact3D and "Compressed
+ * 3D Gaussian Splatting": with the SH codebook of gsr_vq_* a degree-3 Gaussian is 6 + 3 + 1 + 3 + 4 + 2 = 19 bytes.  No
+ * handle, nothing read back to the host.  Arrays are device, contiguous, float32 unless stated.
+ *
+ * A group is an (n, cols) row-major float32 array: 1 <= cols <= 48, 0 <= n < 2^31, 1 <= bits <= 16.  Codes are uint8 when
+ * bits <= 8, else uint16, in the same (n, cols) layout.  block_rows is 0 (one block: the whole array) or a multiple of 64 in
+ * [64, 1024]; block b holds rows [b*block_rows, min(n, (b+1)*block_rows)); n_blocks = 1 for block_rows = 0, else
+ * ceil(n / block_rows).  ranges is (n_blocks, 2, cols) float32: [b][0][c] = lo, [b][1][c] = hi.
+ *
+ * Every operation below is ONE rounded fp32 operation, with subnormals kept.
+ *
+ *   ranges:  lo / hi = the minimum / maximum over the FINITE values of (block, column) in the order of the monotone integer
+ *            key of the bits (so -0 < +0); a (block, column) without a finite value gets lo = hi = +0
+ *   encode:  span = hi - lo;   ok = span > 0 && span < +Inf          (false also for NaN ranges)
+ *            Lf = (float)(2^bits - 1);   inv = Lf / span;   step = span / Lf
+ *            t = (x - lo) * inv          (the difference is rounded, then the product)
+ *            t = isnan(t) ? 0 : fminf(fmaxf(t, 0), Lf);   q = (uint) rintf(t)   (ties to even);   !ok: q = 0
+ *   decode:  x' = ok ? fmaf((float) min(q, 2^bits - 1), step, lo) : lo
+ *   fake:    x' = decode(encode(x)), the codes never written; the same bits as the two calls
+ *
+ * kind = GSR_QUANT_UNIT_QUAT applies to cols = 4 rows (w, x, y, z).  ranges is not read and may be NULL; the range is the
+ * constant [-1, 1].  In front of encode each row is normalised and sign-fixed:
+ *     n2 = ((w*w + x*x) + y*y) + z*z ;  inv = 1.0f / sqrtf(n2) ;  s = (w < 0) ? -inv : inv ;  u_k = q_k * s
+ * A row whose n2 is not > 0 or not finite becomes (1, 0, 0, 0).  Decode returns the dequantised u without renormalising (the
+ * rasterizer normalises).
+ *
+ * gsr_quant_ranges: `ranges` is fully overwritten, whatever it held.  The one-block form reduces across workgroups through
+ *   integer min / max atomics on the keys (no float atomics): the same bits in every run.
+ * gsr_quant_fake: up to GSR_QUANT_MAX_GROUPS groups of the same n in ONE launch; rows_out == rows_in (in place) is allowed,
+ *   any other overlap is not.
+ * Error bound of a finite x in [lo, hi], ok:  |x' - x| <= step/2 + 9 ulp(max(|lo|, |hi|)), step and 1 / step
+ * normal numbers (derived in DESIGN.md section 25).
+ *
+ * A code > 2^bits - 1 is read as 2^bits - 1, and damaged ranges give wrong numbers: never an access outside the arrays.
+ * GSR_E_INVALID_ARG, before anything touches the device: n, cols, bits, kind or block_rows out of range, UNIT_QUAT with
+ * cols != 4, a null array that is not optional, a misaligned array (float32: 4, uint16 codes: 2 bytes), n_groups outside
+ * [0, GSR_QUANT_MAX_GROUPS].  n == 0: GSR_OK; gsr_quant_ranges with block_rows = 0 still writes its one block (+0, +0). */
+#define GSR_QUANT_LINEAR 0
+#define GSR_QUANT_UNIT_QUAT 1
+#define GSR_QUANT_MAX_GROUPS 8
+typedef struct gsr_quant_group {
+    const float* rows_in;
+    float* rows_out;
+    int32_t cols;
+    int32_t bits;
+    int32_t kind;
+    int32_t block_rows;
+    const float* ranges;
+} gsr_quant_group;
+GSR_API int gsr_quant_ranges(int64_t n, int32_t cols, const float* rows, int32_t block_rows, float* ranges, void* stream);
+GSR_API int gsr_quant_encode(int64_t n, int32_t cols, int32_t bits, int32_t kind, const float* rows, int32_t block_rows,
+                             const float* ranges, void* codes, void* stream);
+GSR_API int gsr_quant_decode(int64_t n, int32_t cols, int32_t bits, int32_t kind, const void* codes, int32_t block_rows,
+                             const float* ranges, float* rows_out, void* stream);
+GSR_API int gsr_quant_fake(const gsr_quant_group* groups, int32_t n_groups, int64_t n, void* stream);
+
 /* TSDF fusion of rendered depth frames and surface-nets mesh extraction: one surface of the scene from the :rgbd / :rgbdn
  * frames, made on the device.  No handle, no struct, nothing read back to the host.
  *
