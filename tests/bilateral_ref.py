@@ -91,6 +91,71 @@ def slice_backward(image, grid, vout):
     return vimage, vgrid
 
 
+def slice_forward_terms(image, grid):
+    """What a per-pixel bound on the forward slice needs: -> (acc, A), both (H, W, 3) float64.  acc is the sum
+    Σ G·wt·s4 over the 8 corners x 4 inputs BEFORE the finite check of slice_forward, A the sum of the absolute values
+    of the same 32 terms."""
+    gz, gy, gx = grid.shape[1:]
+    c = coords(image, gx, gy, gz)
+    G = grid.astype(np.float64)
+    s4 = [c["s"][..., 0], c["s"][..., 1], c["s"][..., 2], np.ones_like(c["fx"])]
+    acc = np.zeros(image.shape[:2] + (3,))
+    A = np.zeros(image.shape[:2] + (3,))
+    for xi, yi, zi, wt, _ in _corners(c, gz):
+        for d in range(3):
+            for si in range(4):
+                t = G[d * 4 + si, zi, yi, xi] * wt * s4[si]
+                acc[..., d] += t
+                A[..., d] += np.abs(t)
+    return acc, A
+
+
+def slice_backward_terms(image, grid, vout):
+    """The pullback of slice_backward with what an entry-by-entry bound needs.  -> dict of float64 arrays:
+      vimage (H, W, C), vgrid (12, gz, gy, gx)   the sums, as slice_backward gives them
+      vgrid_abs (12, gz, gy, gx)                 Σ|wt·s4·d| over the (pixel, corner) terms of the entry
+      vgrid_count (12, gz, gy, gx) int64         the number of those terms with wt != 0
+      gs_abs (H, W, 3)                           Σ|v·wt·d| over the 8 corners x 3 outputs, per input channel
+      gz_abs (H, W)                              Σ|dwdz·v·gb| over the 96 terms; 0 where z_interior is False
+    so that |∇image[..., k]|'s terms sum to gs_abs[..., k] + C2G[k]·gz_abs.  Cell, level, saturation and z_interior are
+    decided by the fp32 coordinates of coords(), every product and sum is float64."""
+    gz, gy, gx = grid.shape[1:]
+    c = coords(image, gx, gy, gz)
+    G = grid.astype(np.float64)
+    d = vout[..., :3].astype(np.float64)
+    d = np.where(np.isfinite(d), d, 0.0)
+    s4 = [c["s"][..., 0], c["s"][..., 1], c["s"][..., 2], np.ones_like(c["fx"])]
+    ng = gz * gy * gx
+    gs, gs_abs = np.zeros(image.shape[:2] + (3,)), np.zeros(image.shape[:2] + (3,))
+    gzs, gz_abs = np.zeros(image.shape[:2]), np.zeros(image.shape[:2])
+    vgrid, vgrid_abs, count = np.zeros(G.shape), np.zeros(G.shape), np.zeros(G.shape, np.int64)
+    for xi, yi, zi, wt, dwdz in _corners(c, gz):
+        flat = ((zi * gy + yi) * gx + xi).ravel()
+        hit = np.bincount(flat, weights=(wt != 0).ravel().astype(np.float64), minlength=ng).astype(np.int64).reshape(gz, gy, gx)
+        for di in range(3):
+            for si in range(4):
+                ci = di * 4 + si
+                v = G[ci, zi, yi, xi]
+                gb = s4[si] * d[..., di]
+                if si < 3:
+                    t = v * wt * d[..., di]
+                    gs[..., si] += t
+                    gs_abs[..., si] += np.abs(t)
+                t = dwdz * v * gb
+                gzs += t
+                gz_abs += np.abs(t)
+                t = (wt * gb).ravel()
+                vgrid[ci] += np.bincount(flat, weights=t, minlength=ng).reshape(gz, gy, gx)
+                vgrid_abs[ci] += np.bincount(flat, weights=np.abs(t), minlength=ng).reshape(gz, gy, gx)
+                count[ci] += hit
+    gzs = np.where(c["z_interior"], gzs, 0.0)
+    gz_abs = np.where(c["z_interior"], gz_abs, 0.0)
+    vimage = vout.astype(np.float64).copy()
+    for k in range(3):
+        vimage[..., k] = gs[..., k] + float(C2G[k]) * gzs
+    return dict(vimage=vimage, vgrid=vgrid, vgrid_abs=vgrid_abs, vgrid_count=count, gs_abs=gs_abs, gz_abs=gz_abs)
+
+
 def tv_loss(grids):
     """tv_loss(grids) (bilateral_grid.jl:106-119), grids (n, 12, gz, gy, gx)."""
     n, _, gz, gy, gx = grids.shape
@@ -112,6 +177,24 @@ def tv_grad(grids):
         g[tuple(lo)] -= d
         g[tuple(hi)] += d
     return g
+
+
+def tv_grad_terms(grids):
+    """-> (tv_grad(grids), A): A[entry] is the sum of the absolute values of the (up to six) scaled differences that enter
+    the entry, 2/(norm·12·n)·|a[e] - a[neighbour]| over its neighbours along x, y and z."""
+    n, _, gz, gy, gx = grids.shape
+    a = grids.astype(np.float64)
+    g, A = np.zeros_like(a), np.zeros_like(a)
+    for axis, norm in ((4, max(1, (gx - 1) * gy * gz)), (3, max(1, gx * (gy - 1) * gz)), (2, max(1, gx * gy * (gz - 1)))):
+        d = np.diff(a, axis=axis) * (2.0 / (norm * 12 * n))
+        lo = [slice(None)] * 5
+        hi = [slice(None)] * 5
+        lo[axis], hi[axis] = slice(0, -1), slice(1, None)
+        g[tuple(lo)] -= d
+        g[tuple(hi)] += d
+        A[tuple(lo)] += np.abs(d)
+        A[tuple(hi)] += np.abs(d)
+    return g, A
 
 
 def identity_grids(n, gx, gy, gz):

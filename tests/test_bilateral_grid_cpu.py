@@ -146,6 +146,122 @@ def test_tv_matches_autograd_and_central_differences(shape):
     assert abs(num - (br.tv_grad(grids) * u).sum()) <= 1e-7 * max(1.0, abs(num))
 
 
+def _brute_force_terms(img, grid, vout):
+    """slice_forward_terms / slice_backward_terms as a loop over pixels, corners and coefficients, scalar by scalar, from
+    the fp32 coordinates of coords()."""
+    gz, gy, gx = grid.shape[1:]
+    H, W = img.shape[:2]
+    c = br.coords(img, gx, gy, gz)
+    G = grid.astype(np.float64)
+    acc, facc = np.zeros((H, W, 3)), np.zeros((H, W, 3))
+    r = dict(vimage=vout.astype(np.float64).copy(), vgrid=np.zeros(G.shape), vgrid_abs=np.zeros(G.shape),
+             vgrid_count=np.zeros(G.shape, np.int64), gs_abs=np.zeros((H, W, 3)), gz_abs=np.zeros((H, W)))
+    for h in range(H):
+        for w in range(W):
+            s4 = [c["s"][h, w, 0], c["s"][h, w, 1], c["s"][h, w, 2], 1.0]
+            d = [float(v) if np.isfinite(v) else 0.0 for v in vout[h, w, :3]]
+            fx, fy, fz = c["fx"][h, w], c["fy"][h, w], c["fz"][h, w]
+            gs, gzs = [0.0, 0.0, 0.0], 0.0
+            for xc in (0, 1):
+                for yc in (0, 1):
+                    for zc in (0, 1):
+                        xi, yi, zi = c["x"][xc][h, w], c["y"][yc][h, w], c["z"][zc][h, w]
+                        wxy = (fx if xc else 1 - fx) * (fy if yc else 1 - fy)
+                        wt = wxy * (fz if zc else 1 - fz)
+                        dwdz = wxy * (1.0 if zc else -1.0) * (gz - 1)
+                        for di in range(3):
+                            for si in range(4):
+                                v = G[di * 4 + si, zi, yi, xi]
+                                acc[h, w, di] += v * wt * s4[si]
+                                facc[h, w, di] += abs(v * wt * s4[si])
+                                if si < 3:
+                                    gs[si] += v * wt * d[di]
+                                    r["gs_abs"][h, w, si] += abs(v * wt * d[di])
+                                if c["z_interior"][h, w]:
+                                    gzs += dwdz * v * (s4[si] * d[di])
+                                    r["gz_abs"][h, w] += abs(dwdz * v * (s4[si] * d[di]))
+                                r["vgrid"][di * 4 + si, zi, yi, xi] += wt * (s4[si] * d[di])
+                                r["vgrid_abs"][di * 4 + si, zi, yi, xi] += abs(wt * (s4[si] * d[di]))
+                                r["vgrid_count"][di * 4 + si, zi, yi, xi] += wt != 0
+            for k in range(3):
+                r["vimage"][h, w, k] = gs[k] + float(br.C2G[k]) * gzs
+    return acc, facc, r
+
+
+def test_term_helpers_match_a_brute_force_loop_and_the_definitions():
+    """One tiny case with a column on a cell boundary (W = 5, gx = 3: x = 0, 0.5, 1, 1.5, 2), saturated and non-finite
+    pixels, a non-finite cotangent: the absolute-value sums and term counts of slice_forward_terms / slice_backward_terms
+    against the scalar loop, and their plain sums against slice_forward / slice_backward themselves."""
+    W, H, size = 5, 4, (3, 2, 3)
+    img, grid, vout = _case(W, H, 5, size, 23)
+    img[1, 2, :3] = 2.0                                    # saturated, on the boundary column
+    img[2, 1, :3] = -1.0
+    acc, facc, r = _brute_force_terms(img, grid, vout)
+    a, A = br.slice_forward_terms(img, grid)
+    np.testing.assert_allclose(a, acc, rtol=0, atol=1e-13)
+    np.testing.assert_allclose(A, facc, rtol=1e-13, atol=0)
+    assert np.array_equal(np.where(np.isfinite(a), a, 0.5), br.slice_forward(img, grid)[..., :3])
+    t = br.slice_backward_terms(img, grid, vout)
+    for k in ("vimage", "vgrid"):
+        np.testing.assert_allclose(t[k], r[k], rtol=0, atol=1e-13, err_msg=k)
+    for k in ("vgrid_abs", "gs_abs", "gz_abs"):
+        np.testing.assert_allclose(t[k], r[k], rtol=1e-13, atol=0, err_msg=k)
+    assert np.array_equal(t["vgrid_count"], r["vgrid_count"])
+    vimg, vgrid = br.slice_backward(img, grid, vout)
+    assert np.array_equal(t["vimage"], vimg, equal_nan=True) and np.array_equal(t["vgrid"], vgrid)
+    # what the sums must satisfy whatever the case: |sum| <= Σ|terms|; an entry without a term is exactly zero; the
+    # boundary column puts its full xy weight on one column, so those pixels count 4 (or 2, on a level) terms, not 8
+    assert (np.abs(t["vgrid"]) <= t["vgrid_abs"] * (1 + 1e-12)).all()
+    assert not t["vgrid"][t["vgrid_count"] == 0].any() and not t["vgrid_abs"][t["vgrid_count"] == 0].any()
+    assert (np.abs(t["vimage"][..., :3]) <= (t["gs_abs"] + np.array(br.C2G, np.float64) * t["gz_abs"][..., None]) * (1 + 1e-12)).all()
+    c = br.coords(img, *size)
+    assert (c["fx"][:, 2] == 0).all() and c["x"][0][0, 2] == 1
+    assert not t["gz_abs"][~c["z_interior"]].any() and t["gz_abs"][c["z_interior"]].all()
+    # every coefficient of an entry has the same terms: 12 equal counts, and they add up to the pixels' live corners
+    assert (t["vgrid_count"] == t["vgrid_count"][:1]).all()
+    live = sum(int((wt != 0).sum()) for *_, wt, _ in br._corners(c, size[2]))
+    assert t["vgrid_count"][0].sum() == live < 8 * W * H
+
+
+def test_the_clamped_corner_carries_no_weight():
+    """A pixel whose cell is the last one (x0 = g - 1, so x1 is clamped onto x0) has fx == 0 in fp32, whatever the sizes:
+    the coordinate never exceeds g - 1.  So the clamped corner adds nothing to ∇grid, and the pullback's sum kernel, which
+    maps the last cell's second corner slot onto the last entry, adds exact zeros there: dropping that clamp cannot change
+    a bit, and no test can tell."""
+    for g in range(1, 34):
+        for n in list(range(1, 80)) + [257, 1000, 1920, 4097]:
+            x = br._axis(n, g)
+            assert x.dtype == np.float32 and (np.diff(x) >= 0).all() and x.max() <= g - 1
+            last = np.floor(x) == g - 1
+            assert (last[-1] or n == 1) and (x[last] == np.float32(g - 1)).all(), (n, g)   # (one pixel sits at 0)
+    # and on the whole path: the entries' terms of shape (2, 2, .)'s last column all come from corners with xc = 0 or x1 = x0 + 1
+    img, grid, vout = _case(9, 7, 3, (2, 3, 2), 3)
+    c = br.coords(img, 2, 3, 2)
+    assert (c["fx"][c["x"][0] == c["x"][1]] == 0).all() and (c["fy"][c["y"][0] == c["y"][1]] == 0).all()
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 1, 1), (3, 4, 2, 3), (2, 1, 5, 1), (22, 1, 1, 257)])
+def test_tv_grad_terms_match_a_loop_and_tv_grad(shape):
+    n, gz, gy, gx = shape
+    grids = np.random.default_rng(sum(shape)).normal(size=(n, 12, gz, gy, gx)).astype(np.float32)
+    g, A = br.tv_grad_terms(grids)
+    assert np.array_equal(g, br.tv_grad(grids))
+    a = grids.astype(np.float64)
+    norms = (max(1, (gx - 1) * gy * gz), max(1, gx * (gy - 1) * gz), max(1, gx * gy * (gz - 1)))
+    want = np.zeros_like(a)
+    for z in range(gz):
+        for y in range(gy):
+            for x in range(gx):
+                for (dz, dy, dx), norm in (((0, 0, 1), norms[0]), ((0, 1, 0), norms[1]), ((1, 0, 0), norms[2])):
+                    for sgn in (-1, 1):
+                        zz, yy, xx = z + sgn * dz, y + sgn * dy, x + sgn * dx
+                        if 0 <= zz < gz and 0 <= yy < gy and 0 <= xx < gx:
+                            want[:, :, z, y, x] += np.abs(a[:, :, z, y, x] - a[:, :, zz, yy, xx]) * (2.0 / (norm * 12 * n))
+    np.testing.assert_allclose(A, want, rtol=1e-13, atol=0)
+    assert (np.abs(g) <= A * (1 + 1e-12)).all()
+    assert not br.tv_grad_terms(br.identity_grids(n, gx, gy, gz))[1].any()
+
+
 def test_reference_testset_reexpressed():
     """test/runtests.jl:521-552: identity grids leave the image unchanged and have no variation; through slice + TV only
     the sliced view receives a gradient, the other views' is exactly zero."""
